@@ -11,9 +11,14 @@ N > 1 (launched by torch.distributed.run, one rank per GPU), weak scaling — pe
   * MSM leg: every rank holds 2^msm_log2n (scalar, point) pairs; lw_hip_msm_sharded_device all-gathers the partial sums.
   torch.distributed is used for the rendezvous, the barriers and the max-over-ranks only.
 
-After the timed region rank 0 (N = 1) runs the CPU oracle on the SAME inputs: single-threaded evaluate_fft at 2^log2n
-(the `cpu_baseline`), compared byte for byte with the timed GPU output ("bit_exact"), plus the all-cores context rows
-(column-parallel NTT, window-parallel MSM over the whole MSM input, also compared).  A mismatch exits non-zero.
+A plain run (`bench.py --gpus N --steps K --warmup W`) times the NTT leg only: set-up, W warm-up steps, K timed steps,
+the result line.  `--full` adds everything else, as one run: the MSM leg of `--workload all`, and after the timed region
+rank 0 (N = 1) runs the CPU oracle on the SAME inputs: single-threaded evaluate_fft at 2^log2n (the `cpu_baseline`),
+compared byte for byte with the timed GPU output ("bit_exact"), plus the all-cores context rows (column-parallel NTT,
+window-parallel MSM over the whole MSM input, also compared), the host-buffer and SRS-handle paths.  A mismatch exits
+non-zero.
+
+`--dump-outputs DIR` writes what the timed path returned in its last step as float64 .npy files (see dump_outputs).
 
 Prints ONE JSON line on rank 0.
 """
@@ -30,6 +35,31 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec (6.3 TB/s achievable)
+DUMP_ROWS = 1 << 18            # --dump-outputs: rows kept of a larger output (2^18 x 8 float64 words = 16 MiB over all ranks)
+
+
+def u64_words_f64(a):
+    """Rows of uint64 words -> float64 rows of their 32-bit halves, high half first (exact, same order)."""
+    a = np.ascontiguousarray(a).view(np.uint64).reshape(len(a), -1)
+    return np.stack([a >> np.uint64(32), a & np.uint64(0xFFFFFFFF)], axis=-1).reshape(len(a), -1).astype(np.float64)
+
+
+def sampled_rows(t, world):
+    """A fixed, seeded sample of the rows of a device tensor: (row indices, the rows as float64 32-bit words)."""
+    import torch
+    n, k = t.shape[0], DUMP_ROWS // world
+    idx = np.arange(n) if n <= k else np.sort(np.random.default_rng(0xD0E5).choice(n, k, replace=False))
+    rows = t[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+    return idx.astype(np.float64), u64_words_f64(rows)
+
+
+def dump_outputs(out_dir, world, rank, arrays):
+    """--dump-outputs: DIR/<name>.npy (DIR/<name>_rank<r>.npy when N > 1), float64.  Field elements and point
+    coordinates are split into 32-bit words, most significant first, so that every value is exact."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        fn = name if world == 1 else "%s_rank%d" % (name, rank)
+        np.save(os.path.join(out_dir, fn + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def rand_field_elems(n, seed, top_bits=59):
@@ -99,7 +129,15 @@ def main():
     ap.add_argument("--dist-mode", choices=["sharded", "independent"], default="sharded")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU legs (and with them the bit-exact checks)")
     ap.add_argument("--no-host-path", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the MSM leg of --workload all, the CPU legs with the bit-exact checks and the host-buffer / "
+                         "SRS paths (without it the CPU legs and host paths are off in every workload)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_cpu_baseline = args.no_host_path = True
 
     import torch
     import torch.distributed as dist
@@ -228,6 +266,9 @@ def main():
         dt = time.perf_counter() - t0
         prof = _lib.profile_end()
         dt = max_over_ranks(dt)
+        if args.dump_outputs:   # the transform's result of the last timed step: this rank's block of the output vector
+            rows_idx, rows = sampled_rows(last, world)
+            dump_outputs(args.dump_outputs, world, rank, {"ntt_output": rows, "ntt_output_rows": rows_idx})
         ms_per_step = dt * 1e3 / args.steps
         value = world * n * args.steps / dt
         # dominant kernel = the LDS-tiled NTT pass (all passes of one transform are launches of it)
@@ -341,9 +382,12 @@ def main():
         torch.cuda.empty_cache()
 
     # ------------------------------------------------------------------ MSM leg
-    if args.workload in ("msm", "all"):
+    if args.workload == "msm" or (args.workload == "all" and args.full):
         from bench_msm import run_msm_leg
         msm_res = run_msm_leg(args, world, rank, barrier, max_over_ranks, all_ranks_ok, comm, comm_error)
+        out = msm_res.pop("output")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, world, rank, out)
         result["msm"] = msm_res
         be = msm_res.pop("bit_exact", None)
         if be is not None:

@@ -107,6 +107,21 @@ def synth_points_device(n, seed):
     return out, rows, cols
 
 
+def affine_words_bls12381_g1(words):
+    """Projective BLS12-381 G1 point in the reference layout (18 u64 words, Montgomery form) -> canonical affine x, y as
+    (1, 12) u64 words, most significant first; the neutral element -> zeros.  Independent of the point's Z."""
+    p = BLS_P
+    rinv = pow(1 << 384, -1, p)
+    x, y, z = (sum(int(words[6 * c + j]) << (64 * (5 - j)) for j in range(6)) * rinv % p for c in range(3))
+    out = np.zeros((1, 12), dtype=np.uint64)
+    if z:
+        zi = pow(z, -1, p)
+        for k, v in enumerate((x * zi % p, y * zi % p)):
+            for j in range(6):
+                out[0, 6 * k + j] = (v >> (64 * (5 - j))) & ((1 << 64) - 1)
+    return out
+
+
 def synth_scalars_mod_r(n, seed):
     """n uniform 256-bit integers reduced mod r (canonical U256, MS limb first), as math/benches/criterion_msm.rs:17-32
     draws them.  2^256 / r < 2.21, so at most two subtractions of r."""
@@ -252,7 +267,7 @@ def run_msm_leg(args, world, rank, barrier, max_over_ranks, all_ranks_ok, comm, 
     acc_ms = sum(prof[k][1] for k in acc_names)
     dom = max(prof.items(), key=lambda kv: kv[1][1]) if prof else ("", (0, 0.0))
     alg_bytes = n * (32 + 144)
-    from bench import traffic_entry, pmc_counter
+    from bench import traffic_entry, pmc_counter, u64_words_f64
     traffic, traffic_src = traffic_entry("msm", L)
     # additions the device's accumulation performs: one per (point, window) item minus one per non-empty bucket
     # (signed digits, csrc/msm.hip: W = ceil(257/c) windows of 2^(c-1) buckets; csrc/msm_core.cuh pick_window)
@@ -285,4 +300,7 @@ def run_msm_leg(args, world, rank, barrier, max_over_ranks, all_ranks_ok, comm, 
                                      "isomorphic curve) in the newest profiles/rNN_pmc_summary.csv"},
         "kernel_times_ms": {k: {"launches": v[0], "avg_ms": v[1] / max(v[0], 1)} for k, v in prof.items()},
         "cpu_baseline": cpu, "cpu_all_cores": cpu_all, "bit_exact": bit_exact, "host_path": host_path, "srs_path": srs_path,
+        # the last timed step's result (popped by bench.py for --dump-outputs): projective as returned, and its affine image
+        "output": {"msm_output": u64_words_f64(out.reshape(1, -1)),
+                   "msm_output_affine": u64_words_f64(affine_words_bls12381_g1(out))},
     }

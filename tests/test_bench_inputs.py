@@ -63,3 +63,21 @@ def test_cfg5_inputs_and_closed_form_match_the_oracle():
         sc6 = B.scalars_mod(6, 3, B.BN_R)
         a, b = B.weighted_scalar_sums(sc6, 0)
         assert B.point_to_affine(name, O.msm(oid, sc6, pts)) == B.closed_form_msm(name, 5, 3, a, b, B.BN_R)
+
+
+def test_dumped_outputs_are_exact_32_bit_words_and_the_msm_affine_image_ignores_z():
+    import bench
+    a = np.array([[0xFFFFFFFFFFFFFFFF, 0x0123456789ABCDEF], [0, 1 << 63]], dtype=np.uint64)
+    w = bench.u64_words_f64(a)
+    assert w.dtype == np.float64 and w.shape == (2, 4)
+    assert w[0].tolist() == [0xFFFFFFFF, 0xFFFFFFFF, 0x01234567, 0x89ABCDEF] and w[1].tolist() == [0, 0, 1 << 31, 0]
+    oid = O.C_BLS12_381_G1
+    pts = bench_msm.synth_points_bls12381_g1(3, 11)                 # Z != 1, each with its own Z
+    for row in pts:
+        aff = bench_msm.affine_words_bls12381_g1(row)
+        x, y = O.point_to_affine_ints(oid, row)
+        assert O.array_to_ints(aff.reshape(2, 6)) == [x, y]
+    s = O.ec_add(oid, pts[0], pts[1])
+    assert np.array_equal(bench_msm.affine_words_bls12381_g1(s),
+                          bench_msm.affine_words_bls12381_g1(O.ec_add(oid, pts[1], pts[0])))
+    assert not bench_msm.affine_words_bls12381_g1(bench_msm.synth_run_bls12381_g1(1, 0, 5, 3)[0]).any()   # identity

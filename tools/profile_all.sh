@@ -8,10 +8,10 @@ TAG=${1:-r03}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-# the profiled command is bench.py with its default step counts (20 timed NTT steps after 5 warm-up ones; the MSM leg
-# clamps itself to 5 + 2), minus the CPU legs
-B="bench.py --no-cpu-baseline --no-host-path --steps 20 --warmup 5"
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+# the profiled command is bench.py --full with its default step counts (20 timed NTT steps after 5 warm-up ones; the MSM
+# leg clamps itself to 5 + 2), minus the CPU legs
+B="bench.py --full --no-cpu-baseline --no-host-path --steps 20 --warmup 5"
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done" ; tail -c 600 $OUT/bench.err || true
 # same command under the profiler: the JSON it prints (live HIP events) next to rocprofv3's own kernel stats
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $B > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
