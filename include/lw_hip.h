@@ -17,6 +17,7 @@
  *   - lw_hip_bitrev_permutation             <->  bitrev_permutation (math/src/fft/gpu/cuda/ops.rs:68-77),
  *                                                in_place_bit_reverse_permute (math/src/fft/cpu/bit_reversing.rs:2-9)
  *   - lw_hip_msm / lw_hip_msm_device        <->  msm::pippenger::msm (math/src/msm/pippenger.rs:18-32)
+ *   - lw_hip_msm_limbs[_device]             <->  the same for UnsignedInteger<NUM_LIMBS>, NUM_LIMBS = 1 .. 8
  *   - lw_hip_init / lw_hip_shutdown         <->  CudaState::new (math/src/fft/gpu/cuda/state.rs:29-38); the
  *                                                reference builds and drops device state on every call, this
  *                                                library keeps one context (twiddle caches, scratch, streams)
@@ -27,7 +28,8 @@
  * Data crosses the boundary bit-for-bit as the reference keeps it in memory (no conversion, as
  * math/src/gpu/cuda/field/element.rs:30-42): a field element is UnsignedInteger{limbs:[u64;N]} with
  * limbs[0] MOST significant, in Montgomery form; a projective point is X,Y,Z consecutive; an Fp2
- * coordinate is [c0,c1]; MSM scalars are canonical (non-Montgomery) UnsignedInteger<4>.
+ * coordinate is [c0,c1]; MSM scalars are canonical (non-Montgomery) UnsignedInteger<4> (UnsignedInteger<1..8>
+ * through lw_hip_msm_limbs).
  *
  * All functions return 0 on success or a negative lw_status_t; lw_hip_last_error() gives a thread-local
  * message.  No exceptions or panics cross the ABI.  The caller owns every buffer; nothing is retained.
@@ -328,6 +330,19 @@ int lw_hip_msm_fr(lw_curve_t curve, const uint64_t *fr_elements, size_t n_scalar
                   void *out_point);
 int lw_hip_msm_fr_device(lw_curve_t curve, const uint64_t *d_fr_elements, const void *d_points, size_t n,
                          void *out_point_host, void *hip_stream);
+/* Same as lw_hip_msm / lw_hip_msm_device for scalars of any width from 1 to 8 u64 limbs, as the reference's Pippenger is
+ * generic over it: msm<const NUM_LIMBS, G>(cs: &[UnsignedInteger<NUM_LIMBS>], ...) (math/src/msm/pippenger.rs:18-32).
+ * scalars: n x scalar_limbs u64, each a canonical unsigned integer of 64 * scalar_limbs bits, MS limb first (as
+ * UnsignedInteger<scalar_limbs> sits in memory).  The result is sum k_i * P_i over the FULL integers k_i: the scalars are
+ * NOT reduced mod r (that would give the same element only inside the prime-order subgroup, and any curve point is
+ * accepted).  Different lengths -> LW_ERR_LENGTH_MISMATCH (checked first); scalar_limbs outside 1 .. 8 -> LW_ERR_BAD_ARG;
+ * both before any device work.  d_scalars rows are 8 * scalar_limbs bytes: the buffer must be 16-byte aligned for even
+ * scalar_limbs and 8-byte aligned for odd (LW_ERR_BAD_ARG otherwise).  Output as lw_hip_msm; scalar_limbs == 4 is
+ * exactly lw_hip_msm / lw_hip_msm_device. */
+int lw_hip_msm_limbs(lw_curve_t curve, const uint64_t *scalars, uint32_t scalar_limbs, size_t n_scalars, const void *points,
+                     size_t n_points, void *out_point);
+int lw_hip_msm_limbs_device(lw_curve_t curve, const uint64_t *d_scalars, uint32_t scalar_limbs, const void *d_points, size_t n,
+                            void *out_point_host, void *hip_stream);
 
 /* Batched group law, IsGroup::operate_with (math/src/elliptic_curve/short_weierstrass/point.rs:171-207) on device
  * buffers: d_out[j*m + i] = d_rows[i] + d_cols[j] (projective points, reference layout; the sums are generally not

@@ -23,7 +23,7 @@ EXPORTS = [
     "lw_hip_field_elem_bytes", "lw_hip_curve_point_bytes", "lw_hip_ntt", "lw_hip_ntt_device", "lw_hip_ntt_cross_device",
     "lw_hip_gen_twiddles", "lw_hip_gen_powers", "lw_hip_bitrev_permutation", "lw_hip_ntt_lde_device",
     "lw_polynomial_evaluate_fft", "lw_polynomial_interpolate_fft", "lw_hip_msm", "lw_hip_msm_device",
-    "lw_hip_msm_fr", "lw_hip_msm_fr_device", "lw_groth16_h_coefficients",
+    "lw_hip_msm_fr", "lw_hip_msm_fr_device", "lw_hip_msm_limbs", "lw_hip_msm_limbs_device", "lw_groth16_h_coefficients",
     "lw_stark_commit_columns", "lw_stark_commit_columns_device", "lw_stark_commit_columns_layout_device", "lw_stark_fri_layer",
     "lw_hip_srs_create", "lw_hip_srs_create_device", "lw_hip_srs_destroy", "lw_hip_msm_srs", "lw_hip_msm_srs_device",
     "lw_hip_msm_srs_fr", "lw_hip_msm_srs_fr_device", "lw_stark_fri_layer_device", "lw_groth16_h_coefficients_device",
@@ -121,6 +121,10 @@ def lib():
     L.lw_hip_msm_fr.restype = i
     L.lw_hip_msm_fr_device.argtypes = [i, vp, vp, sz, vp, vp]
     L.lw_hip_msm_fr_device.restype = i
+    L.lw_hip_msm_limbs.argtypes = [i, vp, u32, sz, vp, sz, vp]
+    L.lw_hip_msm_limbs.restype = i
+    L.lw_hip_msm_limbs_device.argtypes = [i, vp, u32, vp, sz, vp, vp]
+    L.lw_hip_msm_limbs_device.restype = i
     L.lw_hip_srs_create.argtypes = [i, vp, sz, C.POINTER(vp)]
     L.lw_hip_srs_create.restype = i
     L.lw_hip_srs_create_device.argtypes = [i, vp, sz, vp, C.POINTER(vp)]

@@ -269,7 +269,8 @@ int ntt_bb_device(Context &c, lw_layout_t layout, lw_dir_t dir, const void *d_in
                   uint32_t batch, uint64_t stride, const void *coset_offset, hipStream_t stream, uint32_t in_log2);
 int broadcast_device(size_t elem_bytes, const void *d_in, void *d_out, uint64_t n, uint32_t batch, uint64_t out_stride, hipStream_t stream);
 int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const void *d_points, size_t n, void *out_host,
-               hipStream_t stream, int scalars_montgomery, int affine_points, const void *h_points = nullptr);
+               hipStream_t stream, int scalars_montgomery, int affine_points, const void *h_points = nullptr,
+               uint32_t scalar_limbs = 4);
 int msm_normalize_device(Context &c, lw_curve_t curve, const void *d_in, size_t n, void *d_out, hipStream_t stream);
 size_t msm_affine_bytes(lw_curve_t curve, size_t n);
 int msm_fold_build(Context &c, lw_curve_t curve, void *d_rows, size_t n, uint32_t cbits, hipStream_t stream);
@@ -909,14 +910,19 @@ int lw_polynomial_interpolate_fft(lw_field_t field, lw_layout_t layout, const vo
 }
 
 static int msm_device_entry(lw_curve_t curve, const uint64_t *d_scalars, const void *d_points, size_t n, void *out_point_host,
-                            void *hip_stream, int mont) {
+                            void *hip_stream, int mont, uint32_t limbs = 4) {
+    if (limbs < 1 || limbs > 8) { set_error("scalar_limbs = %u: 1 .. 8 supported", limbs); return LW_ERR_BAD_ARG; }
+    if (n && limbs != 4 && ((uintptr_t)d_scalars & (limbs % 2 ? 7 : 15))) {   // msm_digits_kernel's row loads
+        set_error("scalars of %u limbs must be %d-byte aligned", limbs, limbs % 2 ? 8 : 16);
+        return LW_ERR_BAD_ARG;
+    }
     Entry en(hip_stream);
     if (en.rc) return en.rc;
     Context &c = en.c;
     int rc = LW_OK;
     if (lw_hip_curve_point_bytes(curve) == 0 || !out_point_host) { set_error("bad curve or null output"); return LW_ERR_BAD_ARG; }
     auto t0 = std::chrono::steady_clock::now();
-    rc = msm_device(c, curve, d_scalars, d_points, n, out_point_host, (hipStream_t)hip_stream, mont, 0);
+    rc = msm_device(c, curve, d_scalars, d_points, n, out_point_host, (hipStream_t)hip_stream, mont, 0, nullptr, limbs);
     c.timings.last_msm_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c.timings.msm_calls++;
     return rc;
@@ -1162,13 +1168,14 @@ int lw_hip_msm_fr_device(lw_curve_t curve, const uint64_t *d_fr_elements, const 
 }
 
 static int msm_host_entry(lw_curve_t curve, const uint64_t *scalars, size_t n_scalars, const void *points, size_t n_points,
-                          void *out_point, int mont) {
+                          void *out_point, int mont, uint32_t limbs = 4) {
     const size_t pb = lw_hip_curve_point_bytes(curve);
     if (pb == 0 || !out_point) { set_error("bad curve or null output"); return LW_ERR_BAD_ARG; }
     if (n_scalars != n_points) {   // MSMError::LengthMismatch (math/src/msm/pippenger.rs:25-27)
         set_error("scalars and points have different lengths: %zu vs %zu", n_scalars, n_points);
         return LW_ERR_LENGTH_MISMATCH;
     }
+    if (limbs < 1 || limbs > 8) { set_error("scalar_limbs = %u: 1 .. 8 supported", limbs); return LW_ERR_BAD_ARG; }
     Entry en(nullptr);
     if (en.rc) return en.rc;
     Context &c = en.c;
@@ -1177,13 +1184,13 @@ static int msm_host_entry(lw_curve_t curve, const uint64_t *scalars, size_t n_sc
     const size_t n = n_points;
     if (n) {
         if (!scalars || !points) { set_error("null buffer"); return LW_ERR_BAD_ARG; }
-        if (c.host_io_a.ensure(n * 32) || c.host_io_b.ensure(n * pb)) return LW_ERR_ALLOC;
+        if (c.host_io_a.ensure(n * 8 * limbs) || c.host_io_b.ensure(n * pb)) return LW_ERR_ALLOC;
     }
     hipStream_t io = en.use_lane_stream();
     if (!io) return en.rc;
     // the scalars first: the sort needs nothing else, and msm_device uploads the points while it runs
-    if (n) LW_HIP_CHECK(hipMemcpyAsync(c.host_io_a.p, scalars, n * 32, hipMemcpyHostToDevice, io), LW_ERR_LAUNCH);
-    rc = msm_device(c, curve, (const uint64_t *)c.host_io_a.p, c.host_io_b.p, n, out_point, io, mont, 0, n ? points : nullptr);
+    if (n) LW_HIP_CHECK(hipMemcpyAsync(c.host_io_a.p, scalars, n * 8 * limbs, hipMemcpyHostToDevice, io), LW_ERR_LAUNCH);
+    rc = msm_device(c, curve, (const uint64_t *)c.host_io_a.p, c.host_io_b.p, n, out_point, io, mont, 0, n ? points : nullptr, limbs);
     c.timings.last_msm_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c.timings.msm_calls++;
     return rc;
@@ -1194,6 +1201,14 @@ int lw_hip_msm(lw_curve_t curve, const uint64_t *scalars, size_t n_scalars, cons
 int lw_hip_msm_fr(lw_curve_t curve, const uint64_t *fr_elements, size_t n_scalars, const void *points, size_t n_points,
                   void *out_point) {
     return msm_host_entry(curve, fr_elements, n_scalars, points, n_points, out_point, 1);
+}
+int lw_hip_msm_limbs(lw_curve_t curve, const uint64_t *scalars, uint32_t scalar_limbs, size_t n_scalars, const void *points,
+                     size_t n_points, void *out_point) {
+    return msm_host_entry(curve, scalars, n_scalars, points, n_points, out_point, 0, scalar_limbs);
+}
+int lw_hip_msm_limbs_device(lw_curve_t curve, const uint64_t *d_scalars, uint32_t scalar_limbs, const void *d_points, size_t n,
+                            void *out_point_host, void *hip_stream) {
+    return msm_device_entry(curve, d_scalars, d_points, n, out_point_host, hip_stream, 0, scalar_limbs);
 }
 
 // batched operate_with: out[j*m + i] = rows[i] + cols[j]

@@ -5,9 +5,9 @@
 // schedule is rebuilt for a GPU:
 //   0. normalise   large projective inputs -> affine rows on a side stream (batch inversion; BLS12-381 G1 and BN254 G2
 //                  land on a cheaper isomorphic curve, ec.cuh), so that step 3 uses the mixed addition.
-//   1. digits      every scalar is recoded into W = ceil(257/c) SIGNED c-bit digits (the reference uses unsigned ones,
-//                  pippenger.rs:76-77); (window, |digit| - 1) is a bucket key, the sign negates the point; digit 0
-//                  contributes nothing (:78).  c = 8 / 16 / 20 by size (msm_core.cuh pick_window).
+//   1. digits      every B-bit scalar (B = 64 x its 1 .. 8 limbs) is recoded into W = 1 + floor(B/c) SIGNED c-bit digits
+//                  (the reference uses unsigned ones, pippenger.rs:76-77); (window, |digit| - 1) is a bucket key, the sign
+//                  negates the point; digit 0 contributes nothing (:78).  c by size and width (msm_core.cuh pick_window).
 //   2. scatter     two-level counting sort of (point index, sign) by key through LDS (coarse bins per window, then the
 //                  keys of every coarse bin); the order inside a bucket is irrelevant to the group sum.
 //   3. accumulate  segmented reduction over each bucket's list: every work-item sums one piece (<= CH points) of ONE
@@ -46,9 +46,9 @@ void msm_launch_scalar_prep(int bn254, const void *in, void *out, uint64_t n, hi
 // window, so |digit| <= 2^(c-1) and a window has 2^(c-1) buckets — half the running-sum work of the reference's unsigned
 // digits (pippenger.rs:76-81) for the same c, which is what makes c = 20 affordable at 2^24 points (13 windows instead
 // of 16: 19 % fewer bucket additions).  A negative digit adds -P (one field negation of y in the accumulate kernel).
-// W = ceil(257 / c) windows, so the top window never carries out (scalars are below 2^256).  Same group element as the
+// W = 1 + floor(B / c) windows (ceil(257 / c) for 256-bit scalars), so the top window never carries out (scalars are below 2^B).  Same group element as the
 // reference's sum; bucket j of a window stands for the multiplier j + 1.
-// Level 0 cuts every scalar into its W digits once (msm_digits_kernel: 32 B read, W x 4 B written per point), so the
+// Level 0 cuts every scalar into its W digits once (msm_digits_kernel: 8L bytes read, W x 4 B written per point), so the
 // per-window passes below read 4 bytes per point instead of the whole scalar.
 // Level A partitions the N items of ONE window (grid.y = window) into coarse bins (high key bits): a workgroup takes
 // 16384 points, histograms them in LDS, reserves one contiguous run per bin with a single global atomic and writes its
@@ -77,34 +77,58 @@ static SortSplit sort_split(uint32_t c, uint64_t n) {   // n: one more than the 
     return sp;
 }
 
+// The L limbs of scalar i as 2L 32-bit words in memory order.  Rows are 8L bytes: 16-byte loads for even L, 8-byte loads for
+// odd L, whose rows are only 8-byte aligned.
+template <uint32_t L>
 __device__ __forceinline__ void load_scalar_words(const uint32_t *scalars, uint64_t i, uint32_t *s) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(scalars + i * 8);
-    uint4 a = q[0], b = q[1];
-    s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w; s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
+    if constexpr (L % 2 == 0) {
+        const uint4 *q = reinterpret_cast<const uint4 *>(scalars + i * (2 * L));
+#pragma unroll
+        for (uint32_t k = 0; k < L / 2; k++) {
+            const uint4 a = q[k];
+            s[4 * k] = a.x; s[4 * k + 1] = a.y; s[4 * k + 2] = a.z; s[4 * k + 3] = a.w;
+        }
+    } else {
+        const uint2 *q = reinterpret_cast<const uint2 *>(scalars + i * (2 * L));
+#pragma unroll
+        for (uint32_t k = 0; k < L; k++) {
+            const uint2 a = q[k];
+            s[2 * k] = a.x; s[2 * k + 1] = a.y;
+        }
+    }
 }
 
 // dig[w * n_pad + i] = (|d| << 1) | (d < 0) for the signed digit d of window w of scalar i; 0 when d = 0; rows padded with
-// zeros to n_pad.  The scalar's words are walked with compile-time register indices (a runtime word index would send the
-// eight words through scratch memory: 3.2 ms instead of 0.4 at 2^24).
+// zeros to n_pad.  Scalars are L u64 limbs, most significant first (UnsignedInteger<L>, pippenger.rs:18-32), B = 64 L bits,
+// W = 1 + floor(B / c) windows.  The scalar's 2L words are walked with compile-time register indices (a runtime word index
+// would send them through scratch memory: 3.2 ms instead of 0.4 at 2^24, L = 4), hence one instantiation per L.
 constexpr uint32_t DIGITS_PER_THREAD = 8;   // points per work-item: 8192 workgroups at 2^24 instead of 65536 tiny ones
-// When c divides 256 (c = 8, 16) the window at bit 256 would hold nothing but the carry of the one below it: zero for every
-// scalar below 2^255 (all the reference's callers pass representatives below r), but ONE bucket with half of all points
-// for uniform 256-bit scalars.  So the top c-bit window is not recoded: its value u = raw + carry <= 2^c is taken
+// When c divides B (L = 4: c = 8, 16) the window at bit B would hold nothing but the carry of the one below it: zero for every
+// scalar below 2^(B-1) (all the reference's 4-limb callers pass representatives below r), but ONE bucket with half of all
+// points for uniform B-bit scalars.  So the top c-bit window is not recoded: its value u = raw + carry <= 2^c is taken
 // unsigned and split over the last two window slots, u <= 2^(c-1) into slot W-2 (bucket u - 1) and larger values into slot
-// W-1 (bucket u - 2^(c-1) - 1); both slots sit at bit 256 - c and the host fold adds 2^(c-1) times slot W-1's plain sum
+// W-1 (bucket u - 2^(c-1) - 1); both slots sit at bit B - c and the host fold adds 2^(c-1) times slot W-1's plain sum
 // (msm_core.cuh run()).
+template <uint32_t L>
 __global__ __launch_bounds__(256) void msm_digits_kernel(const uint32_t *scalars, uint64_t n, uint64_t n_pad, uint32_t c, uint32_t W,
                                                          uint32_t *dig) {
+    constexpr uint32_t NWORDS = 2 * L, B = 64 * L;
     const uint32_t mask = (1u << c) - 1, half = 1u << (c - 1);
-    const bool split_top = (W - 1) * c == 256;
+    const bool split_top = (W - 1) * c == B;
     const uint64_t i0 = (uint64_t)blockIdx.x * (256 * DIGITS_PER_THREAD) + threadIdx.x;
 #pragma nounroll
     for (uint32_t q = 0; q < DIGITS_PER_THREAD; q++) {
         const uint64_t i = i0 + (uint64_t)q * 256;
         if (i >= n_pad) return;
-        uint32_t s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (i < n) load_scalar_words(scalars, i, s);
-        const uint32_t t[9] = {s[6], s[7], s[4], s[5], s[2], s[3], s[0], s[1], 0u};   // 32-bit words, least significant first
+        uint32_t s[NWORDS] = {};
+        if (i < n) load_scalar_words<L>(scalars, i, s);
+        uint32_t t[NWORDS + 1];   // 32-bit words, least significant first: limb L-1-j is (t[2j], t[2j+1])
+#pragma unroll
+        for (uint32_t j = 0; j < L; j++) {
+            t[2 * j] = s[2 * (L - 1 - j)];
+            t[2 * j + 1] = s[2 * (L - 1 - j) + 1];
+        }
+        t[NWORDS] = 0u;
         uint32_t o = 0, w = 0, carry = 0;
         uint32_t *out = dig + i;
         auto emit = [&](uint32_t raw) {
@@ -124,14 +148,14 @@ __global__ __launch_bounds__(256) void msm_digits_kernel(const uint32_t *scalars
             w++;
         };
 #pragma unroll
-        for (uint32_t j = 0; j < 8; j++) {
+        for (uint32_t j = 0; j < NWORDS; j++) {
             const uint64_t v = (uint64_t)t[j] | ((uint64_t)t[j + 1] << 32);
             while (w < W && o < 32u * (j + 1)) {
                 emit((uint32_t)(v >> (o - 32u * j)) & mask);
                 o += c;
             }
         }
-        while (w < W) emit(0u);   // a window that starts at bit 256 (c divides 256) holds only the carry
+        while (w < W) emit(0u);   // a window that starts at bit B (c divides B) holds only the carry
     }
 }
 
@@ -664,12 +688,22 @@ uint32_t msm_max_window_bits() { return MSM_MAX_C; }
 // writes do not all fall on the same memory channel
 uint64_t msm_sort_padded_points(uint64_t n) { return ((n + 7) & ~(uint64_t)7) + 1032; }
 // level 0: the W x n_pad digit matrix of all windows (shared by the window slices of msm_core.cuh run())
-void msm_launch_digits(Context &c, const uint32_t *scalars, uint64_t n, uint32_t cb, uint32_t W, uint32_t *dig, hipStream_t s) {
+int msm_launch_digits(Context &c, const uint32_t *scalars, uint64_t n, uint32_t cb, uint32_t W, uint32_t *dig, hipStream_t s,
+                      uint32_t scalar_limbs) {
     const uint64_t n_pad = msm_sort_padded_points(n);
+    const dim3 grid((uint32_t)((n_pad + 256 * DIGITS_PER_THREAD - 1) / (256 * DIGITS_PER_THREAD)));
     hipEvent_t pe = c.prof_begin(s);
-    hipLaunchKernelGGL(msm_digits_kernel, dim3((uint32_t)((n_pad + 256 * DIGITS_PER_THREAD - 1) / (256 * DIGITS_PER_THREAD))), dim3(256), 0, s,
-                       scalars, n, n_pad, cb, W, dig);
+    switch (scalar_limbs) {
+#define LW_DIGITS_CASE(L) \
+        case L: hipLaunchKernelGGL((msm_digits_kernel<L>), grid, dim3(256), 0, s, scalars, n, n_pad, cb, W, dig); break;
+        LW_DIGITS_CASE(1) LW_DIGITS_CASE(2) LW_DIGITS_CASE(3) LW_DIGITS_CASE(4)
+        LW_DIGITS_CASE(5) LW_DIGITS_CASE(6) LW_DIGITS_CASE(7) LW_DIGITS_CASE(8)
+#undef LW_DIGITS_CASE
+        default: set_error("scalars of %u limbs (1 .. 8 supported)", scalar_limbs); return LW_ERR_BAD_ARG;
+    }
     c.prof_end("msm_digits_kernel", pe, s);
+    LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
+    return LW_OK;
 }
 // `dig`: row 0 = the first of the W windows sorted here (a slice of the matrix); win0: that window's number in the MSM
 template <class ITEM>
@@ -755,13 +789,13 @@ int msm_waves_per_simd() {
 }
 
 int msm_run_bls12381_g1(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_points, size_t n, void *out, int affine,
-                      hipEvent_t points_ready);
+                      hipEvent_t points_ready, uint32_t scalar_limbs);
 int msm_run_bn254_g1(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_points, size_t n, void *out, int affine,
-                      hipEvent_t points_ready);
+                      hipEvent_t points_ready, uint32_t scalar_limbs);
 int msm_run_bn254_g2(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_points, size_t n, void *out, int affine,
-                      hipEvent_t points_ready);
+                      hipEvent_t points_ready, uint32_t scalar_limbs);
 int msm_run_bls12381_g2(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_points, size_t n, void *out, int affine,
-                      hipEvent_t points_ready);
+                      hipEvent_t points_ready, uint32_t scalar_limbs);
 int msm_normalize_bls12381_g1(Context &c, hipStream_t s, const void *d_in, size_t n, void *d_out);
 int msm_normalize_bn254_g1(Context &c, hipStream_t s, const void *d_in, size_t n, void *d_out);
 int msm_normalize_bn254_g2(Context &c, hipStream_t s, const void *d_in, size_t n, void *d_out);
@@ -843,11 +877,16 @@ int ensure_aux_stream(Context &c) {
     return LW_OK;
 }
 
+// scalar_limbs: the scalars are n x scalar_limbs u64 (1 .. 8); the Montgomery and affine (SRS) forms take 4 only.
 int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const void *d_points, size_t n, void *out_host,
-               hipStream_t stream, int scalars_montgomery, int affine_points, const void *h_points) {
+               hipStream_t stream, int scalars_montgomery, int affine_points, const void *h_points, uint32_t scalar_limbs) {
     // h_points (host-buffer entry points): the points are still in host memory and d_points is the device buffer they go to.
     // The sort needs the scalars only, so it is enqueued first and the upload runs under it (msm_after_sort below);
     // without a normalisation the points are needed by the first kernel after the sort and go up front.
+    if (scalar_limbs < 1 || scalar_limbs > 8 || ((scalars_montgomery || affine_points) && scalar_limbs != 4)) {
+        set_error("MSM scalars of %u limbs", scalar_limbs);
+        return LW_ERR_BAD_ARG;
+    }
     const size_t pbytes = lw_hip_curve_point_bytes(curve);
     bool upload_pending = h_points != nullptr && n != 0;
     if (scalars_montgomery && n) {
@@ -937,10 +976,10 @@ int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const vo
         LW_HIP_CHECK(hipMemcpyAsync((void *)d_points, h_points, n * pbytes, hipMemcpyHostToDevice, stream), LW_ERR_LAUNCH);
     int rc;
     switch (curve) {
-        case LW_CURVE_BLS12_381_G1: rc = msm_run_bls12381_g1(c, stream, d_scalars, d_points, n, out_host, affine_points, join); break;
-        case LW_CURVE_BN254_G1: rc = msm_run_bn254_g1(c, stream, d_scalars, d_points, n, out_host, affine_points, join); break;
-        case LW_CURVE_BN254_G2: rc = msm_run_bn254_g2(c, stream, d_scalars, d_points, n, out_host, affine_points, join); break;
-        case LW_CURVE_BLS12_381_G2: rc = msm_run_bls12381_g2(c, stream, d_scalars, d_points, n, out_host, affine_points, join); break;
+        case LW_CURVE_BLS12_381_G1: rc = msm_run_bls12381_g1(c, stream, d_scalars, d_points, n, out_host, affine_points, join, scalar_limbs); break;
+        case LW_CURVE_BN254_G1: rc = msm_run_bn254_g1(c, stream, d_scalars, d_points, n, out_host, affine_points, join, scalar_limbs); break;
+        case LW_CURVE_BN254_G2: rc = msm_run_bn254_g2(c, stream, d_scalars, d_points, n, out_host, affine_points, join, scalar_limbs); break;
+        case LW_CURVE_BLS12_381_G2: rc = msm_run_bls12381_g2(c, stream, d_scalars, d_points, n, out_host, affine_points, join, scalar_limbs); break;
         default: set_error("bad curve %d", (int)curve); return LW_ERR_BAD_ARG;
     }
     c.msm_after_sort = nullptr;                                  // (a run that failed before its sort never took it)
@@ -958,7 +997,7 @@ int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const vo
     void msm_shard_combine_##SUFFIX(const char *sa_all, uint32_t G, uint32_t cbits, void *out);
 LW_SHARD_DECL(bls12381_g1) LW_SHARD_DECL(bn254_g1) LW_SHARD_DECL(bn254_g2) LW_SHARD_DECL(bls12381_g2)
 #undef LW_SHARD_DECL
-uint32_t msm_window_bits_for(size_t n) { return pick_window(n); }
+uint32_t msm_window_bits_for(size_t n) { return pick_window(n, 256); }
 // local pairs -> dense bucket array in the context workspace.  The points are normalised first whatever n is, so that every
 // rank's buckets live on the same curve model (the isomorphic one where the curve has it) and can be added across ranks.
 int msm_shard_accumulate(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const void *d_points, size_t n, uint32_t cbits, hipStream_t s,

@@ -20,7 +20,8 @@ constexpr int MSM_THREADS = 128;
 uint32_t msm_sort_coarse_bins(uint32_t c, uint32_t W, uint64_t n);
 uint32_t msm_max_window_bits();
 uint64_t msm_sort_padded_points(uint64_t n);
-void msm_launch_digits(Context &c, const uint32_t *scalars, uint64_t n, uint32_t cb, uint32_t W, uint32_t *dig, hipStream_t s);
+int msm_launch_digits(Context &c, const uint32_t *scalars, uint64_t n, uint32_t cb, uint32_t W, uint32_t *dig, hipStream_t s,
+                      uint32_t scalar_limbs);   // scalars: n x scalar_limbs u64, 1 .. 8
 void msm_launch_sort(Context &c, const uint32_t *dig, uint64_t n, uint32_t cb, uint32_t W, uint32_t *coarse_cnt,
                      uint32_t *coarse_off, uint32_t *coarse_cursor, uint64_t *items, uint32_t *sorted, uint32_t *off, uint32_t K,
                      uint32_t *maxlen, uint32_t *scan_tmp, uint32_t *sub_off, uint32_t *key_cnt, uint32_t *key_cursor, uint64_t fold_stride,
@@ -441,13 +442,23 @@ struct Carver {   // bump allocator over the context workspace
 // top window of 0-3 bits puts N items into a handful of buckets and costs extra rounds (2^22: c = 16 15.6 ms, c = 17
 // 18.9, c = 18 18.3, c = 19 17.1, c = 20 16.5).  Measured with LW_HIP_MSM_C (tools/ab_msm_csweep.sh): 2^14 c = 8 1.60 ms
 // against 1.92 at c = 16; 2^16 2.02 (c = 16) against 2.10; 2^23 c = 20 27.3 against 28.6; 2^24 c = 20 49.1 against 54.8.
-static uint32_t pick_window(size_t n) {
+// Scalars of other widths (B = 64 L bits, L != 4; lw_hip_msm_limbs).  c = 16 (top window split, W = B/16 + 1) wins up to 2^22
+// for every width measured: a thin top window costs more than the extra windows save, 384 bits 2^22 c = 16 19.8 ms, c = 19
+// (4-bit top) 21.3, c = 20 23.3; 2^20 6.1 / 9.0 / 11.9.  From 2^23 the bucket additions dominate: 384 bits 2^24 c = 16 73.7,
+// c = 18 71.3, c = 19 70.2, c = 20 69.6 ms (as for 256 bits); 128 bits 2^24 c = 16 27.6, c = 19 (W = 7, 14-bit top) 26.0,
+// c = 20 (8-bit top) 27.5; 64 bits 2^24 c = 16 (W = 5) 16.4, c = 18 17.0, c = 20 (W = 4, 4-bit top) 18.8.  BLS12-381 G1,
+// distinct points, tools/ab_msm_limbs.py --sweep (profiles/msm_scalar_limbs.txt).
+static uint32_t pick_window_wide(size_t n, uint32_t bits) {
+    if (n < ((size_t)1 << 23) || bits <= 64) return 16u;
+    return bits == 128 ? 19u : 20u;
+}
+static uint32_t pick_window(size_t n, uint32_t bits) {
     const char *e = tuning_env("LW_HIP_MSM_C");   // tuning and tests only; read per call so a test can sweep it
     const int c_env = e ? atoi(e) : 0;
     if (c_env >= 3 && c_env <= (int)msm_max_window_bits()) return (uint32_t)c_env;
     if (n < ((size_t)1 << 15)) return 8u;
-    if (n < ((size_t)1 << 23)) return 16u;
-    return 20u;
+    if (bits == 256) return n < ((size_t)1 << 23) ? 16u : 20u;
+    return pick_window_wide(n, bits);
 }
 
 template <class C>
@@ -712,14 +723,15 @@ struct MsmRunner {
     }
 
     // window sums -> the MSM: fold most-significant first, acc <- 2^c * acc + sum_w (pippenger.rs:101).  a_top: the plain sum of
-    // the top slot's buckets, needed when c divides 256 (see below).
-    static Point<C> fold_windows(const std::vector<Point<C>> &wsum, const Point<C> &a_top, uint32_t cbits, uint32_t W, bool folded) {
+    // the top slot's buckets, needed when c divides the scalar width `bits` (see below).
+    static Point<C> fold_windows(const std::vector<Point<C>> &wsum, const Point<C> &a_top, uint32_t cbits, uint32_t W, bool folded,
+                                 uint32_t bits) {
         const uint32_t NW = folded ? 1u : W;
         uint32_t top = NW - 1;
         Point<C> result = wsum[top];   // folded: the copies already carry the 2^(c w) factors, one sum is the result
-        if (!folded && (W - 1) * cbits == 256) {
+        if (!folded && (W - 1) * cbits == bits) {
             // the top window's values above 2^(c-1) live in slot W-1 with 2^(c-1) taken off (msm_digits_kernel): both slots
-            // weigh 2^(256-c); slot W-1 owes 2^(c-1) times its plain sum
+            // weigh 2^(bits-c); slot W-1 owes 2^(c-1) times its plain sum
             Point<C> extra = a_top;
             for (uint32_t i = 0; i + 1 < cbits; i++) extra = pt_dbl<C>(extra);
             top--;
@@ -763,8 +775,8 @@ struct MsmRunner {
         if (rc) return rc;
         sl.maxlen_h = c.pinned_words;
         *sl.maxlen_h = 0;
-        msm_launch_digits(c, (const uint32_t *)d_scalars, (uint64_t)n, cbits, W, dig, stream);
-        rc = launch_sort(sl, dig, n, cbits, stream);
+        rc = msm_launch_digits(c, (const uint32_t *)d_scalars, (uint64_t)n, cbits, W, dig, stream, 4);
+        if (!rc) rc = launch_sort(sl, dig, n, cbits, stream);
         if (rc) return rc;
         LW_HIP_CHECK(hipStreamSynchronize(stream), LW_ERR_LAUNCH);
         if (points_ready) LW_HIP_CHECK(hipStreamWaitEvent(stream, points_ready, 0), LW_ERR_LAUNCH);
@@ -824,14 +836,20 @@ struct MsmRunner {
             wsum[w] = pt_add<C>(x, t);
             if (w + 1 == W) a_top = a_all;
         }
-        Point<C> result = fold_windows(wsum, a_top, cbits, W, false);
+        Point<C> result = fold_windows(wsum, a_top, cbits, W, false, 256);
         result = pt_unmap_result<C>(pt_to_affine<C>(result));
         pt_store<C>(out_host, result);
     }
 
-    int run(const uint64_t *d_scalars, const void *d_points, size_t n, void *out_host) {
+    // d_scalars: n x scalar_limbs u64 (1 .. 8), each an unsigned integer of B = 64 x scalar_limbs bits, MS limb first
+    int run(const uint64_t *d_scalars, const void *d_points, size_t n, void *out_host, uint32_t scalar_limbs) {
         Point<C> result = pt_identity<C>();
+        const uint32_t bits = 64 * scalar_limbs;
         if (n > 0) {
+            if (scalar_limbs < 1 || scalar_limbs > 8 || (fold_stride && bits != 256)) {   // folded SRS: 4-limb scalars only
+                set_error("MSM scalars of %u limbs", scalar_limbs);
+                return LW_ERR_BAD_ARG;
+            }
             if (n >> 32) {
                 set_error("MSM of %zu points: index width is 32 bits", n);
                 return LW_ERR_BAD_ARG;
@@ -840,8 +858,8 @@ struct MsmRunner {
                 set_error("MSM of %zu points: the sorted list keeps the digit's sign in bit 31 of the index", n);
                 return LW_ERR_BAD_ARG;
             }
-            const uint32_t cbits = fold_stride ? fold_c : pick_window(n);
-            W = (256 + cbits) / cbits;   // ceil(257 / c): the signed recoding of a 256-bit scalar never carries out of the top window
+            const uint32_t cbits = fold_stride ? fold_c : pick_window(n, bits);
+            W = (bits + cbits) / cbits;   // 1 + floor(B / c): the signed recoding of a B-bit scalar never carries out of the top window
             if (fold_stride && (((uint64_t)W * fold_stride) >> 31)) {
                 set_error("folded SRS of %llu x %u rows overflows the 31-bit point index", (unsigned long long)fold_stride, W);
                 return LW_ERR_BAD_ARG;
@@ -901,8 +919,8 @@ struct MsmRunner {
                 side = c.aux_hi;   // high priority: its short kernels take CU slots as the long accumulate kernel's workgroups retire
             }
             // digits of all windows, then the sort of the first slice, on the caller's stream
-            msm_launch_digits(c, (const uint32_t *)d_scalars, (uint64_t)n, cbits, W, dig, stream);
-            rc = launch_sort(sl[0], dig, n, cbits, stream);
+            rc = msm_launch_digits(c, (const uint32_t *)d_scalars, (uint64_t)n, cbits, W, dig, stream, scalar_limbs);
+            if (!rc) rc = launch_sort(sl[0], dig, n, cbits, stream);
             if (rc) return rc;
             if (c.msm_after_sort) {   // host-buffer call: the points are uploaded (and normalised) while the sort above runs
                 auto hook = std::move(c.msm_after_sort);
@@ -947,7 +965,7 @@ struct MsmRunner {
             // window sum = sum (j + 1) * bucket[j] = S_w + A_w
             std::vector<Point<C>> wsum(NW);
             for (uint32_t w = 0; w < NW; w++) wsum[w] = pt_add<C>(pt_load<C>(S.data() + PB * w), pt_load<C>(A.data() + PB * w));
-            result = fold_windows(wsum, pt_load<C>(A.data() + PB * (NW - 1)), cbits, W, fold_stride != 0);
+            result = fold_windows(wsum, pt_load<C>(A.data() + PB * (NW - 1)), cbits, W, fold_stride != 0, bits);
         }
         result = pt_unmap_result<C>(pt_to_affine<C>(result));
         pt_store<C>(out_host, result);
@@ -958,14 +976,14 @@ struct MsmRunner {
 // one translation unit per curve (they compile in parallel): the three entry points msm.hip dispatches to
 #define LW_MSM_INSTANTIATE(CURVE, SUFFIX)                                                                                        \
     int msm_run_##SUFFIX(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_points, size_t n, void *out, int affine, \
-                         hipEvent_t points_ready) {                                                                                \
+                         hipEvent_t points_ready, uint32_t scalar_limbs) {                                                         \
         if (affine && IsoOf<CURVE>::has) {   /* normalised rows live on the isomorphic model (msm_to_affine_kernel) */           \
             MsmRunner<typename IsoOf<CURVE>::type> ri{c, s, 0};                                                                    \
             ri.affine = true;                                                                                                      \
             ri.points_ready = points_ready;                                                                                        \
             ri.fold_c = c.msm_fold_c;                                                                                              \
             ri.fold_stride = c.msm_fold_stride;                                                                                    \
-            return ri.run(d_scalars, d_points, n, out);                                                                            \
+            return ri.run(d_scalars, d_points, n, out, scalar_limbs);                                                              \
         }                                                                                                                          \
         MsmRunner<CURVE> r{c, s, 0};                                                                                               \
         r.affine = affine != 0;                                                                                                    \
@@ -974,7 +992,7 @@ struct MsmRunner {
             r.fold_c = c.msm_fold_c;                                                                                               \
             r.fold_stride = c.msm_fold_stride;                                                                                     \
         }                                                                                                                          \
-        return r.run(d_scalars, d_points, n, out);                                                                                 \
+        return r.run(d_scalars, d_points, n, out, scalar_limbs);                                                                   \
     }                                                                                                                              \
     int msm_normalize_##SUFFIX(Context &c, hipStream_t s, const void *d_in, size_t n, void *d_out) {                               \
         MsmRunner<CURVE> r{c, s, 0};                                                                                               \

@@ -32,35 +32,54 @@ def msm_fr(curve, fr_elements, points):
     return out
 
 
-def msm(curve, cs, points):
-    """pippenger::msm(cs, points): cs = (n,4) uint64 canonical scalars (MS limb first), points = (n, 3*coord_words)
+def _scalar_rows(cs, scalar_limbs):
+    s = np.ascontiguousarray(cs, dtype=np.uint64)
+    if 1 <= scalar_limbs <= 8:
+        return s.reshape(-1, scalar_limbs)
+    return s.reshape(s.shape[0] if s.ndim > 1 else 1, -1)   # a width the library refuses (LW_ERR_BAD_ARG): rows as given
+
+
+def msm(curve, cs, points, scalar_limbs=4):
+    """pippenger::msm(cs, points): cs = (n, scalar_limbs) uint64 canonical scalars (MS limb first), points = (n, 3*coord_words)
     uint64 projective points.  Returns one projective point; only its affine image is canonical.
-    Different lengths -> LengthMismatch (pippenger.rs:25-27); empty input -> neutral element."""
-    s = np.ascontiguousarray(cs, dtype=np.uint64).reshape(-1, 4)
+    Different lengths -> LengthMismatch (pippenger.rs:25-27); empty input -> neutral element.
+    scalar_limbs: 1 .. 8, the NUM_LIMBS of the reference's UnsignedInteger<NUM_LIMBS> scalars (pippenger.rs:18-32); the
+    sum is over the full integers, not reduced mod r.  4 goes through lw_hip_msm, any other width through lw_hip_msm_limbs."""
+    s = _scalar_rows(cs, scalar_limbs)
     p = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, curve.point_words)
     out = np.zeros(curve.point_words, dtype=np.uint64)
-    check(L.lib().lw_hip_msm(curve.curve, s.ctypes.data_as(C.c_void_p), s.shape[0], p.ctypes.data_as(C.c_void_p),
-                             p.shape[0], out.ctypes.data_as(C.c_void_p)))
+    if scalar_limbs == 4:
+        check(L.lib().lw_hip_msm(curve.curve, s.ctypes.data_as(C.c_void_p), s.shape[0], p.ctypes.data_as(C.c_void_p),
+                                 p.shape[0], out.ctypes.data_as(C.c_void_p)))
+    else:
+        check(L.lib().lw_hip_msm_limbs(curve.curve, s.ctypes.data_as(C.c_void_p), scalar_limbs, s.shape[0],
+                                       p.ctypes.data_as(C.c_void_p), p.shape[0], out.ctypes.data_as(C.c_void_p)))
     return out
 
 
-def msm_with(curve, cs, points, window_size):
+def msm_with(curve, cs, points, window_size, scalar_limbs=4):
     """pippenger::msm_with (math/src/msm/pippenger.rs:42-103).  The window only shapes the reference's schedule;
     the group element is the same for every window, so this is msm() (the device picks its own window)."""
-    if len(np.asarray(cs).reshape(-1, 4)) != len(np.asarray(points).reshape(-1, curve.point_words)):
+    if len(_scalar_rows(cs, scalar_limbs)) != len(np.asarray(points).reshape(-1, curve.point_words)):
         from .errors import LengthMismatch
         raise LengthMismatch("scalars and points have different lengths")
-    return msm(curve, cs, points)
+    return msm(curve, cs, points, scalar_limbs=scalar_limbs)
 
 
-def msm_device(curve, t_scalars, t_points, n, stream=None):
-    """Device-resident MSM on torch tensors; returns the projective result as a numpy array."""
+def msm_device(curve, t_scalars, t_points, n, stream=None, scalar_limbs=4):
+    """Device-resident MSM on torch tensors; returns the projective result as a numpy array.  t_scalars holds
+    n x scalar_limbs u64 (see msm())."""
     import torch
     if stream is None:
         stream = torch.cuda.current_stream().cuda_stream
     out = np.zeros(curve.point_words, dtype=np.uint64)
-    check(L.lib().lw_hip_msm_device(curve.curve, C.c_void_p(t_scalars.data_ptr()), C.c_void_p(t_points.data_ptr()), n,
-                                    out.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
+    if scalar_limbs == 4:
+        check(L.lib().lw_hip_msm_device(curve.curve, C.c_void_p(t_scalars.data_ptr()), C.c_void_p(t_points.data_ptr()), n,
+                                        out.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
+    else:
+        check(L.lib().lw_hip_msm_limbs_device(curve.curve, C.c_void_p(t_scalars.data_ptr()), scalar_limbs,
+                                              C.c_void_p(t_points.data_ptr()), n, out.ctypes.data_as(C.c_void_p),
+                                              C.c_void_p(stream)))
     return out
 
 

@@ -177,6 +177,10 @@ extern "C" {
                          out_point: *mut c_void) -> c_int;
     pub fn lw_hip_msm_fr_device(curve: Curve, d_fr_elements: *const u64, d_points: *const c_void, n: usize,
                                 out_point_host: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_hip_msm_limbs(curve: Curve, scalars: *const u64, scalar_limbs: u32, n_scalars: usize, points: *const c_void,
+                            n_points: usize, out_point: *mut c_void) -> c_int;
+    pub fn lw_hip_msm_limbs_device(curve: Curve, d_scalars: *const u64, scalar_limbs: u32, d_points: *const c_void, n: usize,
+                                   out_point_host: *mut c_void, hip_stream: *mut c_void) -> c_int;
     pub fn lw_hip_ec_add_outer_device(curve: Curve, d_rows: *const c_void, m: usize, d_cols: *const c_void, k: usize,
                                       d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
     pub fn lw_hip_srs_create(curve: Curve, points: *const c_void, n_points: usize, out_srs: *mut *mut lw_srs_t) -> c_int;

@@ -202,6 +202,27 @@ pub fn msm<P: Copy>(curve: Curve, scalars: &[[u64; 4]], points: &[P]) -> Result<
     Ok(unsafe { out.assume_init() })
 }
 
+/// [`msm`] for scalars of `L` limbs, 1 <= L <= 8 — `UnsignedInteger<L>` as it sits in memory, most significant limb first
+/// (math/src/msm/pippenger.rs:18-32 is generic over the width).  The sum is over the full integers, not reduced mod r.
+/// `L == 4` is exactly [`msm`].
+pub fn msm_limbs<P: Copy, const L: usize>(curve: Curve, scalars: &[[u64; L]], points: &[P]) -> Result<P, HipError> {
+    if size_of::<P>() != curve_point_bytes(curve) {
+        return Err(HipError::BadArgument(format!("point type is {} bytes, the backend expects {}", size_of::<P>(), curve_point_bytes(curve))));
+    }
+    if !(1..=8).contains(&L) {
+        return Err(HipError::BadArgument(format!("scalars of {L} limbs: 1 ..= 8 supported")));
+    }
+    let mut out = core::mem::MaybeUninit::<P>::uninit();
+    // SAFETY: as in `msm`; [u64; L] rows are 8 L bytes with no padding, which is the layout lw_hip_msm_limbs reads.
+    let rc = unsafe {
+        ffi::lw_hip_msm_limbs(curve, scalars.as_ptr() as *const u64, L as u32, scalars.len(), points.as_ptr() as *const c_void, points.len(),
+                              out.as_mut_ptr() as *mut c_void)
+    };
+    check(rc)?;
+    // SAFETY: initialised by the successful call.
+    Ok(unsafe { out.assume_init() })
+}
+
 /// Same with the scalars given as stored `FrElement`s (Montgomery form): the `.representative()` loop every reference
 /// caller runs on the CPU first (provers/groth16/src/prover.rs:69-78) happens on the device.
 pub fn msm_fr<P: Copy>(curve: Curve, fr_elements: &[[u64; 4]], points: &[P]) -> Result<P, HipError> {
