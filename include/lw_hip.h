@@ -374,6 +374,44 @@ int lw_hip_msm_srs_fr(const lw_srs_t *srs, const uint64_t *fr_elements, size_t n
 int lw_hip_msm_srs_fr_device(const lw_srs_t *srs, const uint64_t *d_fr_elements, size_t n_scalars, void *out_point_host,
                              void *hip_stream);
 
+/* ---- polynomial evaluation and Ruffini division; KZG openings ----
+ * Elements are 4 x u64, MS limb first, in Montgomery form, exactly as FieldElement sits in memory: the coefficients, the
+ * points, x, upsilon and every returned value.  Inputs are canonical residues (< p).  field: LW_FIELD_STARK252 or
+ * LW_FIELD_BLS12_381_FR (4-limb layout); anything else is LW_ERR_BAD_ARG.  Device buffers are 16-byte aligned.  Every
+ * argument is checked before any device work.  Points, x and upsilon are host memory in the _device forms too.
+ *
+ * Polynomial::evaluate (math/src/polynomial/mod.rs:98-109) of K polynomials at M points:
+ * out_values[k * m + j] = polys[k](points[j]).  Polynomial k has lens[k] coefficients (0 gives the value 0). */
+int lw_poly_evaluate(lw_field_t field, const void *const *polys, const size_t *lens, uint32_t k, const void *points, uint32_t m,
+                     void *out_values);
+int lw_poly_evaluate_device(lw_field_t field, const void *const *d_polys, const size_t *lens, uint32_t k, const void *points,
+                            uint32_t m, void *out_values_host, void *hip_stream);
+/* Polynomial::ruffini_division_inplace (mod.rs:157-164) by (X - x): a quotient of n - 1 elements (none for n <= 1) and the
+ * remainder p(x) that the reference pops (n = 0: 0; n = 1: a_0).  The _device form writes d_out_quotient (which must not
+ * overlap d_coeffs: LW_ERR_BAD_ARG) and synchronises only when the remainder is asked for. */
+int lw_poly_ruffini_division(lw_field_t field, const void *coeffs, size_t n, const void *x, void *out_quotient,
+                             void *out_remainder_or_null);
+int lw_poly_ruffini_division_device(lw_field_t field, const void *d_coeffs, size_t n, const void *x, void *d_out_quotient,
+                                    void *out_remainder_host_or_null, void *hip_stream);
+/* KateZaveruchaGoldberg::open / open_batch (crypto/src/commitments/kzg.rs:171-180, 206-226) against an SRS handle.  The
+ * scalar field is the SRS curve's: BLS12-381 -> Fr381, BN254 -> Fr254.  out_proof is one projective point of the curve
+ * (lw_hip_msm's output form).
+ * There is no y argument: open(x, y, p) commits the quotient of (p - y) by (X - x), and y changes only coefficient 0,
+ * which no quotient coefficient reads (the remainder is popped).  When p - y strips to the zero polynomial the quotient
+ * is empty and the proof is the neutral element either way.
+ * n <= 1 coefficients give the neutral element.  out_eval: p(x).  open_batch folds sum_k upsilon^k p_k while the division
+ * loads the coefficients (the combined polynomial is never stored) and opens it; the polynomials may differ in length
+ * and k has no fixed cap; out_evals[k] are the K individual values p_k(x), not the folded remainder.  upsilon may be
+ * null when k <= 1.  A quotient (longest n - 1) longer than the SRS is LW_ERR_LENGTH_MISMATCH (the reference panics
+ * slicing srs[..len]).  Host results synchronise before returning. */
+int lw_kzg_open(const lw_srs_t *srs, const uint64_t *coeffs, size_t n, const uint64_t *x, void *out_proof, uint64_t *out_eval_or_null);
+int lw_kzg_open_device(const lw_srs_t *srs, const uint64_t *d_coeffs, size_t n, const uint64_t *x, void *out_proof_host,
+                       uint64_t *out_eval_host_or_null, void *hip_stream);
+int lw_kzg_open_batch(const lw_srs_t *srs, const uint64_t *const *polys, const size_t *lens, uint32_t k, const uint64_t *x,
+                      const uint64_t *upsilon, void *out_proof, uint64_t *out_evals_or_null);
+int lw_kzg_open_batch_device(const lw_srs_t *srs, const uint64_t *const *d_polys, const size_t *lens, uint32_t k, const uint64_t *x,
+                             const uint64_t *upsilon, void *out_proof_host, uint64_t *out_evals_host_or_null, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,8 @@ EXPORTS = [
     "lw_hip_comm_unique_id", "lw_hip_comm_init", "lw_hip_comm_shutdown", "lw_hip_comm_info",
     "lw_hip_ntt_sharded_device", "lw_hip_ntt_sharded_selftest_device", "lw_hip_ntt_sharded_selftest_steps_device",
     "lw_hip_msm_sharded_device", "lw_hip_msm_sharded_selftest_device",
+    "lw_poly_evaluate", "lw_poly_evaluate_device", "lw_poly_ruffini_division", "lw_poly_ruffini_division_device",
+    "lw_kzg_open", "lw_kzg_open_device", "lw_kzg_open_batch", "lw_kzg_open_batch_device",
 ]
 
 
@@ -162,6 +164,22 @@ def lib():
     L.lw_hip_msm_sharded_device.restype = i
     L.lw_hip_msm_sharded_selftest_device.argtypes = [i, vp, vp, sz, u32, vp, vp]
     L.lw_hip_msm_sharded_selftest_device.restype = i
+    L.lw_poly_evaluate.argtypes = [i, vp, vp, u32, vp, u32, vp]
+    L.lw_poly_evaluate.restype = i
+    L.lw_poly_evaluate_device.argtypes = [i, vp, vp, u32, vp, u32, vp, vp]
+    L.lw_poly_evaluate_device.restype = i
+    L.lw_poly_ruffini_division.argtypes = [i, vp, sz, vp, vp, vp]
+    L.lw_poly_ruffini_division.restype = i
+    L.lw_poly_ruffini_division_device.argtypes = [i, vp, sz, vp, vp, vp, vp]
+    L.lw_poly_ruffini_division_device.restype = i
+    L.lw_kzg_open.argtypes = [vp, vp, sz, vp, vp, vp]
+    L.lw_kzg_open.restype = i
+    L.lw_kzg_open_device.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+    L.lw_kzg_open_device.restype = i
+    L.lw_kzg_open_batch.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp]
+    L.lw_kzg_open_batch.restype = i
+    L.lw_kzg_open_batch_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp]
+    L.lw_kzg_open_batch_device.restype = i
     _lib = L
     return L
 

@@ -182,6 +182,8 @@ void Context::release_all() {
     host_io_a.release();
     host_io_b.release();
     pipe_tmp.release();
+    poly_ws.release();
+    poly_q.release();
     timings.twiddle_bytes = timings.scratch_bytes = 0;
 }
 
@@ -1287,6 +1289,29 @@ int lw_hip_srs_destroy(lw_srs_t *srs) {
     delete srs;
     return LW_OK;
 }
+}  // extern "C"
+namespace lw {
+size_t srs_len(const lw_srs_t *srs) { return srs->n; }
+lw_curve_t srs_curve(const lw_srs_t *srs) { return srs->curve; }
+// The MSM against the first n points of an SRS, under an Entry the caller already holds (lw_hip_msm_srs*, and the KZG
+// openings in poly.hip, which commit their quotient with it).
+int msm_srs_locked(Context &c, const lw_srs_t *srs, const uint64_t *d_scalars, size_t n, void *out_point, hipStream_t stream, int mont) {
+    auto t0 = std::chrono::steady_clock::now();
+    // the shifted copies serve calls that use a good part of the set (KZG commits of shorter polynomials take a prefix:
+    // below a quarter of it the 2^19 shared buckets would be mostly empty and the plain schedule on copy 0 is faster)
+    if (srs->fold_c && n >= srs->n / 4) {
+        c.msm_fold_c = srs->fold_c;
+        c.msm_fold_stride = srs->n;
+    }
+    int rc = msm_device(c, srs->curve, d_scalars, srs->pts.p, n, out_point, stream, mont, 1);
+    c.msm_fold_c = 0;
+    c.msm_fold_stride = 0;
+    c.timings.last_msm_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c.timings.msm_calls++;
+    return rc;
+}
+}  // namespace lw
+extern "C" {
 static int msm_srs_entry(const lw_srs_t *srs, const uint64_t *scalars, size_t n, void *out_point, hipStream_t stream, int host_scalars,
                          int mont) {
     if (!srs || !out_point) { set_error("null SRS or output"); return LW_ERR_BAD_ARG; }
@@ -1298,8 +1323,6 @@ static int msm_srs_entry(const lw_srs_t *srs, const uint64_t *scalars, size_t n,
     Entry en((void *)stream);
     if (en.rc) return en.rc;
     Context &c = en.c;
-    int rc = LW_OK;
-    auto t0 = std::chrono::steady_clock::now();
     const uint64_t *d_scalars = scalars;
     if (host_scalars) {   // host-buffer form: on the lane's own stream
         stream = en.use_lane_stream();
@@ -1310,18 +1333,7 @@ static int msm_srs_entry(const lw_srs_t *srs, const uint64_t *scalars, size_t n,
         LW_HIP_CHECK(hipMemcpyAsync(c.host_io_a.p, scalars, n * 32, hipMemcpyHostToDevice, stream), LW_ERR_LAUNCH);
         d_scalars = (const uint64_t *)c.host_io_a.p;
     }
-    // the shifted copies serve calls that use a good part of the set (KZG commits of shorter polynomials take a prefix:
-    // below a quarter of it the 2^19 shared buckets would be mostly empty and the plain schedule on copy 0 is faster)
-    if (srs->fold_c && n >= srs->n / 4) {
-        c.msm_fold_c = srs->fold_c;
-        c.msm_fold_stride = srs->n;
-    }
-    rc = msm_device(c, srs->curve, d_scalars, srs->pts.p, n, out_point, stream, mont, 1);
-    c.msm_fold_c = 0;
-    c.msm_fold_stride = 0;
-    c.timings.last_msm_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c.timings.msm_calls++;
-    return rc;
+    return msm_srs_locked(c, srs, d_scalars, n, out_point, stream, mont);
 }
 int lw_hip_msm_srs(const lw_srs_t *srs, const uint64_t *scalars, size_t n_scalars, void *out_point) {
     return msm_srs_entry(srs, scalars, n_scalars, out_point, 0, 1, 0);

@@ -122,6 +122,8 @@ struct Context {
     DeviceBuf host_io_a, host_io_b;   // device staging for the host-buffer entry points
     hipStream_t io_stream = nullptr;  // ... and the stream they run on
     DeviceBuf pipe_tmp;               // intermediates of the device-resident pipelines (FRI layer evaluation, Groth16 cosets)
+    DeviceBuf poly_ws;                // polynomial evaluation / division: tile sums, carries, totals (poly.hip)
+    DeviceBuf poly_q;                 // the quotient a KZG opening commits (canonical scalars for the SRS MSM)
     lw_timings_t timings = {};
     // Cross-stream ordering of the context-owned buffers (scratch, tables, staging, MSM workspace): every entry point
     // records `order_event` on its launch stream when it returns; a call arriving on a different stream first makes

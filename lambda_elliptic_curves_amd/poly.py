@@ -1,0 +1,70 @@
+"""Polynomial::evaluate and Polynomial::ruffini_division_inplace (math/src/polynomial/mod.rs:98-109, 157-164) on the
+device, over Stark252 and BLS12-381 Fr.  Elements are (n, 4) uint64 arrays in the reference's memory form (Montgomery,
+MS limb first); points and x are host values in every form."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from .errors import check
+
+
+def _elems(a):
+    return np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
+
+
+def _one(x):
+    return np.ascontiguousarray(x, dtype=np.uint64).reshape(-1)[:4].copy()
+
+
+def _stream(stream):
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    return C.c_void_p(stream)
+
+
+def evaluate(field, polys, points):
+    """(K, M, 4) table: [k, j] = polys[k](points[j]).  polys: a list of coefficient arrays of any lengths (0 included)."""
+    ps = [_elems(p) for p in polys]
+    pts = _elems(points) if len(points) else np.zeros((0, 4), np.uint64)
+    out = np.zeros((len(ps), pts.shape[0], 4), np.uint64)
+    ptrs = (C.c_void_p * max(1, len(ps)))(*[p.ctypes.data for p in ps])
+    lens = (C.c_size_t * max(1, len(ps)))(*[p.shape[0] for p in ps])
+    check(L.lib().lw_poly_evaluate(field.field, ptrs, lens, len(ps), pts.ctypes.data_as(C.c_void_p), pts.shape[0],
+                                   out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def evaluate_device(field, t_polys, lens, points, stream=None):
+    """evaluate() on device-resident torch tensors; t_polys[k] holds at least lens[k] elements."""
+    pts = _elems(points) if len(points) else np.zeros((0, 4), np.uint64)
+    out = np.zeros((len(t_polys), pts.shape[0], 4), np.uint64)
+    ptrs = (C.c_void_p * max(1, len(t_polys)))(*[t.data_ptr() for t in t_polys])
+    ln = (C.c_size_t * max(1, len(t_polys)))(*[int(n) for n in lens])
+    check(L.lib().lw_poly_evaluate_device(field.field, ptrs, ln, len(t_polys), pts.ctypes.data_as(C.c_void_p), pts.shape[0],
+                                          out.ctypes.data_as(C.c_void_p), _stream(stream)))
+    return out
+
+
+def ruffini_division(field, coeffs, x):
+    """-> (quotient (n - 1, 4), remainder p(x) (4,)); n = 0 and n = 1 give an empty quotient."""
+    a = _elems(coeffs)
+    n = a.shape[0]
+    q = np.zeros((max(0, n - 1), 4), np.uint64)
+    rem = np.zeros(4, np.uint64)
+    xv = _one(x)
+    check(L.lib().lw_poly_ruffini_division(field.field, a.ctypes.data_as(C.c_void_p), n, xv.ctypes.data_as(C.c_void_p),
+                                           q.ctypes.data_as(C.c_void_p), rem.ctypes.data_as(C.c_void_p)))
+    return q, rem
+
+
+def ruffini_division_device(field, t_coeffs, n, x, t_quotient, stream=None, remainder=True):
+    """Quotient of the first n elements of t_coeffs into t_quotient (n - 1 elements, not overlapping t_coeffs); returns
+    the remainder, or None without a synchronisation when remainder=False."""
+    rem = np.zeros(4, np.uint64)
+    xv = _one(x)
+    check(L.lib().lw_poly_ruffini_division_device(field.field, C.c_void_p(t_coeffs.data_ptr()), n, xv.ctypes.data_as(C.c_void_p),
+                                                  C.c_void_p(t_quotient.data_ptr()),
+                                                  rem.ctypes.data_as(C.c_void_p) if remainder else None, _stream(stream)))
+    return rem if remainder else None

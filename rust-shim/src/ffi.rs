@@ -193,6 +193,25 @@ extern "C" {
     pub fn lw_hip_msm_srs_fr(srs: *const lw_srs_t, fr_elements: *const u64, n_scalars: usize, out_point: *mut c_void) -> c_int;
     pub fn lw_hip_msm_srs_fr_device(srs: *const lw_srs_t, d_fr_elements: *const u64, n_scalars: usize, out_point_host: *mut c_void,
                                     hip_stream: *mut c_void) -> c_int;
+    // ---- polynomial evaluation / Ruffini division; KZG openings (4 x u64 Montgomery elements; points, x, upsilon on the host)
+    pub fn lw_poly_evaluate(field: Field, polys: *const *const c_void, lens: *const usize, k: u32, points: *const c_void, m: u32,
+                            out_values: *mut c_void) -> c_int;
+    pub fn lw_poly_evaluate_device(field: Field, d_polys: *const *const c_void, lens: *const usize, k: u32, points: *const c_void,
+                                   m: u32, out_values_host: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_poly_ruffini_division(field: Field, coeffs: *const c_void, n: usize, x: *const c_void, out_quotient: *mut c_void,
+                                    out_remainder_or_null: *mut c_void) -> c_int;
+    pub fn lw_poly_ruffini_division_device(field: Field, d_coeffs: *const c_void, n: usize, x: *const c_void,
+                                           d_out_quotient: *mut c_void, out_remainder_host_or_null: *mut c_void,
+                                           hip_stream: *mut c_void) -> c_int;
+    pub fn lw_kzg_open(srs: *const lw_srs_t, coeffs: *const u64, n: usize, x: *const u64, out_proof: *mut c_void,
+                       out_eval_or_null: *mut u64) -> c_int;
+    pub fn lw_kzg_open_device(srs: *const lw_srs_t, d_coeffs: *const u64, n: usize, x: *const u64, out_proof_host: *mut c_void,
+                              out_eval_host_or_null: *mut u64, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_kzg_open_batch(srs: *const lw_srs_t, polys: *const *const u64, lens: *const usize, k: u32, x: *const u64,
+                             upsilon: *const u64, out_proof: *mut c_void, out_evals_or_null: *mut u64) -> c_int;
+    pub fn lw_kzg_open_batch_device(srs: *const lw_srs_t, d_polys: *const *const u64, lens: *const usize, k: u32, x: *const u64,
+                                    upsilon: *const u64, out_proof_host: *mut c_void, out_evals_host_or_null: *mut u64,
+                                    hip_stream: *mut c_void) -> c_int;
 }
 
 // The C structs above must keep the sizes the header gives them.

@@ -283,6 +283,74 @@ impl Srs {
         // SAFETY: initialised by the successful call.
         Ok(unsafe { out.assume_init() })
     }
+
+    /// `KateZaveruchaGoldberg::open(x, y, p)` (crypto/src/commitments/kzg.rs:171-180) with `p` as stored
+    /// `FieldElement`s (Montgomery form); returns the proof and p(x).  `y` does not enter: it changes only coefficient 0,
+    /// which the quotient does not read (include/lw_hip.h).  The SRS curve fixes the scalar field.
+    pub fn open<P: Copy>(&self, coeffs: &[[u64; 4]], x: &[u64; 4]) -> Result<(P, [u64; 4]), HipError> {
+        if size_of::<P>() != curve_point_bytes(self.curve) {
+            return Err(HipError::BadArgument("point type has the wrong size".into()));
+        }
+        let mut out = core::mem::MaybeUninit::<P>::uninit();
+        let mut eval = [0u64; 4];
+        // SAFETY: the handle is live until drop; one point and one element are written on success.
+        let rc = unsafe {
+            ffi::lw_kzg_open(self.handle, coeffs.as_ptr() as *const u64, coeffs.len(), x.as_ptr(), out.as_mut_ptr() as *mut c_void,
+                             eval.as_mut_ptr())
+        };
+        check(rc)?;
+        // SAFETY: initialised by the successful call.
+        Ok((unsafe { out.assume_init() }, eval))
+    }
+
+    /// `KateZaveruchaGoldberg::open_batch(x, ys, polynomials, upsilon)` (kzg.rs:206-226); returns the proof and the
+    /// individual values p_k(x) (the `ys` a prover passes in).
+    pub fn open_batch<P: Copy>(&self, polys: &[&[[u64; 4]]], x: &[u64; 4], upsilon: &[u64; 4]) -> Result<(P, Vec<[u64; 4]>), HipError> {
+        if size_of::<P>() != curve_point_bytes(self.curve) {
+            return Err(HipError::BadArgument("point type has the wrong size".into()));
+        }
+        let ptrs: Vec<*const u64> = polys.iter().map(|p| p.as_ptr() as *const u64).collect();
+        let lens: Vec<usize> = polys.iter().map(|p| p.len()).collect();
+        let mut evals = vec![[0u64; 4]; polys.len()];
+        let mut out = core::mem::MaybeUninit::<P>::uninit();
+        // SAFETY: every pointer is valid for its length; the handle is live; k points' worth of values are written.
+        let rc = unsafe {
+            ffi::lw_kzg_open_batch(self.handle, ptrs.as_ptr(), lens.as_ptr(), polys.len() as u32, x.as_ptr(), upsilon.as_ptr(),
+                                   out.as_mut_ptr() as *mut c_void, evals.as_mut_ptr() as *mut u64)
+        };
+        check(rc)?;
+        // SAFETY: initialised by the successful call.
+        Ok((unsafe { out.assume_init() }, evals))
+    }
+}
+
+/// `Polynomial::evaluate` (math/src/polynomial/mod.rs:98-109) of every polynomial at every point:
+/// `out[k * points.len() + j] = polys[k](points[j])`.  `field`: Stark252 or BLS12-381 Fr (4 x u64 Montgomery elements).
+pub fn poly_evaluate(field: Field, polys: &[&[[u64; 4]]], points: &[[u64; 4]]) -> Result<Vec<[u64; 4]>, HipError> {
+    let ptrs: Vec<*const c_void> = polys.iter().map(|p| p.as_ptr() as *const c_void).collect();
+    let lens: Vec<usize> = polys.iter().map(|p| p.len()).collect();
+    let mut out = vec![[0u64; 4]; polys.len() * points.len()];
+    // SAFETY: every pointer is valid for its length; `out` holds k x m elements.
+    let rc = unsafe {
+        ffi::lw_poly_evaluate(field, ptrs.as_ptr(), lens.as_ptr(), polys.len() as u32, points.as_ptr() as *const c_void,
+                              points.len() as u32, out.as_mut_ptr() as *mut c_void)
+    };
+    check(rc)?;
+    Ok(out)
+}
+
+/// `Polynomial::ruffini_division_inplace(x)` (mod.rs:157-164): the quotient (n - 1 coefficients) and the remainder
+/// p(x) that the reference pops.
+pub fn ruffini_division(field: Field, coeffs: &[[u64; 4]], x: &[u64; 4]) -> Result<(Vec<[u64; 4]>, [u64; 4]), HipError> {
+    let mut q = vec![[0u64; 4]; coeffs.len().saturating_sub(1)];
+    let mut rem = [0u64; 4];
+    // SAFETY: `coeffs` is valid for its length, `q` for n - 1 elements, `rem` for one.
+    let rc = unsafe {
+        ffi::lw_poly_ruffini_division(field, coeffs.as_ptr() as *const c_void, coeffs.len(), x.as_ptr() as *const c_void,
+                                      q.as_mut_ptr() as *mut c_void, rem.as_mut_ptr() as *mut c_void)
+    };
+    check(rc)?;
+    Ok((q, rem))
 }
 
 impl Drop for Srs {
