@@ -9,8 +9,8 @@
 #include <new>
 #include <thread>
 #include <vector>
-#include "context.h"
 #include "field.cuh"
+#include "internal.h"
 
 namespace lw {
 
@@ -80,11 +80,7 @@ const char *tuning_env(const char *name) {
     return on ? getenv(name) : nullptr;
 }
 
-void ntt_set_max_pass_stages(uint32_t r);
-void ntt_set_debug(uint32_t d);
-
 void host_pool_release_all();
-void comm_release(Context &c);   // comm.hip
 // every cached device object of every lane and the shared tables (shutdown / device change); SharedState::rw held unique
 static void release_everything() {
     (void)hipDeviceSynchronize();
@@ -264,42 +260,6 @@ int ensure_init() {
     return init_locked(nullptr, 0);
 }
 
-// defined in ntt256.hip / ntt_bb.hip / msm.hip
-int ntt256_device(Context &c, int field, lw_dir_t dir, const void *d_in, void *d_out, uint32_t log2n, uint32_t batch,
-                  uint64_t stride, const uint32_t *coset_words, hipStream_t stream, uint32_t in_log2);
-int ntt_bb_device(Context &c, lw_layout_t layout, lw_dir_t dir, const void *d_in, void *d_out, uint32_t log2n,
-                  uint32_t batch, uint64_t stride, const void *coset_offset, hipStream_t stream, uint32_t in_log2);
-int broadcast_device(size_t elem_bytes, const void *d_in, void *d_out, uint64_t n, uint32_t batch, uint64_t out_stride, hipStream_t stream);
-int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const void *d_points, size_t n, void *out_host,
-               hipStream_t stream, int scalars_montgomery, int affine_points, const void *h_points = nullptr,
-               uint32_t scalar_limbs = 4);
-int msm_normalize_device(Context &c, lw_curve_t curve, const void *d_in, size_t n, void *d_out, hipStream_t stream);
-size_t msm_affine_bytes(lw_curve_t curve, size_t n);
-int msm_fold_build(Context &c, lw_curve_t curve, void *d_rows, size_t n, uint32_t cbits, hipStream_t stream);
-int ec_add_outer_device(Context &c, lw_curve_t curve, const void *d_rows, uint32_t m, const void *d_cols, uint32_t k, void *d_out,
-                        hipStream_t stream);
-int ntt_cross_device(Context &c, lw_field_t field, lw_layout_t layout, lw_dir_t dir, const void *d_in, void *d_out,
-                     uint32_t log2_total, uint32_t log2_g, uint64_t j2_begin, uint64_t slice_len, uint64_t chunk_stride,
-                     uint32_t batch, uint64_t batch_stride, hipStream_t stream);
-int ntt_device_locked(Context &c, lw_field_t field, lw_layout_t layout, lw_dir_t dir, const void *d_in, void *d_out,
-                      uint32_t log2n, uint32_t batch, size_t stride, const void *coset, hipStream_t stream,
-                      uint32_t in_log2 = 0xffffffffu);
-int merkle_commit_device(Context &c, const void *d_cols, uint32_t n_cols, uint64_t col_stride, uint32_t log2n, int bit_reverse,
-                         void *d_nodes, hipStream_t stream, uint32_t elem_bytes = 32);
-int fri_layer_device(Context &c, lw_field_t field, const void *d_coeffs, uint64_t n, const uint32_t *d_zeta, const void *offset_ref,
-                     uint32_t log2_domain, void *d_poly, uint32_t log2_block, void *d_eval, void *d_eval_br, void *d_nodes,
-                     hipStream_t stream);
-int groth16_h_device(Context &c, const void *d_l, const void *d_r, const void *d_o, uint32_t log2_gates, void *d_out, void *d_tmp,
-                     hipStream_t stream);
-int stripped_length_device(const void *d_elems, uint64_t n, uint64_t *d_len, hipStream_t stream);
-
-int ntt256_gen_powers(int field, uint32_t order, uint64_t count, uint32_t bitrev, bool inverse, const uint32_t *scale_words, void *d_out,
-                      hipStream_t stream);
-int ntt_bb_gen_powers(lw_layout_t layout, uint32_t order, uint64_t count, uint32_t bitrev, bool inverse, const void *scale, void *d_out,
-                      hipStream_t stream);
-int gen_twiddles_device(Context &c, lw_field_t field, lw_layout_t layout, uint32_t order, int config, void *d_out, hipStream_t stream);
-int bitrev_device(size_t elem_bytes, const void *d_in, void *d_out, uint32_t log2n, hipStream_t stream);
-
 uint32_t field_two_adicity(lw_field_t f) {
     switch (f) {
         case LW_FIELD_STARK252: return Stark252::TWO_ADICITY;
@@ -326,9 +286,53 @@ static void words_from_ref(const void *ref, uint32_t *w) {
     for (int k = 0; k < 8; k++) w[k] = m[2 * (3 - k / 2) + (k & 1)];
 }
 
-// in_log2 < log2n (forward only): low-degree extension of dense blocks of 2^in_log2 coefficients, see ntt256.hip / ntt_bb.hip
-int ntt_device_locked(Context &c, lw_field_t field, lw_layout_t layout, lw_dir_t dir, const void *d_in, void *d_out,
-                      uint32_t log2n, uint32_t batch, size_t stride, const void *coset, hipStream_t stream, uint32_t in_log2) {
+// ---- argument checks and bookkeeping shared by the entry points
+// smallest x with 2^x >= n
+static uint32_t ceil_log2(uint64_t n) {
+    uint32_t x = 0;
+    while (((uint64_t)1 << x) < n) x++;
+    return x;
+}
+// a power of two, at least `min` (ops::fft rejects anything else, math/src/fft/cpu/ops.rs:17-19)
+static int check_pow2(size_t n, size_t min) {
+    if (n >= min && (n & (n - 1)) == 0) return LW_OK;
+    set_error("Input length is %zu, which is not a power of two", n);
+    return LW_ERR_INPUT_NOT_POW2;
+}
+static int check_root(lw_field_t field, uint64_t log2n) {
+    if (log2n <= field_two_adicity(field)) return LW_OK;   // traits.rs:88-90
+    set_error("no primitive 2^%llu-th root of unity in this field", (unsigned long long)log2n);
+    return LW_ERR_ROOT_OF_UNITY;
+}
+// Polynomial::new strips trailing zero coefficients (math/src/polynomial/mod.rs:19-31): the length that is left
+static size_t stripped_len(const void *elems, size_t n, size_t eb) {
+    const unsigned char *p = (const unsigned char *)elems;
+    for (; n > 0; n--)
+        for (size_t i = 0; i < eb; i++)
+            if (p[(n - 1) * eb + i]) return n;
+    return 0;
+}
+// device -> host on s, complete on return
+static int download(void *dst, const void *src, size_t bytes, hipStream_t s) {
+    LW_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s), LW_ERR_LAUNCH);
+    LW_HIP_CHECK(hipStreamSynchronize(s), LW_ERR_LAUNCH);
+    return LW_OK;
+}
+// the lane's call statistics (lw_hip_get_timings)
+using Clock = std::chrono::steady_clock;
+static double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+static void note_ntt(Context &c, Clock::time_point t0) {
+    c.timings.last_ntt_ms = ms_since(t0);
+    c.timings.ntt_calls++;
+}
+static void note_msm(Context &c, Clock::time_point t0) {
+    c.timings.last_msm_ms = ms_since(t0);
+    c.timings.msm_calls++;
+}
+
+// The checks of every NTT form, before any device work (ntt_device_locked repeats them for its internal callers)
+static int ntt_check(lw_field_t field, lw_layout_t layout, lw_dir_t dir, uint32_t log2n, uint32_t batch, size_t stride,
+                     const void *in, const void *out) {
     int rc = check_field_layout(field, layout);
     if (rc) return rc;
     if (dir != LW_DIR_FORWARD && dir != LW_DIR_INVERSE) {
@@ -339,10 +343,8 @@ int ntt_device_locked(Context &c, lw_field_t field, lw_layout_t layout, lw_dir_t
         set_error("order %u > 63", log2n);
         return LW_ERR_ORDER_TOO_LARGE;
     }
-    if (log2n > field_two_adicity(field)) {   // traits.rs:88-90
-        set_error("no primitive 2^%u-th root of unity in this field", log2n);
-        return LW_ERR_ROOT_OF_UNITY;
-    }
+    rc = check_root(field, log2n);
+    if (rc) return rc;
     if (log2n > 34) {
         set_error("2^%u elements exceed device memory", log2n);
         return LW_ERR_ALLOC;
@@ -352,10 +354,17 @@ int ntt_device_locked(Context &c, lw_field_t field, lw_layout_t layout, lw_dir_t
         set_error("batch stride %zu < transform length", stride);
         return LW_ERR_BAD_ARG;
     }
-    if (!d_in || !d_out) {
+    if (!in || !out) {
         set_error("null buffer");
         return LW_ERR_BAD_ARG;
     }
+    return LW_OK;
+}
+
+int ntt_device_locked(Context &c, lw_field_t field, lw_layout_t layout, lw_dir_t dir, const void *d_in, void *d_out,
+                      uint32_t log2n, uint32_t batch, size_t stride, const void *coset, hipStream_t stream, uint32_t in_log2) {
+    int rc = ntt_check(field, layout, dir, log2n, batch, stride, d_in, d_out);
+    if (rc || batch == 0) return rc;
     if (in_log2 > log2n) in_log2 = log2n;
     if (in_log2 < log2n && (dir != LW_DIR_FORWARD || d_in == d_out)) {
         set_error("low-degree extension needs the forward direction and distinct buffers");
@@ -481,8 +490,6 @@ struct Prefault {
 }  // namespace lw
 
 using namespace lw;
-
-static bool elem_is_zero(const unsigned char *p, size_t eb);
 
 extern "C" {
 
@@ -657,15 +664,13 @@ int lw_hip_result_release(void *ptr) {
 
 int lw_hip_ntt_device(lw_field_t field, lw_layout_t layout, lw_dir_t dir, const void *d_in, void *d_out, uint32_t log2n,
                       uint32_t batch, size_t batch_stride_elems, const void *coset_offset_or_null, void *hip_stream) {
+    int rc = ntt_check(field, layout, dir, log2n, batch, batch_stride_elems, d_in, d_out);
+    if (rc) return rc;
     Entry en(hip_stream);
     if (en.rc) return en.rc;
-    Context &c = en.c;
-    int rc = LW_OK;
-    auto t0 = std::chrono::steady_clock::now();
-    rc = ntt_device_locked(c, field, layout, dir, d_in, d_out, log2n, batch, batch_stride_elems, coset_offset_or_null,
-                           (hipStream_t)hip_stream);
-    c.timings.last_ntt_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c.timings.ntt_calls++;
+    const auto t0 = Clock::now();
+    rc = ntt_device_locked(en.c, field, layout, dir, d_in, d_out, log2n, batch, batch_stride_elems, coset_offset_or_null, en.stream);
+    note_ntt(en.c, t0);
     return rc;
 }
 
@@ -675,20 +680,22 @@ int lw_hip_gen_twiddles(lw_field_t field, lw_layout_t layout, uint64_t order, in
     if (rc) return rc;
     if (order > 63) { set_error("Order should be less than or equal to 63, but is %llu", (unsigned long long)order); return LW_ERR_ORDER_TOO_LARGE; }
     if (config < 0 || config > 3) { set_error("bad roots config %d", config); return LW_ERR_BAD_ARG; }
-    if (order > field_two_adicity(field)) { set_error("no primitive 2^%llu-th root of unity in this field", (unsigned long long)order); return LW_ERR_ROOT_OF_UNITY; }
+    rc = check_root(field, order);
+    if (rc) return rc;
     const uint64_t count = (1ull << order) / 2;
     if (count == 0) return LW_OK;
     if (!out) { set_error("null buffer"); return LW_ERR_BAD_ARG; }
     Entry en(nullptr);
     if (en.rc) return en.rc;
     Context &c = en.c;
+    hipStream_t io = en.use_lane_stream();
+    if (!io) return en.rc;
     // twiddles live in the domain field: one base word per entry for every BabyBear shape
     const size_t eb = field == LW_FIELD_BABYBEAR ? (layout == LW_LAYOUT_BABYBEAR_U32_R32 ? 4 : 8) : 32;
     if (c.host_io_b.ensure(count * eb)) return LW_ERR_ALLOC;
-    rc = gen_twiddles_device(c, field, layout, (uint32_t)order, config, c.host_io_b.p, 0);
+    rc = gen_twiddles_device(c, field, layout, (uint32_t)order, config, c.host_io_b.p, io);
     if (rc) return rc;
-    LW_HIP_CHECK(hipMemcpy(out, c.host_io_b.p, count * eb, hipMemcpyDeviceToHost), LW_ERR_LAUNCH);
-    return LW_OK;
+    return download(out, c.host_io_b.p, count * eb, io);
 }
 
 // get_powers_of_primitive_root / get_powers_of_primitive_root_coset (math/src/fft/cpu/roots_of_unity.rs:13-61)
@@ -700,32 +707,31 @@ int lw_hip_gen_powers(lw_field_t field, lw_layout_t layout, uint64_t order, size
     if (offset_or_null && config != 0) { set_error("the coset variant is defined for the Natural configuration only"); return LW_ERR_BAD_ARG; }
     if (out_len) *out_len = 0;
     if (count == 0) return LW_OK;   // roots_of_unity.rs:18-20: nothing computed, not even the root
-    if (order > field_two_adicity(field)) { set_error("no primitive 2^%llu-th root of unity in this field", (unsigned long long)order); return LW_ERR_ROOT_OF_UNITY; }
+    rc = check_root(field, order);
+    if (rc) return rc;
     const bool bitrev = config >= 2, inverse = (config & 1) != 0;
-    size_t up_to = count;
-    uint32_t bits = 0;
-    if (bitrev) {   // "in bit reverse form we could need as many as (1 << count.bits()) - 1 roots": the result has next_power_of_two(count) entries
-        while (((size_t)1 << bits) < count) bits++;
-        up_to = (size_t)1 << bits;
-    }
+    // "in bit reverse form we could need as many as (1 << count.bits()) - 1 roots": the result has next_power_of_two(count) entries
+    const uint32_t bits = bitrev ? ceil_log2(count) : 0;
+    const size_t up_to = bitrev ? (size_t)1 << bits : count;
     if (out_len) *out_len = up_to;
     if (!out) return LW_OK;       // size query
     if (up_to >> 32) { set_error("%zu powers exceed the 32-bit index range", up_to); return LW_ERR_ALLOC; }
     Entry en(nullptr);
     if (en.rc) return en.rc;
     Context &c = en.c;
+    hipStream_t io = en.use_lane_stream();
+    if (!io) return en.rc;
     const size_t eb = field == LW_FIELD_BABYBEAR ? (layout == LW_LAYOUT_BABYBEAR_U32_R32 ? 4 : 8) : 32;   // domain-field words
     if (c.host_io_b.ensure(up_to * eb)) return LW_ERR_ALLOC;
     if (field == LW_FIELD_BABYBEAR) {
-        rc = ntt_bb_gen_powers(layout, (uint32_t)order, up_to, bitrev ? bits : 0, inverse, offset_or_null, c.host_io_b.p, 0);
+        rc = ntt_bb_gen_powers(layout, (uint32_t)order, up_to, bits, inverse, offset_or_null, c.host_io_b.p, io);
     } else {
         uint32_t ow[8];
         if (offset_or_null) words_from_ref(offset_or_null, ow);
-        rc = ntt256_gen_powers((int)field, (uint32_t)order, up_to, bitrev ? bits : 0, inverse, offset_or_null ? ow : nullptr, c.host_io_b.p, 0);
+        rc = ntt256_gen_powers((int)field, (uint32_t)order, up_to, bits, inverse, offset_or_null ? ow : nullptr, c.host_io_b.p, io);
     }
     if (rc) return rc;
-    LW_HIP_CHECK(hipMemcpy(out, c.host_io_b.p, up_to * eb, hipMemcpyDeviceToHost), LW_ERR_LAUNCH);
-    return LW_OK;
+    return download(out, c.host_io_b.p, up_to * eb, io);
 }
 
 // bitrev_permutation (math/src/fft/gpu/cuda/ops.rs:68-77): out[i] = in[bitrev(i)]; in may alias out
@@ -733,72 +739,65 @@ int lw_hip_bitrev_permutation(lw_field_t field, lw_layout_t layout, const void *
     int rc = check_field_layout(field, layout);
     if (rc) return rc;
     if (n == 0) return LW_OK;
-    if (n & (n - 1)) { set_error("Input length is %zu, which is not a power of two", n); return LW_ERR_INPUT_NOT_POW2; }
+    rc = check_pow2(n, 1);
+    if (rc) return rc;
     if (!in || !out) { set_error("null buffer"); return LW_ERR_BAD_ARG; }
-    uint32_t log2n = 0;
-    while (((size_t)1 << log2n) < n) log2n++;
+    const uint32_t log2n = ceil_log2(n);
     if (log2n > 32) { set_error("2^%u elements exceed device memory", log2n); return LW_ERR_ALLOC; }
     Entry en(nullptr);
     if (en.rc) return en.rc;
     Context &c = en.c;
+    hipStream_t io = en.use_lane_stream();
+    if (!io) return en.rc;
     const size_t eb = lw_hip_field_elem_bytes(field, layout);
     if (c.host_io_a.ensure(n * eb) || c.host_io_b.ensure(n * eb)) return LW_ERR_ALLOC;
-    LW_HIP_CHECK(hipMemcpy(c.host_io_a.p, in, n * eb, hipMemcpyHostToDevice), LW_ERR_LAUNCH);
-    rc = bitrev_device(eb, c.host_io_a.p, c.host_io_b.p, log2n, 0);
+    LW_HIP_CHECK(hipMemcpyAsync(c.host_io_a.p, in, n * eb, hipMemcpyHostToDevice, io), LW_ERR_LAUNCH);
+    rc = bitrev_device(eb, c.host_io_a.p, c.host_io_b.p, log2n, io);
     if (rc) return rc;
-    LW_HIP_CHECK(hipMemcpy(out, c.host_io_b.p, n * eb, hipMemcpyDeviceToHost), LW_ERR_LAUNCH);
-    return LW_OK;
+    return download(out, c.host_io_b.p, n * eb, io);
 }
 
 int lw_hip_ntt_cross_device(lw_field_t field, lw_layout_t layout, lw_dir_t dir, const void *d_in, void *d_out,
                             uint32_t log2n_total, uint32_t log2_shards, uint64_t j2_begin, uint64_t slice_len,
                             uint64_t chunk_stride_elems, uint32_t batch, uint64_t batch_stride_elems, void *hip_stream) {
-    Entry en(hip_stream);
-    if (en.rc) return en.rc;
-    Context &c = en.c;
-    int rc = LW_OK;
-    rc = check_field_layout(field, layout);
+    int rc = check_field_layout(field, layout);
     if (rc) return rc;
     if (log2n_total > 63) { set_error("order %u > 63", log2n_total); return LW_ERR_ORDER_TOO_LARGE; }
-    if (log2n_total > field_two_adicity(field)) { set_error("no primitive 2^%u-th root of unity in this field", log2n_total); return LW_ERR_ROOT_OF_UNITY; }
+    rc = check_root(field, log2n_total);
+    if (rc) return rc;
     if (!d_in || !d_out || d_in == d_out) { set_error("cross step needs distinct non-null buffers"); return LW_ERR_BAD_ARG; }
     if (batch == 0 || slice_len == 0) return LW_OK;
-    return ntt_cross_device(c, field, layout, dir, d_in, d_out, log2n_total, log2_shards, j2_begin, slice_len, chunk_stride_elems,
-                            batch, batch_stride_elems, (hipStream_t)hip_stream);
+    Entry en(hip_stream);
+    if (en.rc) return en.rc;
+    return ntt_cross_device(en.c, field, layout, dir, d_in, d_out, log2n_total, log2_shards, j2_begin, slice_len, chunk_stride_elems,
+                            batch, batch_stride_elems, en.stream);
 }
 
 int lw_hip_ntt_lde_device(lw_field_t field, lw_layout_t layout, const void *d_coeffs, uint32_t log2_coeffs, void *d_out,
                           uint32_t log2n, uint32_t batch, const void *coset_offset_or_null, void *hip_stream) {
+    if (log2_coeffs > log2n) { set_error("2^%u coefficients do not fit a 2^%u domain", log2_coeffs, log2n); return LW_ERR_BAD_ARG; }
+    int rc = ntt_check(field, layout, LW_DIR_FORWARD, log2n, batch, 0, d_coeffs, d_out);
+    if (rc) return rc;
     Entry en(hip_stream);
     if (en.rc) return en.rc;
-    Context &c = en.c;
-    int rc = LW_OK;
-    if (log2_coeffs > log2n) { set_error("2^%u coefficients do not fit a 2^%u domain", log2_coeffs, log2n); return LW_ERR_BAD_ARG; }
-    auto t0 = std::chrono::steady_clock::now();
-    rc = ntt_device_locked(c, field, layout, LW_DIR_FORWARD, d_coeffs, d_out, log2n, batch, 0, coset_offset_or_null,
-                           (hipStream_t)hip_stream, log2_coeffs);
-    c.timings.last_ntt_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c.timings.ntt_calls++;
+    const auto t0 = Clock::now();
+    rc = ntt_device_locked(en.c, field, layout, LW_DIR_FORWARD, d_coeffs, d_out, log2n, batch, 0, coset_offset_or_null, en.stream,
+                           log2_coeffs);
+    note_ntt(en.c, t0);
     return rc;
 }
 
 int lw_hip_ntt(lw_field_t field, lw_layout_t layout, lw_dir_t dir, const void *in, void *out, uint32_t log2n, uint32_t batch,
                size_t batch_stride_elems, const void *coset_offset_or_null) {
+    int rc = ntt_check(field, layout, dir, log2n, batch, batch_stride_elems, in, out);
+    if (rc || batch == 0) return rc;
     Entry en(nullptr);
     if (en.rc) return en.rc;
     Context &c = en.c;
-    int rc = LW_OK;
-    rc = check_field_layout(field, layout);
-    if (rc) return rc;
-    if (log2n > 63) { set_error("order %u > 63", log2n); return LW_ERR_ORDER_TOO_LARGE; }
-    if (log2n > field_two_adicity(field)) { set_error("no primitive 2^%u-th root of unity in this field", log2n); return LW_ERR_ROOT_OF_UNITY; }
-    if (batch == 0) return LW_OK;
-    if (!in || !out) { set_error("null buffer"); return LW_ERR_BAD_ARG; }
-    auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = Clock::now();
     const size_t eb = lw_hip_field_elem_bytes(field, layout);
     const size_t n = (size_t)1 << log2n;
     const size_t stride = batch_stride_elems ? batch_stride_elems : n;
-    if (stride < n) { set_error("batch stride %zu < transform length", stride); return LW_ERR_BAD_ARG; }
     const size_t span = ((size_t)(batch - 1) * stride + n) * eb;
     if (c.host_io_a.ensure(span) || c.host_io_b.ensure(span)) return LW_ERR_ALLOC;
     hipStream_t io = en.use_lane_stream();
@@ -817,15 +816,8 @@ int lw_hip_ntt(lw_field_t field, lw_layout_t layout, lw_dir_t dir, const void *i
         LW_HIP_CHECK(hipMemcpy2DAsync(out, stride * eb, c.host_io_b.p, stride * eb, n * eb, batch, hipMemcpyDeviceToHost, io), LW_ERR_LAUNCH);
         LW_HIP_CHECK(hipStreamSynchronize(io), LW_ERR_LAUNCH);
     }
-    c.timings.last_ntt_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c.timings.ntt_calls++;
+    note_ntt(c, t0);
     return LW_OK;
-}
-
-static bool elem_is_zero(const unsigned char *p, size_t eb) {
-    for (size_t i = 0; i < eb; i++)
-        if (p[i]) return false;
-    return true;
 }
 
 // Polynomial::evaluate_fft / evaluate_offset_fft (math/src/fft/polynomial.rs:25-68,74-82)
@@ -836,9 +828,7 @@ int lw_polynomial_evaluate_fft(lw_field_t field, lw_layout_t layout, const void 
     if (rc) return rc;
     if (!out_len || (n_coeffs && !coeffs)) { set_error("null argument"); return LW_ERR_BAD_ARG; }
     const size_t eb = lw_hip_field_elem_bytes(field, layout);
-    // Polynomial::new strips trailing zero coefficients (math/src/polynomial/mod.rs:19-31)
-    size_t clen = n_coeffs;
-    while (clen > 0 && elem_is_zero((const unsigned char *)coeffs + (clen - 1) * eb, eb)) clen--;
+    const size_t clen = stripped_len(coeffs, n_coeffs, eb);
     size_t m = clen > domain_size ? clen : domain_size;
     size_t p2 = 1;
     while (p2 < m) p2 <<= 1;
@@ -850,26 +840,21 @@ int lw_polynomial_evaluate_fft(lw_field_t field, lw_layout_t layout, const void 
         memset(out, 0, len * eb);
         return LW_OK;
     }
-    if (len == 0 || (len & (len - 1))) {   // ops::fft rejects it (math/src/fft/cpu/ops.rs:17-19)
-        set_error("Input length is %zu, which is not a power of two", len);
-        return LW_ERR_INPUT_NOT_POW2;
-    }
-    uint32_t log2n = 0;
-    while (((size_t)1 << log2n) < len) log2n++;
-    if (log2n > field_two_adicity(field)) { set_error("no primitive 2^%u-th root of unity in this field", log2n); return LW_ERR_ROOT_OF_UNITY; }
+    rc = check_pow2(len, 1);
+    if (rc) return rc;
+    const uint32_t log2n = ceil_log2(len);
+    rc = check_root(field, log2n);
+    if (rc) return rc;
 
     Entry en(nullptr);
     if (en.rc) return en.rc;
     Context &c = en.c;
-    auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = Clock::now();
     // Zero padding happens after scaling in the reference, so padded slots stay zero either way.  Only the power-of-two
     // block that holds the coefficients is uploaded; the transform extends it (LDE path).
-    size_t block = 1;
-    while (block < clen) block <<= 1;
-    uint32_t in_log2 = 0;
-    while (((size_t)1 << in_log2) < block) in_log2++;
+    const uint32_t in_log2 = ceil_log2(clen);
     const bool lde = in_log2 >= 1 && in_log2 < log2n;
-    const size_t up = lde ? block : len;
+    const size_t up = lde ? (size_t)1 << in_log2 : len;
     if (c.host_io_a.ensure(up * eb) || c.host_io_b.ensure(len * eb)) return LW_ERR_ALLOC;
     hipStream_t io = en.use_lane_stream();
     if (!io) return en.rc;
@@ -883,8 +868,7 @@ int lw_polynomial_evaluate_fft(lw_field_t field, lw_layout_t layout, const void 
     LW_HIP_CHECK(hipStreamSynchronize(io), LW_ERR_LAUNCH);
     rc = pf.copy_back(c.host_io_b.p, len * eb, io);
     if (rc) return rc;
-    c.timings.last_ntt_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c.timings.ntt_calls++;
+    note_ntt(c, t0);
     return LW_OK;
 }
 
@@ -894,47 +878,32 @@ int lw_polynomial_interpolate_fft(lw_field_t field, lw_layout_t layout, const vo
     int rc = check_field_layout(field, layout);
     if (rc) return rc;
     if (!evals || !out_coeffs) { set_error("null argument"); return LW_ERR_BAD_ARG; }
-    if (n == 0 || (n & (n - 1))) {
-        set_error("Input length is %zu, which is not a power of two", n);
-        return LW_ERR_INPUT_NOT_POW2;
-    }
-    uint32_t log2n = 0;
-    while (((size_t)1 << log2n) < n) log2n++;
-    rc = lw_hip_ntt(field, layout, LW_DIR_INVERSE, evals, out_coeffs, log2n, 1, 0, offset_or_null);
+    rc = check_pow2(n, 1);
     if (rc) return rc;
-    if (coeff_len) {
-        const size_t eb = lw_hip_field_elem_bytes(field, layout);
-        size_t clen = n;
-        while (clen > 0 && elem_is_zero((const unsigned char *)out_coeffs + (clen - 1) * eb, eb)) clen--;
-        *coeff_len = clen;
-    }
+    rc = lw_hip_ntt(field, layout, LW_DIR_INVERSE, evals, out_coeffs, ceil_log2(n), 1, 0, offset_or_null);
+    if (rc) return rc;
+    if (coeff_len) *coeff_len = stripped_len(out_coeffs, n, lw_hip_field_elem_bytes(field, layout));
     return LW_OK;
 }
 
-static int msm_device_entry(lw_curve_t curve, const uint64_t *d_scalars, const void *d_points, size_t n, void *out_point_host,
-                            void *hip_stream, int mont, uint32_t limbs = 4) {
-    if (limbs < 1 || limbs > 8) { set_error("scalar_limbs = %u: 1 .. 8 supported", limbs); return LW_ERR_BAD_ARG; }
-    if (n && limbs != 4 && ((uintptr_t)d_scalars & (limbs % 2 ? 7 : 15))) {   // msm_digits_kernel's row loads
-        set_error("scalars of %u limbs must be %d-byte aligned", limbs, limbs % 2 ? 8 : 16);
-        return LW_ERR_BAD_ARG;
-    }
-    Entry en(hip_stream);
-    if (en.rc) return en.rc;
-    Context &c = en.c;
-    int rc = LW_OK;
-    if (lw_hip_curve_point_bytes(curve) == 0 || !out_point_host) { set_error("bad curve or null output"); return LW_ERR_BAD_ARG; }
-    auto t0 = std::chrono::steady_clock::now();
-    rc = msm_device(c, curve, d_scalars, d_points, n, out_point_host, (hipStream_t)hip_stream, mont, 0, nullptr, limbs);
-    c.timings.last_msm_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c.timings.msm_calls++;
-    return rc;
-}
 // interpolate_and_commit_main's commitment step (provers/stark/src/prover.rs:229-244) on device-resident LDE columns
 // the element size the commitment hashes, or 0 when the (field, layout) pair has no AsBytes in the reference
 static uint32_t commit_elem_bytes(lw_field_t field, lw_layout_t layout) {
     if (check_field_layout(field, layout)) return 0;
     if (layout == LW_LAYOUT_EXT4_INTERLEAVED) { set_error("the quartic extension has no AsBytes in the reference (quartic_babybear.rs)"); return 0; }
     return (uint32_t)lw_hip_field_elem_bytes(field, layout);
+}
+// the host and _device forms take the 256-bit fields only
+static int check_field_256(lw_field_t field, const char *what) {
+    if (field == LW_FIELD_STARK252 || field == LW_FIELD_BLS12_381_FR) return LW_OK;
+    set_error("%s supports the 256-bit fields", what);
+    return LW_ERR_BAD_ARG;
+}
+// checks of every commitment form
+static int commit_check(const void *columns, const void *nodes_or_root, uint32_t n_cols, uint32_t log2n) {
+    if (!columns || !nodes_or_root || n_cols == 0) { set_error("null buffer or no columns"); return LW_ERR_BAD_ARG; }
+    if (log2n > 31) { set_error("2^%u leaves", log2n); return LW_ERR_ALLOC; }
+    return LW_OK;
 }
 // A Merkle root for the caller's transcript: through the lane's pinned words (a 32-byte copy into pageable memory goes
 // through the runtime's staging path, ~2x the latency; FRI reads one root per layer with the GPU idle meanwhile)
@@ -950,96 +919,95 @@ int lw_stark_commit_columns_layout_device(lw_field_t field, lw_layout_t layout, 
                                           uint32_t log2n, int bit_reverse, void *d_nodes, uint8_t *out_root, void *hip_stream) {
     const uint32_t eb = commit_elem_bytes(field, layout);
     if (!eb) return LW_ERR_BAD_ARG;
-    if (!d_columns || !d_nodes || n_cols == 0) { set_error("null buffer or no columns"); return LW_ERR_BAD_ARG; }
-    if (log2n > 31) { set_error("2^%u leaves", log2n); return LW_ERR_ALLOC; }
+    int rc = commit_check(d_columns, d_nodes, n_cols, log2n);
+    if (rc) return rc;
     if ((uint64_t)n_cols * eb >= (1ull << 31)) { set_error("%u columns per row", n_cols); return LW_ERR_BAD_ARG; }
     Entry en(hip_stream);
     if (en.rc) return en.rc;
-    Context &c = en.c;
     if (col_stride_elems == 0) col_stride_elems = 1ull << log2n;
-    int rc = merkle_commit_device(c, d_columns, n_cols, col_stride_elems, log2n, bit_reverse, d_nodes, (hipStream_t)hip_stream, eb);
+    rc = merkle_commit_device(en.c, d_columns, n_cols, col_stride_elems, log2n, bit_reverse, d_nodes, en.stream, eb);
     if (rc) return rc;
-    if (out_root) return read_root(c, d_nodes, out_root, (hipStream_t)hip_stream);
+    if (out_root) return read_root(en.c, d_nodes, out_root, en.stream);
     return LW_OK;
 }
 int lw_stark_commit_columns_device(lw_field_t field, const void *d_columns, uint32_t n_cols, uint64_t col_stride_elems, uint32_t log2n,
                                    int bit_reverse, void *d_nodes, uint8_t *out_root, void *hip_stream) {
-    if (field != LW_FIELD_STARK252 && field != LW_FIELD_BLS12_381_FR) { set_error("Merkle commitment supports the 256-bit fields"); return LW_ERR_BAD_ARG; }
-    if (!d_columns || !d_nodes || n_cols == 0) { set_error("null buffer or no columns"); return LW_ERR_BAD_ARG; }
-    if (log2n > 31) { set_error("2^%u leaves", log2n); return LW_ERR_ALLOC; }
-    Entry en(hip_stream);
-    if (en.rc) return en.rc;
-    Context &c = en.c;
-    int rc = LW_OK;
-    if (col_stride_elems == 0) col_stride_elems = 1ull << log2n;
-    rc = merkle_commit_device(c, d_columns, n_cols, col_stride_elems, log2n, bit_reverse, d_nodes, (hipStream_t)hip_stream);
+    const int rc = check_field_256(field, "Merkle commitment");
     if (rc) return rc;
-    if (out_root) return read_root(c, d_nodes, out_root, (hipStream_t)hip_stream);
-    return LW_OK;
+    return lw_stark_commit_columns_layout_device(field, LW_LAYOUT_U64_LIMBS_MS_FIRST, d_columns, n_cols, col_stride_elems, log2n,
+                                                 bit_reverse, d_nodes, out_root, hip_stream);
 }
 
 int lw_stark_commit_columns(lw_field_t field, const void *columns, uint32_t n_cols, uint32_t log2n, int bit_reverse, uint8_t *out_root,
                             uint8_t *out_nodes_or_null) {
-    if (field != LW_FIELD_STARK252 && field != LW_FIELD_BLS12_381_FR) { set_error("Merkle commitment supports the 256-bit fields"); return LW_ERR_BAD_ARG; }
-    if (!columns || !out_root || n_cols == 0) { set_error("null buffer or no columns"); return LW_ERR_BAD_ARG; }
-    if (log2n > 31) { set_error("2^%u leaves", log2n); return LW_ERR_ALLOC; }
+    int rc = check_field_256(field, "Merkle commitment");
+    if (rc) return rc;
+    rc = commit_check(columns, out_root, n_cols, log2n);
+    if (rc) return rc;
     const size_t n = (size_t)1 << log2n;
-    {
-        Entry en(nullptr);
-        if (en.rc) return en.rc;
-        Context &c = en.c;
-        int rc = LW_OK;
-        if (c.host_io_a.ensure((size_t)n_cols * n * 32) || c.host_io_b.ensure((2 * n - 1) * 32)) return LW_ERR_ALLOC;
-        LW_HIP_CHECK(hipMemcpy(c.host_io_a.p, columns, (size_t)n_cols * n * 32, hipMemcpyHostToDevice), LW_ERR_LAUNCH);
-        rc = merkle_commit_device(c, c.host_io_a.p, n_cols, n, log2n, bit_reverse, c.host_io_b.p, 0);
+    Entry en(nullptr);
+    if (en.rc) return en.rc;
+    Context &c = en.c;
+    hipStream_t io = en.use_lane_stream();
+    if (!io) return en.rc;
+    if (c.host_io_a.ensure((size_t)n_cols * n * 32) || c.host_io_b.ensure((2 * n - 1) * 32)) return LW_ERR_ALLOC;
+    LW_HIP_CHECK(hipMemcpyAsync(c.host_io_a.p, columns, (size_t)n_cols * n * 32, hipMemcpyHostToDevice, io), LW_ERR_LAUNCH);
+    rc = merkle_commit_device(c, c.host_io_a.p, n_cols, n, log2n, bit_reverse, c.host_io_b.p, io);
+    if (rc) return rc;
+    if (out_nodes_or_null) {
+        rc = download(out_nodes_or_null, c.host_io_b.p, (2 * n - 1) * 32, io);
         if (rc) return rc;
-        LW_HIP_CHECK(hipMemcpy(out_root, c.host_io_b.p, 32, hipMemcpyDeviceToHost), LW_ERR_LAUNCH);
-        if (out_nodes_or_null) LW_HIP_CHECK(hipMemcpy(out_nodes_or_null, c.host_io_b.p, (2 * n - 1) * 32, hipMemcpyDeviceToHost), LW_ERR_LAUNCH);
+        memcpy(out_root, out_nodes_or_null, 32);
+        return LW_OK;
     }
-    return LW_OK;
+    return download(out_root, c.host_io_b.p, 32, io);
+}
+
+// checks of both FRI layer forms; a layer (evaluation + tree) needs a power-of-two domain of at least 2 that holds the
+// folded polynomial.  *lgd = log2 of that domain (0 without a layer), *lgb = log2 of the folded block (at least 2 elements).
+static int fri_check(lw_field_t field, size_t n_coeffs, size_t domain_size, bool layer, uint32_t *lgd, uint32_t *lgb) {
+    int rc = check_field_256(field, "FRI layer");
+    if (rc) return rc;
+    const size_t n_out = (n_coeffs + 1) / 2;
+    *lgd = 0;
+    *lgb = n_out > 2 ? ceil_log2(n_out) : 1;
+    if (!layer) return LW_OK;
+    rc = check_pow2(domain_size, 2);
+    if (rc) return rc;
+    if (((size_t)1 << *lgb) > domain_size) { set_error("folded polynomial of %zu coefficients exceeds the domain %zu", n_out, domain_size); return LW_ERR_BAD_ARG; }
+    *lgd = ceil_log2(domain_size);
+    return check_root(field, *lgd);
 }
 
 // One layer of the FRI commit phase (provers/stark/src/fri/mod.rs:44-58 + :115-141), host buffers
 int lw_stark_fri_layer(lw_field_t field, const void *coeffs, size_t n_coeffs, const void *zeta, const void *coset_offset, size_t domain_size,
                        void *out_poly, size_t *out_poly_len, void *out_evaluation, uint8_t *out_root, uint8_t *out_nodes_or_null) {
-    if (field != LW_FIELD_STARK252 && field != LW_FIELD_BLS12_381_FR) { set_error("FRI layer supports the 256-bit fields"); return LW_ERR_BAD_ARG; }
     if (!coeffs || !zeta || !coset_offset || !out_poly || !out_evaluation || !out_root || n_coeffs == 0) { set_error("null or empty argument"); return LW_ERR_BAD_ARG; }
-    if (domain_size < 2 || (domain_size & (domain_size - 1))) {
-        set_error("Input length is %zu, which is not a power of two", domain_size);
-        return LW_ERR_INPUT_NOT_POW2;
-    }
-    const size_t n_out = (n_coeffs + 1) / 2;
-    if (n_out > domain_size) { set_error("folded polynomial of %zu coefficients exceeds the domain %zu", n_out, domain_size); return LW_ERR_BAD_ARG; }
-    uint32_t lgd = 0, lgb = 1;
-    while (((size_t)1 << lgd) < domain_size) lgd++;
-    while (((size_t)1 << lgb) < n_out) lgb++;
-    if (lgb > lgd) lgb = lgd;
-    if (lgd > field_two_adicity(field)) { set_error("no primitive 2^%u-th root of unity in this field", lgd); return LW_ERR_ROOT_OF_UNITY; }
+    uint32_t lgd, lgb;
+    int rc = fri_check(field, n_coeffs, domain_size, true, &lgd, &lgb);
+    if (rc) return rc;
     Entry en(nullptr);
     if (en.rc) return en.rc;
     Context &c = en.c;
-    int rc = LW_OK;
-    const size_t blk = (size_t)1 << lgb;
+    hipStream_t io = en.use_lane_stream();
+    if (!io) return en.rc;
+    const size_t blk = (size_t)1 << lgb, n_out = (n_coeffs + 1) / 2;
     // a: [coeffs | zeta words | folded block]   b: [eval | eval_br | nodes]
     const size_t a_coeffs = n_coeffs * 32, a_zeta = 256, a_poly = blk * 32;
     if (c.host_io_a.ensure(a_coeffs + a_zeta + a_poly) || c.host_io_b.ensure(2 * domain_size * 32 + (domain_size - 1) * 32)) return LW_ERR_ALLOC;
     char *da = (char *)c.host_io_a.p, *db = (char *)c.host_io_b.p;
     uint32_t zw[8];
     words_from_ref(zeta, zw);
-    LW_HIP_CHECK(hipMemcpy(da, coeffs, a_coeffs, hipMemcpyHostToDevice), LW_ERR_LAUNCH);
+    LW_HIP_CHECK(hipMemcpyAsync(da, coeffs, a_coeffs, hipMemcpyHostToDevice, io), LW_ERR_LAUNCH);
     char *d_poly = da + a_coeffs + a_zeta;
     char *d_eval = db, *d_eval_br = db + domain_size * 32, *d_nodes = db + 2 * domain_size * 32;
-    rc = fri_layer_device(c, field, da, n_coeffs, zw, coset_offset, lgd, d_poly, lgb, d_eval, d_eval_br, d_nodes, 0);
+    rc = fri_layer_device(c, field, da, n_coeffs, zw, coset_offset, lgd, d_poly, lgb, d_eval, d_eval_br, d_nodes, io);
     if (rc) return rc;
-    LW_HIP_CHECK(hipMemcpy(out_poly, d_poly, n_out * 32, hipMemcpyDeviceToHost), LW_ERR_LAUNCH);
-    LW_HIP_CHECK(hipMemcpy(out_evaluation, d_eval_br, domain_size * 32, hipMemcpyDeviceToHost), LW_ERR_LAUNCH);
-    LW_HIP_CHECK(hipMemcpy(out_root, d_nodes, 32, hipMemcpyDeviceToHost), LW_ERR_LAUNCH);
-    if (out_nodes_or_null) LW_HIP_CHECK(hipMemcpy(out_nodes_or_null, d_nodes, (domain_size - 1) * 32, hipMemcpyDeviceToHost), LW_ERR_LAUNCH);
-    if (out_poly_len) {   // Polynomial::new strips trailing zeros of the folded polynomial
-        size_t clen = n_out;
-        while (clen > 0 && elem_is_zero((const unsigned char *)out_poly + (clen - 1) * 32, 32)) clen--;
-        *out_poly_len = clen;
-    }
+    if ((rc = download(out_poly, d_poly, n_out * 32, io)) || (rc = download(out_evaluation, d_eval_br, domain_size * 32, io)) ||
+        (rc = download(out_root, d_nodes, 32, io)))
+        return rc;
+    if (out_nodes_or_null && (rc = download(out_nodes_or_null, d_nodes, (domain_size - 1) * 32, io))) return rc;
+    if (out_poly_len) *out_poly_len = stripped_len(out_poly, n_out, 32);
     return LW_OK;
 }
 
@@ -1048,23 +1016,13 @@ int lw_stark_fri_layer(lw_field_t field, const void *coeffs, size_t n_coeffs, co
 int lw_stark_fri_layer_device(lw_field_t field, const void *d_coeffs, size_t n_coeffs, const void *zeta, const void *coset_offset,
                               size_t domain_size, void *d_out_poly, void *d_out_evaluation_or_null, void *d_nodes_or_null,
                               uint8_t *out_root_or_null, void *hip_stream) {
-    if (field != LW_FIELD_STARK252 && field != LW_FIELD_BLS12_381_FR) { set_error("FRI layer supports the 256-bit fields"); return LW_ERR_BAD_ARG; }
     if (!d_coeffs || !zeta || !d_out_poly || n_coeffs == 0 || d_out_poly == d_coeffs) { set_error("null, empty or aliased argument"); return LW_ERR_BAD_ARG; }
     const bool layer = d_nodes_or_null != nullptr;
     if (!layer && (d_out_evaluation_or_null || out_root_or_null)) { set_error("an evaluation or a root needs d_nodes"); return LW_ERR_BAD_ARG; }
-    const size_t n_out = (n_coeffs + 1) / 2;
-    uint32_t lgd = 0, lgb = 1;
-    while (((size_t)1 << lgb) < n_out) lgb++;
-    if (layer) {
-        if (!coset_offset) { set_error("null coset offset"); return LW_ERR_BAD_ARG; }
-        if (domain_size < 2 || (domain_size & (domain_size - 1))) {
-            set_error("Input length is %zu, which is not a power of two", domain_size);
-            return LW_ERR_INPUT_NOT_POW2;
-        }
-        while (((size_t)1 << lgd) < domain_size) lgd++;
-        if (((size_t)1 << lgb) > domain_size) { set_error("folded polynomial of %zu coefficients exceeds the domain %zu", n_out, domain_size); return LW_ERR_BAD_ARG; }
-        if (lgd > field_two_adicity(field)) { set_error("no primitive 2^%u-th root of unity in this field", lgd); return LW_ERR_ROOT_OF_UNITY; }
-    }
+    if (layer && !coset_offset) { set_error("null coset offset"); return LW_ERR_BAD_ARG; }
+    uint32_t lgd, lgb;
+    int rc = fri_check(field, n_coeffs, domain_size, layer, &lgd, &lgb);
+    if (rc) return rc;
     Entry en(hip_stream);
     if (en.rc) return en.rc;
     Context &c = en.c;
@@ -1072,105 +1030,93 @@ int lw_stark_fri_layer_device(lw_field_t field, const void *d_coeffs, size_t n_c
     if (layer && c.pipe_tmp.ensure(domain_size * 32)) return LW_ERR_ALLOC;
     uint32_t zw[8];
     words_from_ref(zeta, zw);
-    int rc = fri_layer_device(c, field, d_coeffs, n_coeffs, zw, coset_offset, lgd, d_out_poly, lgb, layer ? c.pipe_tmp.p : nullptr,
-                              d_out_evaluation_or_null, d_nodes_or_null, en.stream);
+    rc = fri_layer_device(c, field, d_coeffs, n_coeffs, zw, coset_offset, lgd, d_out_poly, lgb, layer ? c.pipe_tmp.p : nullptr,
+                          d_out_evaluation_or_null, d_nodes_or_null, en.stream);
     if (rc) return rc;
     if (out_root_or_null) return read_root(c, d_nodes_or_null, out_root_or_null, en.stream);
     return LW_OK;
 }
 
-// calculate_h_coefficients on device-resident coefficient vectors; h stays in HBM for the MSM that consumes it
-// (provers/groth16/src/prover.rs:68-72,97-101 -> lw_hip_msm_srs_fr_device)
-int lw_groth16_h_coefficients_device(const void *d_l, const void *d_r, const void *d_o, size_t n_coeffs, size_t num_gates, void *d_out_h,
-                                     size_t *coeff_len_or_null, void *hip_stream) {
-    if (!d_out_h || (n_coeffs && (!d_l || !d_r || !d_o))) { set_error("null argument"); return LW_ERR_BAD_ARG; }
-    if (num_gates < 1 || (num_gates & (num_gates - 1))) {
-        set_error("Input length is %zu, which is not a power of two", num_gates);
-        return LW_ERR_INPUT_NOT_POW2;
-    }
+// checks of both Groth16 forms (the host form wants all three vectors even when they are empty); *lg = log2 of the gates
+static int groth16_check(const void *l, const void *r, const void *o, size_t n_coeffs, size_t num_gates, const void *out_h, bool device,
+                         uint32_t *lg) {
+    if (!out_h || ((n_coeffs || !device) && (!l || !r || !o))) { set_error("null argument"); return LW_ERR_BAD_ARG; }
+    int rc = check_pow2(num_gates, 1);   // from_r1cs pads the gate count to a power of two (qap.rs:72-75)
+    if (rc) return rc;
     if (n_coeffs > num_gates) { set_error("%zu coefficients for %zu gates", n_coeffs, num_gates); return LW_ERR_BAD_ARG; }
-    uint32_t lg = 0;
-    while (((size_t)1 << lg) < num_gates) lg++;
-    if (lg + 1 > Fr381::TWO_ADICITY) { set_error("no primitive 2^%u-th root of unity in this field", lg + 1); return LW_ERR_ROOT_OF_UNITY; }
-    Entry en(hip_stream);
-    if (en.rc) return en.rc;
-    Context &c = en.c;
+    *lg = ceil_log2(num_gates);
+    return check_root(LW_FIELD_BLS12_381_FR, *lg + 1);
+}
+
+// QuadraticArithmeticProgram::calculate_h_coefficients (provers/groth16/src/qap.rs:15-39) after the variable
+// polynomials have been accumulated: three coset LDEs, (l*r - o) / t pointwise, one coset INTT — one device pipeline.
+// src: the three device-resident coefficient vectors (n_coeffs each); h (2 * num_gates elements) goes to d_out_h.
+static int groth16_h_locked(Context &c, const void *const (&src_in)[3], size_t n_coeffs, size_t num_gates, uint32_t lg, void *d_out_h,
+                            size_t *coeff_len_or_null, hipStream_t s) {
     const size_t n = 2 * num_gates, blk = num_gates < 2 ? 2 : num_gates;
     const bool staged = n_coeffs != blk;   // shorter vectors are zero padded into library scratch first
     if (c.pipe_tmp.ensure((3 * n + (staged ? 3 * blk : 0)) * 32 + 256)) return LW_ERR_ALLOC;
     char *ev = (char *)c.pipe_tmp.p, *st = ev + 3 * n * 32;
-    const void *src[3] = {d_l, d_r, d_o};
+    const void *src[3] = {src_in[0], src_in[1], src_in[2]};
     if (staged) {
-        LW_HIP_CHECK(hipMemsetAsync(st, 0, 3 * blk * 32, en.stream), LW_ERR_LAUNCH);
+        LW_HIP_CHECK(hipMemsetAsync(st, 0, 3 * blk * 32, s), LW_ERR_LAUNCH);
         for (int k = 0; k < 3; k++) {
-            if (n_coeffs) LW_HIP_CHECK(hipMemcpyAsync(st + (size_t)k * blk * 32, src[k], n_coeffs * 32, hipMemcpyDeviceToDevice, en.stream), LW_ERR_LAUNCH);
+            if (n_coeffs) LW_HIP_CHECK(hipMemcpyAsync(st + (size_t)k * blk * 32, src[k], n_coeffs * 32, hipMemcpyDeviceToDevice, s), LW_ERR_LAUNCH);
             src[k] = st + (size_t)k * blk * 32;
         }
     }
-    int rc = groth16_h_device(c, src[0], src[1], src[2], lg, d_out_h, ev, en.stream);
+    int rc = groth16_h_device(c, src[0], src[1], src[2], lg, d_out_h, ev, s);
     if (rc) return rc;
     if (coeff_len_or_null) {   // Polynomial::new's stripped length, for callers that slice the SRS by it (prover.rs:98-100)
         uint64_t *d_len = (uint64_t *)(ev + 3 * n * 32 + (staged ? 3 * blk * 32 : 0));
-        rc = stripped_length_device(d_out_h, n, d_len, en.stream);
+        rc = stripped_length_device(d_out_h, n, d_len, s);
         if (rc) return rc;
         uint64_t len = 0;
-        LW_HIP_CHECK(hipMemcpyAsync(&len, d_len, 8, hipMemcpyDeviceToHost, en.stream), LW_ERR_LAUNCH);
-        LW_HIP_CHECK(hipStreamSynchronize(en.stream), LW_ERR_LAUNCH);
+        rc = download(&len, d_len, 8, s);
+        if (rc) return rc;
         *coeff_len_or_null = (size_t)len;
     }
     return LW_OK;
 }
 
-// QuadraticArithmeticProgram::calculate_h_coefficients (provers/groth16/src/qap.rs:15-39) after the variable
-// polynomials have been accumulated: three coset LDEs, (l*r - o) / t pointwise, one coset INTT — one device pipeline.
+// h stays in HBM for the MSM that consumes it (provers/groth16/src/prover.rs:68-72,97-101 -> lw_hip_msm_srs_fr_device)
+int lw_groth16_h_coefficients_device(const void *d_l, const void *d_r, const void *d_o, size_t n_coeffs, size_t num_gates, void *d_out_h,
+                                     size_t *coeff_len_or_null, void *hip_stream) {
+    uint32_t lg;
+    int rc = groth16_check(d_l, d_r, d_o, n_coeffs, num_gates, d_out_h, true, &lg);
+    if (rc) return rc;
+    Entry en(hip_stream);
+    if (en.rc) return en.rc;
+    const void *src[3] = {d_l, d_r, d_o};
+    return groth16_h_locked(en.c, src, n_coeffs, num_gates, lg, d_out_h, coeff_len_or_null, en.stream);
+}
+
 int lw_groth16_h_coefficients(const void *l_coeffs, const void *r_coeffs, const void *o_coeffs, size_t n_coeffs, size_t num_gates,
                               void *out_h, size_t *coeff_len) {
-    if (!l_coeffs || !r_coeffs || !o_coeffs || !out_h) { set_error("null argument"); return LW_ERR_BAD_ARG; }
-    if (num_gates < 1 || (num_gates & (num_gates - 1))) {   // from_r1cs pads the gate count to a power of two (qap.rs:72-75)
-        set_error("Input length is %zu, which is not a power of two", num_gates);
-        return LW_ERR_INPUT_NOT_POW2;
-    }
-    if (n_coeffs > num_gates) { set_error("%zu coefficients for %zu gates", n_coeffs, num_gates); return LW_ERR_BAD_ARG; }
-    uint32_t lg = 0;
-    while (((size_t)1 << lg) < num_gates) lg++;
-    if (lg + 1 > Fr381::TWO_ADICITY) { set_error("no primitive 2^%u-th root of unity in this field", lg + 1); return LW_ERR_ROOT_OF_UNITY; }
+    uint32_t lg;
+    int rc = groth16_check(l_coeffs, r_coeffs, o_coeffs, n_coeffs, num_gates, out_h, false, &lg);
+    if (rc) return rc;
     Entry en(nullptr);
     if (en.rc) return en.rc;
     Context &c = en.c;
-    int rc = LW_OK;
+    hipStream_t io = en.use_lane_stream();
+    if (!io) return en.rc;
     const size_t n = 2 * num_gates;
-    const size_t blk = num_gates < 2 ? 2 : num_gates;   // coefficient block per polynomial on the device (zero padded)
-    // device staging: [l | r | o] coefficient blocks, then 3 evaluation vectors + output
-    if (c.host_io_a.ensure(3 * blk * 32) || c.host_io_b.ensure(4 * n * 32)) return LW_ERR_ALLOC;
-    LW_HIP_CHECK(hipMemsetAsync(c.host_io_a.p, 0, 3 * blk * 32, 0), LW_ERR_LAUNCH);
-    const void *src[3] = {l_coeffs, r_coeffs, o_coeffs};
-    for (int k = 0; k < 3; k++)
-        if (n_coeffs)
-            LW_HIP_CHECK(hipMemcpy((char *)c.host_io_a.p + (size_t)k * blk * 32, src[k], n_coeffs * 32, hipMemcpyHostToDevice), LW_ERR_LAUNCH);
-    char *ev = (char *)c.host_io_b.p;
-    rc = groth16_h_device(c, c.host_io_a.p, (char *)c.host_io_a.p + blk * 32, (char *)c.host_io_a.p + 2 * blk * 32, lg,
-                          ev + 3 * n * 32, ev, 0);
-    if (rc) return rc;
-    LW_HIP_CHECK(hipMemcpy(out_h, ev + 3 * n * 32, n * 32, hipMemcpyDeviceToHost), LW_ERR_LAUNCH);
-    if (coeff_len) {
-        size_t clen = n;
-        while (clen > 0 && elem_is_zero((const unsigned char *)out_h + (clen - 1) * 32, 32)) clen--;
-        *coeff_len = clen;
+    // device staging: [l | r | o] coefficient vectors, then h
+    if (c.host_io_a.ensure(3 * n_coeffs * 32) || c.host_io_b.ensure(n * 32)) return LW_ERR_ALLOC;
+    const void *host[3] = {l_coeffs, r_coeffs, o_coeffs}, *src[3];
+    for (int k = 0; k < 3; k++) {
+        src[k] = (char *)c.host_io_a.p + (size_t)k * n_coeffs * 32;
+        if (n_coeffs) LW_HIP_CHECK(hipMemcpyAsync((void *)src[k], host[k], n_coeffs * 32, hipMemcpyHostToDevice, io), LW_ERR_LAUNCH);
     }
-    return LW_OK;
+    rc = groth16_h_locked(c, src, n_coeffs, num_gates, lg, c.host_io_b.p, coeff_len, io);
+    if (rc) return rc;
+    return download(out_h, c.host_io_b.p, n * 32, io);
 }
 
-int lw_hip_msm_device(lw_curve_t curve, const uint64_t *d_scalars, const void *d_points, size_t n, void *out_point_host,
-                      void *hip_stream) {
-    return msm_device_entry(curve, d_scalars, d_points, n, out_point_host, hip_stream, 0);
-}
-int lw_hip_msm_fr_device(lw_curve_t curve, const uint64_t *d_fr_elements, const void *d_points, size_t n, void *out_point_host,
-                         void *hip_stream) {
-    return msm_device_entry(curve, d_fr_elements, d_points, n, out_point_host, hip_stream, 1);
-}
-
-static int msm_host_entry(lw_curve_t curve, const uint64_t *scalars, size_t n_scalars, const void *points, size_t n_points,
-                          void *out_point, int mont, uint32_t limbs = 4) {
+// One body for the host and device MSM forms: the host form stages the scalars and hands msm_device the points to upload
+static int msm_entry(lw_curve_t curve, const uint64_t *scalars, size_t n_scalars, const void *points, size_t n_points, void *out_point,
+                     void *hip_stream, int mont, uint32_t limbs, bool device) {
     const size_t pb = lw_hip_curve_point_bytes(curve);
     if (pb == 0 || !out_point) { set_error("bad curve or null output"); return LW_ERR_BAD_ARG; }
     if (n_scalars != n_points) {   // MSMError::LengthMismatch (math/src/msm/pippenger.rs:25-27)
@@ -1178,49 +1124,65 @@ static int msm_host_entry(lw_curve_t curve, const uint64_t *scalars, size_t n_sc
         return LW_ERR_LENGTH_MISMATCH;
     }
     if (limbs < 1 || limbs > 8) { set_error("scalar_limbs = %u: 1 .. 8 supported", limbs); return LW_ERR_BAD_ARG; }
-    Entry en(nullptr);
+    const size_t n = n_points;
+    if (n && !device && (!scalars || !points)) { set_error("null buffer"); return LW_ERR_BAD_ARG; }
+    if (n && device && limbs != 4 && ((uintptr_t)scalars & (limbs % 2 ? 7 : 15))) {   // msm_digits_kernel's row loads
+        set_error("scalars of %u limbs must be %d-byte aligned", limbs, limbs % 2 ? 8 : 16);
+        return LW_ERR_BAD_ARG;
+    }
+    Entry en(hip_stream);
     if (en.rc) return en.rc;
     Context &c = en.c;
-    int rc = LW_OK;
-    auto t0 = std::chrono::steady_clock::now();
-    const size_t n = n_points;
-    if (n) {
-        if (!scalars || !points) { set_error("null buffer"); return LW_ERR_BAD_ARG; }
-        if (c.host_io_a.ensure(n * 8 * limbs) || c.host_io_b.ensure(n * pb)) return LW_ERR_ALLOC;
+    const auto t0 = Clock::now();
+    hipStream_t s = en.stream;
+    const void *h_points = nullptr;
+    if (!device) {
+        s = en.use_lane_stream();
+        if (!s) return en.rc;
+        if (n && (c.host_io_a.ensure(n * 8 * limbs) || c.host_io_b.ensure(n * pb))) return LW_ERR_ALLOC;
+        // the scalars first: the sort needs nothing else, and msm_device uploads the points while it runs
+        if (n) LW_HIP_CHECK(hipMemcpyAsync(c.host_io_a.p, scalars, n * 8 * limbs, hipMemcpyHostToDevice, s), LW_ERR_LAUNCH);
+        h_points = n ? points : nullptr;
+        scalars = (const uint64_t *)c.host_io_a.p;
+        points = c.host_io_b.p;
     }
-    hipStream_t io = en.use_lane_stream();
-    if (!io) return en.rc;
-    // the scalars first: the sort needs nothing else, and msm_device uploads the points while it runs
-    if (n) LW_HIP_CHECK(hipMemcpyAsync(c.host_io_a.p, scalars, n * 8 * limbs, hipMemcpyHostToDevice, io), LW_ERR_LAUNCH);
-    rc = msm_device(c, curve, (const uint64_t *)c.host_io_a.p, c.host_io_b.p, n, out_point, io, mont, 0, n ? points : nullptr, limbs);
-    c.timings.last_msm_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c.timings.msm_calls++;
+    const int rc = msm_device(c, curve, scalars, points, n, out_point, s, mont, 0, h_points, limbs);
+    note_msm(c, t0);
     return rc;
 }
+int lw_hip_msm_device(lw_curve_t curve, const uint64_t *d_scalars, const void *d_points, size_t n, void *out_point_host,
+                      void *hip_stream) {
+    return msm_entry(curve, d_scalars, n, d_points, n, out_point_host, hip_stream, 0, 4, true);
+}
+int lw_hip_msm_fr_device(lw_curve_t curve, const uint64_t *d_fr_elements, const void *d_points, size_t n, void *out_point_host,
+                         void *hip_stream) {
+    return msm_entry(curve, d_fr_elements, n, d_points, n, out_point_host, hip_stream, 1, 4, true);
+}
 int lw_hip_msm(lw_curve_t curve, const uint64_t *scalars, size_t n_scalars, const void *points, size_t n_points, void *out_point) {
-    return msm_host_entry(curve, scalars, n_scalars, points, n_points, out_point, 0);
+    return msm_entry(curve, scalars, n_scalars, points, n_points, out_point, nullptr, 0, 4, false);
 }
 int lw_hip_msm_fr(lw_curve_t curve, const uint64_t *fr_elements, size_t n_scalars, const void *points, size_t n_points,
                   void *out_point) {
-    return msm_host_entry(curve, fr_elements, n_scalars, points, n_points, out_point, 1);
+    return msm_entry(curve, fr_elements, n_scalars, points, n_points, out_point, nullptr, 1, 4, false);
 }
 int lw_hip_msm_limbs(lw_curve_t curve, const uint64_t *scalars, uint32_t scalar_limbs, size_t n_scalars, const void *points,
                      size_t n_points, void *out_point) {
-    return msm_host_entry(curve, scalars, n_scalars, points, n_points, out_point, 0, scalar_limbs);
+    return msm_entry(curve, scalars, n_scalars, points, n_points, out_point, nullptr, 0, scalar_limbs, false);
 }
 int lw_hip_msm_limbs_device(lw_curve_t curve, const uint64_t *d_scalars, uint32_t scalar_limbs, const void *d_points, size_t n,
                             void *out_point_host, void *hip_stream) {
-    return msm_device_entry(curve, d_scalars, d_points, n, out_point_host, hip_stream, 0, scalar_limbs);
+    return msm_entry(curve, d_scalars, n, d_points, n, out_point_host, hip_stream, 0, scalar_limbs, true);
 }
 
 // batched operate_with: out[j*m + i] = rows[i] + cols[j]
 int lw_hip_ec_add_outer_device(lw_curve_t curve, const void *d_rows, size_t m, const void *d_cols, size_t k, void *d_out, void *hip_stream) {
-    if (lw_hip_curve_point_bytes(curve) == 0) { set_error("bad curve"); return LW_ERR_BAD_ARG; }
+    const MsmCurveOps *ops = msm_ops(curve);
+    if (!ops) return LW_ERR_BAD_ARG;
     if (m == 0 || k == 0) return LW_OK;
     if (!d_rows || !d_cols || !d_out || (m >> 31) || (k >> 31)) { set_error("null buffer or oversized operand"); return LW_ERR_BAD_ARG; }
     Entry en(hip_stream);
     if (en.rc) return en.rc;
-    return ec_add_outer_device(en.c, curve, d_rows, (uint32_t)m, d_cols, (uint32_t)k, d_out, en.stream);
+    return ops->add_outer(en.c, en.stream, d_rows, (uint32_t)m, d_cols, (uint32_t)k, d_out);
 }
 
 // ---- device-resident affine SRS (see include/lw_hip.h) ----
@@ -1233,8 +1195,7 @@ struct lw_srs {
 };
 extern "C" {
 
-static int srs_build(Context &c, lw_curve_t curve, const void *d_points, size_t n, hipStream_t stream, lw_srs_t **out_srs) {
-    const size_t pb = lw_hip_curve_point_bytes(curve);
+static int srs_build(Context &c, const MsmCurveOps &ops, lw_curve_t curve, const void *d_points, size_t n, hipStream_t stream, lw_srs_t **out_srs) {
     lw_srs *h = new (std::nothrow) lw_srs{curve, n, {}};
     if (!h) return LW_ERR_ALLOC;
     // Large sets keep W = 13 window-shifted copies (c = 20), so that every MSM over them runs its 13 windows into ONE set
@@ -1248,12 +1209,12 @@ static int srs_build(Context &c, lw_curve_t curve, const void *d_points, size_t 
     bool fold = fold_env && n >= ((size_t)1 << (fold_min < 0 ? 0 : fold_min > 40 ? 40 : fold_min)) && (((uint64_t)n * fold_w) >> 31) == 0;
     if (fold) {
         size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || msm_affine_bytes(curve, n) * fold_w > free_b / 4) fold = false;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || ops.affine_bytes(n) * fold_w > free_b / 4) fold = false;
     }
-    if (n && h->pts.ensure(msm_affine_bytes(curve, n) * (fold ? fold_w : 1))) { delete h; return LW_ERR_ALLOC; }
-    int rc = n ? msm_normalize_device(c, curve, d_points, n, h->pts.p, stream) : LW_OK;
+    if (n && h->pts.ensure(ops.affine_bytes(n) * (fold ? fold_w : 1))) { delete h; return LW_ERR_ALLOC; }
+    int rc = n ? ops.normalize(c, stream, d_points, n, h->pts.p) : LW_OK;
     if (rc == LW_OK && fold) {
-        rc = msm_fold_build(c, curve, h->pts.p, n, fold_c, stream);
+        rc = ops.fold_build(c, stream, h->pts.p, n, fold_c);
         if (rc == LW_OK) h->fold_c = fold_c;
     }
     if (rc == LW_OK && n && hipStreamSynchronize(stream) != hipSuccess) { set_error("SRS normalisation failed"); rc = LW_ERR_LAUNCH; }
@@ -1261,26 +1222,28 @@ static int srs_build(Context &c, lw_curve_t curve, const void *d_points, size_t 
     *out_srs = h;
     return LW_OK;
 }
-int lw_hip_srs_create_device(lw_curve_t curve, const void *d_points, size_t n_points, void *hip_stream, lw_srs_t **out_srs) {
-    if (!out_srs || lw_hip_curve_point_bytes(curve) == 0 || (n_points && !d_points)) { set_error("bad curve or null argument"); return LW_ERR_BAD_ARG; }
+// one body for both forms: the host form stages the points on the lane's stream
+static int srs_create_entry(lw_curve_t curve, const void *points, size_t n_points, void *hip_stream, lw_srs_t **out_srs, bool device) {
+    const size_t pb = lw_hip_curve_point_bytes(curve);
+    if (!out_srs || pb == 0 || (n_points && !points)) { set_error("bad curve or null argument"); return LW_ERR_BAD_ARG; }
     Entry en(hip_stream);
     if (en.rc) return en.rc;
     Context &c = en.c;
-    int rc = LW_OK;
-    return srs_build(c, curve, d_points, n_points, (hipStream_t)hip_stream, out_srs);
+    hipStream_t s = en.stream;
+    if (!device) {
+        s = en.use_lane_stream();
+        if (!s) return en.rc;
+        if (n_points && c.host_io_b.ensure(n_points * pb)) return LW_ERR_ALLOC;
+        if (n_points) LW_HIP_CHECK(hipMemcpyAsync(c.host_io_b.p, points, n_points * pb, hipMemcpyHostToDevice, s), LW_ERR_LAUNCH);
+        points = c.host_io_b.p;
+    }
+    return srs_build(c, *msm_ops(curve), curve, points, n_points, s, out_srs);
+}
+int lw_hip_srs_create_device(lw_curve_t curve, const void *d_points, size_t n_points, void *hip_stream, lw_srs_t **out_srs) {
+    return srs_create_entry(curve, d_points, n_points, hip_stream, out_srs, true);
 }
 int lw_hip_srs_create(lw_curve_t curve, const void *points, size_t n_points, lw_srs_t **out_srs) {
-    const size_t pb = lw_hip_curve_point_bytes(curve);
-    if (!out_srs || pb == 0 || (n_points && !points)) { set_error("bad curve or null argument"); return LW_ERR_BAD_ARG; }
-    Entry en(nullptr);
-    if (en.rc) return en.rc;
-    Context &c = en.c;
-    int rc = LW_OK;
-    if (n_points) {
-        if (c.host_io_b.ensure(n_points * pb)) return LW_ERR_ALLOC;
-        LW_HIP_CHECK(hipMemcpy(c.host_io_b.p, points, n_points * pb, hipMemcpyHostToDevice), LW_ERR_LAUNCH);
-    }
-    return srs_build(c, curve, c.host_io_b.p, n_points, 0, out_srs);
+    return srs_create_entry(curve, points, n_points, nullptr, out_srs, false);
 }
 int lw_hip_srs_destroy(lw_srs_t *srs) {
     if (!srs) return LW_OK;
@@ -1296,7 +1259,7 @@ lw_curve_t srs_curve(const lw_srs_t *srs) { return srs->curve; }
 // The MSM against the first n points of an SRS, under an Entry the caller already holds (lw_hip_msm_srs*, and the KZG
 // openings in poly.hip, which commit their quotient with it).
 int msm_srs_locked(Context &c, const lw_srs_t *srs, const uint64_t *d_scalars, size_t n, void *out_point, hipStream_t stream, int mont) {
-    auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = Clock::now();
     // the shifted copies serve calls that use a good part of the set (KZG commits of shorter polynomials take a prefix:
     // below a quarter of it the 2^19 shared buckets would be mostly empty and the plain schedule on copy 0 is faster)
     if (srs->fold_c && n >= srs->n / 4) {
@@ -1306,8 +1269,7 @@ int msm_srs_locked(Context &c, const lw_srs_t *srs, const uint64_t *d_scalars, s
     int rc = msm_device(c, srs->curve, d_scalars, srs->pts.p, n, out_point, stream, mont, 1);
     c.msm_fold_c = 0;
     c.msm_fold_stride = 0;
-    c.timings.last_msm_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c.timings.msm_calls++;
+    note_msm(c, t0);
     return rc;
 }
 }  // namespace lw

@@ -27,26 +27,9 @@
 #include <rccl/rccl.h>
 #include <string.h>
 #include <vector>
-#include "context.h"
+#include "internal.h"
 
 namespace lw {
-
-int ntt_device_locked(Context &c, lw_field_t field, lw_layout_t layout, lw_dir_t dir, const void *d_in, void *d_out,
-                      uint32_t log2n, uint32_t batch, size_t stride, const void *coset, hipStream_t stream, uint32_t in_log2);
-int ntt_cross_device(Context &c, lw_field_t field, lw_layout_t layout, lw_dir_t dir, const void *d_in, void *d_out,
-                     uint32_t log2_total, uint32_t log2_g, uint64_t j2_begin, uint64_t slice_len, uint64_t chunk_stride,
-                     uint32_t batch, uint64_t batch_stride, hipStream_t stream);
-int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const void *d_points, size_t n, void *out_host,
-               hipStream_t stream, int scalars_montgomery, int affine_points, const void *h_points = nullptr,
-               uint32_t scalar_limbs = 4);
-int msm_sum_points_host(lw_curve_t curve, const void *pts, size_t n, void *out);   // msm.hip
-uint32_t msm_window_bits_for(size_t n);                                              // msm.hip: the single-GPU window rule
-int msm_shard_accumulate(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const void *d_points, size_t n, uint32_t cbits, hipStream_t s,
-                         char **buckets);
-int msm_shard_reduce(Context &c, lw_curve_t curve, const char *recv, uint32_t G, uint32_t cbits, char *d_sa, hipStream_t s);
-int msm_shard_combine(lw_curve_t curve, const char *sa_all, uint32_t G, uint32_t cbits, void *out);
-uint32_t field_two_adicity(lw_field_t f);                                          // api.hip
-int check_field_layout(lw_field_t field, lw_layout_t layout);                      // api.hip
 
 // ---------------------------------------------------------------- RCCL, loaded on demand
 struct Rccl {
@@ -246,7 +229,6 @@ static int chain(SyncEvents &ev, hipStream_t from, hipStream_t to) {
     LW_HIP_CHECK(hipStreamWaitEvent(to, e, 0), LW_ERR_LAUNCH);
     return LW_OK;
 }
-int ensure_aux_stream(Context &c);   // msm.hip: the context's side stream
 
 // in[i] / out[i]: buffers of local rank first + i; batch entries in_bstride / out_bstride elements apart.
 //

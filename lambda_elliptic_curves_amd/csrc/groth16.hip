@@ -5,13 +5,10 @@
 //     h_eval_i = (l_i * r_i - o_i) * t_i^-1                          pointwise
 //     h        = interpolate_offset_fft(h_eval, 7)
 // composed from the NTT kernels plus one elementwise kernel; the reference makes four host round trips.
-#include "context.h"
+#include "internal.h"
 #include "ntt_kernels.cuh"
 
 namespace lw {
-
-int ntt_device_locked(Context &c, lw_field_t field, lw_layout_t layout, lw_dir_t dir, const void *d_in, void *d_out,
-                      uint32_t log2n, uint32_t batch, size_t stride, const void *coset, hipStream_t stream, uint32_t in_log2);
 
 struct QapParams {
     const uint4 *l, *r, *o;

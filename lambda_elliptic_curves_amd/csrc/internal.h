@@ -1,0 +1,122 @@
+// Internal functions that one translation unit defines and others call: each is declared here once, with its default
+// arguments, under the file that defines it.  The exported C ABI is include/lw_hip.h.
+#pragma once
+#include "context.h"
+
+namespace lw {
+
+// ---- api.hip
+uint32_t field_two_adicity(lw_field_t f);
+int check_field_layout(lw_field_t field, lw_layout_t layout);
+// in_log2 < log2n (forward only): low-degree extension of dense blocks of 2^in_log2 coefficients, see ntt256.hip / ntt_bb.hip
+int ntt_device_locked(Context &c, lw_field_t field, lw_layout_t layout, lw_dir_t dir, const void *d_in, void *d_out,
+                      uint32_t log2n, uint32_t batch, size_t stride, const void *coset, hipStream_t stream,
+                      uint32_t in_log2 = 0xffffffffu);
+size_t srs_len(const lw_srs_t *srs);
+lw_curve_t srs_curve(const lw_srs_t *srs);
+int msm_srs_locked(Context &c, const lw_srs_t *srs, const uint64_t *d_scalars, size_t n, void *out_point, hipStream_t stream, int mont);
+
+// ---- ntt256.hip
+void ntt_set_debug(uint32_t d);
+uint32_t ntt_get_debug();
+void ntt_set_max_pass_stages(uint32_t r);
+int ntt256_device(Context &c, int field, lw_dir_t dir, const void *d_in, void *d_out, uint32_t log2n, uint32_t batch,
+                  uint64_t stride, const uint32_t *coset_words, hipStream_t stream, uint32_t in_log2);
+int ntt256_gen_powers(int field, uint32_t order, uint64_t count, uint32_t bitrev, bool inverse, const uint32_t *scale_words, void *d_out,
+                      hipStream_t stream);
+// helpers for the multi-GPU cross step (ntt_cross.hip)
+int ntt256_power_tables(Context &c, int field, int slot, const uint32_t *base_words, bool invert, uint32_t hbits,
+                        uint32_t hi_bits, hipStream_t stream, const uint4 **lo, const uint4 **hi);
+int ntt256_root_words(int field, uint32_t order, bool inverse, uint32_t *words);
+int ntt256_inv_u64_words(int field, uint64_t v, uint32_t *words);
+const uint4 *ntt256_twiddle_table(Context &c, int field, lw_dir_t dir, uint32_t log2n, hipStream_t stream, int *rc);
+
+// ---- ntt_bb.hip
+int ntt_bb_device(Context &c, lw_layout_t layout, lw_dir_t dir, const void *d_in, void *d_out, uint32_t log2n,
+                  uint32_t batch, uint64_t stride, const void *coset_offset, hipStream_t stream, uint32_t in_log2);
+int ntt_bb_gen_powers(lw_layout_t layout, uint32_t order, uint64_t count, uint32_t bitrev, bool inverse, const void *scale, void *d_out,
+                      hipStream_t stream);
+const uint32_t *ntt_bb_twiddle_table(Context &c, lw_dir_t dir, uint32_t log2n, hipStream_t stream, int *rc);
+uint32_t ntt_bb_root(uint32_t order, bool inverse);
+
+// ---- ntt_aux.hip
+int gen_twiddles_device(Context &c, lw_field_t field, lw_layout_t layout, uint32_t order, int config, void *d_out, hipStream_t stream);
+int broadcast_device(size_t elem_bytes, const void *d_in, void *d_out, uint64_t n, uint32_t batch, uint64_t out_stride, hipStream_t stream);
+int bitrev_device(size_t elem_bytes, const void *d_in, void *d_out, uint32_t log2n, hipStream_t stream);
+
+// ---- ntt_cross.hip
+int ntt_cross_device(Context &c, lw_field_t field, lw_layout_t layout, lw_dir_t dir, const void *d_in, void *d_out,
+                     uint32_t log2_total, uint32_t log2_g, uint64_t j2_begin, uint64_t slice_len, uint64_t chunk_stride,
+                     uint32_t batch, uint64_t batch_stride, hipStream_t stream);
+
+// ---- merkle.hip
+int merkle_commit_device(Context &c, const void *d_cols, uint32_t n_cols, uint64_t col_stride, uint32_t log2n, int bit_reverse,
+                         void *d_nodes, hipStream_t stream, uint32_t elem_bytes = 32);
+
+// ---- fri.hip
+int fri_layer_device(Context &c, lw_field_t field, const void *d_coeffs, uint64_t n, const uint32_t *zeta, const void *offset_ref,
+                     uint32_t log2_domain, void *d_poly, uint32_t log2_block, void *d_eval, void *d_eval_br, void *d_nodes,
+                     hipStream_t stream);
+
+// ---- groth16.hip
+int groth16_h_device(Context &c, const void *d_l, const void *d_r, const void *d_o, uint32_t log2_gates, void *d_out, void *d_tmp,
+                     hipStream_t stream);
+int stripped_length_device(const void *d_elems, uint64_t n, uint64_t *d_len, hipStream_t stream);
+
+// ---- comm.hip
+void comm_release(Context &c);
+
+// ---- msm.hip
+int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const void *d_points, size_t n, void *out_host,
+               hipStream_t stream, int scalars_montgomery, int affine_points, const void *h_points = nullptr,
+               uint32_t scalar_limbs = 4);
+int msm_sum_points_host(lw_curve_t curve, const void *pts, size_t n, void *out);
+uint32_t msm_window_bits_for(size_t n);   // the single-GPU window rule
+int msm_shard_accumulate(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const void *d_points, size_t n, uint32_t cbits, hipStream_t s,
+                         char **buckets);
+int msm_shard_reduce(Context &c, lw_curve_t curve, const char *recv, uint32_t G, uint32_t cbits, char *d_sa, hipStream_t s);
+int msm_shard_combine(lw_curve_t curve, const char *sa_all, uint32_t G, uint32_t cbits, void *out);
+int ensure_aux_stream(Context &c);   // the context's side stream
+
+uint32_t msm_ch(uint64_t items);       // max points per accumulate work-item (a bucket is cut into equal pieces <= CH)
+int msm_piece_order_enabled();         // LW_HIP_MSM_ORDER=0: work-items take their pieces in key order (A/B)
+uint64_t msm_quad_max_lanes();          // LW_HIP_MSM_QUAD: levels of the bucket reduce with at most this many lanes (8 per group) spread each addition over a quad; 0 = never, ~0 = not set
+uint64_t msm_accumulate_quad_max_lanes();   // LW_HIP_MSM_ACCQ: accumulate launches of projective rows with at most this many lanes (4 per piece) use the quad kernel
+uint32_t msm_g_log();                  // log2 buckets per running-sum group: 3 (8 buckets; 16 -> 8 saved 1 ms of dependent-add latency per MSM, 4 is no better)
+int msm_waves_per_simd();   // LW_HIP_MSM_WAVES (2 or 3): register budget of the accumulate kernel
+
+// host launchers for the curve-independent kernels
+uint32_t msm_sort_coarse_bins(uint32_t c, uint32_t W, uint64_t n);
+uint32_t msm_max_window_bits();
+uint64_t msm_sort_padded_points(uint64_t n);
+int msm_launch_digits(Context &c, const uint32_t *scalars, uint64_t n, uint32_t cb, uint32_t W, uint32_t *dig, hipStream_t s,
+                      uint32_t scalar_limbs);   // scalars: n x scalar_limbs u64, 1 .. 8
+void msm_launch_sort(Context &c, const uint32_t *dig, uint64_t n, uint32_t cb, uint32_t W, uint32_t *coarse_cnt,
+                     uint32_t *coarse_off, uint32_t *coarse_cursor, uint64_t *items, uint32_t *sorted, uint32_t *off, uint32_t K,
+                     uint32_t *maxlen, uint32_t *scan_tmp, uint32_t *sub_off, uint32_t *key_cnt, uint32_t *key_cursor, uint64_t fold_stride,
+                     uint64_t win0, hipStream_t s);
+void msm_launch_scan(const uint32_t *in, uint32_t *out, uint32_t K, int mode, uint32_t *maxlen, uint32_t *scratch, hipStream_t s);
+size_t msm_scan_scratch_bytes(uint32_t K);
+void msm_launch_piece_order(Context &c, const uint32_t *seg_off, const uint32_t *out_off, uint32_t K, uint32_t P, uint32_t *order_tmp,
+                            uint32_t *perm_t, uint32_t *perm_key, hipStream_t s);
+size_t msm_order_tmp_bytes();
+
+// ---- msm_<curve>.hip (LW_MSM_INSTANTIATE in msm_core.cuh): the per-curve MSM operations
+struct MsmCurveOps {
+    // affine: d_points are affine rows made by normalize; points_ready: an event the accumulation waits for (or nullptr)
+    int (*run)(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_points, size_t n, void *out, int affine,
+               hipEvent_t points_ready, uint32_t scalar_limbs);
+    int (*normalize)(Context &c, hipStream_t s, const void *d_in, size_t n, void *d_out);
+    size_t (*affine_bytes)(size_t n);   // bytes of the device-resident affine form of n points (rows may be padded, ec.cuh aff_stride)
+    int (*fold_build)(Context &c, hipStream_t s, void *d_rows, size_t n, uint32_t cbits);
+    int (*shard_accumulate)(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_aff, size_t n, uint32_t cbits, char **buckets);
+    int (*shard_reduce)(Context &c, hipStream_t s, const char *recv, uint32_t G, uint32_t cbits, char *d_sa);
+    void (*shard_combine)(const char *sa_all, uint32_t G, uint32_t cbits, void *out);
+    int (*add_outer)(Context &c, hipStream_t s, const void *d_rows, uint32_t m, const void *d_cols, uint32_t k, void *d_out);
+    void (*sum_points_host)(const void *pts, size_t n, void *out);   // projective points, normalised like every MSM result
+};
+// (not const: HIP would emit a const table for the device too, where the host functions it points to do not exist)
+extern MsmCurveOps msm_ops_bls12381_g1, msm_ops_bn254_g1, msm_ops_bn254_g2, msm_ops_bls12381_g2;
+const MsmCurveOps *msm_ops(lw_curve_t curve);   // msm.hip; nullptr (error set) for a bad curve
+
+}  // namespace lw

@@ -13,7 +13,7 @@
 // and the original 0x01..0x80 padding.
 #include <algorithm>
 #include <stdlib.h>
-#include "context.h"
+#include "internal.h"
 
 namespace lw {
 

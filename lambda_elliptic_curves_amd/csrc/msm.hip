@@ -788,60 +788,13 @@ int msm_waves_per_simd() {
     return w;
 }
 
-int msm_run_bls12381_g1(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_points, size_t n, void *out, int affine,
-                      hipEvent_t points_ready, uint32_t scalar_limbs);
-int msm_run_bn254_g1(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_points, size_t n, void *out, int affine,
-                      hipEvent_t points_ready, uint32_t scalar_limbs);
-int msm_run_bn254_g2(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_points, size_t n, void *out, int affine,
-                      hipEvent_t points_ready, uint32_t scalar_limbs);
-int msm_run_bls12381_g2(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_points, size_t n, void *out, int affine,
-                      hipEvent_t points_ready, uint32_t scalar_limbs);
-int msm_normalize_bls12381_g1(Context &c, hipStream_t s, const void *d_in, size_t n, void *d_out);
-int msm_normalize_bn254_g1(Context &c, hipStream_t s, const void *d_in, size_t n, void *d_out);
-int msm_normalize_bn254_g2(Context &c, hipStream_t s, const void *d_in, size_t n, void *d_out);
-int msm_normalize_bls12381_g2(Context &c, hipStream_t s, const void *d_in, size_t n, void *d_out);
-
-int msm_normalize_device(Context &c, lw_curve_t curve, const void *d_in, size_t n, void *d_out, hipStream_t stream);
-size_t msm_affine_bytes_bls12381_g1(size_t n);
-size_t msm_affine_bytes_bn254_g1(size_t n);
-size_t msm_affine_bytes_bn254_g2(size_t n);
-size_t msm_affine_bytes_bls12381_g2(size_t n);
-int msm_fold_build_bls12381_g1(Context &c, hipStream_t s, void *d_rows, size_t n, uint32_t cbits);
-int msm_fold_build_bn254_g1(Context &c, hipStream_t s, void *d_rows, size_t n, uint32_t cbits);
-int msm_fold_build_bn254_g2(Context &c, hipStream_t s, void *d_rows, size_t n, uint32_t cbits);
-int msm_fold_build_bls12381_g2(Context &c, hipStream_t s, void *d_rows, size_t n, uint32_t cbits);
-int msm_fold_build(Context &c, lw_curve_t curve, void *d_rows, size_t n, uint32_t cbits, hipStream_t stream) {
+const MsmCurveOps *msm_ops(lw_curve_t curve) {
     switch (curve) {
-        case LW_CURVE_BLS12_381_G1: return msm_fold_build_bls12381_g1(c, stream, d_rows, n, cbits);
-        case LW_CURVE_BN254_G1: return msm_fold_build_bn254_g1(c, stream, d_rows, n, cbits);
-        case LW_CURVE_BN254_G2: return msm_fold_build_bn254_g2(c, stream, d_rows, n, cbits);
-        case LW_CURVE_BLS12_381_G2: return msm_fold_build_bls12381_g2(c, stream, d_rows, n, cbits);
-        default: return LW_ERR_BAD_ARG;
-    }
-}
-// bytes of the device-resident affine form of n points (rows may be padded, ec.cuh aff_stride)
-size_t msm_affine_bytes(lw_curve_t curve, size_t n) {
-    switch (curve) {
-        case LW_CURVE_BLS12_381_G1: return msm_affine_bytes_bls12381_g1(n);
-        case LW_CURVE_BN254_G1: return msm_affine_bytes_bn254_g1(n);
-        case LW_CURVE_BN254_G2: return msm_affine_bytes_bn254_g2(n);
-        case LW_CURVE_BLS12_381_G2: return msm_affine_bytes_bls12381_g2(n);
-        default: return 0;
-    }
-}
-int ec_add_outer_bls12381_g1(Context &c, hipStream_t s, const void *d_rows, uint32_t m, const void *d_cols, uint32_t k, void *d_out);
-int ec_add_outer_bn254_g1(Context &c, hipStream_t s, const void *d_rows, uint32_t m, const void *d_cols, uint32_t k, void *d_out);
-int ec_add_outer_bn254_g2(Context &c, hipStream_t s, const void *d_rows, uint32_t m, const void *d_cols, uint32_t k, void *d_out);
-int ec_add_outer_bls12381_g2(Context &c, hipStream_t s, const void *d_rows, uint32_t m, const void *d_cols, uint32_t k, void *d_out);
-
-int ec_add_outer_device(Context &c, lw_curve_t curve, const void *d_rows, uint32_t m, const void *d_cols, uint32_t k, void *d_out,
-                        hipStream_t stream) {
-    switch (curve) {
-        case LW_CURVE_BLS12_381_G1: return ec_add_outer_bls12381_g1(c, stream, d_rows, m, d_cols, k, d_out);
-        case LW_CURVE_BN254_G1: return ec_add_outer_bn254_g1(c, stream, d_rows, m, d_cols, k, d_out);
-        case LW_CURVE_BN254_G2: return ec_add_outer_bn254_g2(c, stream, d_rows, m, d_cols, k, d_out);
-        case LW_CURVE_BLS12_381_G2: return ec_add_outer_bls12381_g2(c, stream, d_rows, m, d_cols, k, d_out);
-        default: set_error("bad curve %d", (int)curve); return LW_ERR_BAD_ARG;
+        case LW_CURVE_BLS12_381_G1: return &msm_ops_bls12381_g1;
+        case LW_CURVE_BN254_G1: return &msm_ops_bn254_g1;
+        case LW_CURVE_BN254_G2: return &msm_ops_bn254_g2;
+        case LW_CURVE_BLS12_381_G2: return &msm_ops_bls12381_g2;
+        default: set_error("bad curve %d", (int)curve); return nullptr;
     }
 }
 
@@ -855,7 +808,7 @@ static int msm_normalize_min_log2(lw_curve_t curve) {
     }
 }
 
-// affine_points: d_points are affine pairs produced by msm_normalize_device (2 field elements per row)
+// affine_points: d_points are affine pairs produced by the curve's normalize (2 field elements per row)
 // The context's side stream (MSM: normalisation beside the sort; sharded NTT: exchanges beside the kernels).
 int ensure_aux_stream(Context &c) {
     if (c.aux_stream) return LW_OK;
@@ -887,6 +840,8 @@ int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const vo
         set_error("MSM scalars of %u limbs", scalar_limbs);
         return LW_ERR_BAD_ARG;
     }
+    const MsmCurveOps *ops = msm_ops(curve);
+    if (!ops) return LW_ERR_BAD_ARG;
     const size_t pbytes = lw_hip_curve_point_bytes(curve);
     bool upload_pending = h_points != nullptr && n != 0;
     if (scalars_montgomery && n) {
@@ -907,7 +862,7 @@ int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const vo
     static const int norm_min_env = [] { const char *e = tuning_env("LW_HIP_MSM_NORM_MIN"); return e ? atoi(e) : -1; }();   // tuning only
     const int norm_min_log2 = norm_min_env >= 0 ? norm_min_env : msm_normalize_min_log2(curve);
     if (!affine_points && auto_norm && n >= ((size_t)1 << norm_min_log2)) {
-        const size_t aff_bytes = msm_affine_bytes(curve, n);
+        const size_t aff_bytes = ops->affine_bytes(n);
         if (c.msm_affine.ensure(aff_bytes)) return LW_ERR_ALLOC;
         // The normalisation reads only the points and the bucket sort only the scalars, so the normalisation runs on a
         // side stream beside the sort and the main stream joins it just before the first accumulation launch (both are
@@ -918,7 +873,7 @@ int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const vo
                 LW_HIP_CHECK(hipMemcpyAsync((void *)d_points, h_points, n * pbytes, hipMemcpyHostToDevice, stream), LW_ERR_LAUNCH);
                 upload_pending = false;
             }
-            int rc = msm_normalize_device(c, curve, d_points, n, c.msm_affine.p, stream);
+            int rc = ops->normalize(c, stream, d_points, n, c.msm_affine.p);
             if (rc) return rc;
         } else if (upload_pending) {
             int rc = ensure_aux_stream(c);
@@ -928,8 +883,8 @@ int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const vo
             const void *src = d_points;
             // in chunks of 2^20 points: chunk k is normalised (second side stream) while chunk k + 1 is on the bus, so that what
             // is left after the last byte arrives is one chunk's normalisation, not the whole set's
-            c.msm_after_sort = [&c, curve, src, h_points, n, pbytes]() -> int {
-                const size_t CHUNK = (size_t)1 << 20, astride = msm_affine_bytes(curve, 1);
+            c.msm_after_sort = [&c, ops, src, h_points, n, pbytes]() -> int {
+                const size_t CHUNK = (size_t)1 << 20, astride = ops->affine_bytes(1);
                 hipEvent_t ev = nullptr;
                 if (!c.sync_pool.empty()) { ev = c.sync_pool.back(); c.sync_pool.pop_back(); }
                 else if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { set_error("hipEventCreate failed"); return LW_ERR_LAUNCH; }
@@ -943,7 +898,7 @@ int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const vo
                         r = LW_ERR_LAUNCH;
                         break;
                     }
-                    r = msm_normalize_device(c, curve, d, m, (char *)c.msm_affine.p + off * astride, c.aux_hi);
+                    r = ops->normalize(c, c.aux_hi, d, m, (char *)c.msm_affine.p + off * astride);
                 }
                 c.sync_pool.push_back(ev);
                 if (r) return r;
@@ -963,7 +918,7 @@ int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const vo
         // kernel first overlaps the normalisation takes ~2-3 ms longer, and a later start only moves that cost: 56.9 ms with
         // the normalisation first, 58.2 / 59.5 ms with the sort / the digit kernel first.)
         {
-            int rc = msm_normalize_device(c, curve, d_points, n, c.msm_affine.p, c.aux_stream);
+            int rc = ops->normalize(c, c.aux_stream, d_points, n, c.msm_affine.p);
             if (rc) return rc;
             LW_HIP_CHECK(hipEventRecord(c.aux_join, c.aux_stream), LW_ERR_LAUNCH);
         }
@@ -974,14 +929,7 @@ int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const vo
     }
     if (upload_pending)   // no normalisation: the accumulation reads the rows as they are
         LW_HIP_CHECK(hipMemcpyAsync((void *)d_points, h_points, n * pbytes, hipMemcpyHostToDevice, stream), LW_ERR_LAUNCH);
-    int rc;
-    switch (curve) {
-        case LW_CURVE_BLS12_381_G1: rc = msm_run_bls12381_g1(c, stream, d_scalars, d_points, n, out_host, affine_points, join, scalar_limbs); break;
-        case LW_CURVE_BN254_G1: rc = msm_run_bn254_g1(c, stream, d_scalars, d_points, n, out_host, affine_points, join, scalar_limbs); break;
-        case LW_CURVE_BN254_G2: rc = msm_run_bn254_g2(c, stream, d_scalars, d_points, n, out_host, affine_points, join, scalar_limbs); break;
-        case LW_CURVE_BLS12_381_G2: rc = msm_run_bls12381_g2(c, stream, d_scalars, d_points, n, out_host, affine_points, join, scalar_limbs); break;
-        default: set_error("bad curve %d", (int)curve); return LW_ERR_BAD_ARG;
-    }
+    const int rc = ops->run(c, stream, d_scalars, d_points, n, out_host, affine_points, join, scalar_limbs);
     c.msm_after_sort = nullptr;                                  // (a run that failed before its sort never took it)
     if (rc && join) {   // do not leave the side streams running into a failed call's buffers
         (void)hipStreamSynchronize(c.aux_stream);
@@ -990,75 +938,36 @@ int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const vo
     return rc;
 }
 
-// ---- sharded MSM (comm.hip): per-curve dispatch of the three phases around the bucket-slice exchange ----
-#define LW_SHARD_DECL(SUFFIX)                                                                                                                 \
-    int msm_shard_accumulate_##SUFFIX(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_aff, size_t n, uint32_t cbits, char **buckets); \
-    int msm_shard_reduce_##SUFFIX(Context &c, hipStream_t s, const char *recv, uint32_t G, uint32_t cbits, char *d_sa);                        \
-    void msm_shard_combine_##SUFFIX(const char *sa_all, uint32_t G, uint32_t cbits, void *out);
-LW_SHARD_DECL(bls12381_g1) LW_SHARD_DECL(bn254_g1) LW_SHARD_DECL(bn254_g2) LW_SHARD_DECL(bls12381_g2)
-#undef LW_SHARD_DECL
+// ---- sharded MSM (comm.hip): the three phases around the bucket-slice exchange ----
 uint32_t msm_window_bits_for(size_t n) { return pick_window(n, 256); }
 // local pairs -> dense bucket array in the context workspace.  The points are normalised first whatever n is, so that every
 // rank's buckets live on the same curve model (the isomorphic one where the curve has it) and can be added across ranks.
 int msm_shard_accumulate(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const void *d_points, size_t n, uint32_t cbits, hipStream_t s,
                          char **buckets) {
+    const MsmCurveOps *ops = msm_ops(curve);
+    if (!ops) return LW_ERR_BAD_ARG;
     if (n) {
-        if (c.msm_affine.ensure(msm_affine_bytes(curve, n))) return LW_ERR_ALLOC;
-        int rc = msm_normalize_device(c, curve, d_points, n, c.msm_affine.p, s);
+        if (c.msm_affine.ensure(ops->affine_bytes(n))) return LW_ERR_ALLOC;
+        int rc = ops->normalize(c, s, d_points, n, c.msm_affine.p);
         if (rc) return rc;
     }
-    switch (curve) {
-        case LW_CURVE_BLS12_381_G1: return msm_shard_accumulate_bls12381_g1(c, s, d_scalars, c.msm_affine.p, n, cbits, buckets);
-        case LW_CURVE_BN254_G1: return msm_shard_accumulate_bn254_g1(c, s, d_scalars, c.msm_affine.p, n, cbits, buckets);
-        case LW_CURVE_BN254_G2: return msm_shard_accumulate_bn254_g2(c, s, d_scalars, c.msm_affine.p, n, cbits, buckets);
-        case LW_CURVE_BLS12_381_G2: return msm_shard_accumulate_bls12381_g2(c, s, d_scalars, c.msm_affine.p, n, cbits, buckets);
-        default: set_error("bad curve %d", (int)curve); return LW_ERR_BAD_ARG;
-    }
+    return ops->shard_accumulate(c, s, d_scalars, c.msm_affine.p, n, cbits, buckets);
 }
 int msm_shard_reduce(Context &c, lw_curve_t curve, const char *recv, uint32_t G, uint32_t cbits, char *d_sa, hipStream_t s) {
-    switch (curve) {
-        case LW_CURVE_BLS12_381_G1: return msm_shard_reduce_bls12381_g1(c, s, recv, G, cbits, d_sa);
-        case LW_CURVE_BN254_G1: return msm_shard_reduce_bn254_g1(c, s, recv, G, cbits, d_sa);
-        case LW_CURVE_BN254_G2: return msm_shard_reduce_bn254_g2(c, s, recv, G, cbits, d_sa);
-        case LW_CURVE_BLS12_381_G2: return msm_shard_reduce_bls12381_g2(c, s, recv, G, cbits, d_sa);
-        default: set_error("bad curve %d", (int)curve); return LW_ERR_BAD_ARG;
-    }
+    const MsmCurveOps *ops = msm_ops(curve);
+    return ops ? ops->shard_reduce(c, s, recv, G, cbits, d_sa) : LW_ERR_BAD_ARG;
 }
 int msm_shard_combine(lw_curve_t curve, const char *sa_all, uint32_t G, uint32_t cbits, void *out) {
-    switch (curve) {
-        case LW_CURVE_BLS12_381_G1: msm_shard_combine_bls12381_g1(sa_all, G, cbits, out); return LW_OK;
-        case LW_CURVE_BN254_G1: msm_shard_combine_bn254_g1(sa_all, G, cbits, out); return LW_OK;
-        case LW_CURVE_BN254_G2: msm_shard_combine_bn254_g2(sa_all, G, cbits, out); return LW_OK;
-        case LW_CURVE_BLS12_381_G2: msm_shard_combine_bls12381_g2(sa_all, G, cbits, out); return LW_OK;
-        default: set_error("bad curve %d", (int)curve); return LW_ERR_BAD_ARG;
-    }
-}
-
-// Sum of a few projective points on the host, normalised like every MSM result (the combine step of the sharded MSM).
-template <class C>
-static void sum_points_host_t(const void *pts, size_t n, void *out) {
-    Point<C> acc = pt_identity<C>();
-    for (size_t i = 0; i < n; i++) acc = pt_add<C>(acc, pt_load<C>((const char *)pts + i * 3 * C::B::BYTES));
-    pt_store<C>(out, pt_to_affine<C>(acc));
+    const MsmCurveOps *ops = msm_ops(curve);
+    if (!ops) return LW_ERR_BAD_ARG;
+    ops->shard_combine(sa_all, G, cbits, out);
+    return LW_OK;
 }
 int msm_sum_points_host(lw_curve_t curve, const void *pts, size_t n, void *out) {
-    switch (curve) {
-        case LW_CURVE_BLS12_381_G1: sum_points_host_t<Bls12381G1>(pts, n, out); return LW_OK;
-        case LW_CURVE_BN254_G1: sum_points_host_t<Bn254G1>(pts, n, out); return LW_OK;
-        case LW_CURVE_BN254_G2: sum_points_host_t<Bn254G2>(pts, n, out); return LW_OK;
-        case LW_CURVE_BLS12_381_G2: sum_points_host_t<Bls12381G2>(pts, n, out); return LW_OK;
-        default: set_error("bad curve %d", (int)curve); return LW_ERR_BAD_ARG;
-    }
-}
-
-int msm_normalize_device(Context &c, lw_curve_t curve, const void *d_in, size_t n, void *d_out, hipStream_t stream) {
-    switch (curve) {
-        case LW_CURVE_BLS12_381_G1: return msm_normalize_bls12381_g1(c, stream, d_in, n, d_out);
-        case LW_CURVE_BN254_G1: return msm_normalize_bn254_g1(c, stream, d_in, n, d_out);
-        case LW_CURVE_BN254_G2: return msm_normalize_bn254_g2(c, stream, d_in, n, d_out);
-        case LW_CURVE_BLS12_381_G2: return msm_normalize_bls12381_g2(c, stream, d_in, n, d_out);
-        default: set_error("bad curve %d", (int)curve); return LW_ERR_BAD_ARG;
-    }
+    const MsmCurveOps *ops = msm_ops(curve);
+    if (!ops) return LW_ERR_BAD_ARG;
+    ops->sum_points_host(pts, n, out);
+    return LW_OK;
 }
 
 }  // namespace lw

@@ -4,35 +4,12 @@
 #include <stdlib.h>
 #include <algorithm>
 #include <vector>
-#include "context.h"
+#include "internal.h"
 #include "ec.cuh"
 
 namespace lw {
 
-uint32_t msm_ch(uint64_t items);       // max points per accumulate work-item (a bucket is cut into equal pieces <= CH)
-int msm_piece_order_enabled();         // LW_HIP_MSM_ORDER=0: work-items take their pieces in key order (A/B)
-uint64_t msm_quad_max_lanes();          // LW_HIP_MSM_QUAD: levels of the bucket reduce with at most this many lanes (8 per group) spread each addition over a quad; 0 = never, ~0 = not set
-uint64_t msm_accumulate_quad_max_lanes();   // LW_HIP_MSM_ACCQ: accumulate launches of projective rows with at most this many lanes (4 per piece) use the quad kernel
-uint32_t msm_g_log();                  // log2 buckets per running-sum group: 3 (8 buckets; 16 -> 8 saved 1 ms of dependent-add latency per MSM, 4 is no better)
 constexpr int MSM_THREADS = 128;
-
-// host launchers for the curve-independent kernels (defined in msm.hip)
-uint32_t msm_sort_coarse_bins(uint32_t c, uint32_t W, uint64_t n);
-uint32_t msm_max_window_bits();
-uint64_t msm_sort_padded_points(uint64_t n);
-int msm_launch_digits(Context &c, const uint32_t *scalars, uint64_t n, uint32_t cb, uint32_t W, uint32_t *dig, hipStream_t s,
-                      uint32_t scalar_limbs);   // scalars: n x scalar_limbs u64, 1 .. 8
-void msm_launch_sort(Context &c, const uint32_t *dig, uint64_t n, uint32_t cb, uint32_t W, uint32_t *coarse_cnt,
-                     uint32_t *coarse_off, uint32_t *coarse_cursor, uint64_t *items, uint32_t *sorted, uint32_t *off, uint32_t K,
-                     uint32_t *maxlen, uint32_t *scan_tmp, uint32_t *sub_off, uint32_t *key_cnt, uint32_t *key_cursor, uint64_t fold_stride,
-                     uint64_t win0, hipStream_t s);
-int ensure_aux_stream(Context &c);   // msm.hip: the context's side stream
-void msm_launch_scan(const uint32_t *in, uint32_t *out, uint32_t K, int mode, uint32_t *maxlen, uint32_t *scratch, hipStream_t s);
-size_t msm_scan_scratch_bytes(uint32_t K);
-void msm_launch_piece_order(Context &c, const uint32_t *seg_off, const uint32_t *out_off, uint32_t K, uint32_t P, uint32_t *order_tmp,
-                            uint32_t *perm_t, uint32_t *perm_key, hipStream_t s);
-size_t msm_order_tmp_bytes();
-int msm_waves_per_simd();   // LW_HIP_MSM_WAVES (2 or 3): register budget of the accumulate kernel
 
 // ---------------------------------------------------------------- accumulate
 // All device point arrays (caller's points, partial sums, buckets, running-sum temporaries) use the reference
@@ -973,10 +950,18 @@ struct MsmRunner {
     }
 };
 
-// one translation unit per curve (they compile in parallel): the three entry points msm.hip dispatches to
+// Sum of a few projective points on the host, normalised like every MSM result (the combine step of the sharded MSM).
+template <class C>
+static void sum_points_host_t(const void *pts, size_t n, void *out) {
+    Point<C> acc = pt_identity<C>();
+    for (size_t i = 0; i < n; i++) acc = pt_add<C>(acc, pt_load<C>((const char *)pts + i * 3 * C::B::BYTES));
+    pt_store<C>(out, pt_to_affine<C>(acc));
+}
+
+// one translation unit per curve (they compile in parallel): the operations msm.hip dispatches to through msm_ops_SUFFIX
 #define LW_MSM_INSTANTIATE(CURVE, SUFFIX)                                                                                        \
-    int msm_run_##SUFFIX(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_points, size_t n, void *out, int affine, \
-                         hipEvent_t points_ready, uint32_t scalar_limbs) {                                                         \
+    static int msm_run_##SUFFIX(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_points, size_t n, void *out,  \
+                                int affine, hipEvent_t points_ready, uint32_t scalar_limbs) {                                     \
         if (affine && IsoOf<CURVE>::has) {   /* normalised rows live on the isomorphic model (msm_to_affine_kernel) */           \
             MsmRunner<typename IsoOf<CURVE>::type> ri{c, s, 0};                                                                    \
             ri.affine = true;                                                                                                      \
@@ -994,32 +979,36 @@ struct MsmRunner {
         }                                                                                                                          \
         return r.run(d_scalars, d_points, n, out, scalar_limbs);                                                                   \
     }                                                                                                                              \
-    int msm_normalize_##SUFFIX(Context &c, hipStream_t s, const void *d_in, size_t n, void *d_out) {                               \
+    static int msm_normalize_##SUFFIX(Context &c, hipStream_t s, const void *d_in, size_t n, void *d_out) {                        \
         MsmRunner<CURVE> r{c, s, 0};                                                                                               \
         return r.normalize(d_in, n, d_out);                                                                                        \
     }                                                                                                                              \
-    size_t msm_affine_bytes_##SUFFIX(size_t n) { return MsmRunner<CURVE>::affine_bytes(n); }                                      \
-    int msm_fold_build_##SUFFIX(Context &c, hipStream_t s, void *d_rows, size_t n, uint32_t cbits) {   /* rows live on IsoOf<CURVE> */ \
+    static size_t msm_affine_bytes_##SUFFIX(size_t n) { return MsmRunner<CURVE>::affine_bytes(n); }                               \
+    static int msm_fold_build_##SUFFIX(Context &c, hipStream_t s, void *d_rows, size_t n, uint32_t cbits) {   /* rows live on IsoOf<CURVE> */ \
         MsmRunner<typename IsoOf<CURVE>::type> r{c, s, 0};                                                                         \
         return r.build_fold(d_rows, n, cbits);                                                                                     \
     }                                      \
     /* sharded MSM phases: always on the normalised (affine) rows, i.e. on IsoOf<CURVE> where the curve has a cheaper model */  \
-    int msm_shard_accumulate_##SUFFIX(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_aff, size_t n, uint32_t cbits, \
-                                      char **buckets) {                                                                             \
+    static int msm_shard_accumulate_##SUFFIX(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_aff, size_t n,  \
+                                             uint32_t cbits, char **buckets) {                                                     \
         MsmRunner<typename IsoOf<CURVE>::type> r{c, s, 0};                                                                         \
         r.affine = true;                                                                                                           \
         return r.shard_accumulate(d_scalars, d_aff, n, cbits, buckets);                                                            \
     }                                                                                                                              \
-    int msm_shard_reduce_##SUFFIX(Context &c, hipStream_t s, const char *recv, uint32_t G, uint32_t cbits, char *d_sa) {           \
+    static int msm_shard_reduce_##SUFFIX(Context &c, hipStream_t s, const char *recv, uint32_t G, uint32_t cbits, char *d_sa) {    \
         MsmRunner<typename IsoOf<CURVE>::type> r{c, s, 0};                                                                         \
         return r.shard_reduce(recv, G, cbits, d_sa);                                                                               \
     }                                                                                                                              \
-    void msm_shard_combine_##SUFFIX(const char *sa_all, uint32_t G, uint32_t cbits, void *out) {                                   \
+    static void msm_shard_combine_##SUFFIX(const char *sa_all, uint32_t G, uint32_t cbits, void *out) {                            \
         MsmRunner<typename IsoOf<CURVE>::type>::shard_combine_host(sa_all, G, cbits, out);                                         \
     }                                                                                                                              \
-    int ec_add_outer_##SUFFIX(Context &c, hipStream_t s, const void *d_rows, uint32_t m, const void *d_cols, uint32_t k, void *d_out) { \
+    static int ec_add_outer_##SUFFIX(Context &c, hipStream_t s, const void *d_rows, uint32_t m, const void *d_cols, uint32_t k,    \
+                                     void *d_out) {                                                                                \
         MsmRunner<CURVE> r{c, s, 0};                                                                                               \
         return r.add_outer(d_rows, m, d_cols, k, d_out);                                                                           \
-    }
+    }                                                                                                                              \
+    MsmCurveOps msm_ops_##SUFFIX = {msm_run_##SUFFIX,          msm_normalize_##SUFFIX,   msm_affine_bytes_##SUFFIX,        \
+                                          msm_fold_build_##SUFFIX,   msm_shard_accumulate_##SUFFIX, msm_shard_reduce_##SUFFIX,   \
+                                          msm_shard_combine_##SUFFIX, ec_add_outer_##SUFFIX, sum_points_host_t<CURVE>};
 
 }  // namespace lw

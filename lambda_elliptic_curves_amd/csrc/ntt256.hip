@@ -1,7 +1,7 @@
 // Host side of the 256-bit-field NTT: twiddle cache, pass planning, launches.
 #include <stdlib.h>
 #include <vector>
-#include "context.h"
+#include "internal.h"
 #include "ntt_kernels.cuh"
 
 namespace lw {

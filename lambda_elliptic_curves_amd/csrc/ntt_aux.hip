@@ -3,13 +3,10 @@
 //                                    (math/src/fft/cpu/roots_of_unity.rs:13-75)
 //   bitrev_permutation(input)     -> out[i] = in[bitrev(i)]  (math/src/fft/cpu/bit_reversing.rs:2-18)
 // Both are served from the library's cached bit-reversed twiddle table / a plain gather kernel.
-#include "context.h"
+#include "internal.h"
 #include "ntt_kernels.cuh"
 
 namespace lw {
-
-const uint4 *ntt256_twiddle_table(Context &c, int field, lw_dir_t dir, uint32_t log2n, hipStream_t stream, int *rc);
-const uint32_t *ntt_bb_twiddle_table(Context &c, lw_dir_t dir, uint32_t log2n, hipStream_t stream, int *rc);
 
 // out (reference layout) [i] = T[natural ? bitrev(i) : i]   (T[g] = w^bitrev(g), internal layout)
 template <class F>

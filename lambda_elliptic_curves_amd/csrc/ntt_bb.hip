@@ -9,12 +9,10 @@
 // converted on load/store (field.cuh bb_from_r64 / bb_to_r64), which returns the same canonical residues.
 #include <stdlib.h>
 #include <vector>
-#include "context.h"
+#include "internal.h"
 #include "field.cuh"
 
 namespace lw {
-
-uint32_t ntt_get_debug();
 
 constexpr int BB_TILE_LOG = 13;            // 8192 u32 = 32 KiB of LDS
 constexpr int BB_TILE = 1 << BB_TILE_LOG;

@@ -8,16 +8,10 @@
 // The reference has no multi-device path; the result is the same vector Polynomial::evaluate_fft
 // returns (math/src/fft/polynomial.rs:25-68), sharded.
 #include <vector>
-#include "context.h"
+#include "internal.h"
 #include "ntt_kernels.cuh"
 
 namespace lw {
-
-int ntt256_power_tables(Context &c, int field, int slot, const uint32_t *base_words, bool invert, uint32_t hbits,
-                        uint32_t hi_bits, hipStream_t stream, const uint4 **lo, const uint4 **hi);
-int ntt256_root_words(int field, uint32_t order, bool inverse, uint32_t *words);
-int ntt256_inv_u64_words(int field, uint64_t v, uint32_t *words);
-const uint4 *ntt256_twiddle_table(Context &c, int field, lw_dir_t dir, uint32_t log2n, hipStream_t stream, int *rc);
 
 struct CrossParams {
     const uint4 *in;
@@ -138,9 +132,6 @@ __global__ __launch_bounds__(256) void bb_cross_kernel(CrossParamsBb p) {
         else reinterpret_cast<uint32_t *>(p.out)[off + k1 * p.chunk_stride] = y;
     }
 }
-
-const uint32_t *ntt_bb_twiddle_table(Context &c, lw_dir_t dir, uint32_t log2n, hipStream_t stream, int *rc);
-uint32_t ntt_bb_root(uint32_t order, bool inverse);
 
 template <class F>
 static int cross256(Context &c, int field, lw_dir_t dir, const void *d_in, void *d_out, uint32_t log2_total, uint32_t lg,

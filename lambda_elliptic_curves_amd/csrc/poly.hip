@@ -17,7 +17,7 @@
 // return canonical residues for canonical operands, including Stark252 (LAZY applies to the NTT butterflies only).
 #include <string.h>
 #include <vector>
-#include "context.h"
+#include "internal.h"
 #include "field.cuh"
 
 namespace lw {
@@ -326,10 +326,6 @@ static int kzg_scalar_field(lw_curve_t curve) {
         default: return -1;
     }
 }
-
-size_t srs_len(const lw_srs_t *srs);
-lw_curve_t srs_curve(const lw_srs_t *srs);
-int msm_srs_locked(Context &c, const lw_srs_t *srs, const uint64_t *d_scalars, size_t n, void *out_point, hipStream_t stream, int mont);
 
 // KZG open of sum_kk u^kk p_kk at x under an Entry: quotient (canonical) into library memory, then the SRS MSM
 static int kzg_open_locked(Context &c, const lw_srs_t *srs, const PolyRef *refs, uint32_t k, const void *x, const void *ups,

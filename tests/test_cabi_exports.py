@@ -1,5 +1,6 @@
 """CPU-side checks of the drop-in boundary: the shared library loads and exports every symbol that
 include/lw_hip.h declares; without a GPU every compute entry point fails loudly (no CPU fallback)."""
+import ctypes as C
 import os
 import re
 
@@ -45,6 +46,62 @@ def test_host_side_argument_checks_do_not_need_a_device():
     # zero polynomial: len zeros, no transform, no device needed (fft/polynomial.rs:33-35)
     z = fft.evaluate_fft(fft.Stark252PrimeField, np.zeros((3, 4), np.uint64), 2, 8)
     assert z.shape == (16, 4) and not z.any()
+    # every C entry point, one bad argument at a time: the same code with or without a device
+    from lambda_elliptic_curves_amd import _lib
+    L = C.CDLL(_lib.LIB_PATH)   # a handle of its own: plain ctypes arguments, no argtypes
+    buf = np.zeros(4096, np.uint8)
+    P, Q, N = C.c_void_p(buf.ctypes.data), C.c_void_p(buf.ctypes.data + 2048), C.c_void_p(None)
+    i, u32, sz = C.c_int, C.c_uint32, C.c_size_t
+    S, FR, BB, U64, R32, EXT4, FWD = i(0), i(1), i(2), i(0), i(1), i(3), i(0)
+    G1, BAD_CURVE = i(0), i(7)
+    nttd = lambda f, l, lg, batch, stride, d_in: L.lw_hip_ntt_device(f, l, FWD, d_in, P, u32(lg), u32(batch), sz(stride), N, N)
+    ntth = lambda f, l, lg, batch, stride, d_in: L.lw_hip_ntt(f, l, FWD, d_in, P, u32(lg), u32(batch), sz(stride), N)
+    cross = lambda f, l, lg, d_in: L.lw_hip_ntt_cross_device(f, l, FWD, d_in, P, u32(lg), u32(1), sz(0), sz(8), sz(8), u32(1), sz(16), N)
+    cases = []
+    for name, ntt in (("ntt", ntth), ("ntt_device", nttd)):
+        cases += [
+            (name + " layout", lambda ntt=ntt: ntt(S, R32, 4, 1, 0, P), _lib.ERR_BAD_ARG),
+            (name + " order 64", lambda ntt=ntt: ntt(S, U64, 64, 1, 0, P), _lib.ERR_ORDER_TOO_LARGE),
+            (name + " root", lambda ntt=ntt: ntt(FR, U64, 33, 1, 0, P), _lib.ERR_ROOT_OF_UNITY),
+            (name + " stride", lambda ntt=ntt: ntt(S, U64, 4, 2, 8, P), _lib.ERR_BAD_ARG),
+            (name + " null", lambda ntt=ntt: ntt(S, U64, 4, 1, 0, N), _lib.ERR_BAD_ARG),
+        ]
+    cases += [
+        ("ntt_lde_device layout", lambda: L.lw_hip_ntt_lde_device(S, EXT4, P, u32(2), P, u32(4), u32(1), N, N), _lib.ERR_BAD_ARG),
+        ("ntt_lde_device order 64", lambda: L.lw_hip_ntt_lde_device(S, U64, P, u32(2), P, u32(64), u32(1), N, N), _lib.ERR_ORDER_TOO_LARGE),
+        ("ntt_lde_device null", lambda: L.lw_hip_ntt_lde_device(S, U64, N, u32(2), P, u32(4), u32(1), N, N), _lib.ERR_BAD_ARG),
+        ("ntt_cross_device layout", lambda: cross(S, R32, 4, P), _lib.ERR_BAD_ARG),
+        ("ntt_cross_device order 64", lambda: cross(S, U64, 64, P), _lib.ERR_ORDER_TOO_LARGE),
+        ("ntt_cross_device null", lambda: cross(S, U64, 4, N), _lib.ERR_BAD_ARG),
+        ("bitrev pow2", lambda: L.lw_hip_bitrev_permutation(S, U64, P, P, sz(3)), _lib.ERR_INPUT_NOT_POW2),
+        ("interpolate pow2", lambda: L.lw_polynomial_interpolate_fft(S, U64, P, sz(3), N, P, N), _lib.ERR_INPUT_NOT_POW2),
+        ("fri_layer pow2", lambda: L.lw_stark_fri_layer(S, P, sz(4), P, P, sz(6), P, N, P, P, N), _lib.ERR_INPUT_NOT_POW2),
+        ("fri_layer_device pow2", lambda: L.lw_stark_fri_layer_device(S, P, sz(4), P, P, sz(6), Q, N, P, N, N), _lib.ERR_INPUT_NOT_POW2),
+        ("fri_layer field", lambda: L.lw_stark_fri_layer(BB, P, sz(4), P, P, sz(8), P, N, P, P, N), _lib.ERR_BAD_ARG),
+        ("groth16_h pow2", lambda: L.lw_groth16_h_coefficients(P, P, P, sz(2), sz(3), P, N), _lib.ERR_INPUT_NOT_POW2),
+        ("groth16_h_device pow2", lambda: L.lw_groth16_h_coefficients_device(P, P, P, sz(2), sz(3), P, N, N), _lib.ERR_INPUT_NOT_POW2),
+        ("groth16_h null", lambda: L.lw_groth16_h_coefficients(N, P, P, sz(0), sz(4), P, N), _lib.ERR_BAD_ARG),
+        ("msm_limbs 0", lambda: L.lw_hip_msm_limbs(G1, P, u32(0), sz(1), P, sz(1), P), _lib.ERR_BAD_ARG),
+        ("msm_limbs 9", lambda: L.lw_hip_msm_limbs(G1, P, u32(9), sz(1), P, sz(1), P), _lib.ERR_BAD_ARG),
+        ("msm_limbs_device 0", lambda: L.lw_hip_msm_limbs_device(G1, P, u32(0), P, sz(1), P, N), _lib.ERR_BAD_ARG),
+        ("msm_limbs_device 9", lambda: L.lw_hip_msm_limbs_device(G1, P, u32(9), P, sz(1), P, N), _lib.ERR_BAD_ARG),
+        ("msm curve", lambda: L.lw_hip_msm(BAD_CURVE, P, sz(1), P, sz(1), P), _lib.ERR_BAD_ARG),
+        ("msm_device curve", lambda: L.lw_hip_msm_device(BAD_CURVE, P, P, sz(1), P, N), _lib.ERR_BAD_ARG),
+        ("msm_fr_device curve", lambda: L.lw_hip_msm_fr_device(BAD_CURVE, P, P, sz(1), P, N), _lib.ERR_BAD_ARG),
+        ("msm lengths", lambda: L.lw_hip_msm(G1, P, sz(2), P, sz(1), P), _lib.ERR_LENGTH_MISMATCH),
+        ("msm null", lambda: L.lw_hip_msm(G1, N, sz(1), P, sz(1), P), _lib.ERR_BAD_ARG),
+        ("srs_create curve", lambda: L.lw_hip_srs_create(BAD_CURVE, P, sz(1), P), _lib.ERR_BAD_ARG),
+        ("srs_create_device curve", lambda: L.lw_hip_srs_create_device(BAD_CURVE, P, sz(1), N, P), _lib.ERR_BAD_ARG),
+        ("ec_add_outer_device curve", lambda: L.lw_hip_ec_add_outer_device(BAD_CURVE, P, sz(1), P, sz(1), P, N), _lib.ERR_BAD_ARG),
+        ("commit_columns field", lambda: L.lw_stark_commit_columns(BB, P, u32(1), u32(2), i(0), P, N), _lib.ERR_BAD_ARG),
+        ("commit_columns leaves", lambda: L.lw_stark_commit_columns(S, P, u32(1), u32(32), i(0), P, N), _lib.ERR_ALLOC),
+        ("commit_columns_device field", lambda: L.lw_stark_commit_columns_device(BB, P, u32(1), sz(0), u32(2), i(0), P, N, N), _lib.ERR_BAD_ARG),
+        ("commit_columns_device row bytes", lambda: L.lw_stark_commit_columns_device(S, P, u32(1 << 26), sz(0), u32(0), i(0), P, N, N), _lib.ERR_BAD_ARG),
+        ("commit_columns_layout_device ext4", lambda: L.lw_stark_commit_columns_layout_device(BB, EXT4, P, u32(1), sz(0), u32(2), i(0), P, N, N), _lib.ERR_BAD_ARG),
+        ("commit_columns_layout_device null", lambda: L.lw_stark_commit_columns_layout_device(BB, R32, N, u32(1), sz(0), u32(2), i(0), P, N, N), _lib.ERR_BAD_ARG),
+    ]
+    got = {name: call() for name, call, _ in cases}
+    assert got == {name: code for name, _, code in cases}
 
 
 def test_product_never_touches_the_oracle():
