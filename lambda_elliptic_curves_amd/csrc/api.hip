@@ -100,7 +100,6 @@ static int init_locked(const int *device_ids, int n_devices) {
 #ifdef LW_HIP_ABLATION
     if (const char *e = tuning_env("LW_HIP_NTT_DBG")) ntt_set_debug((uint32_t)atoi(e));   // wrong results, timing only
 #endif
-    if (const char *e = tuning_env("LW_HIP_NTT_MAX_R")) ntt_set_max_pass_stages((uint32_t)atoi(e));
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count <= 0) {
@@ -417,7 +416,7 @@ void host_pool_release_all() {
 // A fresh result buffer (a Rust `Vec::with_capacity`, numpy's `empty`) has never been touched: the device-to-host copy
 // into it then runs at the kernel's page-fault rate (512 MiB = 131072 first-touch faults: 35-45 ms) instead of the PCIe rate
 // (~9 ms).  The host-buffer entry points therefore (a) ask for transparent huge pages on the 2 MiB-aligned interior of a
-// large output (madvise MADV_HUGEPAGE: 256 faults instead of 131072 where the host allows it, LW_HIP_HOST_THP=0 skips it),
+// large output (madvise MADV_HUGEPAGE: 256 faults instead of 131072 where the host allows it),
 // (b) populate it with a few threads, chunk by chunk in address order, WHILE the upload and the kernels run
 // (MADV_POPULATE_WRITE maps the pages without changing their contents), and (c) copy each chunk back as soon as it is
 // mapped, so the download runs behind the populate front instead of after it.  Callers that can hold results in a
@@ -436,11 +435,8 @@ struct Prefault {
         if (nbytes < ((size_t)32 << 20) || (a < b + in_bytes && b < a + nbytes) || host_pool_owns(p)) return;   // small, aliases the input (already mapped), or pinned
         const size_t page = (size_t)sysconf(_SC_PAGESIZE);
 #ifdef MADV_HUGEPAGE
-        static const bool thp = [] { const char *e = tuning_env("LW_HIP_HOST_THP"); return !e || atoi(e) != 0; }();
-        if (thp) {
-            const uintptr_t H = (uintptr_t)2 << 20, hlo = (a + H - 1) & ~(H - 1), hhi = (a + nbytes) & ~(H - 1);
-            if (hhi > hlo) (void)madvise((void *)hlo, hhi - hlo, MADV_HUGEPAGE);   // best effort
-        }
+        const uintptr_t H = (uintptr_t)2 << 20, hlo = (a + H - 1) & ~(H - 1), hhi = (a + nbytes) & ~(H - 1);
+        if (hhi > hlo) (void)madvise((void *)hlo, hhi - hlo, MADV_HUGEPAGE);   // best effort
 #endif
         nchunks = (nbytes + CHUNK - 1) / CHUNK;
         done = std::vector<std::atomic<int>>(nchunks);

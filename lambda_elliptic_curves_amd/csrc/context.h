@@ -23,7 +23,7 @@
 namespace lw {
 
 void set_error(const char *fmt, ...);
-// Diagnostic / A-B switches (LW_HIP_MSM_C, LW_HIP_NTT_PLAN, ...) are honoured only in processes started with
+// Diagnostic / A-B switches (LW_HIP_MSM_C, LW_HIP_SRS_FOLD, ...) are honoured only in processes started with
 // LW_HIP_TUNING=1 (read once): a stray variable in a prover's environment cannot change the schedule.
 const char *tuning_env(const char *name);
 extern thread_local std::string g_last_error;

@@ -19,7 +19,6 @@ int msm_srs_locked(Context &c, const lw_srs_t *srs, const uint64_t *d_scalars, s
 // ---- ntt256.hip
 void ntt_set_debug(uint32_t d);
 uint32_t ntt_get_debug();
-void ntt_set_max_pass_stages(uint32_t r);
 int ntt256_device(Context &c, int field, lw_dir_t dir, const void *d_in, void *d_out, uint32_t log2n, uint32_t batch,
                   uint64_t stride, const uint32_t *coset_words, hipStream_t stream, uint32_t in_log2);
 int ntt256_gen_powers(int field, uint32_t order, uint64_t count, uint32_t bitrev, bool inverse, const uint32_t *scale_words, void *d_out,
@@ -79,11 +78,8 @@ int msm_shard_combine(lw_curve_t curve, const char *sa_all, uint32_t G, uint32_t
 int ensure_aux_stream(Context &c);   // the context's side stream
 
 uint32_t msm_ch(uint64_t items);       // max points per accumulate work-item (a bucket is cut into equal pieces <= CH)
-int msm_piece_order_enabled();         // LW_HIP_MSM_ORDER=0: work-items take their pieces in key order (A/B)
 uint64_t msm_quad_max_lanes();          // LW_HIP_MSM_QUAD: levels of the bucket reduce with at most this many lanes (8 per group) spread each addition over a quad; 0 = never, ~0 = not set
 uint64_t msm_accumulate_quad_max_lanes();   // LW_HIP_MSM_ACCQ: accumulate launches of projective rows with at most this many lanes (4 per piece) use the quad kernel
-uint32_t msm_g_log();                  // log2 buckets per running-sum group: 3 (8 buckets; 16 -> 8 saved 1 ms of dependent-add latency per MSM, 4 is no better)
-int msm_waves_per_simd();   // LW_HIP_MSM_WAVES (2 or 3): register budget of the accumulate kernel
 
 // host launchers for the curve-independent kernels
 uint32_t msm_sort_coarse_bins(uint32_t c, uint32_t W, uint64_t n);

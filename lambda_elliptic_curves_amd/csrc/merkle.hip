@@ -203,18 +203,16 @@ __global__ __launch_bounds__(256) void merkle_top_kernel(uint64_t *nodes, uint64
 int merkle_commit_device(Context &c, const void *d_cols, uint32_t n_cols, uint64_t col_stride, uint32_t log2n, int bit_reverse,
                          void *d_nodes, hipStream_t stream, uint32_t elem_bytes) {
     const uint64_t n = 1ull << log2n;
-    // Levels per launch (LW_HIP_MERKLE_FUSE, tuning: 1 = a launch per level as before): the tree above 2^m nodes is built
-    // by the top kernel once m <= 9 (256 parents), by launches of up to `fuse` levels before that, the first of them inside
-    // the leaf kernel.
-    static const uint32_t fuse = [] { const char *e = tuning_env("LW_HIP_MERKLE_FUSE"); int v = e ? atoi(e) : 4; return (uint32_t)(v < 1 ? 1 : (v > 7 ? 7 : v)); }();
+    // Levels per launch: the tree above 2^m nodes is built by the top kernel once m <= 9 (256 parents), by launches of up
+    // to `fuse` levels before that, the first of them inside the leaf kernel (profiles/r03_ab_merkle_fuse.txt).
+    constexpr uint32_t fuse = 4;
     // Wide levels are bound by the hashes' throughput and take a launch each (in a fused launch the upper levels of a
     // subtree run on 128, 64, 32 ... of the workgroup's 256 work-items while its other waves hold their slots: 1 x 2^24
     // 4.19 -> 4.35 ms fused everywhere); from 2^16 nodes down a level is a few microseconds long and the launches count.
     constexpr uint32_t FUSE_BELOW = 16;
     uint32_t m = log2n;   // the level whose parents are built next holds 2^m nodes
-    const uint32_t leaf_fused = (fuse > 1 && m > 9 && m <= FUSE_BELOW) ? std::min(fuse, m - 9) : 0u;
-    static const bool tile_env = [] { const char *e = tuning_env("LW_HIP_MERKLE_TILE"); return !e || atoi(e) != 0; }();   // A/B only
-    if (bit_reverse) bit_reverse = (tile_env && leaf_fused == 0 && log2n >= 12) ? 2 : 1;
+    const uint32_t leaf_fused = (m > 9 && m <= FUSE_BELOW) ? std::min(fuse, m - 9) : 0u;
+    if (bit_reverse) bit_reverse = (leaf_fused == 0 && log2n >= 12) ? 2 : 1;
     hipEvent_t pe = c.prof_begin(stream);
     const dim3 grid((uint32_t)((n + 255) / 256));
     if (elem_bytes == 4)

@@ -241,27 +241,8 @@ __device__ __forceinline__ uint32_t digit_of(const uint4 &v, int e) { return e =
 // coarse bin of an encoded digit (SORT_MAX_COARSE = the dummy slot of zero digits, which contribute nothing, pippenger.rs:78)
 __device__ __forceinline__ uint32_t coarse_bin(uint32_t enc, uint32_t fine_bits) { return enc ? (((enc >> 1) - 1) >> fine_bits) : SORT_MAX_COARSE; }
 
-// A/B only (LW_HIP_MSM_BALLOT=1): rank of an item among the items of its wave with the same bin by wave-wide
-// ballots — a match-any over the 10 bin bits, lane rank = popcount of the matching lanes below, one LDS atomic per
-// distinct bin and wave instead of one per item.  Returns the rank the plain atomicAdd(&h[bin], 1) would have returned
-// (up to the order inside the bin, which is irrelevant).
-__device__ __forceinline__ uint32_t ballot_rank_add(uint32_t *h, uint32_t bin) {
-    uint64_t m = __ballot(1);
-#pragma unroll
-    for (int b = 0; b < 10; b++) {
-        const uint32_t bit = (bin >> b) & 1u;
-        const uint64_t bal = __ballot(bit);
-        m &= bit ? bal : ~bal;
-    }
-    const uint32_t lane = __lane_id();
-    const uint32_t below = __popcll(m & ((1ull << lane) - 1));
-    uint32_t base = 0;
-    if (below == 0) base = atomicAdd(&h[bin], (uint32_t)__popcll(m));
-    base = __shfl(base, __ffsll((long long)m) - 1);
-    return base + below;
-}
-
-template <bool BALLOT = false>
+// (Measured and dropped, profiles/r03_ab_msm_ballot.txt, DESIGN 4.4: ranks inside a wave by ten __ballot rounds instead of
+// one LDS atomic per item — a wave's 64 items fall into about 60 distinct bins, 2^24 uniform 46.4-46.6 ms against 45.2-45.3.)
 __global__ __launch_bounds__(SORT_THREADS) void msm_coarse_count_kernel(const uint32_t *dig, uint64_t n_pad, uint32_t hb, uint32_t fine_bits,
                                                                        uint32_t folded, uint32_t *coarse_cnt) {
     __shared__ uint32_t h[SORT_MAX_COARSE + 1];
@@ -271,24 +252,16 @@ __global__ __launch_bounds__(SORT_THREADS) void msm_coarse_count_kernel(const ui
     const uint64_t q0 = (uint64_t)blockIdx.x * (SORT_PPB / 4);
     const uint64_t q1 = min(n_pad / 4, q0 + SORT_PPB / 4);
     const uint4 *d4 = reinterpret_cast<const uint4 *>(dig + (uint64_t)w * n_pad);
-    if constexpr (BALLOT) {
-        for (uint64_t q = q0; q < q1; q += SORT_THREADS) {   // whole waves stay in the loop: ballots need every lane
-            const uint4 v = q + tid < q1 ? d4[q + tid] : make_uint4(0, 0, 0, 0);
-#pragma unroll
-            for (int e = 0; e < 4; e++) (void)ballot_rank_add(h, coarse_bin(digit_of(v, e), fine_bits));
-        }
-    } else {
     for (uint64_t q = q0 + tid; q < q1; q += SORT_THREADS) {
         const uint4 v = d4[q];
 #pragma unroll
         for (int e = 0; e < 4; e++) atomicAdd(&h[coarse_bin(digit_of(v, e), fine_bits)], 1u);
     }
-    }
     __syncthreads();
     for (uint32_t b = tid; b < NB; b += SORT_THREADS)
         if (h[b]) atomicAdd(&coarse_cnt[(folded ? 0u : (w << hb)) + b], h[b]);
 }
-template <class ITEM, bool BALLOT = false>
+template <class ITEM>
 __global__ __launch_bounds__(SORT_THREADS) void msm_coarse_kernel(const uint32_t *dig, uint64_t n_pad, uint32_t hb, uint32_t fine_bits,
                                                                  uint64_t idx_stride, uint32_t folded, uint32_t win0, const uint32_t *coarse_off,
                                                                  uint32_t *coarse_cursor, ItemMem<ITEM> items) {
@@ -306,18 +279,10 @@ __global__ __launch_bounds__(SORT_THREADS) void msm_coarse_kernel(const uint32_t
     const uint64_t q0 = (uint64_t)blockIdx.x * (SORT_PPB / 4);
     const uint64_t q1 = min(n_pad / 4, q0 + SORT_PPB / 4);
     const uint4 *d4 = reinterpret_cast<const uint4 *>(dig + (uint64_t)w * n_pad);
-    if constexpr (BALLOT) {
-        for (uint64_t q = q0; q < q1; q += SORT_THREADS) {
-            const uint4 v = q + tid < q1 ? d4[q + tid] : make_uint4(0, 0, 0, 0);
-#pragma unroll
-            for (int e = 0; e < 4; e++) (void)ballot_rank_add(h, coarse_bin(digit_of(v, e), fine_bits));
-        }
-    } else {
     for (uint64_t q = q0 + tid; q < q1; q += SORT_THREADS) {
         const uint4 v = d4[q];
 #pragma unroll
         for (int e = 0; e < 4; e++) atomicAdd(&h[coarse_bin(digit_of(v, e), fine_bits)], 1u);
-    }
     }
     __syncthreads();
     for (uint32_t b = tid; b < SORT_MAX_COARSE; b += SORT_THREADS) {   // one global atomic per bin reserves this workgroup's run
@@ -340,8 +305,7 @@ __global__ __launch_bounds__(SORT_THREADS) void msm_coarse_kernel(const uint32_t
         for (int l = 0; l < COARSE_LOADS; l++)
 #pragma unroll
             for (int e = 0; e < 4; e++)
-                rk[l][e] = BALLOT ? ballot_rank_add(h, coarse_bin(digit_of(v[l], e), fine_bits))
-                                  : atomicAdd(&h[coarse_bin(digit_of(v[l], e), fine_bits)], 1u);
+                rk[l][e] = atomicAdd(&h[coarse_bin(digit_of(v[l], e), fine_bits)], 1u);
         __syncthreads();
         for (uint32_t b = tid; b < SORT_MAX_COARSE; b += SORT_THREADS) pre[b] = h[b];   // zero digits stay in the dummy slot
         __syncthreads();
@@ -677,17 +641,13 @@ uint32_t msm_ch(uint64_t items) {
     // against 1.53 at 8 (tools/ab_msm_ch_small.sh, profiles/r03_ab_msm_ch_small.txt)
     return items < (1ull << 20) ? 8u : items < (1ull << 22) ? 16u : items < (1ull << 27) ? 32u : 64u;
 }
-int msm_piece_order_enabled() {
-    static int v = [] { const char *e = tuning_env("LW_HIP_MSM_ORDER"); return e ? atoi(e) : 1; }();
-    return v;
-}
 
 uint32_t msm_sort_coarse_bins(uint32_t c, uint32_t W, uint64_t n) { return W << sort_split(c, n).hb; }   // folded: W = 1, n = W * stride
 uint32_t msm_max_window_bits() { return MSM_MAX_C; }
 // row length of the digit matrix: a multiple of 8 (uint4 loads) that is not a power of two, so that the W rows a wave
 // writes do not all fall on the same memory channel
 uint64_t msm_sort_padded_points(uint64_t n) { return ((n + 7) & ~(uint64_t)7) + 1032; }
-// level 0: the W x n_pad digit matrix of all windows (shared by the window slices of msm_core.cuh run())
+// level 0: the W x n_pad digit matrix of all windows (msm_core.cuh run())
 int msm_launch_digits(Context &c, const uint32_t *scalars, uint64_t n, uint32_t cb, uint32_t W, uint32_t *dig, hipStream_t s,
                       uint32_t scalar_limbs) {
     const uint64_t n_pad = msm_sort_padded_points(n);
@@ -705,7 +665,7 @@ int msm_launch_digits(Context &c, const uint32_t *scalars, uint64_t n, uint32_t 
     LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
     return LW_OK;
 }
-// `dig`: row 0 = the first of the W windows sorted here (a slice of the matrix); win0: that window's number in the MSM
+// `dig`: row 0 = the first of the W windows sorted here; win0: that window's number in the MSM
 template <class ITEM>
 static void launch_sort_t(Context &c, uint64_t n, uint32_t cb, uint32_t W, const SortSplit &sp, uint32_t CB,
                           const uint32_t *dig, uint32_t *coarse_cnt, uint32_t *coarse_off, uint32_t *coarse_cursor, ItemMem<ITEM> items,
@@ -716,16 +676,12 @@ static void launch_sort_t(Context &c, uint64_t n, uint32_t cb, uint32_t W, const
     const uint32_t fine = sp.fine, hb = sp.hb;
     const dim3 grid((uint32_t)((n_pad + SORT_PPB - 1) / SORT_PPB), W);
     hipEvent_t pe = c.prof_begin(s);
-    static const bool ballot = [] { const char *e = tuning_env("LW_HIP_MSM_BALLOT"); return e && atoi(e) == 1; }();   // A/B only
-    if (ballot) hipLaunchKernelGGL((msm_coarse_count_kernel<true>), grid, dim3(SORT_THREADS), 0, s, (const uint32_t *)dig, n_pad, hb, fine, folded, coarse_cnt);
-    else hipLaunchKernelGGL((msm_coarse_count_kernel<false>), grid, dim3(SORT_THREADS), 0, s, (const uint32_t *)dig, n_pad, hb, fine, folded, coarse_cnt);
+    hipLaunchKernelGGL(msm_coarse_count_kernel, grid, dim3(SORT_THREADS), 0, s, (const uint32_t *)dig, n_pad, hb, fine, folded, coarse_cnt);
     c.prof_end("msm_coarse_kernel<count>", pe, s);
     msm_launch_scan(coarse_cnt, coarse_off, CB, 0, maxlen + 1, scan_tmp, s);   // maxlen[1]: coarse max (unused)
     pe = c.prof_begin(s);
-    if (ballot) hipLaunchKernelGGL((msm_coarse_kernel<ITEM, true>), grid, dim3(SORT_THREADS), 0, s, (const uint32_t *)dig, n_pad, hb, fine, fold_stride, folded,
-                                   win0, (const uint32_t *)coarse_off, coarse_cursor, items);
-    else hipLaunchKernelGGL((msm_coarse_kernel<ITEM, false>), grid, dim3(SORT_THREADS), 0, s, (const uint32_t *)dig, n_pad, hb, fine, fold_stride, folded,
-                            win0, (const uint32_t *)coarse_off, coarse_cursor, items);
+    hipLaunchKernelGGL((msm_coarse_kernel<ITEM>), grid, dim3(SORT_THREADS), 0, s, (const uint32_t *)dig, n_pad, hb, fine, fold_stride, folded,
+                       win0, (const uint32_t *)coarse_off, coarse_cursor, items);
     c.prof_end("msm_coarse_kernel<scatter>", pe, s);
     // level B: sub-blocks of the coarse bins -> key counts -> key offsets (+ the longest bucket) -> sorted index list
     msm_launch_scan(coarse_off, sub_off, CB, (int)FINE_SUB, maxlen + 1, scan_tmp, s);
@@ -768,10 +724,6 @@ void msm_launch_scan(const uint32_t *in, uint32_t *out, uint32_t K, int mode, ui
 }
 size_t msm_scan_scratch_bytes(uint32_t K) { return 8 * (size_t)((K + SCAN_TILE - 1) / SCAN_TILE) + 256; }
 
-uint32_t msm_g_log() {
-    static uint32_t g = [] { const char *e = tuning_env("LW_HIP_MSM_GLOG"); int v = e ? atoi(e) : 3; return (uint32_t)(v < 1 ? 1 : (v > 6 ? 6 : v)); }();
-    return g;
-}
 uint64_t msm_quad_max_lanes() {   // tuning: LW_HIP_MSM_QUAD = log2 of the widest level (in lanes) that takes the quad kernels, 0 = none
     const char *e = tuning_env("LW_HIP_MSM_QUAD");   // read per call so that a test can sweep it
     if (!e) return ~(uint64_t)0;                     // not set: the group's own default (msm_core.cuh launch_group_sum)
@@ -782,10 +734,6 @@ uint64_t msm_accumulate_quad_max_lanes() {   // tuning: LW_HIP_MSM_ACCQ = log2 o
     const char *e = tuning_env("LW_HIP_MSM_ACCQ");
     const int v = e ? atoi(e) : 19;
     return v <= 0 ? (uint64_t)0 : (uint64_t)1 << (v > 30 ? 30 : v);
-}
-int msm_waves_per_simd() {
-    static int w = [] { const char *e = tuning_env("LW_HIP_MSM_WAVES"); int v = e ? atoi(e) : 2; return v == 3 ? 3 : 2; }();
-    return w;
 }
 
 const MsmCurveOps *msm_ops(lw_curve_t curve) {
@@ -798,7 +746,7 @@ const MsmCurveOps *msm_ops(lw_curve_t curve) {
     }
 }
 
-// smallest input (log2 points) for which normalising first pays, per group (tools/ab_msm_curve.py, LW_HIP_MSM_NORM_MIN)
+// smallest input (log2 points) for which normalising first pays, per group (tools/ab_msm_curve.py)
 static int msm_normalize_min_log2(lw_curve_t curve) {
     switch (curve) {   // measured break-even (normalise + mixed additions against projective additions)
         case LW_CURVE_BN254_G2: return 18;        // 2^20: 12.3 -> 11.2 ms, 2^21: 18.7 -> 16.6 (mixed addition on the isomorphic curve)
@@ -856,30 +804,18 @@ int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const vo
     // Large projective inputs are normalised first (batch inversion, ~3 ms at 2^24) so that the accumulation can use
     // the mixed addition, one-line gathers and — BLS12-381 G1, BN254 G2 — the cheaper isomorphic curve (~10 ms less at
     // 2^24); below the per-group threshold (msm_normalize_min_log2) the conversion costs more than it saves.
-    // LW_HIP_MSM_NORMALIZE=0 keeps the projective path.
-    static const bool auto_norm = [] { const char *e = tuning_env("LW_HIP_MSM_NORMALIZE"); return !e || atoi(e) != 0; }();
     hipEvent_t join = nullptr;
-    static const int norm_min_env = [] { const char *e = tuning_env("LW_HIP_MSM_NORM_MIN"); return e ? atoi(e) : -1; }();   // tuning only
-    const int norm_min_log2 = norm_min_env >= 0 ? norm_min_env : msm_normalize_min_log2(curve);
-    if (!affine_points && auto_norm && n >= ((size_t)1 << norm_min_log2)) {
+    if (!affine_points && n >= ((size_t)1 << msm_normalize_min_log2(curve))) {
         const size_t aff_bytes = ops->affine_bytes(n);
         if (c.msm_affine.ensure(aff_bytes)) return LW_ERR_ALLOC;
         // The normalisation reads only the points and the bucket sort only the scalars, so the normalisation runs on a
         // side stream beside the sort and the main stream joins it just before the first accumulation launch (both are
-        // memory-bound: side by side they take about the sum of their standalone times less 0.5 ms, LW_HIP_MSM_SIDE).
-        static const bool side = [] { const char *e = tuning_env("LW_HIP_MSM_SIDE"); return !e || atoi(e) != 0; }();   // A/B only
-        if (!side) {
-            if (upload_pending) {
-                LW_HIP_CHECK(hipMemcpyAsync((void *)d_points, h_points, n * pbytes, hipMemcpyHostToDevice, stream), LW_ERR_LAUNCH);
-                upload_pending = false;
-            }
-            int rc = ops->normalize(c, stream, d_points, n, c.msm_affine.p);
-            if (rc) return rc;
-        } else if (upload_pending) {
-            int rc = ensure_aux_stream(c);
-            if (rc) return rc;
-            LW_HIP_CHECK(hipEventRecord(c.aux_fork, stream), LW_ERR_LAUNCH);
-            LW_HIP_CHECK(hipStreamWaitEvent(c.aux_stream, c.aux_fork, 0), LW_ERR_LAUNCH);
+        // memory-bound: side by side they take about the sum of their standalone times less 0.5 ms).
+        int rc = ensure_aux_stream(c);
+        if (rc) return rc;
+        LW_HIP_CHECK(hipEventRecord(c.aux_fork, stream), LW_ERR_LAUNCH);
+        LW_HIP_CHECK(hipStreamWaitEvent(c.aux_stream, c.aux_fork, 0), LW_ERR_LAUNCH);
+        if (upload_pending) {
             const void *src = d_points;
             // in chunks of 2^20 points: chunk k is normalised (second side stream) while chunk k + 1 is on the bus, so that what
             // is left after the last byte arrives is one chunk's normalisation, not the whole set's
@@ -906,24 +842,15 @@ int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const vo
                 return LW_OK;
             };
             upload_pending = false;
-            join = c.aux_join;
         } else {
-        {
-            int rc = ensure_aux_stream(c);
-            if (rc) return rc;
-        }
-        LW_HIP_CHECK(hipEventRecord(c.aux_fork, stream), LW_ERR_LAUNCH);
-        LW_HIP_CHECK(hipStreamWaitEvent(c.aux_stream, c.aux_fork, 0), LW_ERR_LAUNCH);
-        // (Enqueueing the normalisation behind the sort, or behind the digit kernel only, measured worse: whichever sort
-        // kernel first overlaps the normalisation takes ~2-3 ms longer, and a later start only moves that cost: 56.9 ms with
-        // the normalisation first, 58.2 / 59.5 ms with the sort / the digit kernel first.)
-        {
-            int rc = ops->normalize(c, c.aux_stream, d_points, n, c.msm_affine.p);
+            // (Enqueueing the normalisation behind the sort, or behind the digit kernel only, measured worse: whichever sort
+            // kernel first overlaps the normalisation takes ~2-3 ms longer, and a later start only moves that cost: 56.9 ms with
+            // the normalisation first, 58.2 / 59.5 ms with the sort / the digit kernel first.)
+            rc = ops->normalize(c, c.aux_stream, d_points, n, c.msm_affine.p);
             if (rc) return rc;
             LW_HIP_CHECK(hipEventRecord(c.aux_join, c.aux_stream), LW_ERR_LAUNCH);
         }
         join = c.aux_join;
-        }
         d_points = c.msm_affine.p;
         affine_points = 1;
     }

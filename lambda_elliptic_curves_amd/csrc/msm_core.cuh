@@ -10,6 +10,8 @@
 namespace lw {
 
 constexpr int MSM_THREADS = 128;
+// log2 buckets per running-sum group (8 buckets; 16 -> 8 saved 1 ms of dependent-add latency per MSM, 4 is no better)
+constexpr uint32_t MSM_G_LOG = 3;
 
 // ---------------------------------------------------------------- accumulate
 // All device point arrays (caller's points, partial sums, buckets, running-sum temporaries) use the reference
@@ -454,10 +456,9 @@ struct MsmRunner {
         hipEvent_t pe = nullptr;
         // run length: long runs amortise the inversion (2^24 points: 5.8 ms at 128 against 8.3 ms at 32), short ones
         // keep enough work-items in flight for small sets (2^20: 1.2 ms at 32 against 2.0 ms at 128)
-        static const uint32_t chk_env = [] { const char *e = tuning_env("LW_HIP_MSM_CHK"); return e ? (uint32_t)atoi(e) : 0u; }();   // tuning only
         // (2^22 and 2^23 sit between the two: inside an MSM, where this kernel runs beside the sort and is the longer of the two
         // below 2^24, 2^22 takes 13.7 ms at 32 against 14.0 at 128 and 2^23 24.1 at 64 against 24.5, profiles/r03_ab_msm_chk_mid.txt)
-        const uint32_t chk = chk_env ? std::min(std::max(chk_env, 1u), 1024u) : (n >= ((size_t)1 << 24) ? 128 : n >= ((size_t)1 << 23) ? 64 : 32);
+        const uint32_t chk = n >= ((size_t)1 << 24) ? 128 : n >= ((size_t)1 << 23) ? 64 : 32;
         const uint64_t items = (n + chk - 1) / chk;
         const uint32_t blocks = (uint32_t)((items + MSM_THREADS - 1) / MSM_THREADS);
         if (c.msm_prefix.ensure(n * C::B::BYTES)) return LW_ERR_ALLOC;   // running products, one element per point
@@ -526,7 +527,6 @@ struct MsmRunner {
     // in: nwin arrays of n points.  Returns device arrays S[nwin] (sum d*in[d]) and A[nwin] (sum in[d]).
     static constexpr size_t PB = 3 * C::B::BYTES;
     int reduce(const char *in, uint32_t n, uint32_t nwin, Carver &cv, char **S_out, char **A_out, hipStream_t stream) {
-        const uint32_t MSM_G_LOG = msm_g_log();
         const uint32_t g = 1u << MSM_G_LOG;
         if (n <= g) {   // one work-item per array: S = Q (d0 = 0), A = running sum
             char *out = (char *)cv.take(PB * 2 * (size_t)nwin);
@@ -560,12 +560,9 @@ struct MsmRunner {
         return LW_OK;
     }
 
-    // The windows of one MSM are processed as one or two independent SLICES [w0, w0 + Wh): each has its own sort arrays,
-    // bucket array and running sums, exactly as if it were an MSM with Wh windows; the digit matrix is shared.  Two
-    // slices let the memory-bound sort of the second and the latency-bound running sums of the first run on the side
-    // stream UNDER the compute-bound accumulation of the other slice (run() below).
+    // The arrays of one sort over all W windows of an MSM, its bucket array and its running sums.
     struct Slice {
-        uint32_t w0 = 0, Wh = 0, NW = 0, K = 0, CB = 0;
+        uint32_t NW = 0, K = 0, CB = 0;
         uint32_t *coarse_cnt = nullptr, *coarse_cursor = nullptr, *maxlen_d = nullptr, *key_cnt = nullptr, *key_cursor = nullptr;
         uint32_t *coarse_off = nullptr, *sub_off = nullptr, *off = nullptr, *scan_tmp = nullptr, *sorted = nullptr, *order_tmp = nullptr;
         uint64_t *items = nullptr;
@@ -573,9 +570,9 @@ struct MsmRunner {
         volatile uint32_t *maxlen_h = nullptr;   // pinned host word the sort's longest bucket is copied to
     };
 
-    // carve-outs of a slice's sort; with cv.base == nullptr only the sizes are added up
+    // carve-outs of the sort; with cv.base == nullptr only the sizes are added up
     int carve_sort(Slice &sl, size_t n, uint32_t cbits, Carver &cv) {
-        sl.NW = fold_stride ? 1u : sl.Wh;       // bucket sets: one per window, or one for all (folded SRS)
+        sl.NW = fold_stride ? 1u : W;           // bucket sets: one per window, or one for all (folded SRS)
         sl.K = sl.NW << (cbits - 1);            // signed digits: 2^(c-1) buckets per window, bucket j = multiplier j + 1
         sl.CB = msm_sort_coarse_bins(cbits, sl.NW, fold_stride ? (uint64_t)W * fold_stride : n);
         sl.coarse_cnt = (uint32_t *)cv.take(4 * (size_t)(sl.CB + 1));
@@ -587,46 +584,40 @@ struct MsmRunner {
         sl.sub_off = (uint32_t *)cv.take(4 * (size_t)(sl.CB + 1));
         sl.off = (uint32_t *)cv.take(4 * (size_t)(sl.K + 1));
         sl.scan_tmp = (uint32_t *)cv.take(msm_scan_scratch_bytes(sl.K));
-        sl.sorted = (uint32_t *)cv.take(4 * n * sl.Wh);
-        sl.items = (uint64_t *)cv.take(8 * n * sl.Wh);
+        sl.sorted = (uint32_t *)cv.take(4 * n * W);
+        sl.items = (uint64_t *)cv.take(8 * n * W);
         sl.order_tmp = (uint32_t *)cv.take(msm_order_tmp_bytes());
         sl.buckets = (char *)cv.take(PB * (size_t)sl.K);
         LW_MSM_WS_CHECK(cv);
         return LW_OK;
     }
 
-    // sort of the slice's windows (rows w0 .. w0 + Wh - 1 of the digit matrix) on stream `s`; the longest bucket lands in
-    // *sl.maxlen_h once `s` gets there
+    // sort of the digit matrix on stream `s`; the longest bucket lands in *sl.maxlen_h once `s` gets there
     int launch_sort(Slice &sl, const uint32_t *dig, size_t n, uint32_t cbits, hipStream_t s) {
         // coarse_cnt, coarse_cursor, maxlen, key_cnt and key_cursor are adjacent carve-outs: one memset clears them all
         LW_HIP_CHECK(hipMemsetAsync(sl.coarse_cnt, 0, (size_t)((char *)sl.coarse_off - (char *)sl.coarse_cnt), s), LW_ERR_LAUNCH);
-        msm_launch_sort(c, dig + (size_t)sl.w0 * msm_sort_padded_points(n), (uint64_t)n, cbits, sl.Wh, sl.coarse_cnt, sl.coarse_off,
+        msm_launch_sort(c, dig, (uint64_t)n, cbits, W, sl.coarse_cnt, sl.coarse_off,
                         sl.coarse_cursor, sl.items, sl.sorted, sl.off, sl.K, sl.maxlen_d, sl.scan_tmp, sl.sub_off, sl.key_cnt,
-                        sl.key_cursor, fold_stride, (uint64_t)sl.w0, s);
+                        sl.key_cursor, fold_stride, (uint64_t)0, s);
         LW_HIP_CHECK(hipMemcpyAsync((void *)sl.maxlen_h, sl.maxlen_d, 4, hipMemcpyDeviceToHost, s), LW_ERR_LAUNCH);
         return LW_OK;
     }
 
-    // accumulate rounds of a slice on stream `s`: while some bucket is longer than CH, cut every bucket into CH-sized
-    // pieces.  `maxlen`: the longest bucket (real run: from the sort; dry run: the worst case).  before_first_launch() is
-    // called once, right before the first accumulate kernel is enqueued.
-    template <class Hook>
-    int accumulate(Slice &sl, const void *d_points, size_t n, uint32_t maxlen, Carver &cv, hipStream_t s, Hook before_first_launch) {
+    // accumulate rounds on stream `s`: while some bucket is longer than CH, cut every bucket into CH-sized pieces.
+    // `maxlen`: the longest bucket (real run: from the sort; dry run: the worst case).
+    int accumulate(Slice &sl, const void *d_points, size_t n, uint32_t maxlen, Carver &cv, hipStream_t s) {
         const bool dry = cv.base == nullptr;
         const uint32_t K = sl.K;
         const uint32_t CH = msm_ch((uint64_t)n * W);
-        const bool ordered = msm_piece_order_enabled() != 0;   // first round only: later rounds sum equal numbers of partials
         const uint32_t *seg = sl.off;
         const void *pts = d_points;         // first round: the caller's points through the sorted index list
         const uint32_t *index = sl.sorted;
         uint64_t len = maxlen;             // longest segment
-        uint64_t items_bound = (uint64_t)n * sl.Wh;   // upper bound on items in this round
+        uint64_t items_bound = (uint64_t)n * W;   // upper bound on items in this round
         bool first = true;                 // (the dry run has no pointers to tell the rounds apart)
-        bool hooked = false;
         char *buckets = sl.buckets;
         auto launch = [&](const uint32_t *out_off, const uint32_t *perm_t, const uint32_t *perm_key, uint32_t total, void *pout,
                           const char *name) {
-            if (!hooked) { before_first_launch(); hooked = true; }
             const uint32_t blocks = (total + MSM_THREADS - 1) / MSM_THREADS;
             hipEvent_t pe = c.prof_begin(s);
             if (4 * (uint64_t)total <= msm_accumulate_quad_max_lanes()) {   // few pieces: their chains are the kernel time
@@ -640,9 +631,6 @@ struct MsmRunner {
             } else if (index && affine)
                 hipLaunchKernelGGL((msm_accumulate_kernel<C, C::ACC_WAVES, true>), dim3(blocks), dim3(MSM_THREADS), 0, s, pts, index, seg,
                                    out_off, perm_t, perm_key, K, total, pout, (void *)buckets);
-            else if (out_off && C::ACC_WAVES == 2 && msm_waves_per_simd() == 3)
-                hipLaunchKernelGGL((msm_accumulate_kernel<C, (C::ACC_WAVES == 2 ? 3 : C::ACC_WAVES), false>), dim3(blocks), dim3(MSM_THREADS), 0,
-                                   s, pts, index, seg, out_off, perm_t, perm_key, K, total, pout, (void *)buckets);
             else
                 hipLaunchKernelGGL((msm_accumulate_kernel<C, C::ACC_WAVES, false>), dim3(blocks), dim3(MSM_THREADS), 0, s, pts, index, seg,
                                    out_off, perm_t, perm_key, K, total, pout, (void *)buckets);
@@ -652,9 +640,9 @@ struct MsmRunner {
             uint32_t *out_off = (uint32_t *)cv.take(4 * (size_t)(K + 1));
             uint64_t out_bound = items_bound / CH + K;
             char *pout = (char *)cv.take(PB * out_bound);
-            const bool ord = ordered && first;
-            uint32_t *perm_t = ord ? (uint32_t *)cv.take(4 * out_bound) : nullptr;
-            uint32_t *perm_key = ord ? (uint32_t *)cv.take(4 * out_bound) : nullptr;
+            // pieces longest first (msm_piece_order_kernel) in the first round only: later rounds sum equal numbers of partials
+            uint32_t *perm_t = first ? (uint32_t *)cv.take(4 * out_bound) : nullptr;
+            uint32_t *perm_key = first ? (uint32_t *)cv.take(4 * out_bound) : nullptr;
             LW_MSM_WS_CHECK(cv);
             if (!dry) {
                 msm_launch_scan(seg, out_off, K, (int)CH, sl.maxlen_d, sl.scan_tmp, s);
@@ -665,7 +653,7 @@ struct MsmRunner {
                     set_error("internal: MSM partial count %u exceeds bound %llu", total, (unsigned long long)out_bound);
                     return LW_ERR_LAUNCH;
                 }
-                if (ord) msm_launch_piece_order(c, seg, out_off, K, total, sl.order_tmp, perm_t, perm_key, s);
+                if (first) msm_launch_piece_order(c, seg, out_off, K, total, sl.order_tmp, perm_t, perm_key, s);
                 if (total) launch(out_off, perm_t, perm_key, total, (void *)pout, index ? "msm_accumulate_kernel" : "msm_accumulate_kernel<partials>");
             }
             seg = out_off;
@@ -676,26 +664,13 @@ struct MsmRunner {
             items_bound = out_bound;
         }
         {
-            const bool ord = ordered && first;
-            uint32_t *perm_t = ord ? (uint32_t *)cv.take(4 * (size_t)K) : nullptr;
+            uint32_t *perm_t = first ? (uint32_t *)cv.take(4 * (size_t)K) : nullptr;
             LW_MSM_WS_CHECK(cv);
             if (!dry) {
-                if (ord) msm_launch_piece_order(c, seg, nullptr, K, K, sl.order_tmp, perm_t, nullptr, s);
+                if (first) msm_launch_piece_order(c, seg, nullptr, K, K, sl.order_tmp, perm_t, nullptr, s);
                 launch(nullptr, perm_t, nullptr, K, nullptr, index ? "msm_accumulate_kernel" : "msm_accumulate_kernel<final>");
             }
         }
-        return LW_OK;
-    }
-
-    // `to` waits for everything enqueued on `from` so far (untimed event from the context pool)
-    int chain(hipStream_t from, hipStream_t to, std::vector<hipEvent_t> &taken, hipEvent_t *out = nullptr) {
-        hipEvent_t e = nullptr;
-        if (!c.sync_pool.empty()) { e = c.sync_pool.back(); c.sync_pool.pop_back(); }
-        else if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { set_error("hipEventCreate failed"); return LW_ERR_LAUNCH; }
-        taken.push_back(e);
-        LW_HIP_CHECK(hipEventRecord(e, from), LW_ERR_LAUNCH);
-        if (to) LW_HIP_CHECK(hipStreamWaitEvent(to, e, 0), LW_ERR_LAUNCH);
-        if (out) *out = e;
         return LW_OK;
     }
 
@@ -728,8 +703,6 @@ struct MsmRunner {
         if ((n >> 31) || (((uint64_t)n * ((256 + cbits) / cbits)) >> 32)) { set_error("MSM shard of %zu points: index width", n); return LW_ERR_BAD_ARG; }
         W = (256 + cbits) / cbits;
         Slice sl;
-        sl.w0 = 0;
-        sl.Wh = W;
         if (n == 0) {   // no pairs here: identity buckets (this rank still owns a slice of everybody's)
             const uint64_t K = (uint64_t)W << (cbits - 1);
             if (c.msm_ws.ensure(PB * K + 4096)) return LW_ERR_ALLOC;
@@ -738,11 +711,10 @@ struct MsmRunner {
             *buckets_out = (char *)c.msm_ws.p;
             return LW_OK;
         }
-        auto nothing = [] {};
         Carver dry{nullptr, 0};
         uint32_t *dig = (uint32_t *)dry.take(4 * (size_t)W * msm_sort_padded_points(n));
         int rc = carve_sort(sl, n, cbits, dry);
-        if (!rc) rc = accumulate(sl, nullptr, n, (uint32_t)std::min<size_t>(n, 0xffffffffu), dry, stream, nothing);
+        if (!rc) rc = accumulate(sl, nullptr, n, (uint32_t)std::min<size_t>(n, 0xffffffffu), dry, stream);
         if (rc) return rc;
         if (c.msm_ws.ensure(dry.used + 4096)) return LW_ERR_ALLOC;
         if (!c.pinned_words) LW_HIP_CHECK(hipHostMalloc((void **)&c.pinned_words, 256, hipHostMallocDefault), LW_ERR_ALLOC);
@@ -757,7 +729,7 @@ struct MsmRunner {
         if (rc) return rc;
         LW_HIP_CHECK(hipStreamSynchronize(stream), LW_ERR_LAUNCH);
         if (points_ready) LW_HIP_CHECK(hipStreamWaitEvent(stream, points_ready, 0), LW_ERR_LAUNCH);
-        rc = accumulate(sl, d_points, n, *sl.maxlen_h, cv, stream, nothing);
+        rc = accumulate(sl, d_points, n, *sl.maxlen_h, cv, stream);
         if (rc) return rc;
         LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
         *buckets_out = sl.buckets;
@@ -845,59 +817,36 @@ struct MsmRunner {
                 set_error("MSM of %zu points x %u windows overflows 32-bit item offsets; shard the input", n, W);
                 return LW_ERR_BAD_ARG;
             }
-            // Two slices (LW_HIP_MSM_SLICES=2, off by default): MEASURED AND DROPPED as the default — with the second slice's
-            // sort and the first slice's running sums on a high-priority side stream under the other slice's accumulation,
-            // 2^24 BLS12-381 G1 took 45.6 ms against 45.2-45.6 ms in one slice, and 2^22 15.6 against 14.8
-            // (profiles/r03_ab_msm_slices.txt): the accumulate kernel is bound by VALU issue with 3 waves per SIMD hiding its
-            // gathers, so every wave slot, LDS allocation and issue cycle the side kernels take comes out of it one for one
-            // (it ran 1.3 ms longer; the side kernels, starved, took 3-5x their standalone time).
-            static const bool split_env = [] { const char *e = tuning_env("LW_HIP_MSM_SLICES"); return e && atoi(e) == 2; }();   // A/B only
-            const bool two = split_env && !fold_stride && W >= 4 && n >= ((size_t)1 << 22);
-            Slice sl[2];
-            const int ns = two ? 2 : 1;
-            sl[0].w0 = 0;
-            sl[0].Wh = two ? (W + 1) / 2 : W;
-            sl[1].w0 = sl[0].Wh;
-            sl[1].Wh = W - sl[0].Wh;
+            // One sort and one set of running sums over all windows.  (Measured and dropped, profiles/r03_ab_msm_slices.txt:
+            // the windows as two halves, the second half's sort and the first half's running sums on a high-priority side
+            // stream under the other half's accumulation — 2^24 BLS12-381 G1 45.6 ms against 45.2-45.6, 2^22 15.6 against
+            // 14.8: the accumulate kernel is bound by VALU issue, every wave slot the side kernels take comes out of it.)
+            Slice sl;
             // size the workspace for the worst case: one bucket holding every item.  A folded SRS sorts the items of all W
             // windows into one bucket set, so its longest bucket can hold n * W items (every scalar with the same digit in
             // every window), which takes more rounds of partial sums than n items do.
             const uint64_t worst_len = fold_stride ? (uint64_t)n * W : (uint64_t)n;
             const uint32_t worst = (uint32_t)std::min<uint64_t>(worst_len, 0xffffffffu);
-            auto nothing = [] {};
             auto plan = [&](Carver &cv, uint32_t **dig_out) -> int {   // every carve-out that does not depend on the data
                 *dig_out = (uint32_t *)cv.take(4 * (size_t)W * msm_sort_padded_points(n));
-                for (int k = 0; k < ns; k++) {
-                    int rc = carve_sort(sl[k], n, cbits, cv);
-                    if (rc) return rc;
-                }
-                return LW_OK;
+                return carve_sort(sl, n, cbits, cv);
             };
             Carver dry{nullptr, 0};
             uint32_t *dig = nullptr;
             int rc = plan(dry, &dig);
-            for (int k = 0; k < ns && !rc; k++) {
-                rc = accumulate(sl[k], nullptr, n, worst, dry, stream, nothing);
-                if (!rc) rc = reduce(sl[k].buckets, 1u << (cbits - 1), sl[k].NW, dry, &sl[k].S, &sl[k].A, stream);
-            }
+            if (!rc) rc = accumulate(sl, nullptr, n, worst, dry, stream);
+            if (!rc) rc = reduce(sl.buckets, 1u << (cbits - 1), sl.NW, dry, &sl.S, &sl.A, stream);
             if (rc) return rc;
             if (c.msm_ws.ensure(dry.used + 4096)) return LW_ERR_ALLOC;
             if (!c.pinned_words) LW_HIP_CHECK(hipHostMalloc((void **)&c.pinned_words, 256, hipHostMallocDefault), LW_ERR_ALLOC);
             Carver cv{(char *)c.msm_ws.p, c.msm_ws.bytes};
             rc = plan(cv, &dig);
             if (rc) return rc;
-            std::vector<hipEvent_t> taken;
-            struct Giveback { Context &c; std::vector<hipEvent_t> &t; ~Giveback() { for (hipEvent_t e : t) c.sync_pool.push_back(e); } } giveback{c, taken};
-            for (int k = 0; k < ns; k++) { sl[k].maxlen_h = c.pinned_words + k; *sl[k].maxlen_h = 0; }
-            hipStream_t side = nullptr;
-            if (two) {
-                rc = ensure_aux_stream(c);
-                if (rc) return rc;
-                side = c.aux_hi;   // high priority: its short kernels take CU slots as the long accumulate kernel's workgroups retire
-            }
-            // digits of all windows, then the sort of the first slice, on the caller's stream
+            sl.maxlen_h = c.pinned_words;
+            *sl.maxlen_h = 0;
+            // digits of all windows, then their sort, on the caller's stream
             rc = msm_launch_digits(c, (const uint32_t *)d_scalars, (uint64_t)n, cbits, W, dig, stream, scalar_limbs);
-            if (!rc) rc = launch_sort(sl[0], dig, n, cbits, stream);
+            if (!rc) rc = launch_sort(sl, dig, n, cbits, stream);
             if (rc) return rc;
             if (c.msm_after_sort) {   // host-buffer call: the points are uploaded (and normalised) while the sort above runs
                 auto hook = std::move(c.msm_after_sort);
@@ -907,37 +856,14 @@ struct MsmRunner {
             }
             LW_HIP_CHECK(hipStreamSynchronize(stream), LW_ERR_LAUNCH);
             if (points_ready) LW_HIP_CHECK(hipStreamWaitEvent(stream, points_ready, 0), LW_ERR_LAUNCH);   // normalised points
-            hipEvent_t sorted1 = nullptr;
-            int hook_rc = LW_OK;
-            auto start_side_sort = [&] {   // the second slice's sort starts when the first slice's accumulation does
-                if (!two) return;
-                hook_rc = chain(stream, side, taken);
-                if (!hook_rc) hook_rc = launch_sort(sl[1], dig, n, cbits, side);
-                if (!hook_rc) hook_rc = chain(side, nullptr, taken, &sorted1);
-            };
-            rc = accumulate(sl[0], d_points, n, *sl[0].maxlen_h, cv, stream, start_side_sort);
-            if (rc || hook_rc) return rc ? rc : hook_rc;
-            if (two) {
-                // running sums of the first slice on the side stream, under the second slice's accumulation
-                rc = chain(stream, side, taken);
-                if (!rc) rc = reduce(sl[0].buckets, 1u << (cbits - 1), sl[0].NW, cv, &sl[0].S, &sl[0].A, side);
-                if (rc) return rc;
-                LW_HIP_CHECK(hipEventSynchronize(sorted1), LW_ERR_LAUNCH);           // the host needs the longest bucket
-                LW_HIP_CHECK(hipStreamWaitEvent(stream, sorted1, 0), LW_ERR_LAUNCH);
-                rc = accumulate(sl[1], d_points, n, *sl[1].maxlen_h, cv, stream, nothing);
-                if (!rc) rc = reduce(sl[1].buckets, 1u << (cbits - 1), sl[1].NW, cv, &sl[1].S, &sl[1].A, stream);
-                if (!rc) rc = chain(side, stream, taken);
-            } else {
-                rc = reduce(sl[0].buckets, 1u << (cbits - 1), sl[0].NW, cv, &sl[0].S, &sl[0].A, stream);
-            }
+            rc = accumulate(sl, d_points, n, *sl.maxlen_h, cv, stream);
+            if (!rc) rc = reduce(sl.buckets, 1u << (cbits - 1), sl.NW, cv, &sl.S, &sl.A, stream);
             if (rc) return rc;
             LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
-            const uint32_t NW = fold_stride ? 1u : W;
+            const uint32_t NW = sl.NW;
             std::vector<char> S(PB * NW), A(PB * NW);
-            for (int k = 0; k < ns; k++) {
-                LW_HIP_CHECK(hipMemcpyAsync(S.data() + PB * sl[k].w0, sl[k].S, PB * sl[k].NW, hipMemcpyDeviceToHost, stream), LW_ERR_LAUNCH);
-                LW_HIP_CHECK(hipMemcpyAsync(A.data() + PB * sl[k].w0, sl[k].A, PB * sl[k].NW, hipMemcpyDeviceToHost, stream), LW_ERR_LAUNCH);
-            }
+            LW_HIP_CHECK(hipMemcpyAsync(S.data(), sl.S, PB * NW, hipMemcpyDeviceToHost, stream), LW_ERR_LAUNCH);
+            LW_HIP_CHECK(hipMemcpyAsync(A.data(), sl.A, PB * NW, hipMemcpyDeviceToHost, stream), LW_ERR_LAUNCH);
             LW_HIP_CHECK(hipStreamSynchronize(stream), LW_ERR_LAUNCH);
             // window sum = sum (j + 1) * bucket[j] = S_w + A_w
             std::vector<Point<C>> wsum(NW);

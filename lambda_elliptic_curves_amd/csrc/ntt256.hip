@@ -89,8 +89,9 @@ static int cfg_tile_log() { return NttCfgA::TILE_LOG; }
 static int cfg_kmax() { return NttCfgA::KMAX; }
 
 // stages [skip, L): the first `skip` stages of a zero-padded input only replicate it (see ntt256_run)
-static NttPlan plan_passes(uint32_t L, uint32_t max_r, uint32_t skip = 0) {
+static NttPlan plan_passes(uint32_t L, uint32_t skip = 0) {
     const uint32_t NTT_TILE_LOG = (uint32_t)cfg_tile_log();
+    const uint32_t max_r = 8;   // stages per pass: the staged twiddles and the lazy bound need r <= 8 (ntt_kernels.cuh)
     NttPlan pl{};
     const uint32_t Ls = L - skip;
     pl.npass = (int)((Ls + max_r - 1) / max_r);
@@ -100,7 +101,7 @@ static NttPlan plan_passes(uint32_t L, uint32_t max_r, uint32_t skip = 0) {
     for (int i = 0; i < pl.npass; i++) rr[i] = base + ((uint32_t)i < extra ? 1 : 0);
     // From 2^16 up: the last pass (per-element twiddles, bit-reversed stores, wave-local exchanges) takes a full max_r
     // stages and the others share the rest as evenly as possible in EVEN sizes — an odd pass ends in a radix-2 register
-    // step with two items per thread.  Measured (tools/ab_ntt_plan.py): 2^20 (7,7,6) 0.1056 -> (6,6,8) 0.1030 ms,
+    // step with two items per thread.  Measured: 2^20 (7,7,6) 0.1056 -> (6,6,8) 0.1030 ms,
     // 2^22 (8,7,7) 0.3588 -> (6,8,8) 0.3533, 2^26 (7,7,6,6) 6.45 -> (6,6,6,8) 6.19 ms; a short LAST pass is the worst
     // choice (2^26 (8,8,8,2): 9.1 ms).
     if (pl.npass >= 2 && Ls >= 16 && Ls > max_r) {
@@ -115,23 +116,6 @@ static NttPlan plan_passes(uint32_t L, uint32_t max_r, uint32_t skip = 0) {
                 rr[i]--;
                 rr[i + 1]++;
             }
-    }
-    // tuning only: LW_HIP_NTT_PLAN="8,8,6" fixes the stages per pass for transforms whose stage count matches the sum
-    static const char *plan_env = tuning_env("LW_HIP_NTT_PLAN");
-    if (plan_env) {
-        uint32_t v[8], cnt = 0, sum = 0;
-        for (const char *q = plan_env; *q && cnt < 8;) {
-            v[cnt] = (uint32_t)atoi(q);
-            sum += v[cnt++];
-            while (*q && *q != ',') q++;
-            if (*q == ',') q++;
-        }
-        bool ok = sum == Ls && cnt >= 1;
-        for (uint32_t i = 0; i < cnt && ok; i++) ok = v[i] >= 1 && v[i] <= max_r;
-        if (ok) {
-            pl.npass = (int)cnt;
-            for (uint32_t i = 0; i < cnt; i++) rr[i] = v[i];
-        }
     }
     uint32_t s = skip;
     for (int i = 0; i < pl.npass; i++) {
@@ -158,49 +142,43 @@ static void split_steps(uint32_t r, NttPassParams &p) {
     }
 }
 
-static bool g_ntt_wave_local_all = [] { const char *e = tuning_env("LW_HIP_NTT_WAVE_LOCAL"); return e && atoi(e) == 2; }();   // A/B: also in non-last passes
-static bool g_ntt_wave_local = [] { const char *e = tuning_env("LW_HIP_NTT_WAVE_LOCAL"); return !e || atoi(e) != 0; }();   // A/B switch
-static uint32_t g_ntt_max_r = 8;
-void ntt_set_max_pass_stages(uint32_t r) { g_ntt_max_r = r < 1 ? 1 : (r > 8 ? 8 : r); }
-
 template <class F, class CFG>
 static void launch_pass(bool last, dim3 grid, hipStream_t stream, const NttPassParams &p) {
     const bool extra = p.cos_in || p.cos_out || p.scale;
     // Column layout with wave-local exchanges (ntt_kernels.cuh lds_slot): full-size tiles only — every register step has
     // exactly one work-item per thread, so a column's items sit in the same wavefront in every step with the same k.
-    // The exchange before step s stays inside the wave when steps s-1 and s both walk rows fastest with the same k
-    // (last pass: from step 1; other passes: from step 2, their first step walks columns fastest for coalesced loads).
+    // The exchange before step s >= 1 stays inside the wave when steps s-1 and s both walk rows fastest with the same k.
     // Used by the LAST pass only: there it removes all three inter-step barriers and makes the per-lane twiddle fetches of
     // a wave consecutive table entries (0.537 -> 0.506 ms at 2^24).  In the other passes rows-fastest work-items read 64
     // different staged twiddles per wave where columns-fastest ones read 8 (broadcast over the columns), which costs more
     // LDS bandwidth than the two barriers it saves (0.437 -> 0.461 ms); fetching them from the table instead, as the last
-    // pass does, is worse still (0.440 -> 0.478 ms, LW_HIP_NTT_WAVE_LOCAL=2): they keep the plain layout.
-    bool wl = g_ntt_wave_local && (last || g_ntt_wave_local_all) && p.r >= 6;
+    // pass does, is worse still (0.440 -> 0.478 ms): they keep the plain layout, and no wave-local form of them is built.
+    bool wl = last && p.r >= 6;
     uint32_t ws = 0;
     for (uint32_t st = 0; st < p.nsteps && wl; st++)
         if ((1u << (p.r + p.logC - p.k[st])) != (uint32_t)CFG::THREADS) wl = false;
     if (wl)
-        for (uint32_t st = (last ? 1 : 2); st < p.nsteps; st++)
+        for (uint32_t st = 1; st < p.nsteps; st++)
             if (p.k[st] == p.k[st - 1] && (1u << (p.r - p.k[st])) <= 64u) ws |= 1u << st;
     NttPassParams q = p;
     q.wave_sync = ws;
+    // wl implies last: the WL template argument of the wave-local launches is LASTV, so other passes instantiate WL = false only
 #define LW_LAUNCH_PASS(LASTV, EXTRAV)                                                                                          \
     do {                                                                                                                       \
-        if (fx == 8 && wl) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, CFG, EXTRAV, true, FXOK ? 8 : 0>), grid, dim3(CFG::THREADS), 0, stream, q);   \
+        if (fx == 8 && wl) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, CFG, EXTRAV, LASTV, FXOK ? 8 : 0>), grid, dim3(CFG::THREADS), 0, stream, q);   \
         else if (fx == 8) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, CFG, EXTRAV, false, FXOK ? 8 : 0>), grid, dim3(CFG::THREADS), 0, stream, q);   \
         else if (fx == 6 && !wl) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, CFG, EXTRAV, false, FXOK ? 6 : 0>), grid, dim3(CFG::THREADS), 0, stream, q);   \
         else if (fx == 7 && !wl) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, CFG, EXTRAV, false, FXOK ? 7 : 0>), grid, dim3(CFG::THREADS), 0, stream, q);   \
-        else if (wl) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, CFG, EXTRAV, true>), grid, dim3(CFG::THREADS), 0, stream, q);  \
+        else if (wl) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, CFG, EXTRAV, LASTV>), grid, dim3(CFG::THREADS), 0, stream, q);  \
         else hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, CFG, EXTRAV, false>), grid, dim3(CFG::THREADS), 0, stream, q);      \
     } while (0)
     // full-size tiles (every pass of a 2^24 transform, the last pass from 2^16 on, the 6-stage passes of 2^20 and 2^26):
     // kernels with the tile shape compiled in
     constexpr bool FXOK = CFG::TILE == 2048 && CFG::THREADS == 512;
-    static const bool fx_env = [] { const char *e = tuning_env("LW_HIP_NTT_FX"); return !e || atoi(e) != 0; }();   // A/B only
     int fx = 0;
-    if (FXOK && fx_env && p.r == 8 && p.logC == 3 && p.nsteps == 4 && p.k[0] == 2 && p.k[1] == 2 && p.k[2] == 2 && p.k[3] == 2) fx = 8;
-    if (FXOK && fx_env && p.r == 7 && p.logC == 4 && p.nsteps == 4 && p.k[0] == 2 && p.k[1] == 2 && p.k[2] == 2 && p.k[3] == 1) fx = 7;   // (7,7,8)
-    if (FXOK && fx_env && p.r == 6 && p.logC == 5 && p.nsteps == 3 && p.k[0] == 2 && p.k[1] == 2 && p.k[2] == 2) fx = 6;   // (6,6,8), (6,6,6,8)
+    if (FXOK && p.r == 8 && p.logC == 3 && p.nsteps == 4 && p.k[0] == 2 && p.k[1] == 2 && p.k[2] == 2 && p.k[3] == 2) fx = 8;
+    if (FXOK && p.r == 7 && p.logC == 4 && p.nsteps == 4 && p.k[0] == 2 && p.k[1] == 2 && p.k[2] == 2 && p.k[3] == 1) fx = 7;   // (7,7,8)
+    if (FXOK && p.r == 6 && p.logC == 5 && p.nsteps == 3 && p.k[0] == 2 && p.k[1] == 2 && p.k[2] == 2) fx = 6;   // (6,6,8), (6,6,6,8)
     if (last) {
         if (extra) LW_LAUNCH_PASS(true, true);
         else LW_LAUNCH_PASS(true, false);
@@ -277,7 +255,7 @@ static int ntt256_run(Context &c, int field, lw_dir_t dir, const void *d_in, voi
     if (rc) return rc;
     const uint4 *tw = (const uint4 *)c.tw[field][dir].buf.p;
 
-    NttPlan pl = plan_passes(log2n, g_ntt_max_r, skip);
+    NttPlan pl = plan_passes(log2n, skip);
     const bool need_scratch = pl.npass > 1 || d_in == d_out;
     if (need_scratch && c.scratch.ensure((size_t)n * batch * 32)) return LW_ERR_ALLOC;
     c.timings.scratch_bytes = c.scratch.bytes;

@@ -7,7 +7,7 @@
 // the stages are scheduled; here they are scheduled for the GPU:
 //
 //   * log2(N) stages are cut into passes of r <= 8 stages (the staged twiddles ltw[2][256] and the 17p lazy bound
-//     both need r <= 8; ntt_set_max_pass_stages enforces it).  One workgroup owns a tile of 2^r "rows"
+//     both need r <= 8; plan_passes never plans more).  One workgroup owns a tile of 2^r "rows"
 //     (the index bits the pass's stages touch) x C adjacent "columns" (contiguous elements), stages it in
 //     LDS once and runs all r stages there: a pass costs one HBM read + one HBM write of the vector,
 //     versus one round trip per stage in the reference's CUDA path (math/src/fft/gpu/cuda/ops.rs:28-38).

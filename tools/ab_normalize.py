@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Standalone time of the projective -> affine normalisation (lw_hip_srs_create_device) for the current environment
-(LW_HIP_MSM_CHK = points per work-item): usage ab_normalize.py CURVE L [L ...]"""
+"""Standalone time of the projective -> affine normalisation (lw_hip_srs_create_device):
+usage ab_normalize.py CURVE L [L ...]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -16,4 +16,4 @@ for L in map(int, sys.argv[2:]):
         msm.Srs(crv, t_points=tp, n=n).close()
     torch.cuda.synchronize()
     prof = _lib.profile_end()
-    print("chk=%s %s 2^%d:" % (os.environ.get("LW_HIP_MSM_CHK", "auto"), sys.argv[1], L), {k: round(v[1] / max(v[0], 1), 3) for k, v in prof.items()}, flush=True)
+    print("%s 2^%d:" % (sys.argv[1], L), {k: round(v[1] / max(v[0], 1), 3) for k, v in prof.items()}, flush=True)
