@@ -457,6 +457,13 @@ __device__ __forceinline__ void col_mp(uint64_t &lo, uint32_t &hi, const uint32_
         col_mp<F, K, I + 1, IEND>(lo, hi, m);
     }
 }
+// Fields for which mac_chains.inc has FusedCol<F, K>: every column of a single product as one statement (fips_fused)
+template <class F>
+struct lw_fused_columns {
+    static constexpr bool value = false;
+};
+template <class F, int K>
+struct FusedCol;
 #include "mac_chains.inc"
 
 // every limb of p in [LO, HI) is a literal (> 64, so not an inline constant and not zero): the whole m*p part of a
@@ -534,12 +541,67 @@ __device__ __forceinline__ void fips_col(uint64_t init, const Fe<F> *const (&a)[
         fips_col<F, P, K + 1>((lo >> 32) | ((uint64_t)hi << 32), a, b, m, t);
     }
 }
+// Unit low limb (p = 1 mod 2^32, INV = -1): m_k = -t_k, and t_k + m_k*p_0 = 2^32*(t_k != 0), so the reduction MAC
+// m_k*p_0 is a negation whose borrow is the carry into word 1.  Out: m_k and {mid, top} = (acc + m_k) >> 32, written
+// by 32-bit instructions so that the compiler can place them straight into the next column's addend pair.
+// (v_sub_co + 2 v_addc_co instead of v_sub + v_mad + v_addc + the v_mov that moved word 1 into an aligned pair.)
+__device__ __forceinline__ void lw_redc_unit(uint32_t &m, uint32_t &mid, uint32_t &top, uint32_t t, uint32_t w1, uint32_t w2) {
+    asm("v_sub_co_u32_e32 %0, vcc, 0, %3\n\t"
+        "v_addc_co_u32_e32 %1, vcc, 0, %4, vcc\n\t"
+        "v_addc_co_u32_e32 %2, vcc, 0, %5, vcc"
+        : "=&v"(m), "=&v"(mid), "=v"(top)
+        : "v"(t), "v"(w1), "v"(w2)
+        : "vcc");
+}
+// the same for column 0, whose top word is 0
+__device__ __forceinline__ void lw_redc_unit0(uint32_t &m, uint32_t &mid, uint32_t &top, uint32_t t, uint32_t w1) {
+    asm("v_sub_co_u32_e32 %0, vcc, 0, %3\n\t"
+        "v_addc_co_u32_e32 %1, vcc, 0, %4, vcc\n\t"
+        "v_addc_co_u32_e64 %2, vcc, 0, 0, vcc"
+        : "=&v"(m), "=&v"(mid), "=v"(top)
+        : "v"(t), "v"(w1)
+        : "vcc");
+}
+// Column K of a single product a*b + m*p for a field with FusedCol columns: one statement for the column's MACs, one
+// for the unit limb (columns K < N).  Every column sum is the exact integer fips_col<F, 1, K> forms (only the order of
+// its MACs differs), so the same m and the same result words come out.
+template <class F, int K>
+__device__ __forceinline__ void fips_fused(uint64_t init, const Fe<F> &a, const Fe<F> &b, uint32_t (&m)[F::N], uint32_t (&t)[F::N]) {
+    constexpr int N = F::N;
+    static_assert(F::p(0) == 1u && F::INV == 0xffffffffu, "fused columns need a unit low limb of the modulus");
+    if constexpr (K == 2 * N - 1) {
+        t[N - 1] = (uint32_t)init;   // no products left: the last carry is the top limb
+    } else {
+        uint64_t lo;
+        uint32_t hi;
+        FusedCol<F, K>::run(lo, hi, init, a, b, m);
+        if constexpr (K < N) {
+            uint32_t mid, top;
+            if constexpr (K == 0) lw_redc_unit0(m[0], mid, top, (uint32_t)lo, (uint32_t)(lo >> 32));
+            else lw_redc_unit(m[K], mid, top, (uint32_t)lo, (uint32_t)(lo >> 32), hi);
+            fips_fused<F, K + 1>(((uint64_t)top << 32) | mid, a, b, m, t);
+        } else {
+            t[K - N] = (uint32_t)lo;
+            fips_fused<F, K + 1>((lo >> 32) | ((uint64_t)hi << 32), a, b, m, t);
+        }
+    }
+}
+// a*b + m*p over all columns into t (t < 2p for a < p), by the fused columns where the field has them
+template <class F>
+__device__ __forceinline__ void fips_product(const Fe<F> &a, const Fe<F> &b, uint32_t (&t)[F::N]) {
+    uint32_t m[F::N];
+    if constexpr (lw_fused_columns<F>::value) {
+        fips_fused<F, 0>(0ull, a, b, m, t);
+    } else {
+        const Fe<F> *const pa[1] = {&a}, *const pb[1] = {&b};
+        fips_col<F, 1, 0>(0ull, pa, pb, m, t);
+    }
+}
 template <class F>
 __device__ __forceinline__ Fe<F> fe_mul_gfx9(const Fe<F> &a, const Fe<F> &b) {
     constexpr int N = F::N;
-    uint32_t m[N], t[N];
-    const Fe<F> *const pa[1] = {&a}, *const pb[1] = {&b};
-    fips_col<F, 1, 0>(0ull, pa, pb, m, t);
+    uint32_t t[N];
+    fips_product<F>(a, b, t);
     Fe<F> r;
 #pragma unroll
     for (int i = 0; i < N; i++) r.v[i] = t[i];
@@ -659,9 +721,8 @@ template <class F>
 LW_HD Fe<F> fe_mul_lazy(const Fe<F> &a, const Fe<F> &b) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int N = F::N;
-    uint32_t m[N], t[N];
-    const Fe<F> *const pa[1] = {&a}, *const pb[1] = {&b};
-    fips_col<F, 1, 0>(0ull, pa, pb, m, t);
+    uint32_t t[N];
+    fips_product<F>(a, b, t);
     Fe<F> r;
 #pragma unroll
     for (int i = 0; i < N; i++) r.v[i] = t[i];
