@@ -97,9 +97,6 @@ static void release_everything() {
 // SharedState::rw held unique
 static int init_locked(const int *device_ids, int n_devices) {
     SharedState &sh = shared_state();
-#ifdef LW_HIP_ABLATION
-    if (const char *e = tuning_env("LW_HIP_NTT_DBG")) ntt_set_debug((uint32_t)atoi(e));   // wrong results, timing only
-#endif
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count <= 0) {

@@ -12,14 +12,6 @@
 #include <vector>
 #include "../../include/lw_hip.h"
 
-// Ablation switches (skip butterflies / loads / stores: WRONG results, timing only) exist only in builds made with
-// -DLW_HIP_ABLATION (tools/ab_ntt.sh); in the shipped library LW_DBG() is the constant 0 and the branches fold away.
-#ifdef LW_HIP_ABLATION
-#define LW_DBG(p) ((p).dbg)
-#else
-#define LW_DBG(p) 0u
-#endif
-
 namespace lw {
 
 void set_error(const char *fmt, ...);
@@ -170,6 +162,33 @@ struct ExclusiveScope {
         if (c.call_lock) c.call_lock->lock();
     }
 };
+
+// The cache skeleton of the shared twiddle tables (ntt256.hip, ntt_bb.hip): `t` serves every transform of up to 2^t.log_n
+// points once valid.  Otherwise it is rebuilt for 2^L points, L = max(log2n, 16) — so that small transforms never trigger a
+// rebuild storm — unless the field has no root of that order.  The tables are shared by all lanes: (re)building one needs
+// every other call out of the library (the old table is freed), so the call's shared hold is given up for the scope and
+// taken back afterwards; another lane may have built the table in between.  fill(L) enqueues on `stream` whatever writes
+// the 2^(L-1) entries of entry_bytes each into t.buf and returns LW_OK or an error code.  The table is marked invalid
+// before its buffer is touched and valid only once the fill has completed: a failed rebuild leaves no lane a stale table.
+template <class Fill>
+int ensure_twiddle_table(Context &c, TwiddleTable &t, uint32_t log2n, uint32_t two_adicity, size_t entry_bytes, hipStream_t stream,
+                         Fill fill) {
+    if (t.valid && t.log_n >= log2n) return LW_OK;
+    if (log2n < 1) return LW_OK;
+    ExclusiveScope excl(c);
+    if (t.valid && t.log_n >= log2n) return LW_OK;
+    uint32_t L = log2n < 16 ? 16 : log2n;
+    if (L > two_adicity) L = log2n;
+    t.valid = false;
+    if (t.buf.ensure(((size_t)1 << (L - 1)) * entry_bytes)) return LW_ERR_ALLOC;
+    const int rc = fill(L);
+    if (rc) return rc;
+    LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
+    LW_HIP_CHECK(hipStreamSynchronize(stream), LW_ERR_LAUNCH);
+    t.log_n = L;
+    t.valid = true;
+    return LW_OK;
+}
 
 Context &lane(int i);
 inline Context &ctx() { return lane(0); }

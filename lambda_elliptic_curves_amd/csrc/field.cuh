@@ -392,21 +392,6 @@ __device__ __forceinline__ void mac96_x4(uint64_t &lo, uint32_t &hi, uint32_t a0
 // addend and the first add-with-carry materialises the top word (0 + 0 + carry), so a column change costs one
 // register copy instead of three.
 #define LW_MAC_FIRST(A, B, INIT) "v_mad_u64_u32 %0, vcc, " A ", " B ", " INIT "\n\tv_addc_co_u32_e64 %1, vcc, 0, 0, vcc\n\t"
-__device__ __forceinline__ void mac96_first_x1(uint64_t &lo, uint32_t &hi, uint64_t init, uint32_t a0, uint32_t b0) {
-    asm(LW_MAC_FIRST("%3", "%4", "%2") : "=v"(lo), "=v"(hi) : "v"(init), "v"(a0), "v"(b0) : "vcc");
-}
-__device__ __forceinline__ void mac96_first_x2(uint64_t &lo, uint32_t &hi, uint64_t init, uint32_t a0, uint32_t b0, uint32_t a1,
-                                               uint32_t b1) {
-    asm(LW_MAC_FIRST("%3", "%4", "%2") LW_MAC_V("%5", "%6")
-        : "=&v"(lo), "=&v"(hi) : "v"(init), "v"(a0), "v"(b0), "v"(a1), "v"(b1) : "vcc");
-}
-__device__ __forceinline__ void mac96_first_x4(uint64_t &lo, uint32_t &hi, uint64_t init, uint32_t a0, uint32_t b0, uint32_t a1,
-                                               uint32_t b1, uint32_t a2, uint32_t b2, uint32_t a3, uint32_t b3) {
-    asm(LW_MAC_FIRST("%3", "%4", "%2") LW_MAC_V("%5", "%6") LW_MAC_V("%7", "%8") LW_MAC_V("%9", "%10")
-        : "=&v"(lo), "=&v"(hi)
-        : "v"(init), "v"(a0), "v"(b0), "v"(a1), "v"(b1), "v"(a2), "v"(b2), "v"(a3), "v"(b3)
-        : "vcc");
-}
 // acc(96) += m * C for a compile-time constant C
 template <uint32_t C>
 __device__ __forceinline__ void mac96_c1(uint64_t &lo, uint32_t &hi, uint32_t m0) {
@@ -475,20 +460,6 @@ constexpr bool lw_all_literal() {
     return true;
 }
 
-// column K, first chunk: acc = init + a[I]*b[K-I] + ...; returns via lo/hi, continues with col_ab
-template <class F, int K, int I, int IEND>
-__device__ __forceinline__ void col_ab_first(uint64_t &lo, uint32_t &hi, uint64_t init, const Fe<F> &a, const Fe<F> &b) {
-    if constexpr (I + 4 <= IEND) {
-        mac96_first_x4(lo, hi, init, a.v[I], b.v[K - I], a.v[I + 1], b.v[K - I - 1], a.v[I + 2], b.v[K - I - 2], a.v[I + 3], b.v[K - I - 3]);
-        col_ab<F, K, I + 4, IEND>(lo, hi, a, b);
-    } else if constexpr (I + 2 <= IEND) {
-        mac96_first_x2(lo, hi, init, a.v[I], b.v[K - I], a.v[I + 1], b.v[K - I - 1]);
-        col_ab<F, K, I + 2, IEND>(lo, hi, a, b);
-    } else {
-        static_assert(I + 1 <= IEND, "column without products");
-        mac96_first_x1(lo, hi, init, a.v[I], b.v[K - I]);
-    }
-}
 // Column K of sum_{q<P} a[q]*b[q] + m*p.  P > 1 accumulates several products before the single Montgomery
 // reduction (fe_dot below): the a*b MACs of every product land in the same 96-bit column accumulator and the m*p
 // MACs are paid once, so a sum of P products costs (P+1)*N^2 MACs instead of 2*P*N^2.
@@ -502,40 +473,24 @@ __device__ __forceinline__ void fips_col(uint64_t init, const Fe<F> *const (&a)[
         uint64_t lo;
         uint32_t hi;
         if constexpr (K < N) {
-#if defined(LW_NO_COLUMN_CHAINS)
-            col_ab_first<F, K, 0, K + 1>(lo, hi, init, *a[0], *b[0]);
-#else
             col_ab_first_dispatch<F, K, 0, K + 1>(lo, hi, init, *a[0], *b[0]);
-#endif
             if constexpr (P > 1) col_ab<F, K, 0, K + 1>(lo, hi, *a[1], *b[1]);
             if constexpr (P > 2) col_ab<F, K, 0, K + 1>(lo, hi, *a[2], *b[2]);
             if constexpr (P > 3) col_ab<F, K, 0, K + 1>(lo, hi, *a[3], *b[3]);
-#if defined(LW_NO_COLUMN_CHAINS)
-            col_mp<F, K, 0, K>(lo, hi, m);
-#else
             if constexpr (K >= 1 && lw_all_literal<F, 1, K + 1>()) col_mp_dispatch<F, K, 0, K>(lo, hi, m);
             else col_mp<F, K, 0, K>(lo, hi, m);
-#endif
             uint32_t mk;
             if constexpr (F::INV == 0xffffffffu) mk = 0u - (uint32_t)lo;
             else mk = (uint32_t)lo * F::INV;
             m[K] = mk;
             mac96_c1<F::p(0)>(lo, hi, mk);
         } else {
-#if defined(LW_NO_COLUMN_CHAINS)
-            col_ab_first<F, K, K - N + 1, N>(lo, hi, init, *a[0], *b[0]);
-#else
             col_ab_first_dispatch<F, K, K - N + 1, 2 * N - 1 - K>(lo, hi, init, *a[0], *b[0]);
-#endif
             if constexpr (P > 1) col_ab<F, K, K - N + 1, N>(lo, hi, *a[1], *b[1]);
             if constexpr (P > 2) col_ab<F, K, K - N + 1, N>(lo, hi, *a[2], *b[2]);
             if constexpr (P > 3) col_ab<F, K, K - N + 1, N>(lo, hi, *a[3], *b[3]);
-#if defined(LW_NO_COLUMN_CHAINS)
-            col_mp<F, K, K - N + 1, N>(lo, hi, m);
-#else
             if constexpr (lw_all_literal<F, K - N + 1, N>()) col_mp_dispatch<F, K, K - N + 1, 2 * N - 1 - K>(lo, hi, m);
             else col_mp<F, K, K - N + 1, N>(lo, hi, m);
-#endif
             t[K - N] = (uint32_t)lo;
         }
         fips_col<F, P, K + 1>((lo >> 32) | ((uint64_t)hi << 32), a, b, m, t);

@@ -17,8 +17,6 @@ lw_curve_t srs_curve(const lw_srs_t *srs);
 int msm_srs_locked(Context &c, const lw_srs_t *srs, const uint64_t *d_scalars, size_t n, void *out_point, hipStream_t stream, int mont);
 
 // ---- ntt256.hip
-void ntt_set_debug(uint32_t d);
-uint32_t ntt_get_debug();
 int ntt256_device(Context &c, int field, lw_dir_t dir, const void *d_in, void *d_out, uint32_t log2n, uint32_t batch,
                   uint64_t stride, const uint32_t *coset_words, hipStream_t stream, uint32_t in_log2);
 int ntt256_gen_powers(int field, uint32_t order, uint64_t count, uint32_t bitrev, bool inverse, const uint32_t *scale_words, void *d_out,

@@ -3,8 +3,18 @@
 #include <vector>
 #include "internal.h"
 #include "ntt_kernels.cuh"
+#include "ntt_plan.h"
 
 namespace lw {
+
+// The two 256-bit NTT fields: f(F{}) with F = Stark252 or Fr381 (f returns int)
+template <class Fn>
+static int with_field(int field, Fn f) {
+    if (field == LW_FIELD_STARK252) return f(Stark252{});
+    if (field == LW_FIELD_BLS12_381_FR) return f(Fr381{});
+    set_error("field %d has no 256-bit NTT", field);
+    return LW_ERR_BAD_ARG;
+}
 
 // ---- host field helpers (same limb code as the device, compiled for x86) ----
 template <class F>
@@ -45,104 +55,22 @@ static int upload_power_tables(const Fe<F> &base, uint32_t hbits, uint64_t hi_co
 template <class F>
 static int ensure_twiddles(Context &c, int field, lw_dir_t dir, uint32_t log2n, hipStream_t stream) {
     TwiddleTable &t = c.tw[field][dir];
-    if (t.valid && t.log_n >= log2n) return LW_OK;
-    if (log2n < 1) return LW_OK;
-    // The tables are shared by all lanes: (re)building one needs every other call out of the library (the old table is
-    // freed).  The call's shared hold is given up for the scope and taken back afterwards; another lane may have built the
-    // table in between.
-    ExclusiveScope excl(c);
-    if (t.valid && t.log_n >= log2n) return LW_OK;
-    // build for at least 2^16 so small transforms never trigger a rebuild storm
-    uint32_t L = log2n < 16 ? 16 : log2n;
-    if (L > F::TWO_ADICITY) L = log2n;
-    const uint32_t bits = L - 1;
-    const uint64_t count = 1ull << bits;
-    if (t.buf.ensure(count * 32)) return LW_ERR_ALLOC;
-    const uint32_t hbits = (bits + 1) / 2;
-    Fe<F> w = host_root_of_unity<F>(L, dir == LW_DIR_INVERSE);
-    DeviceBuf lo, hi;
-    int rc = upload_power_tables<F>(w, hbits, 1ull << (bits - hbits), lo, hi);
-    if (rc) { lo.release(); hi.release(); return rc; }
-    const uint32_t threads = 256;
-    const uint64_t blocks = (count + threads - 1) / threads;
-    hipLaunchKernelGGL((twiddle_fill_kernel<F>), dim3((uint32_t)blocks), dim3(threads), 0, stream, (uint4 *)t.buf.p,
-                       (const uint4 *)lo.p, (const uint4 *)hi.p, bits, hbits, count);
-    LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
-    LW_HIP_CHECK(hipStreamSynchronize(stream), LW_ERR_LAUNCH);
+    DeviceBuf lo, hi;   // the two power tables the fill kernel reads: alive until the skeleton has synchronised
+    const int rc = ensure_twiddle_table(c, t, log2n, F::TWO_ADICITY, 32, stream, [&](uint32_t L) {
+        const uint32_t bits = L - 1, hbits = (bits + 1) / 2;
+        const uint64_t count = 1ull << bits;
+        const int urc = upload_power_tables<F>(host_root_of_unity<F>(L, dir == LW_DIR_INVERSE), hbits, 1ull << (bits - hbits), lo, hi);
+        if (urc) return urc;
+        hipLaunchKernelGGL((twiddle_fill_kernel<F>), dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, stream, (uint4 *)t.buf.p,
+                           (const uint4 *)lo.p, (const uint4 *)hi.p, bits, hbits, count);
+        return (int)LW_OK;
+    });
     lo.release();
     hi.release();
-    t.log_n = L;
-    t.valid = true;
-    return LW_OK;
+    return rc;
 }
 
-// ---- pass planning ----
-struct NttPlan {
-    int npass;
-    uint32_t s0[8], r[8], logC[8];
-};
-
-static uint32_t g_ntt_dbg = 0;     // diagnostics: see NttPassParams::dbg (results are wrong when set)
-void ntt_set_debug(uint32_t d) { g_ntt_dbg = d; }
-uint32_t ntt_get_debug() { return g_ntt_dbg; }
-static int cfg_tile_log() { return NttCfgA::TILE_LOG; }
-static int cfg_kmax() { return NttCfgA::KMAX; }
-
-// stages [skip, L): the first `skip` stages of a zero-padded input only replicate it (see ntt256_run)
-static NttPlan plan_passes(uint32_t L, uint32_t skip = 0) {
-    const uint32_t NTT_TILE_LOG = (uint32_t)cfg_tile_log();
-    const uint32_t max_r = 8;   // stages per pass: the staged twiddles and the lazy bound need r <= 8 (ntt_kernels.cuh)
-    NttPlan pl{};
-    const uint32_t Ls = L - skip;
-    pl.npass = (int)((Ls + max_r - 1) / max_r);
-    if (pl.npass < 1) pl.npass = 1;
-    uint32_t rr[8];
-    uint32_t base = Ls / pl.npass, extra = Ls % pl.npass;
-    for (int i = 0; i < pl.npass; i++) rr[i] = base + ((uint32_t)i < extra ? 1 : 0);
-    // From 2^16 up: the last pass (per-element twiddles, bit-reversed stores, wave-local exchanges) takes a full max_r
-    // stages and the others share the rest as evenly as possible in EVEN sizes — an odd pass ends in a radix-2 register
-    // step with two items per thread.  Measured: 2^20 (7,7,6) 0.1056 -> (6,6,8) 0.1030 ms,
-    // 2^22 (8,7,7) 0.3588 -> (6,8,8) 0.3533, 2^26 (7,7,6,6) 6.45 -> (6,6,6,8) 6.19 ms; a short LAST pass is the worst
-    // choice (2^26 (8,8,8,2): 9.1 ms).
-    if (pl.npass >= 2 && Ls >= 16 && Ls > max_r) {
-        const int q = pl.npass - 1;
-        rr[q] = max_r;
-        const uint32_t R = Ls - max_r;
-        base = R / q;
-        extra = R % q;
-        for (int i = 0; i < q; i++) rr[i] = base + ((uint32_t)i >= (uint32_t)q - extra ? 1 : 0);
-        for (int i = 0; i + 1 < q; i++)
-            if ((rr[i] & 1) && (rr[i + 1] & 1) && rr[i + 1] < max_r && rr[i] > 1) {
-                rr[i]--;
-                rr[i + 1]++;
-            }
-    }
-    uint32_t s = skip;
-    for (int i = 0; i < pl.npass; i++) {
-        const uint32_t r = rr[i];
-        pl.s0[i] = s;
-        pl.r[i] = r;
-        uint32_t room = NTT_TILE_LOG - r;
-        uint32_t avail = L - s - r;   // non-last: log2 of the row stride; last: 0 unless multi-pass
-        if (i == pl.npass - 1) avail = L - r;
-        pl.logC[i] = room < avail ? room : avail;
-        s += r;
-    }
-    return pl;
-}
-
-static void split_steps(uint32_t r, NttPassParams &p) {
-    const uint32_t NTT_KMAX = (uint32_t)cfg_kmax();
-    uint32_t nsteps = (r + NTT_KMAX - 1) / NTT_KMAX, left = r;
-    p.nsteps = nsteps;
-    for (uint32_t i = 0; i < nsteps; i++) {
-        uint32_t k = (left + (nsteps - i) - 1) / (nsteps - i);
-        p.k[i] = k;
-        left -= k;
-    }
-}
-
-template <class F, class CFG>
+template <class F>
 static void launch_pass(bool last, dim3 grid, hipStream_t stream, const NttPassParams &p) {
     const bool extra = p.cos_in || p.cos_out || p.scale;
     // Column layout with wave-local exchanges (ntt_kernels.cuh lds_slot): full-size tiles only — every register step has
@@ -156,7 +84,7 @@ static void launch_pass(bool last, dim3 grid, hipStream_t stream, const NttPassP
     bool wl = last && p.r >= 6;
     uint32_t ws = 0;
     for (uint32_t st = 0; st < p.nsteps && wl; st++)
-        if ((1u << (p.r + p.logC - p.k[st])) != (uint32_t)CFG::THREADS) wl = false;
+        if ((1u << (p.r + p.logC - p.k[st])) != (uint32_t)NTT_THREADS) wl = false;
     if (wl)
         for (uint32_t st = 1; st < p.nsteps; st++)
             if (p.k[st] == p.k[st - 1] && (1u << (p.r - p.k[st])) <= 64u) ws |= 1u << st;
@@ -165,16 +93,16 @@ static void launch_pass(bool last, dim3 grid, hipStream_t stream, const NttPassP
     // wl implies last: the WL template argument of the wave-local launches is LASTV, so other passes instantiate WL = false only
 #define LW_LAUNCH_PASS(LASTV, EXTRAV)                                                                                          \
     do {                                                                                                                       \
-        if (fx == 8 && wl) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, CFG, EXTRAV, LASTV, FXOK ? 8 : 0>), grid, dim3(CFG::THREADS), 0, stream, q);   \
-        else if (fx == 8) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, CFG, EXTRAV, false, FXOK ? 8 : 0>), grid, dim3(CFG::THREADS), 0, stream, q);   \
-        else if (fx == 6 && !wl) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, CFG, EXTRAV, false, FXOK ? 6 : 0>), grid, dim3(CFG::THREADS), 0, stream, q);   \
-        else if (fx == 7 && !wl) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, CFG, EXTRAV, false, FXOK ? 7 : 0>), grid, dim3(CFG::THREADS), 0, stream, q);   \
-        else if (wl) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, CFG, EXTRAV, LASTV>), grid, dim3(CFG::THREADS), 0, stream, q);  \
-        else hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, CFG, EXTRAV, false>), grid, dim3(CFG::THREADS), 0, stream, q);      \
+        if (fx == 8 && wl) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, EXTRAV, LASTV, FXOK ? 8 : 0>), grid, dim3(NTT_THREADS), 0, stream, q);   \
+        else if (fx == 8) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, EXTRAV, false, FXOK ? 8 : 0>), grid, dim3(NTT_THREADS), 0, stream, q);   \
+        else if (fx == 6 && !wl) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, EXTRAV, false, FXOK ? 6 : 0>), grid, dim3(NTT_THREADS), 0, stream, q);   \
+        else if (fx == 7 && !wl) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, EXTRAV, false, FXOK ? 7 : 0>), grid, dim3(NTT_THREADS), 0, stream, q);   \
+        else if (wl) hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, EXTRAV, LASTV>), grid, dim3(NTT_THREADS), 0, stream, q);  \
+        else hipLaunchKernelGGL((ntt_pass_kernel<F, LASTV, EXTRAV, false>), grid, dim3(NTT_THREADS), 0, stream, q);      \
     } while (0)
     // full-size tiles (every pass of a 2^24 transform, the last pass from 2^16 on, the 6-stage passes of 2^20 and 2^26):
     // kernels with the tile shape compiled in
-    constexpr bool FXOK = CFG::TILE == 2048 && CFG::THREADS == 512;
+    constexpr bool FXOK = NTT_TILE == 2048 && NTT_THREADS == 512;
     int fx = 0;
     if (FXOK && p.r == 8 && p.logC == 3 && p.nsteps == 4 && p.k[0] == 2 && p.k[1] == 2 && p.k[2] == 2 && p.k[3] == 2) fx = 8;
     if (FXOK && p.r == 7 && p.logC == 4 && p.nsteps == 4 && p.k[0] == 2 && p.k[1] == 2 && p.k[2] == 2 && p.k[3] == 1) fx = 7;   // (7,7,8)
@@ -255,7 +183,7 @@ static int ntt256_run(Context &c, int field, lw_dir_t dir, const void *d_in, voi
     if (rc) return rc;
     const uint4 *tw = (const uint4 *)c.tw[field][dir].buf.p;
 
-    NttPlan pl = plan_passes(log2n, skip);
+    const NttPlan pl = plan_passes(log2n, log2n, skip, NTT_TILE_LOG, NTT_KMAX, true);
     const bool need_scratch = pl.npass > 1 || d_in == d_out;
     if (need_scratch && c.scratch.ensure((size_t)n * batch * 32)) return LW_ERR_ALLOC;
     c.timings.scratch_bytes = c.scratch.bytes;
@@ -282,7 +210,6 @@ static int ntt256_run(Context &c, int field, lw_dir_t dir, const void *d_in, voi
         const bool last = (i == pl.npass - 1);
         NttPassParams p{};
         p.tw = tw;
-        p.dbg = g_ntt_dbg;
         p.lazy_in = (F::LAZY && i > 0) ? 1 : 0;
         p.in_mask = i == 0 ? in_mask : ~0ull;
         p.cos_lo = cos_lo;
@@ -294,11 +221,12 @@ static int ntt256_run(Context &c, int field, lw_dir_t dir, const void *d_in, voi
         p.s0 = pl.s0[i];
         p.r = pl.r[i];
         p.logC = pl.logC[i];
-        if (p.r > 8) {   // ltw[2][256] (staged twiddles) and the 17p lazy bound both need r <= 8 (ntt_kernels.cuh)
+        if (p.r > NTT_MAX_R) {
             set_error("internal: NTT pass of %u stages", p.r);
             return LW_ERR_BAD_ARG;
         }
-        split_steps(p.r, p);
+        p.nsteps = pl.nsteps[i];
+        for (uint32_t q = 0; q < p.nsteps; q++) p.k[q] = pl.k[i][q];
         p.in = (const uint4 *)src;
         p.in_batch_stride = src_stride;
         if (last) {
@@ -320,7 +248,7 @@ static int ntt256_run(Context &c, int field, lw_dir_t dir, const void *d_in, voi
         const uint32_t blocks = 1u << (log2n - p.r - p.logC);
         dim3 grid(blocks, batch);
         hipEvent_t pe = c.prof_begin(stream);
-        launch_pass<F, NttCfgA>(last, grid, stream, p);
+        launch_pass<F>(last, grid, stream, p);
         c.prof_end(last ? "ntt_pass_kernel<last>" : "ntt_pass_kernel", pe, stream);
         LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
         src = p.out;
@@ -333,33 +261,26 @@ static int ntt256_run(Context &c, int field, lw_dir_t dir, const void *d_in, voi
 // ---- helpers for the multi-GPU cross step (ntt_cross.hip)
 int ntt256_power_tables(Context &c, int field, int slot, const uint32_t *base_words, bool invert, uint32_t hbits,
                         uint32_t hi_bits, hipStream_t stream, const uint4 **lo, const uint4 **hi) {
-    if (field == LW_FIELD_STARK252) return power_tables<Stark252>(c, field, slot, base_words, invert, hbits, hi_bits, stream, lo, hi);
-    return power_tables<Fr381>(c, field, slot, base_words, invert, hbits, hi_bits, stream, lo, hi);
+    return with_field(field, [&](auto f) { return power_tables<decltype(f)>(c, field, slot, base_words, invert, hbits, hi_bits, stream, lo, hi); });
 }
 int ntt256_root_words(int field, uint32_t order, bool inverse, uint32_t *words) {
-    if (field == LW_FIELD_STARK252) {
-        Fe<Stark252> w = host_root_of_unity<Stark252>(order, inverse);
+    return with_field(field, [&](auto f) {
+        const auto w = host_root_of_unity<decltype(f)>(order, inverse);
         for (int i = 0; i < 8; i++) words[i] = w.v[i];
-    } else {
-        Fe<Fr381> w = host_root_of_unity<Fr381>(order, inverse);
-        for (int i = 0; i < 8; i++) words[i] = w.v[i];
-    }
-    return LW_OK;
+        return (int)LW_OK;
+    });
 }
 int ntt256_inv_u64_words(int field, uint64_t v, uint32_t *words) {
-    if (field == LW_FIELD_STARK252) {
-        Fe<Stark252> w = fe_inv<Stark252>(fe_from_u64<Stark252>(v));
+    return with_field(field, [&](auto f) {
+        using F = decltype(f);
+        const Fe<F> w = fe_inv<F>(fe_from_u64<F>(v));
         for (int i = 0; i < 8; i++) words[i] = w.v[i];
-    } else {
-        Fe<Fr381> w = fe_inv<Fr381>(fe_from_u64<Fr381>(v));
-        for (int i = 0; i < 8; i++) words[i] = w.v[i];
-    }
-    return LW_OK;
+        return (int)LW_OK;
+    });
 }
 const uint4 *ntt256_twiddle_table(Context &c, int field, lw_dir_t dir, uint32_t log2n, hipStream_t stream, int *rc) {
-    *rc = field == LW_FIELD_STARK252 ? ensure_twiddles<Stark252>(c, field, dir, log2n, stream)
-                                     : ensure_twiddles<Fr381>(c, field, dir, log2n, stream);
-    return (const uint4 *)c.tw[field][dir].buf.p;
+    *rc = with_field(field, [&](auto f) { return ensure_twiddles<decltype(f)>(c, field, dir, log2n, stream); });
+    return *rc ? nullptr : (const uint4 *)c.tw[field][dir].buf.p;
 }
 
 // get_powers_of_primitive_root[_coset] (math/src/fft/cpu/roots_of_unity.rs:13-61) on the device: out[i] = scale * w^e(i),
@@ -400,16 +321,15 @@ static int gen_powers_t(uint32_t order, uint64_t count, uint32_t bitrev, bool in
 }
 int ntt256_gen_powers(int field, uint32_t order, uint64_t count, uint32_t bitrev, bool inverse, const uint32_t *scale_words, void *d_out,
                       hipStream_t stream) {
-    if (field == LW_FIELD_STARK252) return gen_powers_t<Stark252>(order, count, bitrev, inverse, scale_words, d_out, stream);
-    return gen_powers_t<Fr381>(order, count, bitrev, inverse, scale_words, d_out, stream);
+    return with_field(field, [&](auto f) { return gen_powers_t<decltype(f)>(order, count, bitrev, inverse, scale_words, d_out, stream); });
 }
 
 // in_log2 < log2n: d_in holds `batch` blocks of 2^in_log2 coefficients (dense), d_out 2^log2n evaluations each
 int ntt256_device(Context &c, int field, lw_dir_t dir, const void *d_in, void *d_out, uint32_t log2n, uint32_t batch,
                   uint64_t stride, const uint32_t *coset_words, hipStream_t stream, uint32_t in_log2) {
-    if (field == LW_FIELD_STARK252)
-        return ntt256_run<Stark252>(c, field, dir, d_in, d_out, log2n, batch, stride, coset_words, stream, in_log2);
-    return ntt256_run<Fr381>(c, field, dir, d_in, d_out, log2n, batch, stride, coset_words, stream, in_log2);
+    return with_field(field, [&](auto f) {
+        return ntt256_run<decltype(f)>(c, field, dir, d_in, d_out, log2n, batch, stride, coset_words, stream, in_log2);
+    });
 }
 
 }  // namespace lw

@@ -11,6 +11,7 @@
 #include <vector>
 #include "internal.h"
 #include "field.cuh"
+#include "ntt_plan.h"
 
 namespace lw {
 
@@ -40,7 +41,6 @@ struct BbPassParams {
     // log2(blow-up) stages that only pair data with padding the vector is the coefficient block replicated, so those
     // stages are skipped (s0 starts there) and the padding is never materialised.  Plain transforms: all ones.
     uint32_t in_mask;
-    uint32_t dbg;              // ablation builds only (-DLW_HIP_ABLATION): bit0 skip butterflies, bit1 skip loads, bit2 skip stores, bit3 old last-pass mapping
 };
 
 __device__ __forceinline__ uint32_t bb_bitrev(uint32_t x, uint32_t bits) { return bits ? (__brev(x) >> (32 - bits)) : 0u; }
@@ -76,9 +76,8 @@ __device__ __forceinline__ void bb_item(const BbPassParams &p, uint32_t *lds, co
     // input (column, row, component); in the later ones it keeps the lanes of a wave inside a few columns, whose
     // twiddles T[(hi_c << t) | x] are then neighbours in the table (columns-fastest made every lane fetch a different
     // cache line).  LDS slots are XOR-swizzled by row bits (lds_slot) so rows-fastest accesses spread over the banks.
-    const bool rows_fastest = LAST && (step == 0 || !(LW_DBG(p) & 8));
     uint32_t c, mr;
-    if (rows_fastest) {
+    if (LAST) {   // rows fastest
         const uint32_t comp = w & ((1u << lgV) - 1);
         mr = (w >> lgV) & ((1u << (r - K)) - 1);
         c = ((w >> (lgV + r - K)) << lgV) | comp;
@@ -86,7 +85,7 @@ __device__ __forceinline__ void bb_item(const BbPassParams &p, uint32_t *lds, co
         c = w & ((1u << logC) - 1);
         mr = w >> logC;
     }
-    const uint32_t swz = (LAST && !(LW_DBG(p) & 8)) ? ((1u << logC) - 1) : 0u;
+    const uint32_t swz = LAST ? ((1u << logC) - 1) : 0u;
     const uint32_t m_low = mr & ((1u << sh) - 1);
     const uint32_t m_high = mr >> sh;
     const uint32_t mbase = (m_high << (sh + K)) | m_low;
@@ -102,7 +101,7 @@ __device__ __forceinline__ void bb_item(const BbPassParams &p, uint32_t *lds, co
             uint32_t g;
             if (LAST) g = ((((hi_c << r) | m)) << lgV) | (c & ((1u << lgV) - 1));
             else g = base + (m << lgS) + c;
-            x[j] = (LW_DBG(p) & 2) ? g : bb_load_word<IN64>(gin, g & p.in_mask);
+            x[j] = bb_load_word<IN64>(gin, g & p.in_mask);
         }
         if (p.cos_in) {   // c_i * h^i, fused into the first pass's load (its own loop: the loads above stay back to back)
 #pragma unroll
@@ -133,68 +132,66 @@ __device__ __forceinline__ void bb_item(const BbPassParams &p, uint32_t *lds, co
     // twiddles w1 w0 and -w2 w0 come from the table dd (same indexing as T).  Non-last passes only (their twiddles are
     // staged in LDS): in the last pass every work-item fetches its own twiddles from the global tables and the two extra
     // values per butterfly cost more than the instructions saved (measured: last pass 0.227 -> 0.235 ms, others 0.165 -> 0.150).
-    if (!(LW_DBG(p) & 1)) {
-        int u = 0;
+    int u = 0;
 #pragma unroll
-        for (; !LAST && u + 1 < K; u += 2) {
-            const int half = 1 << (K - 1 - u), q = half >> 1;
-            const uint32_t gt = (hi_c << (t0 + u)) | (m_high << u);
+    for (; !LAST && u + 1 < K; u += 2) {
+        const int half = 1 << (K - 1 - u), q = half >> 1;
+        const uint32_t gt = (hi_c << (t0 + u)) | (m_high << u);
 #pragma unroll
-            for (int jt = 0; jt < (1 << u); jt++) {
-                uint32_t w0, w1, w2, e1, e2;
-                if (LAST) {
-                    const uint32_t G = gt | (uint32_t)jt;
-                    const uint2 w12 = reinterpret_cast<const uint2 *>(p.tw)[G], e12 = p.dd[G];   // one 8-byte load each
-                    w0 = p.tw[G]; w1 = w12.x; w2 = w12.y; e1 = e12.x; e2 = e12.y;
-                } else {   // the tile's twiddles sit in LDS, stage t group x at slot 2^t - 1 + x
-                    const uint32_t xg = (m_high << u) | (uint32_t)jt;
-                    const uint32_t s0 = (1u << (t0 + u)) - 1 + xg, s1 = (2u << (t0 + u)) - 1 + 2 * xg;
-                    w0 = ltw[s0]; w1 = ltw[s1]; w2 = ltw[s1 + 1]; e1 = ld1[s0]; e2 = ld2[s0];
-                }
+        for (int jt = 0; jt < (1 << u); jt++) {
+            uint32_t w0, w1, w2, e1, e2;
+            if (LAST) {
+                const uint32_t G = gt | (uint32_t)jt;
+                const uint2 w12 = reinterpret_cast<const uint2 *>(p.tw)[G], e12 = p.dd[G];   // one 8-byte load each
+                w0 = p.tw[G]; w1 = w12.x; w2 = w12.y; e1 = e12.x; e2 = e12.y;
+            } else {   // the tile's twiddles sit in LDS, stage t group x at slot 2^t - 1 + x
+                const uint32_t xg = (m_high << u) | (uint32_t)jt;
+                const uint32_t s0 = (1u << (t0 + u)) - 1 + xg, s1 = (2u << (t0 + u)) - 1 + 2 * xg;
+                w0 = ltw[s0]; w1 = ltw[s1]; w2 = ltw[s1 + 1]; e1 = ld1[s0]; e2 = ld2[s0];
+            }
 #pragma unroll
-                for (int jl = 0; jl < q; jl++) {
-                    const int j = (jt << (K - u)) | jl;
-                    const uint32_t a = x[j], cc = x[j + q], b = x[j + half], d = x[j + half + q];
-                    const uint32_t S = bb_mul(w0, b);
-                    const uint32_t U = bb_reduce((uint64_t)w1 * cc + (uint64_t)e1 * d);
-                    const uint32_t V = bb_reduce((uint64_t)w2 * cc + (uint64_t)e2 * d);
-                    const uint32_t ap = bb_add(a, S), am = bb_sub(a, S);
-                    x[j] = bb_add(ap, U);
-                    x[j + q] = bb_sub(ap, U);
-                    x[j + half] = bb_add(am, V);
-                    x[j + half + q] = bb_sub(am, V);
+            for (int jl = 0; jl < q; jl++) {
+                const int j = (jt << (K - u)) | jl;
+                const uint32_t a = x[j], cc = x[j + q], b = x[j + half], d = x[j + half + q];
+                const uint32_t S = bb_mul(w0, b);
+                const uint32_t U = bb_reduce((uint64_t)w1 * cc + (uint64_t)e1 * d);
+                const uint32_t V = bb_reduce((uint64_t)w2 * cc + (uint64_t)e2 * d);
+                const uint32_t ap = bb_add(a, S), am = bb_sub(a, S);
+                x[j] = bb_add(ap, U);
+                x[j + q] = bb_sub(ap, U);
+                x[j + half] = bb_add(am, V);
+                x[j + half + q] = bb_sub(am, V);
+            }
+        }
+    }
+#pragma unroll
+    for (; u < K; u++) {   // odd K: one radix-2 stage is left
+        const int half = 1 << (K - 1 - u);
+        const uint32_t gt = (hi_c << (t0 + u)) | (m_high << u);
+        // last pass: the 2^u twiddles of this stage are consecutive table entries starting at a multiple of 2^u — one
+        // 8- or 16-byte load (two for u = 3) instead of 2^u dword loads: 5 load instructions per radix-16 step, not 15
+        uint32_t twv[K > 1 ? (1 << (K - 1)) : 2];
+        if (LAST) {
+            if (u == 0) twv[0] = p.tw[gt];
+            else if (u == 1) { const uint2 v = *reinterpret_cast<const uint2 *>(p.tw + gt); twv[0] = v.x; twv[1] = v.y; }
+            else {
+#pragma unroll
+                for (int q4 = 0; q4 < (1 << u) / 4; q4++) {
+                    const uint4 v = *reinterpret_cast<const uint4 *>(p.tw + gt + 4 * q4);
+                    twv[4 * q4] = v.x; twv[4 * q4 + 1] = v.y; twv[4 * q4 + 2] = v.z; twv[4 * q4 + 3] = v.w;
                 }
             }
         }
 #pragma unroll
-        for (; u < K; u++) {   // odd K: one radix-2 stage is left
-            const int half = 1 << (K - 1 - u);
-            const uint32_t gt = (hi_c << (t0 + u)) | (m_high << u);
-            // last pass: the 2^u twiddles of this stage are consecutive table entries starting at a multiple of 2^u — one
-            // 8- or 16-byte load (two for u = 3) instead of 2^u dword loads: 5 load instructions per radix-16 step, not 15
-            uint32_t twv[K > 1 ? (1 << (K - 1)) : 2];
-            if (LAST) {
-                if (u == 0) twv[0] = p.tw[gt];
-                else if (u == 1) { const uint2 v = *reinterpret_cast<const uint2 *>(p.tw + gt); twv[0] = v.x; twv[1] = v.y; }
-                else {
+        for (int jt = 0; jt < (1 << u); jt++) {
+            const uint32_t tw = LAST ? twv[jt] : ltw[(1u << (t0 + u)) - 1 + ((m_high << u) | (uint32_t)jt)];
 #pragma unroll
-                    for (int q4 = 0; q4 < (1 << u) / 4; q4++) {
-                        const uint4 v = *reinterpret_cast<const uint4 *>(p.tw + gt + 4 * q4);
-                        twv[4 * q4] = v.x; twv[4 * q4 + 1] = v.y; twv[4 * q4 + 2] = v.z; twv[4 * q4 + 3] = v.w;
-                    }
-                }
-            }
-#pragma unroll
-            for (int jt = 0; jt < (1 << u); jt++) {
-                const uint32_t tw = LAST ? twv[jt] : ltw[(1u << (t0 + u)) - 1 + ((m_high << u) | (uint32_t)jt)];
-#pragma unroll
-                for (int jl = 0; jl < half; jl++) {
-                    const int j = (jt << (K - u)) | jl;
-                    const uint32_t wb = bb_mul(tw, x[j + half]);
-                    const uint32_t a = x[j];
-                    x[j] = bb_add(a, wb);
-                    x[j + half] = bb_sub(a, wb);
-                }
+            for (int jl = 0; jl < half; jl++) {
+                const int j = (jt << (K - u)) | jl;
+                const uint32_t wb = bb_mul(tw, x[j + half]);
+                const uint32_t a = x[j];
+                x[j] = bb_add(a, wb);
+                x[j + half] = bb_sub(a, wb);
             }
         }
     }
@@ -287,10 +284,10 @@ __global__ __launch_bounds__(BB_THREADS) void bb_pass_kernel(BbPassParams p) {
         uint32_t g;
         if (!LAST) g = base + (m << lgS) + c;
         else g = (((bb_bitrev(m, r) << (L - r)) + (b << logCh) + (c >> lgV)) << lgV) | (c & ((1u << lgV) - 1));
-        const uint32_t swz = (LAST && !(LW_DBG(p) & 8)) ? ((1u << logC) - 1) : 0u;   // same slot mapping as bb_item
+        const uint32_t swz = LAST ? ((1u << logC) - 1) : 0u;   // same slot mapping as bb_item
         uint32_t v = lds[(m << logC) | (c ^ ((m ^ (m >> 4)) & swz))];
         if (p.cos_out) v = bb_mul(v, bb_coset_factor(p, g >> lgV));   // h^-i * N^-1, fused into the last pass's store
-        if (!(LW_DBG(p) & 4)) bb_store_word<OUT64>(gout, g, v);
+        bb_store_word<OUT64>(gout, g, v);
     };
     if constexpr (RX != 0) {
 #pragma unroll
@@ -332,24 +329,17 @@ static uint32_t bb_host_root(uint32_t order, bool inverse) {   // traits.rs:82-9
 
 static int bb_ensure_twiddles(Context &c, lw_dir_t dir, uint32_t log2n, hipStream_t stream) {
     TwiddleTable &t = c.tw[LW_FIELD_BABYBEAR][dir];
-    if (t.valid && t.log_n >= log2n) return LW_OK;
-    if (log2n < 1) return LW_OK;
-    ExclusiveScope excl(c);   // shared tables: rebuild with every other call out of the library (ntt256.hip ensure_twiddles)
-    if (t.valid && t.log_n >= log2n) return LW_OK;
-    uint32_t L = log2n < 16 ? 16 : log2n;
-    const uint32_t bits = L - 1;
-    const uint64_t count = 1ull << bits;
-    if (t.buf.ensure(count * 8)) return LW_ERR_ALLOC;   // T[count] | dd[count / 2] (pairs)
-    const uint32_t w = bb_host_root(L, dir == LW_DIR_INVERSE);
-    uint32_t *T = (uint32_t *)t.buf.p;
-    hipLaunchKernelGGL(bb_twiddle_fill_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, stream, T, w, bits, count);
-    hipLaunchKernelGGL(bb_twiddle_pairs_kernel, dim3((uint32_t)((count / 2 + 255) / 256)), dim3(256), 0, stream, (const uint32_t *)T,
-                       reinterpret_cast<uint2 *>(T + count), count / 2);
-    LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
-    LW_HIP_CHECK(hipStreamSynchronize(stream), LW_ERR_LAUNCH);
-    t.log_n = L;
-    t.valid = true;
-    return LW_OK;
+    // 8 bytes per entry: T[count] | dd[count / 2] (pairs)
+    return ensure_twiddle_table(c, t, log2n, BabyBear::TWO_ADICITY, 8, stream, [&](uint32_t L) {
+        const uint32_t bits = L - 1;
+        const uint64_t count = 1ull << bits;
+        uint32_t *T = (uint32_t *)t.buf.p;
+        hipLaunchKernelGGL(bb_twiddle_fill_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, stream, T,
+                           bb_host_root(L, dir == LW_DIR_INVERSE), bits, count);
+        hipLaunchKernelGGL(bb_twiddle_pairs_kernel, dim3((uint32_t)((count / 2 + 255) / 256)), dim3(256), 0, stream, (const uint32_t *)T,
+                           reinterpret_cast<uint2 *>(T + count), count / 2);
+        return (int)LW_OK;
+    });
 }
 
 // in_log2 < log2n: low-degree extension of dense blocks of 2^in_log2 coefficients (forward, d_in != d_out)
@@ -377,11 +367,9 @@ static int bb_run(Context &c, lw_dir_t dir, uint32_t lgV, const void *d_in, void
         if (h == 0) { set_error("coset offset is zero"); return LW_ERR_INV_ZERO; }
     }
 
-    // pass plan: r <= 8 stages per pass; logC columns x components fill the tile
-    const uint32_t max_r = 8;
-    const uint32_t nstages = log2n - skip;
-    int npass = (int)((nstages + max_r - 1) / max_r);
-    if (npass < 1) npass = 1;
+    // pass plan: the stages split evenly; logC columns x components fill the tile
+    const NttPlan pl = plan_passes(log2n + lgV, log2n, skip, BB_TILE_LOG, BB_KMAX, false);
+    const int npass = pl.npass;
     const bool need_scratch = npass > 1 || d_in == d_out;
     if (need_scratch && c.scratch.ensure((size_t)nwords * batch * wbytes)) return LW_ERR_ALLOC;
     // coset factors: h^i fused into the first pass's load (forward), h^-i * N^-1 into the last pass's store (inverse) —
@@ -412,7 +400,6 @@ static int bb_run(Context &c, lw_dir_t dir, uint32_t lgV, const void *d_in, void
         src = c.scratch.p;
         src_stride = nwords;
     }
-    uint32_t base = nstages / npass, extra = nstages % npass, s = skip;
     for (int i = 0; i < npass; i++) {
         const bool last = (i == npass - 1);
         BbPassParams p{};
@@ -423,19 +410,11 @@ static int bb_run(Context &c, lw_dir_t dir, uint32_t lgV, const void *d_in, void
         }
         p.L = log2n;
         p.lgV = lgV;
-        p.dbg = ntt_get_debug();
-        p.s0 = s;
-        p.r = base + ((uint32_t)i < extra ? 1 : 0);
-        const uint32_t room = BB_TILE_LOG - p.r;
-        const uint32_t avail = last ? (log2n - p.r + lgV) : (log2n + lgV - s - p.r);
-        p.logC = room < avail ? room : avail;
-        uint32_t nsteps = (p.r + BB_KMAX - 1) / BB_KMAX, left = p.r;
-        p.nsteps = nsteps;
-        for (uint32_t q = 0; q < nsteps; q++) {
-            uint32_t k = (left + (nsteps - q) - 1) / (nsteps - q);
-            p.k[q] = k;
-            left -= k;
-        }
+        p.s0 = pl.s0[i];
+        p.r = pl.r[i];
+        p.logC = pl.logC[i];
+        p.nsteps = pl.nsteps[i];
+        for (uint32_t q = 0; q < p.nsteps; q++) p.k[q] = pl.k[i][q];
         p.in = src;
         p.in_batch_stride = src_stride;
         p.cos_lo = cos_lo;
@@ -490,7 +469,6 @@ static int bb_run(Context &c, lw_dir_t dir, uint32_t lgV, const void *d_in, void
         src = p.out;
         src_stride = p.out_batch_stride;
         src64 = last ? W64 : false;
-        s += p.r;
     }
     LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
     return LW_OK;

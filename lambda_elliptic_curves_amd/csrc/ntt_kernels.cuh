@@ -7,7 +7,7 @@
 // the stages are scheduled; here they are scheduled for the GPU:
 //
 //   * log2(N) stages are cut into passes of r <= 8 stages (the staged twiddles ltw[2][256] and the 17p lazy bound
-//     both need r <= 8; plan_passes never plans more).  One workgroup owns a tile of 2^r "rows"
+//     both need r <= 8; plan_passes, ntt_plan.h, never plans more).  One workgroup owns a tile of 2^r "rows"
 //     (the index bits the pass's stages touch) x C adjacent "columns" (contiguous elements), stages it in
 //     LDS once and runs all r stages there: a pass costs one HBM read + one HBM write of the vector,
 //     versus one round trip per stage in the reference's CUDA path (math/src/fft/gpu/cuda/ops.rs:28-38).
@@ -21,22 +21,18 @@
 
 namespace lw {
 
-// Kernel geometry: a tile of 2^TILE_LOG elements (32 B each) in LDS per workgroup, THREADS threads, and at
-// most KMAX stages per register step (2^KMAX elements per work-item).
-template <int TILE_LOG_, int THREADS_, int KMAX_>
-struct NttCfg {
-    static constexpr int TILE_LOG = TILE_LOG_;
-    static constexpr int TILE = 1 << TILE_LOG_;
-    static constexpr int THREADS = THREADS_;
-    static constexpr int KMAX = KMAX_;
-    // workgroups per CU by LDS, waves per SIMD that follow (launch bound for the register allocator)
-    static constexpr int WG_PER_CU = (160 * 1024) / (TILE * 32 + 8192) > 8 ? 8 : (160 * 1024) / (TILE * 32 + 8192);   // + staged twiddles
-    static constexpr int WAVES_PER_SIMD = (WG_PER_CU * THREADS / 256) > 8 ? 8 : (WG_PER_CU * THREADS / 256) < 1 ? 1 : (WG_PER_CU * THREADS / 256);
-};
-using NttCfgA = NttCfg<11, 512, 2>;   // 64 KiB tile, 2 workgroups/CU, 4 waves/SIMD
+// Kernel geometry: a tile of 2^NTT_TILE_LOG elements (32 B each) in LDS per workgroup, NTT_THREADS threads, and at
+// most NTT_KMAX stages per register step (2^NTT_KMAX elements per work-item): 64 KiB tile, 2 workgroups/CU, 4 waves/SIMD.
 // (measured and dropped: 32 KiB tile / 256 threads -> 128-byte runs, 5.4 G elem/s; 64 KiB / 256 threads / radix-8 steps
 //  -> 2 waves/SIMD, 7.4 G elem/s, against 9.6 for this geometry at the time)
-constexpr int NTT_MAX_TILE_LOG = 11;
+constexpr int NTT_TILE_LOG = 11;
+constexpr int NTT_TILE = 1 << NTT_TILE_LOG;
+constexpr int NTT_THREADS = 512;
+constexpr int NTT_KMAX = 2;
+// workgroups per CU by LDS, waves per SIMD that follow (launch bound for the register allocator)
+constexpr int NTT_WG_PER_CU = (160 * 1024) / (NTT_TILE * 32 + 8192) > 8 ? 8 : (160 * 1024) / (NTT_TILE * 32 + 8192);   // + staged twiddles
+constexpr int NTT_WAVES_PER_SIMD = (NTT_WG_PER_CU * NTT_THREADS / 256) > 8 ? 8 : (NTT_WG_PER_CU * NTT_THREADS / 256) < 1 ? 1 : (NTT_WG_PER_CU * NTT_THREADS / 256);
+constexpr int NTT_LTW = 256;   // slots of the staged twiddle table: a pass of r <= 8 stages has 2^r - 1 <= 255 twiddles
 
 struct NttPassParams {
     const uint4 *in;       // element e = in[2e], in[2e+1] (reference memory layout)
@@ -56,7 +52,6 @@ struct NttPassParams {
     uint32_t cos_out;      // last pass of an inverse transform: multiply natural output i by h^-i * N^-1 (folded into cos_hi)
     uint64_t in_mask;      // first pass of a low-degree extension: element g is read from in[g & in_mask] (see ntt256.hip)
     uint32_t lazy_in;      // input of this pass may be non-canonical (< 24p): a previous lazy pass wrote it
-    uint32_t dbg;          // ablation builds only (-DLW_HIP_ABLATION, see LW_DBG): bit0 skip butterflies, bit1 skip global loads, bit2 skip global stores
     uint32_t wave_sync;    // WL kernels: bit s set = the exchange before register step s stays inside a wavefront (no workgroup barrier)
     uint32_t scale;        // multiply outputs by sc (last pass of an inverse transform)
     uint32_t sc[8];
@@ -119,15 +114,15 @@ __device__ __forceinline__ void lds_wave_sync() {
 // One work-item: 2^K elements, K stages in registers.
 // EXTRA: the pass carries a coset scaling or the N^-1 factor (kept out of the plain transform's code: the last-pass
 // kernel is ~60 KiB of straight-line MAC chains and shares a 64 KiB instruction cache with its neighbour CU)
-// FX = r: a full-size tile of the 2048-element configuration (r = 8 stages x 8 columns or 6 x 32, r / 2 radix-4 steps, one
+// FX = r: a full-size tile of NTT_TILE = 2048 elements (r = 8 stages x 8 columns or 6 x 32, r / 2 radix-4 steps, one
 // item per work-item and step) with its shape as compile-time constants, so that the shifts, masks, bit reversals and swizzles
 // of the index arithmetic fold (every pass of a 2^24 transform, the last pass from 2^16 on).
-template <class F, int K, bool LAST, int TILE, bool EXTRA, bool WL, int FX = 0>
-__device__ __forceinline__ void ntt_item(const NttPassParams &p, uint4 (*lds)[TILE], uint4 (*ltw)[256], const uint4 *gin,
+template <class F, int K, bool LAST, bool EXTRA, bool WL, int FX = 0>
+__device__ __forceinline__ void ntt_item(const NttPassParams &p, uint4 (*lds)[NTT_TILE], uint4 (*ltw)[NTT_LTW], const uint4 *gin,
                                          uint32_t w, uint32_t step, uint32_t t0, uint64_t base, uint32_t lgS,
                                          uint32_t hi_uniform, uint32_t hi_low, bool last_step, bool stage_tw) {
     constexpr int E = 1 << K;
-    const uint32_t r = FX ? (uint32_t)FX : p.r, logC = FX ? (uint32_t)(11 - FX) : p.logC, L = p.L;
+    const uint32_t r = FX ? (uint32_t)FX : p.r, logC = FX ? (uint32_t)(NTT_TILE_LOG - FX) : p.logC, L = p.L;
     const uint32_t sh = r - t0 - K;
     uint32_t c, mr;
     if ((LAST && step == 0) || (WL && (LAST || step > 0))) {   // rows fastest: contiguous global rows / one column per wave
@@ -165,15 +160,7 @@ __device__ __forceinline__ void ntt_item(const NttPassParams &p, uint4 (*lds)[TI
         for (int j = 0; j < E; j++) {
             const uint32_t m = mbase | ((uint32_t)j << sh);
             const uint64_t g = (LAST ? (gbase + m) : (gbase + ((uint64_t)m << lgS) + c)) & p.in_mask;
-            uint4 q0, q1;
-            if (LW_DBG(p) & 2) {
-                q0 = make_uint4(m, c, 1, 2);
-                q1 = make_uint4(3, 4, 5, 6);
-            } else {
-                q0 = gin[2 * g];
-                q1 = gin[2 * g + 1];
-            }
-            x[j] = unpack_mem<F>(q0, q1);
+            x[j] = unpack_mem<F>(gin[2 * g], gin[2 * g + 1]);
         }
         if (EXTRA && p.cos_in) {   // evaluate_offset_fft: c_e * h^e, fused into the first pass's load
 #pragma unroll
@@ -218,7 +205,7 @@ __device__ __forceinline__ void ntt_item(const NttPassParams &p, uint4 (*lds)[TI
         Fe<F> tw;
         if (LAST || WL) {   // from the table (L1/L2): per-lane twiddles would cost LDS bandwidth the exchanges need
             const uint64_t gt = ((uint64_t)hi_c << (t0 + u)) | ((uint64_t)m_high << u);
-            tw = tw_load<F>(p.tw, (LW_DBG(p) & 32) ? ((gt | (uint32_t)jt) & 0xff) : (gt | (uint32_t)jt));
+            tw = tw_load<F>(p.tw, gt | (uint32_t)jt);
         } else {   // slot 2^t - 1 + x of the staged table
             const uint32_t li = (1u << (t0 + u)) - 1 + ((m_high << u) | (uint32_t)jt);
             uint4 a = ltw[0][li], b = ltw[1][li];
@@ -227,34 +214,32 @@ __device__ __forceinline__ void ntt_item(const NttPassParams &p, uint4 (*lds)[TI
         }
         return tw;
     };
-    if (!(LW_DBG(p) & 1)) {
-        Fe<F> tw_next = fetch_tw(0);
+    Fe<F> tw_next = fetch_tw(0);
 #pragma unroll
-        for (int q = 0; q < E - 1; q++) {
-            const int u = 31 - __builtin_clz(q + 1), jt = q + 1 - (1 << u);
-            const int half = 1 << (K - 1 - u);
-            const Fe<F> tw = tw_next;
-            if (q + 1 < E - 1) tw_next = fetch_tw(q + 1);
-            // T[0] = 1: the first group of every stage multiplies by one (2^-t of stage t's butterflies, i.e. a
-            // quarter of the first pass's products).  The reference multiplies anyway (fft.rs:40-43); the product
-            // by the Montgomery one is the identity on canonical residues, so skipping it changes no byte.
-            const bool unit = (jt == 0) && (hi_c == 0) && (m_high == 0);
+    for (int q = 0; q < E - 1; q++) {
+        const int u = 31 - __builtin_clz(q + 1), jt = q + 1 - (1 << u);
+        const int half = 1 << (K - 1 - u);
+        const Fe<F> tw = tw_next;
+        if (q + 1 < E - 1) tw_next = fetch_tw(q + 1);
+        // T[0] = 1: the first group of every stage multiplies by one (2^-t of stage t's butterflies, i.e. a
+        // quarter of the first pass's products).  The reference multiplies anyway (fft.rs:40-43); the product
+        // by the Montgomery one is the identity on canonical residues, so skipping it changes no byte.
+        const bool unit = (jt == 0) && (hi_c == 0) && (m_high == 0);
 #pragma unroll
-            for (int jl = 0; jl < half; jl++) {
-                const int j = (jt << (K - u)) | jl;
-                if (F::LAZY) {
-                    Fe<F> wb = unit ? fe_reduce_full(x[j + half]) : fe_mul_lazy<F>(tw, x[j + half]);
-                    Fe<F> a = x[j];
-                    x[j] = fe_add_raw<F>(a, wb);
-                    x[j + half] = fe_add2p_sub_raw<F>(a, wb);
-                } else {
-                    Fe<F> wb = unit ? x[j + half] : fe_mul<F>(tw, x[j + half]);
-                    Fe<F> a = x[j];
-                    x[j] = fe_add<F>(a, wb);
-                    x[j + half] = fe_sub<F>(a, wb);
-                }
-                __builtin_amdgcn_sched_barrier(0);   // keep butterflies serial: interleaved products cost too many VGPRs
+        for (int jl = 0; jl < half; jl++) {
+            const int j = (jt << (K - u)) | jl;
+            if (F::LAZY) {
+                Fe<F> wb = unit ? fe_reduce_full(x[j + half]) : fe_mul_lazy<F>(tw, x[j + half]);
+                Fe<F> a = x[j];
+                x[j] = fe_add_raw<F>(a, wb);
+                x[j + half] = fe_add2p_sub_raw<F>(a, wb);
+            } else {
+                Fe<F> wb = unit ? x[j + half] : fe_mul<F>(tw, x[j + half]);
+                Fe<F> a = x[j];
+                x[j] = fe_add<F>(a, wb);
+                x[j + half] = fe_sub<F>(a, wb);
             }
+            __builtin_amdgcn_sched_barrier(0);   // keep butterflies serial: interleaved products cost too many VGPRs
         }
     }
 
@@ -291,16 +276,13 @@ __device__ __forceinline__ void ntt_item(const NttPassParams &p, uint4 (*lds)[TI
     }
 }
 
-template <class F, bool LAST, class CFG, bool EXTRA, bool WL, int FX = 0>
-__global__ __launch_bounds__(CFG::THREADS, CFG::WAVES_PER_SIMD) void ntt_pass_kernel(NttPassParams p) {
-    constexpr int NTT_THREADS = CFG::THREADS;
-    constexpr int NTT_KMAX = CFG::KMAX;
-    constexpr int NTT_TILE = CFG::TILE;
+template <class F, bool LAST, bool EXTRA, bool WL, int FX = 0>
+__global__ __launch_bounds__(NTT_THREADS, NTT_WAVES_PER_SIMD) void ntt_pass_kernel(NttPassParams p) {
     __shared__ uint4 lds[2][NTT_TILE];
-    __shared__ uint4 ltw[LAST ? 1 : 2][LAST ? 1 : 256];   // non-last passes: the tile's twiddles (<= 255 x 32 B)
+    __shared__ uint4 ltw[LAST ? 1 : 2][LAST ? 1 : NTT_LTW];   // non-last passes: the tile's twiddles (<= 255 x 32 B)
     const uint32_t tid = threadIdx.x;
     static_assert(!FX || (NTT_TILE == 2048 && NTT_THREADS == 512 && (FX == 8 || FX == 7 || FX == 6)), "FX: 2^8 x 8, 2^7 x 16 or 2^6 x 32 rows x columns");
-    const uint32_t r = FX ? (uint32_t)FX : p.r, logC = FX ? (uint32_t)(11 - FX) : p.logC, L = p.L;
+    const uint32_t r = FX ? (uint32_t)FX : p.r, logC = FX ? (uint32_t)(NTT_TILE_LOG - FX) : p.logC, L = p.L;
     const uint32_t tile_log = r + logC;
     const uint4 *gin = p.in + 2 * (uint64_t)blockIdx.y * p.in_batch_stride;
     uint4 *gout = p.out + 2 * (uint64_t)blockIdx.y * p.out_batch_stride;
@@ -339,8 +321,8 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WAVES_PER_SIMD) void ntt_pass_ke
             if (WL && ((p.wave_sync >> (S)) & 1u)) lds_wave_sync();                                                                     \
             else __syncthreads();                                                                                                       \
         }                                                                                                                               \
-        ntt_item<F, 2, LAST, NTT_TILE, EXTRA, WL, FX>(p, lds, (uint4 (*)[256])ltw, gin, tid, (S), 2u * (S), base, lgS, hi_uniform,      \
-                                                      hi_low, 2 * ((S) + 1) == FX, stage_inside && (S) == 0);                           \
+        ntt_item<F, 2, LAST, EXTRA, WL, FX>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, tid, (S), 2u * (S), base, lgS, hi_uniform, hi_low,    \
+                                            2 * ((S) + 1) == FX, stage_inside && (S) == 0);                                             \
     } while (0)
         LW_FX_STEP(0u);
         LW_FX_STEP(1u);
@@ -348,9 +330,8 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WAVES_PER_SIMD) void ntt_pass_ke
         if constexpr (FX == 8) LW_FX_STEP(3u);
         if constexpr (FX == 7) {   // the odd stage: a radix-2 step, two items per work-item
             __syncthreads();
-            ntt_item<F, 1, LAST, NTT_TILE, EXTRA, WL, FX>(p, lds, (uint4 (*)[256])ltw, gin, tid, 3u, 6u, base, lgS, hi_uniform, hi_low, true, false);
-            ntt_item<F, 1, LAST, NTT_TILE, EXTRA, WL, FX>(p, lds, (uint4 (*)[256])ltw, gin, tid + NTT_THREADS, 3u, 6u, base, lgS, hi_uniform, hi_low, true,
-                                                          false);
+            ntt_item<F, 1, LAST, EXTRA, WL, FX>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, tid, 3u, 6u, base, lgS, hi_uniform, hi_low, true, false);
+            ntt_item<F, 1, LAST, EXTRA, WL, FX>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, tid + NTT_THREADS, 3u, 6u, base, lgS, hi_uniform, hi_low, true, false);
         }
 #undef LW_FX_STEP
     } else {
@@ -364,9 +345,9 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WAVES_PER_SIMD) void ntt_pass_ke
             else __syncthreads();
         }
         for (uint32_t w = tid; w < nitems; w += NTT_THREADS) {
-            if (NTT_KMAX >= 3 && k == 3) ntt_item<F, (NTT_KMAX >= 3 ? 3 : 1), LAST, NTT_TILE, EXTRA, WL>(p, lds, (uint4 (*)[256])ltw, gin, w, step, t0, base, lgS, hi_uniform, hi_low, last_step, stage_inside && step == 0 && w == tid);
-            else if (k == 2) ntt_item<F, 2, LAST, NTT_TILE, EXTRA, WL>(p, lds, (uint4 (*)[256])ltw, gin, w, step, t0, base, lgS, hi_uniform, hi_low, last_step, stage_inside && step == 0 && w == tid);
-            else ntt_item<F, 1, LAST, NTT_TILE, EXTRA, WL>(p, lds, (uint4 (*)[256])ltw, gin, w, step, t0, base, lgS, hi_uniform, hi_low, last_step, stage_inside && step == 0 && w == tid);
+            if (NTT_KMAX >= 3 && k == 3) ntt_item<F, (NTT_KMAX >= 3 ? 3 : 1), LAST, EXTRA, WL>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, w, step, t0, base, lgS, hi_uniform, hi_low, last_step, stage_inside && step == 0 && w == tid);
+            else if (k == 2) ntt_item<F, 2, LAST, EXTRA, WL>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, w, step, t0, base, lgS, hi_uniform, hi_low, last_step, stage_inside && step == 0 && w == tid);
+            else ntt_item<F, 1, LAST, EXTRA, WL>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, w, step, t0, base, lgS, hi_uniform, hi_low, last_step, stage_inside && step == 0 && w == tid);
         }
         t0 += k;
     }
@@ -381,7 +362,7 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WAVES_PER_SIMD) void ntt_pass_ke
         uint64_t g;
         if (!LAST) g = base + ((uint64_t)m << lgS) + c;
         else g = ((uint64_t)bitrev_bits(m, r) << (L - r)) + ((uint64_t)b << logC) + c;
-        if (!(LW_DBG(p) & 4)) gout[2 * g + plane] = lds[plane][lds_slot<WL>(m, c, r, logC) ^ (WL ? plane : 0u)];
+        gout[2 * g + plane] = lds[plane][lds_slot<WL>(m, c, r, logC) ^ (WL ? plane : 0u)];
     };
     if constexpr (FX) {
 #pragma unroll

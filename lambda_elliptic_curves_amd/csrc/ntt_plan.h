@@ -1,0 +1,74 @@
+// Pass planning shared by the 256-bit-field NTT (ntt256.hip) and the BabyBear NTT (ntt_bb.hip): how the stages of a
+// transform are cut into passes, how wide each pass's tile is and how a pass is split into register steps.
+// Host only, plain C++ (no HIP header): tests/test_ntt_plan_cpu.py compiles it with g++ and pins every plan.
+#pragma once
+#include <stdint.h>
+
+namespace lw {
+
+// stages per pass: the staged twiddles (ltw[2][256], 255 entries) and the 17p lazy bound both need r <= 8 (ntt_kernels.cuh)
+constexpr uint32_t NTT_MAX_R = 8;
+
+struct NttPlan {
+    int npass;
+    uint32_t s0[8], r[8], logC[8];   // per pass: first stage, stages, log2 columns of the tile (in words)
+    uint32_t nsteps[8], k[8][8];     // per pass: register steps and the stages of each, sum k = r
+};
+
+// Stages [skip, L) of a transform of 2^L elements whose word array has Lw index bits (Lw = L for the 256-bit fields, one
+// word per element; Lw = L + lgV for BabyBear, 2^lgV components per element).  The first `skip` stages of a zero-padded
+// input only replicate it (see ntt256_run) and are not planned.  A workgroup's tile holds 2^tile_log words, a register
+// step runs at most kmax stages.
+inline NttPlan plan_passes(uint32_t Lw, uint32_t L, uint32_t skip, uint32_t tile_log, uint32_t kmax, bool full_last_pass) {
+    const uint32_t max_r = NTT_MAX_R;
+    NttPlan pl{};
+    const uint32_t Ls = L - skip;
+    pl.npass = (int)((Ls + max_r - 1) / max_r);
+    if (pl.npass < 1) pl.npass = 1;
+    // even split, the longer passes first
+    uint32_t rr[8];
+    uint32_t base = Ls / pl.npass, extra = Ls % pl.npass;
+    for (int i = 0; i < pl.npass; i++) rr[i] = base + ((uint32_t)i < extra ? 1 : 0);
+    // full_last_pass (the 256-bit fields), from 2^16 up: the last pass (per-element twiddles, bit-reversed stores,
+    // wave-local exchanges) takes a full max_r stages and the others share the rest as evenly as possible in EVEN sizes —
+    // an odd pass ends in a radix-2 register step with two items per thread.  Measured: 2^20 (7,7,6) 0.1056 -> (6,6,8)
+    // 0.1030 ms, 2^22 (8,7,7) 0.3588 -> (6,8,8) 0.3533, 2^26 (7,7,6,6) 6.45 -> (6,6,6,8) 6.19 ms; a short LAST pass is
+    // the worst choice (2^26 (8,8,8,2): 9.1 ms).
+    if (full_last_pass && pl.npass >= 2 && Ls >= 16 && Ls > max_r) {
+        const int q = pl.npass - 1;
+        rr[q] = max_r;
+        const uint32_t R = Ls - max_r;
+        base = R / q;
+        extra = R % q;
+        for (int i = 0; i < q; i++) rr[i] = base + ((uint32_t)i >= (uint32_t)q - extra ? 1 : 0);
+        for (int i = 0; i + 1 < q; i++)
+            if ((rr[i] & 1) && (rr[i + 1] & 1) && rr[i + 1] < max_r && rr[i] > 1) {
+                rr[i]--;
+                rr[i + 1]++;
+            }
+    }
+    uint32_t s = skip;
+    for (int i = 0; i < pl.npass; i++) {
+        const uint32_t r = rr[i];
+        pl.s0[i] = s;
+        pl.r[i] = r;
+        // the tile is as wide as it has room for and the vector has columns
+        const uint32_t room = tile_log - r;
+        uint32_t avail = Lw - s - r;   // non-last: log2 of the row stride; last: 0 unless multi-pass
+        if (i == pl.npass - 1) avail = Lw - r;
+        pl.logC[i] = room < avail ? room : avail;
+        // register steps: as few as kmax allows, the longer ones first
+        const uint32_t nsteps = (r + kmax - 1) / kmax;
+        uint32_t left = r;
+        pl.nsteps[i] = nsteps;
+        for (uint32_t j = 0; j < nsteps; j++) {
+            const uint32_t k = (left + (nsteps - j) - 1) / (nsteps - j);
+            pl.k[i][j] = k;
+            left -= k;
+        }
+        s += r;
+    }
+    return pl;
+}
+
+}  // namespace lw
