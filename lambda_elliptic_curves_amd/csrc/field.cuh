@@ -442,12 +442,12 @@ __device__ __forceinline__ void col_mp(uint64_t &lo, uint32_t &hi, const uint32_
         col_mp<F, K, I + 1, IEND>(lo, hi, m);
     }
 }
-// Fields for which mac_chains.inc has FusedCol<F, K>: every column of a single product as one statement (fips_fused)
+// Fields for which mac_chains.inc has FusedCol<F, K, A_LT_P>: every column of a single product as one statement (fips_fused)
 template <class F>
 struct lw_fused_columns {
     static constexpr bool value = false;
 };
-template <class F, int K>
+template <class F, int K, bool A_LT_P>
 struct FusedCol;
 #include "mac_chains.inc"
 
@@ -520,7 +520,17 @@ __device__ __forceinline__ void lw_redc_unit0(uint32_t &m, uint32_t &mid, uint32
 // Column K of a single product a*b + m*p for a field with FusedCol columns: one statement for the column's MACs, one
 // for the unit limb (columns K < N).  Every column sum is the exact integer fips_col<F, 1, K> forms (only the order of
 // its MACs differs), so the same m and the same result words come out.
-template <class F, int K>
+// A MAC is followed by an add-with-carry into the top word only where the running 64-bit sum can overflow; the generator
+// (tools/gen_mac_chains.py, fused_col_plan) proves the rest carry-less from two bounds:
+//   * the addend of column K is at most floor(S / 2^32) for the largest sum S of column K - 1, unit limb included:
+//     <= 2^32 - 1 into column 1 and <= 2^33 - 2 into column 2, so their first a*b MAC cannot carry for any operands
+//     ((2^32 - 1)^2 + 2^33 - 2 = 2^64 - 1);
+//   * A_LT_P = true only: a[N-1] <= p[N-1] (2^27 for Stark252), so a[7]*b[K-7] < 2^59 issued right behind the two m*p
+//     MACs of columns 7 to 13 cannot carry either (2^36 + 2^37 + 2^59 + 2^59 < 2^64).
+// PRECONDITION of A_LT_P = true: the first operand is canonical, a < p.  With a larger a[N-1] those columns drop a
+// carry and the product is silently wrong, so only fe_mul_lazy, whose contract already says a < p, sets it; fe_mul
+// takes arbitrary operands and keeps the bound-free columns.
+template <class F, int K, bool A_LT_P>
 __device__ __forceinline__ void fips_fused(uint64_t init, const Fe<F> &a, const Fe<F> &b, uint32_t (&m)[F::N], uint32_t (&t)[F::N]) {
     constexpr int N = F::N;
     static_assert(F::p(0) == 1u && F::INV == 0xffffffffu, "fused columns need a unit low limb of the modulus");
@@ -529,24 +539,25 @@ __device__ __forceinline__ void fips_fused(uint64_t init, const Fe<F> &a, const 
     } else {
         uint64_t lo;
         uint32_t hi;
-        FusedCol<F, K>::run(lo, hi, init, a, b, m);
+        FusedCol<F, K, A_LT_P>::run(lo, hi, init, a, b, m);
         if constexpr (K < N) {
             uint32_t mid, top;
             if constexpr (K == 0) lw_redc_unit0(m[0], mid, top, (uint32_t)lo, (uint32_t)(lo >> 32));
             else lw_redc_unit(m[K], mid, top, (uint32_t)lo, (uint32_t)(lo >> 32), hi);
-            fips_fused<F, K + 1>(((uint64_t)top << 32) | mid, a, b, m, t);
+            fips_fused<F, K + 1, A_LT_P>(((uint64_t)top << 32) | mid, a, b, m, t);
         } else {
             t[K - N] = (uint32_t)lo;
-            fips_fused<F, K + 1>((lo >> 32) | ((uint64_t)hi << 32), a, b, m, t);
+            fips_fused<F, K + 1, A_LT_P>((lo >> 32) | ((uint64_t)hi << 32), a, b, m, t);
         }
     }
 }
-// a*b + m*p over all columns into t (t < 2p for a < p), by the fused columns where the field has them
-template <class F>
+// a*b + m*p over all columns into t (t < 2p for a < p), by the fused columns where the field has them.
+// A_LT_P: the caller guarantees a < p (see fips_fused); fields without fused columns ignore it.
+template <class F, bool A_LT_P = false>
 __device__ __forceinline__ void fips_product(const Fe<F> &a, const Fe<F> &b, uint32_t (&t)[F::N]) {
     uint32_t m[F::N];
     if constexpr (lw_fused_columns<F>::value) {
-        fips_fused<F, 0>(0ull, a, b, m, t);
+        fips_fused<F, 0, A_LT_P>(0ull, a, b, m, t);
     } else {
         const Fe<F> *const pa[1] = {&a}, *const pb[1] = {&b};
         fips_col<F, 1, 0>(0ull, pa, pb, m, t);
@@ -672,12 +683,15 @@ LW_HD Fe<F> fe_add2p_sub_raw(const Fe<F> &a, const Fe<F> &b) {   // a + 2p - b, 
 }
 // Montgomery product without the final conditional subtraction: result in [0, 2p) whenever a < p
 // (b may be any N-limb value): (a*b + m*p) / R < a*b/R + p < 2p.
+// a < p is a hard precondition on the device, not only the source of the 2p bound: the fused columns use a[N-1] <= p[N-1]
+// to drop carry adds (fips_fused, A_LT_P), so a non-canonical FIRST operand gives a wrong product.  Pass the table
+// value (twiddle, coset power, N^-1) as a and the lazy data value as b.
 template <class F>
 LW_HD Fe<F> fe_mul_lazy(const Fe<F> &a, const Fe<F> &b) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int N = F::N;
     uint32_t t[N];
-    fips_product<F>(a, b, t);
+    fips_product<F, true>(a, b, t);
     Fe<F> r;
 #pragma unroll
     for (int i = 0; i < N; i++) r.v[i] = t[i];

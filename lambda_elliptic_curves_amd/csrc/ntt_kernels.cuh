@@ -16,6 +16,12 @@
 //   * the last pass folds the bit-reverse permutation into its store addresses: a workgroup takes the C
 //     tiles whose bit-reversed tile ids are consecutive, so natural-order output leaves as C*32-byte runs.
 //   * the INTT's N^-1 scaling (math/src/fft/polynomial.rs:172-173) is fused into the last pass.
+//   * the passes before the last store their result straight from the registers of the last register step: their
+//     work-items walk columns fastest, so the lanes of a row already hold one contiguous run of the output (256 B for an
+//     8-stage tile).  Only the last pass goes back through LDS, for the transpose that turns its bit-reversed rows into
+//     coalesced runs.
+//   * lazy values (< 17p) handed from pass to pass are reduced on load only where the first stage adds them (half of the
+//     elements of a work-item); the other half enters a Montgomery product, which takes any 256-bit operand (ntt_item).
 #pragma once
 #include "field.cuh"
 
@@ -119,7 +125,7 @@ __device__ __forceinline__ void lds_wave_sync() {
 // of the index arithmetic fold (every pass of a 2^24 transform, the last pass from 2^16 on).
 template <class F, int K, bool LAST, bool EXTRA, bool WL, int FX = 0>
 __device__ __forceinline__ void ntt_item(const NttPassParams &p, uint4 (*lds)[NTT_TILE], uint4 (*ltw)[NTT_LTW], const uint4 *gin,
-                                         uint32_t w, uint32_t step, uint32_t t0, uint64_t base, uint32_t lgS,
+                                         uint4 *gout, uint32_t w, uint32_t step, uint32_t t0, uint64_t base, uint32_t lgS,
                                          uint32_t hi_uniform, uint32_t hi_low, bool last_step, bool stage_tw) {
     constexpr int E = 1 << K;
     const uint32_t r = FX ? (uint32_t)FX : p.r, logC = FX ? (uint32_t)(NTT_TILE_LOG - FX) : p.logC, L = p.L;
@@ -189,11 +195,15 @@ __device__ __forceinline__ void ntt_item(const NttPassParams &p, uint4 (*lds)[NT
 
     // Lazy reduction (fields with 4+ spare bits, F::LAZY): values ride in [0, 17p) — a butterfly is
     //   t = w*y in [0,2p) (no final subtraction), x' = x + t, y' = x + 2p - t, so the bound grows by 2p per stage;
-    // a pass has <= 8 stages and fully reduces its input on load (< p, so < 17p at its end); the last pass canonicalises on exit.
+    // a pass has <= 8 stages and starts them from values below p (so < 17p at its end); the last pass canonicalises on exit.
+    // On load only the elements the first stage ADDS are reduced, j < E/2: the others, j >= E/2, go straight into that
+    // stage's Montgomery product as the b operand, which takes any 256-bit value (a lazy input is < 17p < 2^256) and
+    // returns t < 2p (the unit branch reduces its operand itself).  After the stage x'[j] = x + t < 3p and
+    // x'[j + E/2] = x + 2p - t < 3p with x < p, the same p + 2p per stage as if all E had been reduced.
     // Every result is still the unique canonical residue when it leaves the transform, so parity is unaffected.
     if (F::LAZY && step == 0 && p.lazy_in) {
 #pragma unroll
-        for (int j = 0; j < E; j++) x[j] = fe_reduce_full(x[j]);
+        for (int j = 0; j < E / 2; j++) x[j] = fe_reduce_full(x[j]);
     }
 
     // stage u of this step == stage s0 + t0 + u of the transform.  The E-1 twiddle groups of the step are walked in
@@ -266,6 +276,22 @@ __device__ __forceinline__ void ntt_item(const NttPassParams &p, uint4 (*lds)[NT
         for (int j = 0; j < E; j++) x[j] = fe_reduce_full(x[j]);
     }
 
+    if (!LAST && last_step) {
+        // Non-last passes store their result straight from registers: work-items walk columns fastest, so the 2^logC
+        // lanes of a row hold one contiguous run of the output (8 x 32 B = 256 B for an 8-stage tile) and no transpose
+        // through LDS is needed.  Same tile elements as the load of step 0, so an in-place pass stays safe: every load
+        // of the tile is behind the barriers between the steps.
+#pragma unroll
+        for (int j = 0; j < E; j++) {
+            const uint32_t m = mbase | ((uint32_t)j << sh);
+            const uint64_t g = gbase + ((uint64_t)m << lgS) + c;
+            uint4 q0, q1;
+            pack_mem<F>(x[j], q0, q1);
+            gout[2 * g] = q0;
+            gout[2 * g + 1] = q1;
+        }
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < E; j++) {
         const uint32_t idx = lds_slot<WL>(mbase | ((uint32_t)j << sh), c, r, logC);
@@ -321,7 +347,7 @@ __global__ __launch_bounds__(NTT_THREADS, NTT_WAVES_PER_SIMD) void ntt_pass_kern
             if (WL && ((p.wave_sync >> (S)) & 1u)) lds_wave_sync();                                                                     \
             else __syncthreads();                                                                                                       \
         }                                                                                                                               \
-        ntt_item<F, 2, LAST, EXTRA, WL, FX>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, tid, (S), 2u * (S), base, lgS, hi_uniform, hi_low,    \
+        ntt_item<F, 2, LAST, EXTRA, WL, FX>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, gout, tid, (S), 2u * (S), base, lgS, hi_uniform, hi_low,    \
                                             2 * ((S) + 1) == FX, stage_inside && (S) == 0);                                             \
     } while (0)
         LW_FX_STEP(0u);
@@ -330,8 +356,8 @@ __global__ __launch_bounds__(NTT_THREADS, NTT_WAVES_PER_SIMD) void ntt_pass_kern
         if constexpr (FX == 8) LW_FX_STEP(3u);
         if constexpr (FX == 7) {   // the odd stage: a radix-2 step, two items per work-item
             __syncthreads();
-            ntt_item<F, 1, LAST, EXTRA, WL, FX>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, tid, 3u, 6u, base, lgS, hi_uniform, hi_low, true, false);
-            ntt_item<F, 1, LAST, EXTRA, WL, FX>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, tid + NTT_THREADS, 3u, 6u, base, lgS, hi_uniform, hi_low, true, false);
+            ntt_item<F, 1, LAST, EXTRA, WL, FX>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, gout, tid, 3u, 6u, base, lgS, hi_uniform, hi_low, true, false);
+            ntt_item<F, 1, LAST, EXTRA, WL, FX>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, gout, tid + NTT_THREADS, 3u, 6u, base, lgS, hi_uniform, hi_low, true, false);
         }
 #undef LW_FX_STEP
     } else {
@@ -345,23 +371,22 @@ __global__ __launch_bounds__(NTT_THREADS, NTT_WAVES_PER_SIMD) void ntt_pass_kern
             else __syncthreads();
         }
         for (uint32_t w = tid; w < nitems; w += NTT_THREADS) {
-            if (NTT_KMAX >= 3 && k == 3) ntt_item<F, (NTT_KMAX >= 3 ? 3 : 1), LAST, EXTRA, WL>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, w, step, t0, base, lgS, hi_uniform, hi_low, last_step, stage_inside && step == 0 && w == tid);
-            else if (k == 2) ntt_item<F, 2, LAST, EXTRA, WL>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, w, step, t0, base, lgS, hi_uniform, hi_low, last_step, stage_inside && step == 0 && w == tid);
-            else ntt_item<F, 1, LAST, EXTRA, WL>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, w, step, t0, base, lgS, hi_uniform, hi_low, last_step, stage_inside && step == 0 && w == tid);
+            if (NTT_KMAX >= 3 && k == 3) ntt_item<F, (NTT_KMAX >= 3 ? 3 : 1), LAST, EXTRA, WL>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, gout, w, step, t0, base, lgS, hi_uniform, hi_low, last_step, stage_inside && step == 0 && w == tid);
+            else if (k == 2) ntt_item<F, 2, LAST, EXTRA, WL>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, gout, w, step, t0, base, lgS, hi_uniform, hi_low, last_step, stage_inside && step == 0 && w == tid);
+            else ntt_item<F, 1, LAST, EXTRA, WL>(p, lds, (uint4 (*)[NTT_LTW])ltw, gin, gout, w, step, t0, base, lgS, hi_uniform, hi_low, last_step, stage_inside && step == 0 && w == tid);
         }
         t0 += k;
     }
     }
+    if constexpr (!LAST) return;   // stored from registers by the last register step (ntt_item)
     __syncthreads();
 
-    // coalesced write-out: two lanes per element, 16 B each
+    // last pass: coalesced write-out of the bit-reversed tile, two lanes per element, 16 B each
     auto write_one = [&](uint32_t f) {
         const uint32_t e = f >> 1, plane = f & 1;
         const uint32_t c = e & ((1u << logC) - 1);
         const uint32_t m = e >> logC;
-        uint64_t g;
-        if (!LAST) g = base + ((uint64_t)m << lgS) + c;
-        else g = ((uint64_t)bitrev_bits(m, r) << (L - r)) + ((uint64_t)b << logC) + c;
+        const uint64_t g = ((uint64_t)bitrev_bits(m, r) << (L - r)) + ((uint64_t)b << logC) + c;
         gout[2 * g + plane] = lds[plane][lds_slot<WL>(m, c, r, logC) ^ (WL ? plane : 0u)];
     };
     if constexpr (FX) {

@@ -5,7 +5,14 @@ hipcc pads one wait state after every asm statement, so a column written as seve
 s_nop per statement.  This emits, for every product count n = 1..12, a function whose single statement starts the
 column (first MAC takes the previous column's carry as addend) and chains the remaining a*b MACs, and one that
 chains n m*p MACs with the modulus limbs as SGPR literals.  For the fields in FUSED_FIELDS it also emits, per column,
-one statement holding all of the column's a*b and m*p MACs with the sparse modulus compiled in."""
+one statement holding all of the column's a*b and m*p MACs with the sparse modulus compiled in.
+
+A MAC needs an add-with-carry into the column's top word only if the 64-bit running sum can overflow.  fused_col_plan
+proves per column, by exact interval arithmetic over per-limb operand bounds, which leading MACs cannot: (1) the carry into
+column K is at most floor(S_{K-1} / 2^32) for the previous column's largest sum S, unit limb included, which spares the
+first a*b MAC of columns 1 and 2 for any operands; (2) for callers that promise a < p (precondition of the A_LT_P = true
+columns, used by fe_mul_lazy only) a's top limb is at most p's, so in Stark252's columns 7 to 13 a[7]*b[K-7] goes right
+behind the two m*p MACs and needs none either.  Every bound is asserted below 2^64 when the file is generated."""
 MAC = 'LW_MAC_V("%{a}", "%{b}")'
 
 
@@ -56,32 +63,82 @@ FUSED_FIELDS = {
 }
 
 
-def fused_col(field, p, k):
-    """Column k of a*b + m*p as one statement: lo(64) / hi(32) = init + sum a[i]*b[k-i] + sum m[i]*p[k-i] over every
-    MAC of the column except the unit limb's m[k]*p[0] (lw_redc_unit in field.cuh does that one without a multiply).
+W = (1 << 32) - 1          # largest 32-bit word
 
-    The reduction MACs go first.  A column's addend is (previous column) >> 64 < 2^40: each column sums at most
-    2N - 2 + 2 products below 2^64, so its top word is small.  While the running sum provably stays below 2^64 (the
-    addend, then m*p[j] < 2^32 * p[j] for the small limbs of a sparse modulus, or a*b alone in column 0) a MAC cannot
-    carry out of the low pair, so it needs no add-with-carry; the top word starts on the first MAC that can carry.
-    The top word of the last column is never read (the result fits N limbs), so that column has no add-with-carry."""
+
+def operand_bounds(p, a_canonical):
+    """Largest value of every limb of a, b and m.  b and m are arbitrary words.  a is arbitrary too, unless the caller
+    promises a < p (a_canonical): then its top limb is at most p's top limb (the lower limbs stay arbitrary)."""
+    n = len(p)
+    a = [W] * n
+    if a_canonical:
+        a[n - 1] = p[n - 1]
+    return a, [W] * n, [W] * n
+
+
+def fused_col_plan(p, k, a_canonical=False):
+    """Column k of a*b + m*p as a list of MACs in issue order, with the proof that the carry-less ones cannot carry.
+
+    -> dict(macs=[(kind, i, j, carry)], has_hi, carry_in, proof=[(q, bound)], total)
+       kind 'mp': m[i]*p[j], 'ab': a[i]*b[j]; carry: an add-with-carry into the top word follows this MAC;
+       carry_in: largest addend the previous column can hand over; proof: for every carry-less MAC q the largest value
+       the 64-bit running sum can have after it (asserted below 2^64); total: the column's largest sum, unit limb included.
+
+    Interval arithmetic, exact (no rounding up: column 2's first MAC reaches 2^64 - 1):
+      * the carry into column k is floor(S / 2^32) of the largest sum S of column k - 1, where S includes the unit
+        limb's m[k-1] <= 2^32 - 1 (lw_redc_unit adds it before the shift).  Column 0 hands over <= 2^32 - 1 and column 1
+        <= 2^33 - 2, so the first a*b MAC of columns 1 and 2 cannot carry: (2^32 - 1)^2 + 2^33 - 2 = 2^64 - 1.
+      * a MAC is bounded by the product of its operands' bounds: m[i]*p[j] <= (2^32 - 1)*p[j], and with a < p
+        (a_canonical) a[N-1]*b[j] <= p[N-1]*(2^32 - 1), below 2^59 for Stark252.
+    The reduction MACs go first, then the a*b MACs smallest bound first (a stable sort: with equal bounds the order is
+    i ascending), and the top word starts on the first MAC whose running bound reaches 2^64.  The top word of the last
+    column is never read (the result fits N limbs), so that column has no add-with-carry."""
     n = len(p)
     assert p[0] == 1
     last = 2 * n - 2
-    mp = [(i, k - i) for i in range(max(0, k - n + 1), min(k, n)) if p[k - i] != 0]
-    ab = [(i, k - i) for i in range(max(0, k - n + 1), min(k, n - 1) + 1)]
+    amax, bmax, mmax = operand_bounds(p, a_canonical)
+    carry_in = 0
+    if k > 0:
+        carry_in = fused_col_plan(p, k - 1, a_canonical)["total"] >> 32
+    mp = [("mp", i, k - i, mmax[i] * p[k - i]) for i in range(max(0, k - n + 1), min(k, n)) if p[k - i] != 0]
+    ab = [("ab", i, k - i, amax[i] * bmax[k - i]) for i in range(max(0, k - n + 1), min(k, n - 1) + 1)]
+    ab.sort(key=lambda t: t[3])
+    order = mp + ab
     # how many leading MACs cannot carry
-    bound = (1 << 40) if k > 0 else 0
-    safe = 0
-    for _, j in mp:
-        bound += p[j] << 32
-        if bound >= 1 << 64:
+    bound, safe, proof = carry_in, 0, []
+    for q, (_, _, _, mx) in enumerate(order):
+        if bound + mx >= 1 << 64:
             break
+        bound += mx
+        proof.append((q, bound))
         safe += 1
-    if safe == len(mp) and ab and bound + ((1 << 32) - 1) ** 2 < (1 << 64):
-        safe += 1                         # column 0: a[0]*b[0] with no addend
-    # outputs: %0 lo, %1 hi (none in the last column, nor in a column whose MACs cannot carry: its top word is 0)
-    has_hi = k != last and safe < len(mp) + len(ab)
+    for q, b in proof:
+        assert b < 1 << 64, (k, q, hex(b))
+    # none in the last column, nor in a column whose MACs cannot carry: its top word is 0
+    has_hi = k != last and safe < len(order)
+    total = carry_in + sum(t[3] for t in order) + (mmax[k] * p[0] if k < n else 0)
+    # the 96-bit accumulator holds every column; the last column's sum must fit the low pair since its top word is dropped
+    assert total < 1 << 96 and (k != last or not a_canonical or total < 1 << 64), (k, hex(total))
+    macs = [(kind, i, j, has_hi and q >= safe) for q, (kind, i, j, _) in enumerate(order)]
+    return dict(macs=macs, has_hi=has_hi, carry_in=carry_in, proof=proof, total=total)
+
+
+def fused_col(field, p, k, a_canonical=False):
+    """Column k of a*b + m*p as one statement: lo(64) / hi(32) = init + sum a[i]*b[k-i] + sum m[i]*p[k-i] over every
+    MAC of the column except the unit limb's m[k]*p[0] (lw_redc_unit in field.cuh does that one without a multiply).
+    Which MACs carry an add-with-carry, and why the others need none, is fused_col_plan's business.
+
+    a_canonical: the variant FusedCol<F, K, true> for callers whose contract says a < p (fe_mul_lazy: the NTT's
+    twiddles and scale factors).  Where the bound on a's top limb changes nothing it inherits the general column."""
+    n = len(p)
+    last = 2 * n - 2
+    plan = fused_col_plan(p, k, a_canonical)
+    if a_canonical and plan["macs"] == fused_col_plan(p, k, False)["macs"]:
+        return (f"template <>\n"
+                f"struct FusedCol<{field}, {k}, true> : FusedCol<{field}, {k}, false> {{}};   // a < p changes nothing here\n")
+    has_hi = plan["has_hi"]
+    nab = sum(1 for m in plan["macs"] if m[0] == "ab")
+    nmp = len(plan["macs"]) - nab
     ins, macs = [], []
     opn = 2 if has_hi else 1
     init = None
@@ -89,26 +146,26 @@ def fused_col(field, p, k):
         init = f"%{opn}"
         ins.append('"v"(init)')
         opn += 1
-    for i, j in mp:
-        if p[j] <= 64:                    # inline constant
+    for kind, i, j, _ in plan["macs"]:
+        if kind == "mp" and p[j] <= 64:   # inline constant
             macs.append((f"%{opn}", str(p[j])))
             ins.append(f'"v"(m[{i}])')
             opn += 1
-        else:                             # SGPR literal
+        elif kind == "mp":                # SGPR literal
             macs.append((f"%{opn}", f"%{opn + 1}"))
             ins.append(f'"v"(m[{i}])')
             ins.append(f'"s"({field}::p({j}))')
             opn += 2
-    for i, j in ab:
-        macs.append((f"%{opn}", f"%{opn + 1}"))
-        ins.append(f'"v"(a.v[{i}])')
-        ins.append(f'"v"(b.v[{j}])')
-        opn += 2
+        else:
+            macs.append((f"%{opn}", f"%{opn + 1}"))
+            ins.append(f'"v"(a.v[{i}])')
+            ins.append(f'"v"(b.v[{j}])')
+            opn += 2
     body, hi_live = [], False
     for q, (x, y) in enumerate(macs):
         addend = "%0" if q > 0 else (init or "0")
         body.append(f'"v_mad_u64_u32 %0, vcc, {x}, {y}, {addend}\\n\\t"')
-        if not has_hi or q < safe:
+        if not plan["macs"][q][3]:
             continue
         if hi_live:
             body.append('"v_addc_co_u32_e32 %1, vcc, 0, %1, vcc\\n\\t"')
@@ -123,9 +180,15 @@ def fused_col(field, p, k):
         tail = "        hi = 0;\n"
     else:
         tail = ""
+    if plan["proof"]:
+        q, b = plan["proof"][-1]
+        why = f"    // addend <= 0x{plan['carry_in']:x}; no carry out of the low pair up to MAC {q}: sum <= 0x{b:x}\n"
+    else:
+        why = f"    // addend <= 0x{plan['carry_in']:x}; every MAC can carry\n"
     sep = "\n            "
     return (f"template <>\n"
-            f"struct FusedCol<{field}, {k}> {{   // {len(ab)} a*b + {len(mp)} m*p MACs\n"
+            f"struct FusedCol<{field}, {k}, {'true' if a_canonical else 'false'}> {{   // {nab} a*b + {nmp} m*p MACs\n"
+            f"{why}"
             f"    __device__ static __forceinline__ void run(uint64_t &lo, uint32_t &hi, uint64_t init, const Fe<{field}> &a, "
             f"const Fe<{field}> &b, const uint32_t (&m)[{n}]) {{\n"
             f"        asm({sep.join(body)}\n"
@@ -139,11 +202,14 @@ def fused_col(field, p, k):
 def fused_field(field, p):
     n = len(p)
     checks = " && ".join(f"{field}::p({i}) == 0x{v:08x}u" for i, v in enumerate(p))
-    out = [f"// {field}: the whole product, one statement per column (FusedCol<F, K>::run, used by fips_fused)\n"
+    out = [f"// {field}: the whole product, one statement per column (FusedCol<F, K, A_LT_P>::run, used by fips_fused).\n"
+           f"// A_LT_P = true is for callers that promise a < p: a[{n - 1}] <= 0x{p[n - 1]:x} spares one add-with-carry in the columns it is in.\n"
            f"static_assert({field}::N == {n} && {checks}, \"modulus changed: rerun tools/gen_mac_chains.py\");\n"
            f"template <>\nstruct lw_fused_columns<{field}> {{\n    static constexpr bool value = true;\n}};\n"]
     for k in range(2 * n - 1):
         out.append(fused_col(field, p, k))
+    for k in range(2 * n - 1):
+        out.append(fused_col(field, p, k, a_canonical=True))
     return out
 
 
