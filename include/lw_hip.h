@@ -412,6 +412,34 @@ int lw_kzg_open_batch(const lw_srs_t *srs, const uint64_t *const *polys, const s
 int lw_kzg_open_batch_device(const lw_srs_t *srs, const uint64_t *const *d_polys, const size_t *lens, uint32_t k, const uint64_t *x,
                              const uint64_t *upsilon, void *out_proof_host, uint64_t *out_evals_host_or_null, void *hip_stream);
 
+/* ---- STARK DEEP composition polynomial ----
+ * compute_deep_composition_poly / compute_trace_term (provers/stark/src/prover.rs:643-714, 720-747), the step of
+ * round_4_compute_and_run_fri_on_the_deep_composition_polynomial (:536-594) that produces fri::commit_phase's input:
+ *   deep = sum_i gamma'_i (H_i - H_i(z^P)) / (X - z^P)  +  sum_j sum_r gamma_{j,r} (t_j - y_{j,r}) / (X - g^r z).
+ * Stated over K polynomials, M points and a K x M weight matrix (row-major, weights[k * m + j]):
+ *   out = sum_j quot(sum_k weights[k][j] * polys[k], points[j]),    quot(p, x) = ruffini_division_inplace of p by (X - x).
+ * The subtracted evaluations are no input: they change only coefficient 0, which no quotient coefficient reads (the
+ * remainder is popped, as in lw_kzg_open), and division is linear, so the per-term quotients of the reference add up to
+ * one quotient per distinct point.  The prover's call has K = trace columns + composition parts and
+ * M = frame rows + 1; trace rows carry weight 0 at z^P and the parts weight 0 at the frame points.
+ * Elements are as in lw_poly_*: 4 x u64, MS limb first, Montgomery form, canonical; field LW_FIELD_STARK252 or
+ * LW_FIELD_BLS12_381_FR.  points (m elements) and weights (k * m elements) are host memory in both forms.  The
+ * polynomials may differ in length, k and m have no fixed cap, duplicate points and zero weights are legal; the
+ * coefficients of a polynomial are not read for the points where its weight is 0.
+ * out_coeffs receives n - 1 elements, n = the longest length: the Polynomial addition result before Polynomial::new
+ * strips it; *out_len_or_null is the stripped length.  n <= 1 or k = 0: nothing is written, length 0, LW_OK.
+ * out_evals[k * m + j] = polys[k](points[j]) where weights[k][j] != 0 and 0 elsewhere (round 3's trace_ood_evaluations
+ * and composition_poly_parts_ood_evaluation in one table; they are the totals the division computes anyway).
+ * m = 0, a null pointer, a field other than the two: LW_ERR_BAD_ARG; a length above 2^36: LW_ERR_ALLOC.  The _device
+ * form also rejects (LW_ERR_BAD_ARG) a buffer that is not 16-byte aligned and a d_out_coeffs that overlaps an input
+ * polynomial.  d_out_coeffs can go to lw_stark_fri_layer_device as d_coeffs unchanged.  The _device form synchronises
+ * only when out_len or out_evals is asked for; with neither it enqueues and returns (stream contract above). */
+int lw_stark_deep_composition(lw_field_t field, const void *const *polys, const size_t *lens, uint32_t k, const void *points,
+                              uint32_t m, const void *weights, void *out_coeffs, size_t *out_len_or_null, void *out_evals_or_null);
+int lw_stark_deep_composition_device(lw_field_t field, const void *const *d_polys, const size_t *lens, uint32_t k,
+                                     const void *points, uint32_t m, const void *weights, void *d_out_coeffs,
+                                     size_t *out_len_or_null, void *out_evals_host_or_null, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ EXPORTS = [
     "lw_hip_msm_sharded_device", "lw_hip_msm_sharded_selftest_device",
     "lw_poly_evaluate", "lw_poly_evaluate_device", "lw_poly_ruffini_division", "lw_poly_ruffini_division_device",
     "lw_kzg_open", "lw_kzg_open_device", "lw_kzg_open_batch", "lw_kzg_open_batch_device",
+    "lw_stark_deep_composition", "lw_stark_deep_composition_device",
 ]
 
 
@@ -180,6 +181,10 @@ def lib():
     L.lw_kzg_open_batch.restype = i
     L.lw_kzg_open_batch_device.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp]
     L.lw_kzg_open_batch_device.restype = i
+    L.lw_stark_deep_composition.argtypes = [i, vp, vp, u32, vp, u32, vp, vp, C.POINTER(sz), vp]
+    L.lw_stark_deep_composition.restype = i
+    L.lw_stark_deep_composition_device.argtypes = [i, vp, vp, u32, vp, u32, vp, vp, C.POINTER(sz), vp, vp]
+    L.lw_stark_deep_composition_device.restype = i
     _lib = L
     return L
 

@@ -176,6 +176,8 @@ void Context::release_all() {
     pipe_tmp.release();
     poly_ws.release();
     poly_q.release();
+    if (deep_pin) { (void)hipHostFree(deep_pin); deep_pin = nullptr; deep_pin_bytes = 0; }
+    if (deep_pin_read) { (void)hipEventDestroy(deep_pin_read); deep_pin_read = nullptr; }
     timings.twiddle_bytes = timings.scratch_bytes = 0;
 }
 

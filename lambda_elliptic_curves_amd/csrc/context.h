@@ -116,6 +116,11 @@ struct Context {
     DeviceBuf pipe_tmp;               // intermediates of the device-resident pipelines (FRI layer evaluation, Groth16 cosets)
     DeviceBuf poly_ws;                // polynomial evaluation / division: tile sums, carries, totals (poly.hip)
     DeviceBuf poly_q;                 // the quotient a KZG opening commits (canonical scalars for the SRS MSM)
+    // DEEP composition (poly.hip): pinned host staging of the call's tables, and the event after which the device has
+    // read it (a call that hands no host result back returns while its upload is still in flight)
+    void *deep_pin = nullptr;
+    size_t deep_pin_bytes = 0;
+    hipEvent_t deep_pin_read = nullptr;
     lw_timings_t timings = {};
     // Cross-stream ordering of the context-owned buffers (scratch, tables, staging, MSM workspace): every entry point
     // records `order_event` on its launch stream when it returns; a call arriving on a different stream first makes

@@ -182,6 +182,169 @@ __global__ __launch_bounds__(POLY_THREADS) void poly_tile_rescan_kernel(const Po
     }
 }
 
+// ---- DEEP composition: out = sum_j quot(sum_k w[k][j] p_k, x_j) (lw_stark_deep_composition) ----
+// The same three steps over a K x M weight matrix, POLY_PTS points (a "group") per round of launches:
+//   1. deep_tile_reduce_kernel  tile sums of every (polynomial, point) pair with a non-zero weight; the coefficients are
+//                               loaded once for the points of the group.  Only the tile's total is needed, so the 256
+//                               partial sums are folded as a tree (128 + 64 + ... + 1 products), not scanned.
+//   2. deep_tile_scan_kernel    one block per series: per point the w-weighted fold of the pairs' tile sums (carries),
+//                               and per pair its own series when the values p_k(x_j) are asked for.
+//   3. deep_tile_rescan_kernel  per tile, point after point: sum_k w[k][j] p_k[i] formed on load, rescanned with that
+//                               point's carry, the quotient coefficients of all points added up in registers and stored
+//                               once (groups after the first add to what the output holds).
+// Pairs with weight zero are masked on the host: their coefficients are never read, their sums never written or read.
+template <class F>
+struct DeepArgs {
+    const PolyRef *tab;       // k polynomials
+    const uint32_t *mask;     // [k] bit j: the weight of polynomial k at point j of this group is non-zero
+    const char *w;            // [POLY_PTS][k] weights of this group, point-major
+    uint32_t k, mp;           // polynomials; points of this group
+    uint32_t k0;              // reduce: first polynomial of this launch (blockIdx.y counts from it)
+    uint32_t evals;           // scan: the per-pair series too
+    uint32_t m;               // row length of vals
+    uint32_t col[POLY_PTS];   // column of each group point in the caller's matrix
+    uint32_t accumulate;      // rescan: add to the output
+    uint64_t ntiles;
+    uint64_t n;               // the longest length
+    char *sums;               // [k][POLY_PTS][ntiles]
+    char *carries;            // [POLY_PTS][ntiles]
+    char *vals;               // [k][m] p_k(x_j)
+    char *out;                // n - 1 elements
+    Fe<F> pw[POLY_PTS][POLY_NPOW];
+};
+
+template <class F>
+__global__ __launch_bounds__(POLY_THREADS) void deep_tile_reduce_kernel(const DeepArgs<F> a) {
+    __shared__ Fe<F> lds[POLY_THREADS];
+    const uint32_t k = a.k0 + blockIdx.y;
+    const uint64_t t = blockIdx.x;
+    const uint32_t mask = a.mask[k];
+    if (!mask) return;
+    const PolyRef pr = a.tab[k];
+    const int r = threadIdx.x;
+    char *out = a.sums + ((uint64_t)k * POLY_PTS * a.ntiles + t) * 32;
+    if (t * POLY_TILE >= pr.len) {   // past the end of this polynomial: its tiles sum to zero
+        if (r < (int)a.mp && (mask >> r & 1)) fe_store<F>(out + (uint64_t)r * a.ntiles * 32, Fe<F>::zero());
+        return;
+    }
+    const uint64_t base = t * POLY_TILE + (uint64_t)r * POLY_E;
+    Fe<F> c[POLY_E];
+#pragma unroll
+    for (int e = 0; e < POLY_E; e++) c[e] = poly_coeff<F>(pr, base + e);
+#pragma unroll 1
+    for (uint32_t j = 0; j < a.mp; j++) {
+        if (!(mask >> j & 1)) continue;
+        const Fe<F> z = a.pw[j][0];
+        Fe<F> h = c[POLY_E - 1];
+#pragma unroll
+        for (int e = POLY_E - 2; e >= 0; e--) h = fe_add<F>(fe_mul<F>(h, z), c[e]);
+        // sum_r z^(E r) h_r: the upper half of the live threads folds onto the lower half, z^(E d) apart.  A step writes
+        // lds[d, 2d) and reads it back; the next one writes [d/2, d): one barrier per step is enough.
+#pragma unroll 1
+        for (int s = 7; s >= 0; s--) {
+            const int d = 1 << s;
+            if (r >= d && r < 2 * d) lds[r] = h;
+            __syncthreads();
+            if (r < d) h = fe_add<F>(h, fe_mul<F>(a.pw[j][1 + s], lds[r + d]));
+        }
+        if (r == 0) fe_store<F>(out + (uint64_t)j * a.ntiles * 32, h);
+    }
+}
+
+// block b: point b % mp; b / mp == 0 is the point's weighted fold (carries), b / mp == kk + 1 the pair (kk, point)
+template <class F>
+__global__ __launch_bounds__(POLY_THREADS) void deep_tile_scan_kernel(const DeepArgs<F> a) {
+    __shared__ Fe<F> lds[POLY_THREADS];
+    __shared__ Fe<F> mul[8];
+    const uint32_t j = blockIdx.x % a.mp, kb = blockIdx.x / a.mp;
+    const bool fold = kb == 0;
+    if (!fold && !(a.mask[kb - 1] >> j & 1)) return;
+    const Fe<F> P = a.pw[j][POLY_NPOW - 1];   // x^TILE
+    const uint64_t nt = a.ntiles, G = (nt + POLY_THREADS - 1) / POLY_THREADS, t0 = (uint64_t)threadIdx.x * G;
+    auto tile = [&](uint64_t t) -> Fe<F> {
+        if (t >= nt) return Fe<F>::zero();
+        if (!fold) return fe_load<F>(a.sums + (((uint64_t)(kb - 1) * POLY_PTS + j) * nt + t) * 32);
+        Fe<F> v = Fe<F>::zero();
+        for (uint32_t k = 0; k < a.k; k++)
+            if (a.mask[k] >> j & 1)
+                v = fe_add<F>(v, fe_mul<F>(fe_load<F>(a.w + ((uint64_t)j * a.k + k) * 32),
+                                           fe_load<F>(a.sums + (((uint64_t)k * POLY_PTS + j) * nt + t) * 32)));
+        return v;
+    };
+    if (threadIdx.x == 0) {   // neighbouring groups are x^(TILE G) apart
+        Fe<F> w = fe_pow_u64<F>(P, G);
+        for (int s = 0; s < 8; s++) {
+            mul[s] = w;
+            w = fe_sqr<F>(w);
+        }
+    }
+    Fe<F> acc = Fe<F>::zero();
+#pragma unroll 1
+    for (uint64_t g = G; g-- > 0;) acc = fe_add<F>(fe_mul<F>(acc, P), tile(t0 + g));
+    __syncthreads();
+    acc = block_suffix_scan<F>(acc, lds, [&](int s) { return mul[s]; });
+    if (!fold) {
+        if (threadIdx.x == 0) fe_store<F>(a.vals + ((uint64_t)(kb - 1) * a.m + a.col[j]) * 32, acc);
+        return;
+    }
+    Fe<F> c = threadIdx.x + 1 < POLY_THREADS ? lds[threadIdx.x + 1] : Fe<F>::zero();   // c at the top of this group
+#pragma unroll 1
+    for (uint64_t g = G; g-- > 0;) {
+        const uint64_t t = t0 + g;
+        if (t < nt) fe_store<F>(a.carries + ((uint64_t)j * nt + t) * 32, c);
+        c = fe_add<F>(fe_mul<F>(c, P), tile(t));
+    }
+}
+
+// The running sum of the quotients of the group's points lives in LDS between points (each thread its own E slots): next to
+// c[] it would take the kernel past 256 registers.  The last point adds its share and stores.
+template <class F>
+__global__ __launch_bounds__(POLY_THREADS) void deep_tile_rescan_kernel(const DeepArgs<F> a) {
+    __shared__ Fe<F> lds[POLY_THREADS];
+    __shared__ Fe<F> qs[POLY_E * POLY_THREADS];
+    const uint64_t t = blockIdx.x;
+    const uint64_t base = t * POLY_TILE + (uint64_t)threadIdx.x * POLY_E;
+#pragma unroll 1
+    for (uint32_t j = 0; j < a.mp; j++) {
+        Fe<F> c[POLY_E];
+#pragma unroll
+        for (int e = 0; e < POLY_E; e++) c[e] = Fe<F>::zero();
+#pragma unroll 1
+        for (uint32_t k = 0; k < a.k; k++) {
+            if (!(a.mask[k] >> j & 1)) continue;
+            const PolyRef pr = a.tab[k];
+            if (t * POLY_TILE >= pr.len) continue;
+            const Fe<F> w = fe_load<F>(a.w + ((uint64_t)j * a.k + k) * 32);
+#pragma unroll
+            for (int e = 0; e < POLY_E; e++) c[e] = fe_add<F>(c[e], fe_mul<F>(w, poly_coeff<F>(pr, base + e)));
+        }
+        const Fe<F> x = a.pw[j][0];
+        Fe<F> h = c[POLY_E - 1];
+#pragma unroll
+        for (int e = POLY_E - 2; e >= 0; e--) h = fe_add<F>(fe_mul<F>(h, x), c[e]);
+        const Fe<F> top = fe_load<F>(a.carries + ((uint64_t)j * a.ntiles + t) * 32);
+        if (threadIdx.x == POLY_THREADS - 1) h = fe_add<F>(h, fe_mul<F>(a.pw[j][1], top));
+        block_suffix_scan<F>(h, lds, [&](int s) { return a.pw[j][1 + s]; });
+        Fe<F> v = threadIdx.x + 1 < POLY_THREADS ? lds[threadIdx.x + 1] : top;   // c just above this thread's coefficients
+        __syncthreads();   // the next point's scan writes lds
+        const bool last = j + 1 == a.mp;
+#pragma unroll
+        for (int e = POLY_E - 1; e >= 0; e--) {
+            v = fe_add<F>(c[e], fe_mul<F>(x, v));
+            Fe<F> q = j ? fe_add<F>(v, qs[e * POLY_THREADS + threadIdx.x]) : v;
+            if (!last) {
+                qs[e * POLY_THREADS + threadIdx.x] = q;
+                continue;
+            }
+            const uint64_t i = base + e;
+            if (i >= 1 && i < a.n) {
+                char *o = a.out + (i - 1) * 32;
+                fe_store<F>(o, a.accumulate ? fe_add<F>(q, fe_load<F>(o)) : q);
+            }
+        }
+    }
+}
+
 // ---- host side ----
 template <class F>
 static void point_powers(const void *z_ref, Fe<F> (&pw)[POLY_NPOW]) {
@@ -307,6 +470,117 @@ static int divide_locked(Context &c, const PolyRef *refs, uint32_t k, const void
     if (evals_host) LW_HIP_CHECK(hipMemcpyAsync(evals_host, w.vals, (size_t)k * 32, hipMemcpyDeviceToHost, s), LW_ERR_LAUNCH);
     if (rem_host) LW_HIP_CHECK(hipMemcpyAsync(rem_host, w.vals + (size_t)k * 32, 32, hipMemcpyDeviceToHost, s), LW_ERR_LAUNCH);
     if (evals_host || rem_host) LW_HIP_CHECK(hipStreamSynchronize(s), LW_ERR_LAUNCH);
+    return LW_OK;
+}
+
+static bool elem_is_zero(const void *e) {
+    static const char z[32] = {0};
+    return memcmp(e, z, 32) == 0;
+}
+
+// pinned host memory for the tables of a DEEP call; the previous call's upload has been read once deep_pin_read fires
+static int deep_pin(Context &c, size_t bytes) {
+    if (c.deep_pin_read) LW_HIP_CHECK(hipEventSynchronize(c.deep_pin_read), LW_ERR_LAUNCH);
+    else LW_HIP_CHECK(hipEventCreateWithFlags(&c.deep_pin_read, hipEventDisableTiming), LW_ERR_ALLOC);
+    if (c.deep_pin_bytes >= bytes) return LW_OK;
+    if (c.deep_pin) (void)hipHostFree(c.deep_pin);
+    c.deep_pin = nullptr;
+    c.deep_pin_bytes = 0;
+    LW_HIP_CHECK(hipHostMalloc(&c.deep_pin, bytes, hipHostMallocDefault), LW_ERR_ALLOC);
+    c.deep_pin_bytes = bytes;
+    return LW_OK;
+}
+
+// sum_j quot(sum_k w[k][j] p_k, x_j) -> d_out (n - 1 elements, n = the longest length > 1); evals_host: the k x m table
+// of p_k(x_j) (0 where the weight is 0); len_host: the stripped length.  Synchronises when a host result is asked for.
+template <class F>
+static int deep_locked(Context &c, const PolyRef *refs, uint32_t k, const void *points, uint32_t m, const void *weights, void *d_out,
+                       size_t *len_host, void *evals_host, hipStream_t s) {
+    uint64_t n = 0;
+    for (uint32_t i = 0; i < k; i++) n = refs[i].len > n ? refs[i].len : n;
+    const uint64_t nt = tiles_of(n);
+    const char *W = (const char *)weights;
+    std::vector<uint32_t> cols;   // the points that carry any weight
+    for (uint32_t j = 0; j < m; j++)
+        for (uint32_t i = 0; i < k; i++)
+            if (!elem_is_zero(W + ((size_t)i * m + j) * 32)) {
+                cols.push_back(j);
+                break;
+            }
+    const size_t groups = (cols.size() + POLY_PTS - 1) / POLY_PTS;
+    // tables: [polynomials | per group: masks, weights]; workspace after them: [tile sums | carries | values | length]
+    const size_t tab_b = round256((size_t)k * sizeof(PolyRef)), mask_b = round256((size_t)k * 4), w_b = round256((size_t)POLY_PTS * k * 32);
+    const size_t tables = tab_b + groups * (mask_b + w_b);
+    const size_t sums_b = round256((size_t)k * POLY_PTS * nt * 32), car_b = round256((size_t)POLY_PTS * nt * 32);
+    const size_t vals_b = round256(evals_host ? (size_t)k * m * 32 : 0);
+    if (c.poly_ws.ensure(tables + sums_b + car_b + vals_b + 256)) return LW_ERR_ALLOC;
+    char *d_tab = (char *)c.poly_ws.p, *d_sums = d_tab + tables, *d_car = d_sums + sums_b, *d_vals = d_car + car_b, *d_len = d_vals + vals_b;
+    int rc = deep_pin(c, tables);
+    if (rc) return rc;
+    char *h = (char *)c.deep_pin;
+    memset(h, 0, tables);
+    memcpy(h, refs, (size_t)k * sizeof(PolyRef));
+    for (size_t g = 0; g < groups; g++) {
+        uint32_t *mask = (uint32_t *)(h + tab_b + g * (mask_b + w_b));
+        char *w = (char *)mask + mask_b;
+        for (uint32_t jj = 0; jj < (uint32_t)POLY_PTS && g * POLY_PTS + jj < cols.size(); jj++) {
+            const uint32_t j = cols[g * POLY_PTS + jj];
+            for (uint32_t i = 0; i < k; i++) {
+                const char *e = W + ((size_t)i * m + j) * 32;
+                if (elem_is_zero(e)) continue;
+                mask[i] |= 1u << jj;
+                memcpy(w + ((size_t)jj * k + i) * 32, e, 32);
+            }
+        }
+    }
+    LW_HIP_CHECK(hipMemcpyAsync(d_tab, h, tables, hipMemcpyHostToDevice, s), LW_ERR_LAUNCH);
+    LW_HIP_CHECK(hipEventRecord(c.deep_pin_read, s), LW_ERR_LAUNCH);
+    if (evals_host) LW_HIP_CHECK(hipMemsetAsync(d_vals, 0, (size_t)k * m * 32, s), LW_ERR_LAUNCH);
+    if (!groups) LW_HIP_CHECK(hipMemsetAsync(d_out, 0, (size_t)(n - 1) * 32, s), LW_ERR_LAUNCH);   // every weight is zero
+    DeepArgs<F> a;
+    memset(&a, 0, sizeof(a));
+    a.tab = (const PolyRef *)d_tab;
+    a.k = k;
+    a.m = m;
+    a.evals = evals_host ? 1 : 0;
+    a.ntiles = nt;
+    a.n = n;
+    a.sums = d_sums;
+    a.carries = d_car;
+    a.vals = d_vals;
+    a.out = (char *)d_out;
+    for (size_t g = 0; g < groups; g++) {
+        a.mask = (const uint32_t *)(d_tab + tab_b + g * (mask_b + w_b));
+        a.w = (const char *)a.mask + mask_b;
+        a.mp = (uint32_t)(cols.size() - g * POLY_PTS < (size_t)POLY_PTS ? cols.size() - g * POLY_PTS : (size_t)POLY_PTS);
+        a.accumulate = g > 0;
+        for (uint32_t jj = 0; jj < a.mp; jj++) {
+            a.col[jj] = cols[g * POLY_PTS + jj];
+            point_powers<F>((const char *)points + (size_t)a.col[jj] * 32, a.pw[jj]);
+        }
+        for (uint32_t k0 = 0; k0 < k; k0 += 65535) {   // the grid's y extent
+            a.k0 = k0;
+            hipEvent_t pe = c.prof_begin(s);
+            hipLaunchKernelGGL((deep_tile_reduce_kernel<F>), dim3((uint32_t)nt, k - k0 < 65535 ? k - k0 : 65535), dim3(POLY_THREADS), 0, s, a);
+            c.prof_end("deep_tile_reduce_kernel", pe, s);
+        }
+        hipEvent_t pe = c.prof_begin(s);
+        hipLaunchKernelGGL((deep_tile_scan_kernel<F>), dim3(a.mp * (1 + (a.evals ? k : 0))), dim3(POLY_THREADS), 0, s, a);
+        c.prof_end("deep_tile_scan_kernel", pe, s);
+        pe = c.prof_begin(s);
+        hipLaunchKernelGGL((deep_tile_rescan_kernel<F>), dim3((uint32_t)nt), dim3(POLY_THREADS), 0, s, a);
+        c.prof_end("deep_tile_rescan_kernel", pe, s);
+        LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
+    }
+    uint64_t len = 0;
+    if (len_host) {
+        rc = stripped_length_device(d_out, n - 1, (uint64_t *)d_len, s);
+        if (rc) return rc;
+        LW_HIP_CHECK(hipMemcpyAsync(&len, d_len, 8, hipMemcpyDeviceToHost, s), LW_ERR_LAUNCH);
+    }
+    if (evals_host) LW_HIP_CHECK(hipMemcpyAsync(evals_host, d_vals, (size_t)k * m * 32, hipMemcpyDeviceToHost, s), LW_ERR_LAUNCH);
+    if (len_host || evals_host) LW_HIP_CHECK(hipStreamSynchronize(s), LW_ERR_LAUNCH);
+    if (len_host) *len_host = (size_t)len;
     return LW_OK;
 }
 
@@ -474,6 +748,85 @@ int lw_poly_ruffini_division_device(lw_field_t field, const void *d_coeffs, size
     return field == LW_FIELD_STARK252
                ? divide_locked<Stark252, false>(en.c, &ref, 1, x, nullptr, d_out_quotient, nullptr, out_remainder_host_or_null, en.stream)
                : divide_locked<Fr381, false>(en.c, &ref, 1, x, nullptr, d_out_quotient, nullptr, out_remainder_host_or_null, en.stream);
+}
+
+// compute_deep_composition_poly (provers/stark/src/prover.rs:643-714) over a weight matrix, see include/lw_hip.h
+static int deep_entry(lw_field_t field, const void *const *polys, const size_t *lens, uint32_t k, const void *points, uint32_t m,
+                      const void *weights, void *out, size_t *out_len, void *out_evals, void *hip_stream, bool device) {
+    if (!poly_field_ok(field)) return LW_ERR_BAD_ARG;
+    if (m == 0) { set_error("no division point"); return LW_ERR_BAD_ARG; }
+    if (!points || (k && (!polys || !lens || !weights))) { set_error("null argument"); return LW_ERR_BAD_ARG; }
+    uint64_t n = 0;
+    for (uint32_t i = 0; i < k; i++) {
+        if (lens[i] && (!polys[i] || (device && !aligned16(polys[i])))) { set_error("polynomial %u: null or misaligned buffer", i); return LW_ERR_BAD_ARG; }
+        if (lens[i] > POLY_MAX_LEN) { set_error("polynomial %u: %zu coefficients", i, lens[i]); return LW_ERR_ALLOC; }
+        n = lens[i] > n ? lens[i] : n;
+    }
+    if (n > 1) {
+        if (!out) { set_error("null argument"); return LW_ERR_BAD_ARG; }
+        if (device) {
+            if (!aligned16(out)) { set_error("device buffers must be 16-byte aligned"); return LW_ERR_BAD_ARG; }
+            const uintptr_t b = (uintptr_t)out;
+            for (uint32_t i = 0; i < k; i++) {
+                const uintptr_t p = (uintptr_t)polys[i];
+                if (lens[i] && p < b + (n - 1) * 32 && b < p + lens[i] * 32) { set_error("the output overlaps polynomial %u", i); return LW_ERR_BAD_ARG; }
+            }
+        }
+    }
+    const char *W = (const char *)weights;
+    if (n <= 1) {   // constants and empty polynomials: an empty result; the values are the constants themselves
+        if (out_len) *out_len = 0;
+        if (!out_evals) return LW_OK;
+        memset(out_evals, 0, (size_t)k * m * 32);
+        if (n == 0) return LW_OK;
+        std::vector<uint64_t> c0((size_t)k * 4, 0);
+        if (device) {
+            Entry en(hip_stream);
+            if (en.rc) return en.rc;
+            for (uint32_t i = 0; i < k; i++)
+                if (lens[i]) LW_HIP_CHECK(hipMemcpyAsync(&c0[(size_t)i * 4], polys[i], 32, hipMemcpyDeviceToHost, en.stream), LW_ERR_LAUNCH);
+            LW_HIP_CHECK(hipStreamSynchronize(en.stream), LW_ERR_LAUNCH);
+        } else {
+            for (uint32_t i = 0; i < k; i++)
+                if (lens[i]) memcpy(&c0[(size_t)i * 4], polys[i], 32);
+        }
+        for (uint32_t i = 0; i < k; i++)
+            for (uint32_t j = 0; j < m; j++)
+                if (!elem_is_zero(W + ((size_t)i * m + j) * 32)) memcpy((char *)out_evals + ((size_t)i * m + j) * 32, &c0[(size_t)i * 4], 32);
+        return LW_OK;
+    }
+    Entry en(hip_stream);
+    if (en.rc) return en.rc;
+    Context &c = en.c;
+    hipStream_t s = en.stream;
+    std::vector<PolyRef> refs;
+    void *d_out = out;
+    if (device) {
+        refs.resize(k);
+        for (uint32_t i = 0; i < k; i++) refs[i] = PolyRef{polys[i], (uint64_t)lens[i]};
+    } else {
+        s = en.use_lane_stream();
+        if (!s) return en.rc;
+        int rc = stage_polys(c, polys, lens, k, refs, s);
+        if (rc) return rc;
+        if (c.host_io_b.ensure((n - 1) * 32)) return LW_ERR_ALLOC;
+        d_out = c.host_io_b.p;
+    }
+    int rc = field == LW_FIELD_STARK252 ? deep_locked<Stark252>(c, refs.data(), k, points, m, weights, d_out, out_len, out_evals, s)
+                                        : deep_locked<Fr381>(c, refs.data(), k, points, m, weights, d_out, out_len, out_evals, s);
+    if (rc || device) return rc;
+    LW_HIP_CHECK(hipMemcpyAsync(out, d_out, (n - 1) * 32, hipMemcpyDeviceToHost, s), LW_ERR_LAUNCH);
+    LW_HIP_CHECK(hipStreamSynchronize(s), LW_ERR_LAUNCH);
+    return LW_OK;
+}
+int lw_stark_deep_composition(lw_field_t field, const void *const *polys, const size_t *lens, uint32_t k, const void *points, uint32_t m,
+                              const void *weights, void *out_coeffs, size_t *out_len_or_null, void *out_evals_or_null) {
+    return deep_entry(field, polys, lens, k, points, m, weights, out_coeffs, out_len_or_null, out_evals_or_null, nullptr, false);
+}
+int lw_stark_deep_composition_device(lw_field_t field, const void *const *d_polys, const size_t *lens, uint32_t k, const void *points,
+                                     uint32_t m, const void *weights, void *d_out_coeffs, size_t *out_len_or_null,
+                                     void *out_evals_host_or_null, void *hip_stream) {
+    return deep_entry(field, d_polys, lens, k, points, m, weights, d_out_coeffs, out_len_or_null, out_evals_host_or_null, hip_stream, true);
 }
 
 static int kzg_entry(const lw_srs_t *srs, const void *const *polys, const size_t *lens, uint32_t k, const uint64_t *x, const uint64_t *ups,

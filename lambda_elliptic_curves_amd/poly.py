@@ -68,3 +68,49 @@ def ruffini_division_device(field, t_coeffs, n, x, t_quotient, stream=None, rema
                                                   C.c_void_p(t_quotient.data_ptr()),
                                                   rem.ctypes.data_as(C.c_void_p) if remainder else None, _stream(stream)))
     return rem if remainder else None
+
+
+def _weights(weights, k, m):
+    w = np.ascontiguousarray(weights, dtype=np.uint64).reshape(-1, 4)
+    if w.shape[0] != k * m:
+        from .errors import LengthMismatch
+        raise LengthMismatch(f"{w.shape[0]} weights for {k} polynomials and {m} points")
+    return w
+
+
+def deep_composition(field, polys, points, weights):
+    """sum_j quot(sum_k weights[k][j] * polys[k], points[j]) with quot = the Ruffini quotient by (X - points[j])
+    (compute_deep_composition_poly, provers/stark/src/prover.rs:643-714, over a K x M weight matrix).
+    -> (coefficients (n - 1, 4) with n the longest length, stripped length, evals (K, M, 4)); evals[k, j] = polys[k](points[j])
+    where the weight is non-zero and 0 elsewhere."""
+    ps = [_elems(p) for p in polys]
+    pts = _elems(points)
+    k, m = len(ps), pts.shape[0]
+    w = _weights(weights, k, m)
+    n = max((p.shape[0] for p in ps), default=0)
+    out = np.zeros((max(0, n - 1), 4), np.uint64)
+    evals = np.zeros((k, m, 4), np.uint64)
+    ptrs = (C.c_void_p * max(1, k))(*[p.ctypes.data for p in ps])
+    lens = (C.c_size_t * max(1, k))(*[p.shape[0] for p in ps])
+    ln = C.c_size_t(0)
+    check(L.lib().lw_stark_deep_composition(field.field, ptrs, lens, k, pts.ctypes.data_as(C.c_void_p), m,
+                                            w.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), C.byref(ln),
+                                            evals.ctypes.data_as(C.c_void_p)))
+    return out, ln.value, evals
+
+
+def deep_composition_device(field, t_polys, lens, points, weights, t_out, stream=None, evals=True):
+    """deep_composition() on device-resident torch tensors into t_out (n - 1 elements, overlapping no input).
+    evals=True -> (stripped length, evals (K, M, 4)); evals=False -> None, with nothing waited for."""
+    pts = _elems(points)
+    k, m = len(t_polys), pts.shape[0]
+    w = _weights(weights, k, m)
+    ptrs = (C.c_void_p * max(1, k))(*[t.data_ptr() for t in t_polys])
+    lnv = (C.c_size_t * max(1, k))(*[int(n) for n in lens])
+    ev = np.zeros((k, m, 4), np.uint64) if evals else None
+    ln = C.c_size_t(0)
+    check(L.lib().lw_stark_deep_composition_device(field.field, ptrs, lnv, k, pts.ctypes.data_as(C.c_void_p), m,
+                                                   w.ctypes.data_as(C.c_void_p), C.c_void_p(t_out.data_ptr()),
+                                                   C.byref(ln) if evals else None,
+                                                   ev.ctypes.data_as(C.c_void_p) if evals else None, _stream(stream)))
+    return (ln.value, ev) if evals else None

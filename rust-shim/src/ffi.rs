@@ -212,6 +212,14 @@ extern "C" {
     pub fn lw_kzg_open_batch_device(srs: *const lw_srs_t, d_polys: *const *const u64, lens: *const usize, k: u32, x: *const u64,
                                     upsilon: *const u64, out_proof_host: *mut c_void, out_evals_host_or_null: *mut u64,
                                     hip_stream: *mut c_void) -> c_int;
+    // ---- STARK DEEP composition polynomial (points and the k x m weight matrix on the host)
+    pub fn lw_stark_deep_composition(field: Field, polys: *const *const c_void, lens: *const usize, k: u32, points: *const c_void,
+                                     m: u32, weights: *const c_void, out_coeffs: *mut c_void, out_len_or_null: *mut usize,
+                                     out_evals_or_null: *mut c_void) -> c_int;
+    pub fn lw_stark_deep_composition_device(field: Field, d_polys: *const *const c_void, lens: *const usize, k: u32,
+                                            points: *const c_void, m: u32, weights: *const c_void, d_out_coeffs: *mut c_void,
+                                            out_len_or_null: *mut usize, out_evals_host_or_null: *mut c_void,
+                                            hip_stream: *mut c_void) -> c_int;
 }
 
 // The C structs above must keep the sizes the header gives them.

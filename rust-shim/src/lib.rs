@@ -353,6 +353,30 @@ pub fn ruffini_division(field: Field, coeffs: &[[u64; 4]], x: &[u64; 4]) -> Resu
     Ok((q, rem))
 }
 
+/// `compute_deep_composition_poly` (provers/stark/src/prover.rs:643-714) over a weight matrix:
+/// `sum_j quot(sum_k weights[k * m + j] * polys[k], points[j])`, `quot` the Ruffini quotient by `(X - points[j])`.
+/// Returns the coefficients with trailing zeros stripped (as `Polynomial::new` leaves them) and the `k x m` table of
+/// `polys[k](points[j])` (zero where the weight is zero).
+pub fn deep_composition(field: Field, polys: &[&[[u64; 4]]], points: &[[u64; 4]], weights: &[[u64; 4]])
+                        -> Result<(Vec<[u64; 4]>, Vec<[u64; 4]>), HipError> {
+    assert_eq!(weights.len(), polys.len() * points.len(), "weights: one element per (polynomial, point)");
+    let ptrs: Vec<*const c_void> = polys.iter().map(|p| p.as_ptr() as *const c_void).collect();
+    let lens: Vec<usize> = polys.iter().map(|p| p.len()).collect();
+    let n = lens.iter().copied().max().unwrap_or(0);
+    let mut out = vec![[0u64; 4]; n.saturating_sub(1)];
+    let mut evals = vec![[0u64; 4]; polys.len() * points.len()];
+    let mut len = 0usize;
+    // SAFETY: every pointer is valid for its length; `out` holds n - 1 elements, `evals` k x m.
+    let rc = unsafe {
+        ffi::lw_stark_deep_composition(field, ptrs.as_ptr(), lens.as_ptr(), polys.len() as u32, points.as_ptr() as *const c_void,
+                                       points.len() as u32, weights.as_ptr() as *const c_void, out.as_mut_ptr() as *mut c_void,
+                                       &mut len, evals.as_mut_ptr() as *mut c_void)
+    };
+    check(rc)?;
+    out.truncate(len);
+    Ok((out, evals))
+}
+
 impl Drop for Srs {
     fn drop(&mut self) {
         // SAFETY: the handle came from lw_hip_srs_create and is destroyed exactly once.
