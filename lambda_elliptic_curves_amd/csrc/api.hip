@@ -1141,7 +1141,9 @@ static int msm_entry(lw_curve_t curve, const uint64_t *scalars, size_t n_scalars
         scalars = (const uint64_t *)c.host_io_a.p;
         points = c.host_io_b.p;
     }
-    const int rc = msm_device(c, curve, scalars, points, n, out_point, s, mont, 0, h_points, limbs);
+    MsmCall call;
+    call.scalar_limbs = limbs;
+    const int rc = msm_device(c, curve, scalars, points, n, out_point, s, mont, call, h_points);
     note_msm(c, t0);
     return rc;
 }
@@ -1257,13 +1259,13 @@ int msm_srs_locked(Context &c, const lw_srs_t *srs, const uint64_t *d_scalars, s
     const auto t0 = Clock::now();
     // the shifted copies serve calls that use a good part of the set (KZG commits of shorter polynomials take a prefix:
     // below a quarter of it the 2^19 shared buckets would be mostly empty and the plain schedule on copy 0 is faster)
+    MsmCall call;
+    call.affine = 1;
     if (srs->fold_c && n >= srs->n / 4) {
-        c.msm_fold_c = srs->fold_c;
-        c.msm_fold_stride = srs->n;
+        call.fold_c = srs->fold_c;
+        call.fold_stride = srs->n;
     }
-    int rc = msm_device(c, srs->curve, d_scalars, srs->pts.p, n, out_point, stream, mont, 1);
-    c.msm_fold_c = 0;
-    c.msm_fold_stride = 0;
+    const int rc = msm_device(c, srs->curve, d_scalars, srs->pts.p, n, out_point, stream, mont, call);
     note_msm(c, t0);
     return rc;
 }

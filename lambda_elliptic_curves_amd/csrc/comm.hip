@@ -561,7 +561,7 @@ int lw_hip_msm_sharded_device(lw_curve_t curve, const uint64_t *d_scalars, const
         std::vector<uint4> mine_v((slot + 15) / 16), all_v((slot * G + 15) / 16), pts_v((pb * G + 15) / 16);
         char *mine = (char *)mine_v.data(), *all = (char *)all_v.data(), *pts = (char *)pts_v.data();
         memset(mine, 0, slot);
-        const int local_rc = msm_device(c, curve, d_scalars, d_points, n_local, mine + HDR, en.stream, 0, 0);
+        const int local_rc = msm_device(c, curve, d_scalars, d_points, n_local, mine + HDR, en.stream, 0, MsmCall{});
         const int64_t st = local_rc;
         memcpy(mine, &st, 8);
         if (local_rc) memset(mine + HDR, 0, pb);

@@ -1,6 +1,7 @@
 // Internal functions that one translation unit defines and others call: each is declared here once, with its default
 // arguments, under the file that defines it.  The exported C ABI is include/lw_hip.h.
 #pragma once
+#include <functional>
 #include "context.h"
 
 namespace lw {
@@ -64,9 +65,22 @@ int stripped_length_device(const void *d_elems, uint64_t n, uint64_t *d_len, hip
 void comm_release(Context &c);
 
 // ---- msm.hip
+// What is per call in an MSM: handed from the entry points through msm_device to the curve's runner (msm_core.cuh).
+struct MsmCall {
+    int affine = 0;                      // d_points are affine rows made by normalize (a pre-normalised SRS)
+    hipEvent_t points_ready = nullptr;   // recorded on a side stream once d_points is complete; joined before the first accumulation
+    uint32_t scalar_limbs = 4;           // the scalars are n x scalar_limbs u64 (1 .. 8)
+    // folded SRS (lw_hip_srs_*): the point set holds window-shifted copies, d_points[w * fold_stride + i] = 2^(fold_c w) * P_i,
+    // and all windows share one bucket set (msm_core.cuh build_fold); 0: a single copy
+    uint32_t fold_c = 0;
+    uint64_t fold_stride = 0;
+    // host-buffer calls: run right after the sort of the scalars is enqueued (upload of the points and their normalisation
+    // on the side streams, so that the sort runs under the upload)
+    std::function<int()> after_sort;
+};
+// call.points_ready and call.after_sort are msm_device's own; h_points: the points are still in host memory
 int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const void *d_points, size_t n, void *out_host,
-               hipStream_t stream, int scalars_montgomery, int affine_points, const void *h_points = nullptr,
-               uint32_t scalar_limbs = 4);
+               hipStream_t stream, int scalars_montgomery, MsmCall call, const void *h_points = nullptr);
 int msm_sum_points_host(lw_curve_t curve, const void *pts, size_t n, void *out);
 uint32_t msm_window_bits_for(size_t n);   // the single-GPU window rule
 int msm_shard_accumulate(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const void *d_points, size_t n, uint32_t cbits, hipStream_t s,
@@ -79,27 +93,53 @@ uint32_t msm_ch(uint64_t items);       // max points per accumulate work-item (a
 uint64_t msm_quad_max_lanes();          // LW_HIP_MSM_QUAD: levels of the bucket reduce with at most this many lanes (8 per group) spread each addition over a quad; 0 = never, ~0 = not set
 uint64_t msm_accumulate_quad_max_lanes();   // LW_HIP_MSM_ACCQ: accumulate launches of projective rows with at most this many lanes (4 per piece) use the quad kernel
 
+struct Carver {   // bump allocator over the context workspace; with base == nullptr (dry run) only the sizes are added up
+    char *base;
+    size_t cap, used = 0;
+    void *take(size_t bytes) {
+        used = (used + 255) & ~(size_t)255;
+        void *p = base ? base + used : nullptr;
+        used += bytes;
+        return p;
+    }
+    // true once a real (non-dry) carve-out has run past the workspace the dry run sized: checked before every launch
+    // that would touch the new pointers
+    bool overrun() const { return base && used > cap; }
+};
+#define LW_MSM_WS_CHECK(cv)                                                                                          \
+    do {                                                                                                             \
+        if ((cv).overrun()) {                                                                                        \
+            set_error("internal: MSM workspace of %zu bytes is too small (%zu needed so far)", (cv).cap, (cv).used); \
+            return LW_ERR_ALLOC;                                                                                     \
+        }                                                                                                            \
+    } while (0)
+
 // host launchers for the curve-independent kernels
-uint32_t msm_sort_coarse_bins(uint32_t c, uint32_t W, uint64_t n);
 uint32_t msm_max_window_bits();
 uint64_t msm_sort_padded_points(uint64_t n);
 int msm_launch_digits(Context &c, const uint32_t *scalars, uint64_t n, uint32_t cb, uint32_t W, uint32_t *dig, hipStream_t s,
                       uint32_t scalar_limbs);   // scalars: n x scalar_limbs u64, 1 .. 8
-void msm_launch_sort(Context &c, const uint32_t *dig, uint64_t n, uint32_t cb, uint32_t W, uint32_t *coarse_cnt,
-                     uint32_t *coarse_off, uint32_t *coarse_cursor, uint64_t *items, uint32_t *sorted, uint32_t *off, uint32_t K,
-                     uint32_t *maxlen, uint32_t *scan_tmp, uint32_t *sub_off, uint32_t *key_cnt, uint32_t *key_cursor, uint64_t fold_stride,
-                     uint64_t win0, hipStream_t s);
+// The arrays of one sort over all W windows of an MSM: NW bucket sets (one per window, or one for all: folded SRS) of
+// 2^(c-1) keys each, K keys and CB coarse bins in all.
+struct MsmSortBufs {
+    uint32_t NW = 0, K = 0, CB = 0;
+    uint32_t *coarse_cnt = nullptr, *coarse_cursor = nullptr, *maxlen_d = nullptr, *key_cnt = nullptr, *key_cursor = nullptr;
+    uint32_t *coarse_off = nullptr, *sub_off = nullptr, *off = nullptr, *scan_tmp = nullptr, *sorted = nullptr, *order_tmp = nullptr;
+    uint64_t *items = nullptr;
+};
+// carve-outs of the sort of n scalars into W windows of `cbits` bits
+int msm_sort_carve(MsmSortBufs &b, uint64_t n, uint32_t cbits, uint32_t W, uint64_t fold_stride, Carver &cv);
+// sort of the digit matrix (W rows of msm_sort_padded_points(n) u32) on stream `s`: b.sorted holds (sign, point index)
+// by key and b.off the K + 1 key offsets; the longest bucket lands in b.maxlen_d and in *maxlen_h once `s` gets there
+int msm_launch_sort(Context &c, const MsmSortBufs &b, const uint32_t *dig, uint64_t n, uint32_t cbits, uint32_t W, uint64_t fold_stride,
+                    volatile uint32_t *maxlen_h, hipStream_t s);
 void msm_launch_scan(const uint32_t *in, uint32_t *out, uint32_t K, int mode, uint32_t *maxlen, uint32_t *scratch, hipStream_t s);
-size_t msm_scan_scratch_bytes(uint32_t K);
 void msm_launch_piece_order(Context &c, const uint32_t *seg_off, const uint32_t *out_off, uint32_t K, uint32_t P, uint32_t *order_tmp,
                             uint32_t *perm_t, uint32_t *perm_key, hipStream_t s);
-size_t msm_order_tmp_bytes();
 
-// ---- msm_<curve>.hip (LW_MSM_INSTANTIATE in msm_core.cuh): the per-curve MSM operations
+// ---- msm_<curve>.hip (msm_curve_ops<C>() in msm_core.cuh): the per-curve MSM operations
 struct MsmCurveOps {
-    // affine: d_points are affine rows made by normalize; points_ready: an event the accumulation waits for (or nullptr)
-    int (*run)(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_points, size_t n, void *out, int affine,
-               hipEvent_t points_ready, uint32_t scalar_limbs);
+    int (*run)(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_points, size_t n, void *out, const MsmCall &call);
     int (*normalize)(Context &c, hipStream_t s, const void *d_in, size_t n, void *d_out);
     size_t (*affine_bytes)(size_t n);   // bytes of the device-resident affine form of n points (rows may be padded, ec.cuh aff_stride)
     int (*fold_build)(Context &c, hipStream_t s, void *d_rows, size_t n, uint32_t cbits);

@@ -21,6 +21,11 @@
 //                  (pippenger.rs:101), on the host with the same limb code, and normalised to (x/z : y/z : 1).
 // lw_hip_srs_* handles of >= 2^19 points keep window-shifted copies of the points, which lets all windows share one
 // bucket set (msm_core.cuh build_fold).
+// This file: everything that does not depend on the curve — scalar preparation, digits, the sort with the layout of its
+// buffers (msm_sort_carve, msm_launch_sort), the scans and the piece order, the tuning switches, and msm_device, which
+// arranges upload and normalisation around the curve's runner.  msm_core.cuh: the kernels that add points and
+// MsmRunner<C> (workspace plan, accumulate rounds, bucket reduce, host fold), instantiated per curve by msm_<curve>.hip.
+#include <assert.h>
 #include <stdlib.h>
 #include "msm_core.cuh"
 
@@ -263,7 +268,7 @@ __global__ __launch_bounds__(SORT_THREADS) void msm_coarse_count_kernel(const ui
 }
 template <class ITEM>
 __global__ __launch_bounds__(SORT_THREADS) void msm_coarse_kernel(const uint32_t *dig, uint64_t n_pad, uint32_t hb, uint32_t fine_bits,
-                                                                 uint64_t idx_stride, uint32_t folded, uint32_t win0, const uint32_t *coarse_off,
+                                                                 uint64_t idx_stride, uint32_t folded, const uint32_t *coarse_off,
                                                                  uint32_t *coarse_cursor, ItemMem<ITEM> items) {
     __shared__ uint32_t h[SORT_MAX_COARSE + 1];   // + dummy slot for zero digits
     __shared__ uint32_t base[SORT_MAX_COARSE];    // next free slot of this workgroup's run per bin
@@ -273,7 +278,7 @@ __global__ __launch_bounds__(SORT_THREADS) void msm_coarse_kernel(const uint32_t
     __shared__ uint16_t bbin[COARSE_CHUNK];       // bin of every staged item
     const uint32_t NB = 1u << hb, w = blockIdx.y, tid = threadIdx.x;
     const uint32_t bin0 = folded ? 0u : (w << hb);   // folded: every window sorts into the one shared bucket set
-    const uint64_t idx0 = (uint64_t)(win0 + w) * idx_stride;   // and its items point at the window's own copy of the points
+    const uint64_t idx0 = (uint64_t)w * idx_stride;   // and its items point at the window's own copy of the points
     for (uint32_t b = tid; b <= SORT_MAX_COARSE; b += SORT_THREADS) h[b] = 0;
     __syncthreads();
     const uint64_t q0 = (uint64_t)blockIdx.x * (SORT_PPB / 4);
@@ -350,11 +355,7 @@ constexpr int FINE_PER = FINE_CHUNK / SORT_THREADS;
 __device__ __forceinline__ bool fine_locate(const uint32_t *coarse_off, const uint32_t *sub_off, uint32_t CB, uint32_t blk,
                                             uint32_t &bin, uint32_t &i0, uint32_t &i1) {
     if (blk >= sub_off[CB]) return false;
-    uint32_t lo = 0, hi = CB;   // largest bin with sub_off[bin] <= blk (sub-blocks are counted with at least one per bin)
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (sub_off[mid] <= blk) lo = mid; else hi = mid;
-    }
+    const uint32_t lo = msm_last_le(sub_off, CB, blk);   // sub-blocks are counted with at least one per bin
     bin = lo;
     const uint32_t b0 = coarse_off[lo], b1 = coarse_off[lo + 1];
     i0 = b0 + (blk - sub_off[lo]) * FINE_SUB;
@@ -549,14 +550,6 @@ __global__ __launch_bounds__(SCAN_BLOCK) void msm_scan_final_kernel(const uint32
 // pass 0 counts the lengths, pass 1 (same walk) scatters: perm_t[rank] = piece id, perm_key[rank] = its key.
 constexpr uint32_t ORDER_BINS = 130;    // lengths 0 .. 128 (MSM_CH <= 128) + slack
 constexpr uint32_t ORDER_PER = 8;       // consecutive pieces per work-item
-__device__ __forceinline__ uint32_t order_first_key(const uint32_t *out_off, uint32_t K, uint32_t t) {
-    uint32_t lo = 0, hi = K;   // largest key with out_off[key] <= t
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (out_off[mid] <= t) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 template <bool SCATTER>
 __global__ __launch_bounds__(SORT_THREADS) void msm_piece_order_kernel(const uint32_t *seg_off, const uint32_t *out_off, uint32_t K,
                                                                       uint32_t P, uint32_t *bin_cnt, uint32_t *bin_cursor,
@@ -569,7 +562,7 @@ __global__ __launch_bounds__(SORT_THREADS) void msm_piece_order_kernel(const uin
     uint32_t key = 0, o0 = 0, o1 = 0, s0 = 0, len = 0;
     uint32_t bin[ORDER_PER], rk[ORDER_PER], kk[ORDER_PER];
     if (t0 < P && out_off) {
-        key = order_first_key(out_off, K, t0);
+        key = msm_last_le(out_off, K, t0);
         o0 = out_off[key]; o1 = out_off[key + 1]; s0 = seg_off[key]; len = seg_off[key + 1] - s0;
     }
 #pragma unroll
@@ -584,7 +577,7 @@ __global__ __launch_bounds__(SORT_THREADS) void msm_piece_order_kernel(const uin
                 o0 = o1; o1 = out_off[key + 1]; s0 = seg_off[key]; len = seg_off[key + 1] - s0;
             }
             const uint32_t np = o1 - o0, j = t - o0;
-            L = (uint32_t)(((uint64_t)len * (j + 1)) / np) - (uint32_t)(((uint64_t)len * j) / np);
+            L = msm_share(len, j + 1, np) - msm_share(len, j, np);
             kk[q] = key;
         } else {
             L = seg_off[t + 1] - seg_off[t];
@@ -615,7 +608,7 @@ __global__ __launch_bounds__(SORT_THREADS) void msm_piece_order_kernel(const uin
             }
     }
 }
-// order_tmp: 2 * ORDER_BINS u32
+// order_tmp: 2 * ORDER_BINS u32 (msm_sort_carve)
 void msm_launch_piece_order(Context &c, const uint32_t *seg_off, const uint32_t *out_off, uint32_t K, uint32_t P, uint32_t *order_tmp,
                             uint32_t *perm_t, uint32_t *perm_key, hipStream_t s) {
     (void)hipMemsetAsync(order_tmp, 0, 8 * ORDER_BINS, s);
@@ -627,7 +620,6 @@ void msm_launch_piece_order(Context &c, const uint32_t *seg_off, const uint32_t 
                        order_tmp + ORDER_BINS, perm_t, perm_key);
     c.prof_end("msm_piece_order_kernel", pe, s);
 }
-size_t msm_order_tmp_bytes() { return 8 * ORDER_BINS; }
 // Max points per accumulate work-item.  With pieces handed out in order of length the cut only has to bound the longest
 // dependent chain: long pieces (64) save partial sums when there is plenty of work (2^24, c = 20: 49.1 ms against 50.0 at
 // 32); when the items do not fill the machine a work-item's chain IS the kernel time, so short pieces and one more
@@ -642,7 +634,6 @@ uint32_t msm_ch(uint64_t items) {
     return items < (1ull << 20) ? 8u : items < (1ull << 22) ? 16u : items < (1ull << 27) ? 32u : 64u;
 }
 
-uint32_t msm_sort_coarse_bins(uint32_t c, uint32_t W, uint64_t n) { return W << sort_split(c, n).hb; }   // folded: W = 1, n = W * stride
 uint32_t msm_max_window_bits() { return MSM_MAX_C; }
 // row length of the digit matrix: a multiple of 8 (uint4 loads) that is not a power of two, so that the W rows a wave
 // writes do not all fall on the same memory channel
@@ -665,54 +656,73 @@ int msm_launch_digits(Context &c, const uint32_t *scalars, uint64_t n, uint32_t 
     LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
     return LW_OK;
 }
-// `dig`: row 0 = the first of the W windows sorted here; win0: that window's number in the MSM
+static size_t scan_scratch_bytes(uint32_t K) { return 8 * (size_t)((K + SCAN_TILE - 1) / SCAN_TILE) + 256; }
+// fold_stride != 0 (lw_hip_srs_* with window-shifted copies of the points): one bucket set of 2^(cbits-1) keys for all W
+// windows; the item of window w and scalar i points at row w * fold_stride + i
+static SortSplit sort_split_for(uint64_t n, uint32_t cbits, uint32_t W, uint64_t fold_stride) {
+    return sort_split(cbits, fold_stride ? (uint64_t)W * fold_stride : n);
+}
+int msm_sort_carve(MsmSortBufs &b, uint64_t n, uint32_t cbits, uint32_t W, uint64_t fold_stride, Carver &cv) {
+    b.NW = fold_stride ? 1u : W;          // bucket sets: one per window, or one for all (folded SRS)
+    b.K = b.NW << (cbits - 1);            // signed digits: 2^(c-1) buckets per window, bucket j = multiplier j + 1
+    b.CB = b.NW << sort_split_for(n, cbits, W, fold_stride).hb;
+    b.coarse_cnt = (uint32_t *)cv.take(4 * (size_t)(b.CB + 1));
+    b.coarse_cursor = (uint32_t *)cv.take(4 * (size_t)(b.CB + 1));
+    b.maxlen_d = (uint32_t *)cv.take(256);
+    b.key_cnt = (uint32_t *)cv.take(4 * (size_t)b.K);
+    b.key_cursor = (uint32_t *)cv.take(4 * (size_t)b.K);
+    b.coarse_off = (uint32_t *)cv.take(4 * (size_t)(b.CB + 1));
+    // msm_launch_sort clears [coarse_cnt, coarse_off) with one memset: the five arrays that start from zero, in one run
+    assert(!cv.base || (b.coarse_cnt + b.CB + 1 <= b.coarse_cursor && b.coarse_cursor + b.CB + 1 <= b.maxlen_d && b.maxlen_d + 2 <= b.key_cnt &&
+                        b.key_cnt + b.K <= b.key_cursor && b.key_cursor + b.K <= b.coarse_off));
+    b.sub_off = (uint32_t *)cv.take(4 * (size_t)(b.CB + 1));
+    b.off = (uint32_t *)cv.take(4 * (size_t)(b.K + 1));
+    b.scan_tmp = (uint32_t *)cv.take(scan_scratch_bytes(b.K));
+    b.sorted = (uint32_t *)cv.take(4 * n * W);
+    b.items = (uint64_t *)cv.take(8 * n * W);
+    b.order_tmp = (uint32_t *)cv.take(8 * ORDER_BINS);
+    LW_MSM_WS_CHECK(cv);
+    return LW_OK;
+}
 template <class ITEM>
-static void launch_sort_t(Context &c, uint64_t n, uint32_t cb, uint32_t W, const SortSplit &sp, uint32_t CB,
-                          const uint32_t *dig, uint32_t *coarse_cnt, uint32_t *coarse_off, uint32_t *coarse_cursor, ItemMem<ITEM> items,
-                          uint32_t *sorted, uint32_t *off, uint32_t K, uint32_t *maxlen, uint32_t *scan_tmp, uint32_t *sub_off,
-                          uint32_t *key_cnt, uint32_t *key_cursor, uint64_t fold_stride, uint32_t win0, hipStream_t s) {
+static void launch_sort_t(Context &c, const MsmSortBufs &b, const uint32_t *dig, uint64_t n, uint32_t W, const SortSplit &sp,
+                          uint64_t fold_stride, ItemMem<ITEM> items, hipStream_t s) {
     const uint64_t n_pad = msm_sort_padded_points(n);
     const uint32_t folded = fold_stride != 0;
-    const uint32_t fine = sp.fine, hb = sp.hb;
+    const uint32_t fine = sp.fine, hb = sp.hb, CB = b.CB;
+    uint32_t *coarse_max = b.maxlen_d + 1;   // the scans of the coarse level leave their maximum here; nothing reads it
     const dim3 grid((uint32_t)((n_pad + SORT_PPB - 1) / SORT_PPB), W);
     hipEvent_t pe = c.prof_begin(s);
-    hipLaunchKernelGGL(msm_coarse_count_kernel, grid, dim3(SORT_THREADS), 0, s, (const uint32_t *)dig, n_pad, hb, fine, folded, coarse_cnt);
+    hipLaunchKernelGGL(msm_coarse_count_kernel, grid, dim3(SORT_THREADS), 0, s, dig, n_pad, hb, fine, folded, b.coarse_cnt);
     c.prof_end("msm_coarse_kernel<count>", pe, s);
-    msm_launch_scan(coarse_cnt, coarse_off, CB, 0, maxlen + 1, scan_tmp, s);   // maxlen[1]: coarse max (unused)
+    msm_launch_scan(b.coarse_cnt, b.coarse_off, CB, 0, coarse_max, b.scan_tmp, s);
     pe = c.prof_begin(s);
-    hipLaunchKernelGGL((msm_coarse_kernel<ITEM>), grid, dim3(SORT_THREADS), 0, s, (const uint32_t *)dig, n_pad, hb, fine, fold_stride, folded,
-                       win0, (const uint32_t *)coarse_off, coarse_cursor, items);
+    hipLaunchKernelGGL((msm_coarse_kernel<ITEM>), grid, dim3(SORT_THREADS), 0, s, dig, n_pad, hb, fine, fold_stride, folded,
+                       (const uint32_t *)b.coarse_off, b.coarse_cursor, items);
     c.prof_end("msm_coarse_kernel<scatter>", pe, s);
     // level B: sub-blocks of the coarse bins -> key counts -> key offsets (+ the longest bucket) -> sorted index list
-    msm_launch_scan(coarse_off, sub_off, CB, (int)FINE_SUB, maxlen + 1, scan_tmp, s);
+    msm_launch_scan(b.coarse_off, b.sub_off, CB, (int)FINE_SUB, coarse_max, b.scan_tmp, s);
     const uint32_t UB = CB + (uint32_t)(((uint64_t)n * W + FINE_SUB - 1) / FINE_SUB);   // >= sub_off[CB]; surplus workgroups exit
     pe = c.prof_begin(s);
-    hipLaunchKernelGGL((msm_fine_count_kernel<ITEM>), dim3(UB), dim3(SORT_THREADS), 0, s, items, (const uint32_t *)coarse_off,
-                       (const uint32_t *)sub_off, CB, fine, key_cnt);
+    hipLaunchKernelGGL((msm_fine_count_kernel<ITEM>), dim3(UB), dim3(SORT_THREADS), 0, s, items, (const uint32_t *)b.coarse_off,
+                       (const uint32_t *)b.sub_off, CB, fine, b.key_cnt);
     c.prof_end("msm_fine_count_kernel", pe, s);
-    msm_launch_scan(key_cnt, off, K, 0, maxlen, scan_tmp, s);
+    msm_launch_scan(b.key_cnt, b.off, b.K, 0, b.maxlen_d, b.scan_tmp, s);
     pe = c.prof_begin(s);
-    hipLaunchKernelGGL((msm_fine_kernel<ITEM>), dim3(UB), dim3(SORT_THREADS), 0, s, items, (const uint32_t *)coarse_off,
-                       (const uint32_t *)sub_off, CB, fine, (const uint32_t *)off, key_cursor, sorted);
+    hipLaunchKernelGGL((msm_fine_kernel<ITEM>), dim3(UB), dim3(SORT_THREADS), 0, s, items, (const uint32_t *)b.coarse_off,
+                       (const uint32_t *)b.sub_off, CB, fine, (const uint32_t *)b.off, b.key_cursor, b.sorted);
     c.prof_end("msm_fine_kernel", pe, s);
 }
-// dig: W rows of padded(n) u32; coarse_cnt / coarse_cursor: CB + 1 zeroed u32 each; coarse_off, sub_off: CB + 1; items: n*W u64;
-// key_cnt / key_cursor: K zeroed u32 each; off: K + 1; maxlen: zeroed.  K = W << (cb - 1).
-void msm_launch_sort(Context &c, const uint32_t *dig, uint64_t n, uint32_t cb, uint32_t W, uint32_t *coarse_cnt,
-                     uint32_t *coarse_off, uint32_t *coarse_cursor, uint64_t *items, uint32_t *sorted, uint32_t *off, uint32_t K,
-                     uint32_t *maxlen, uint32_t *scan_tmp, uint32_t *sub_off, uint32_t *key_cnt, uint32_t *key_cursor, uint64_t fold_stride,
-                     uint64_t win0, hipStream_t s) {
-    // fold_stride != 0 (lw_hip_srs_* with window-shifted copies of the points): one bucket set of 2^(cb-1) keys for all W
-    // windows; the item of window w and scalar i points at row w * fold_stride + i
-    const SortSplit sp = sort_split(cb, fold_stride ? (uint64_t)W * fold_stride : n);
-    const uint32_t CB = (fold_stride ? 1u : W) << sp.hb;
-    if (!sp.wide)
-        launch_sort_t<uint32_t>(c, n, cb, W, sp, CB, dig, coarse_cnt, coarse_off, coarse_cursor, ItemMem<uint32_t>{(uint32_t *)items},
-                                sorted, off, K, maxlen, scan_tmp, sub_off, key_cnt, key_cursor, fold_stride, (uint32_t)win0, s);
+int msm_launch_sort(Context &c, const MsmSortBufs &b, const uint32_t *dig, uint64_t n, uint32_t cbits, uint32_t W, uint64_t fold_stride,
+                    volatile uint32_t *maxlen_h, hipStream_t s) {
+    LW_HIP_CHECK(hipMemsetAsync(b.coarse_cnt, 0, (size_t)((char *)b.coarse_off - (char *)b.coarse_cnt), s), LW_ERR_LAUNCH);
+    const SortSplit sp = sort_split_for(n, cbits, W, fold_stride);
+    if (!sp.wide) launch_sort_t<uint32_t>(c, b, dig, n, W, sp, fold_stride, ItemMem<uint32_t>{(uint32_t *)b.items}, s);
     else   // the 8 * n * W bytes of `items` hold n * W entries followed by n * W fine keys
-        launch_sort_t<uint64_t>(c, n, cb, W, sp, CB, dig, coarse_cnt, coarse_off, coarse_cursor,
-                                ItemMem<uint64_t>{(uint32_t *)items, (uint16_t *)((uint32_t *)items + n * W)}, sorted, off, K, maxlen,
-                                scan_tmp, sub_off, key_cnt, key_cursor, fold_stride, (uint32_t)win0, s);
+        launch_sort_t<uint64_t>(c, b, dig, n, W, sp, fold_stride,
+                                ItemMem<uint64_t>{(uint32_t *)b.items, (uint16_t *)((uint32_t *)b.items + n * W)}, s);
+    LW_HIP_CHECK(hipMemcpyAsync((void *)maxlen_h, b.maxlen_d, 4, hipMemcpyDeviceToHost, s), LW_ERR_LAUNCH);
+    return LW_OK;
 }
 // scratch: 2 * ceil(K / SCAN_TILE) u32 (block sums, block maxima)
 void msm_launch_scan(const uint32_t *in, uint32_t *out, uint32_t K, int mode, uint32_t *maxlen, uint32_t *scratch, hipStream_t s) {
@@ -722,7 +732,6 @@ void msm_launch_scan(const uint32_t *in, uint32_t *out, uint32_t K, int mode, ui
     hipLaunchKernelGGL(msm_scan_top_kernel, dim3(1), dim3(1024), 0, s, bsum, bmax, nblocks, out, K, maxlen);
     hipLaunchKernelGGL(msm_scan_final_kernel, dim3(nblocks), dim3(SCAN_BLOCK), 0, s, in, out, K, mode, bsum);
 }
-size_t msm_scan_scratch_bytes(uint32_t K) { return 8 * (size_t)((K + SCAN_TILE - 1) / SCAN_TILE) + 256; }
 
 uint64_t msm_quad_max_lanes() {   // tuning: LW_HIP_MSM_QUAD = log2 of the widest level (in lanes) that takes the quad kernels, 0 = none
     const char *e = tuning_env("LW_HIP_MSM_QUAD");   // read per call so that a test can sweep it
@@ -756,7 +765,6 @@ static int msm_normalize_min_log2(lw_curve_t curve) {
     }
 }
 
-// affine_points: d_points are affine pairs produced by the curve's normalize (2 field elements per row)
 // The context's side stream (MSM: normalisation beside the sort; sharded NTT: exchanges beside the kernels).
 int ensure_aux_stream(Context &c) {
     if (c.aux_stream) return LW_OK;
@@ -778,14 +786,15 @@ int ensure_aux_stream(Context &c) {
     return LW_OK;
 }
 
-// scalar_limbs: the scalars are n x scalar_limbs u64 (1 .. 8); the Montgomery and affine (SRS) forms take 4 only.
+// call: affine, scalar_limbs and the fold of the point set, from the entry point; the Montgomery and affine (SRS) forms take
+// 4-limb scalars only.
 int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const void *d_points, size_t n, void *out_host,
-               hipStream_t stream, int scalars_montgomery, int affine_points, const void *h_points, uint32_t scalar_limbs) {
+               hipStream_t stream, int scalars_montgomery, MsmCall call, const void *h_points) {
     // h_points (host-buffer entry points): the points are still in host memory and d_points is the device buffer they go to.
-    // The sort needs the scalars only, so it is enqueued first and the upload runs under it (msm_after_sort below);
+    // The sort needs the scalars only, so it is enqueued first and the upload runs under it (call.after_sort below);
     // without a normalisation the points are needed by the first kernel after the sort and go up front.
-    if (scalar_limbs < 1 || scalar_limbs > 8 || ((scalars_montgomery || affine_points) && scalar_limbs != 4)) {
-        set_error("MSM scalars of %u limbs", scalar_limbs);
+    if (call.scalar_limbs < 1 || call.scalar_limbs > 8 || ((scalars_montgomery || call.affine) && call.scalar_limbs != 4)) {
+        set_error("MSM scalars of %u limbs", call.scalar_limbs);
         return LW_ERR_BAD_ARG;
     }
     const MsmCurveOps *ops = msm_ops(curve);
@@ -804,8 +813,7 @@ int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const vo
     // Large projective inputs are normalised first (batch inversion, ~3 ms at 2^24) so that the accumulation can use
     // the mixed addition, one-line gathers and — BLS12-381 G1, BN254 G2 — the cheaper isomorphic curve (~10 ms less at
     // 2^24); below the per-group threshold (msm_normalize_min_log2) the conversion costs more than it saves.
-    hipEvent_t join = nullptr;
-    if (!affine_points && n >= ((size_t)1 << msm_normalize_min_log2(curve))) {
+    if (!call.affine && n >= ((size_t)1 << msm_normalize_min_log2(curve))) {
         const size_t aff_bytes = ops->affine_bytes(n);
         if (c.msm_affine.ensure(aff_bytes)) return LW_ERR_ALLOC;
         // The normalisation reads only the points and the bucket sort only the scalars, so the normalisation runs on a
@@ -819,7 +827,7 @@ int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const vo
             const void *src = d_points;
             // in chunks of 2^20 points: chunk k is normalised (second side stream) while chunk k + 1 is on the bus, so that what
             // is left after the last byte arrives is one chunk's normalisation, not the whole set's
-            c.msm_after_sort = [&c, ops, src, h_points, n, pbytes]() -> int {
+            call.after_sort = [&c, ops, src, h_points, n, pbytes]() -> int {
                 const size_t CHUNK = (size_t)1 << 20, astride = ops->affine_bytes(1);
                 hipEvent_t ev = nullptr;
                 if (!c.sync_pool.empty()) { ev = c.sync_pool.back(); c.sync_pool.pop_back(); }
@@ -850,15 +858,14 @@ int msm_device(Context &c, lw_curve_t curve, const uint64_t *d_scalars, const vo
             if (rc) return rc;
             LW_HIP_CHECK(hipEventRecord(c.aux_join, c.aux_stream), LW_ERR_LAUNCH);
         }
-        join = c.aux_join;
+        call.points_ready = c.aux_join;
         d_points = c.msm_affine.p;
-        affine_points = 1;
+        call.affine = 1;
     }
     if (upload_pending)   // no normalisation: the accumulation reads the rows as they are
         LW_HIP_CHECK(hipMemcpyAsync((void *)d_points, h_points, n * pbytes, hipMemcpyHostToDevice, stream), LW_ERR_LAUNCH);
-    const int rc = ops->run(c, stream, d_scalars, d_points, n, out_host, affine_points, join, scalar_limbs);
-    c.msm_after_sort = nullptr;                                  // (a run that failed before its sort never took it)
-    if (rc && join) {   // do not leave the side streams running into a failed call's buffers
+    const int rc = ops->run(c, stream, d_scalars, d_points, n, out_host, call);
+    if (rc && call.points_ready) {   // do not leave the side streams running into a failed call's buffers
         (void)hipStreamSynchronize(c.aux_stream);
         if (c.aux_hi) (void)hipStreamSynchronize(c.aux_hi);
     }

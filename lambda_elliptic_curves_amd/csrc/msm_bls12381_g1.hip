@@ -2,5 +2,5 @@
 #include "msm_core.cuh"
 
 namespace lw {
-LW_MSM_INSTANTIATE(Bls12381G1, bls12381_g1)
+MsmCurveOps msm_ops_bls12381_g1 = msm_curve_ops<Bls12381G1>();
 }  // namespace lw

@@ -2,5 +2,5 @@
 #include "msm_core.cuh"
 
 namespace lw {
-LW_MSM_INSTANTIATE(Bls12381G2, bls12381_g2)
+MsmCurveOps msm_ops_bls12381_g2 = msm_curve_ops<Bls12381G2>();
 }  // namespace lw

@@ -2,5 +2,5 @@
 #include "msm_core.cuh"
 
 namespace lw {
-LW_MSM_INSTANTIATE(Bn254G1, bn254_g1)
+MsmCurveOps msm_ops_bn254_g1 = msm_curve_ops<Bn254G1>();
 }  // namespace lw

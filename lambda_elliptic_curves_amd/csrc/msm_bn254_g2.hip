@@ -2,5 +2,5 @@
 #include "msm_core.cuh"
 
 namespace lw {
-LW_MSM_INSTANTIATE(Bn254G2, bn254_g2)
+MsmCurveOps msm_ops_bn254_g2 = msm_curve_ops<Bn254G2>();
 }  // namespace lw

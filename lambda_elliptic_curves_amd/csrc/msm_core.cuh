@@ -1,5 +1,6 @@
-// Curve-generic part of the Pippenger MSM (see msm.hip for the schedule); instantiated once per curve in its own
-// translation unit so the four groups compile in parallel.
+// Curve-generic part of the Pippenger MSM (see msm.hip for the schedule, the sort and msm_device): the kernels that add
+// points, and MsmRunner<C> — workspace plan, accumulate rounds, bucket reduce, host fold.  msm_curve_ops<C>() instantiates
+// it once per curve in that curve's own translation unit (msm_<curve>.hip), so the four groups compile in parallel.
 #pragma once
 #include <stdlib.h>
 #include <algorithm>
@@ -13,6 +14,56 @@ constexpr int MSM_THREADS = 128;
 // log2 buckets per running-sum group (8 buckets; 16 -> 8 saved 1 ms of dependent-add latency per MSM, 4 is no better)
 constexpr uint32_t MSM_G_LOG = 3;
 
+// ---------------------------------------------------------------- pieces of a bucket (also used by the sort, msm.hip)
+// largest k in [0, K) with off[k] <= t (off ascending, off[0] <= t)
+__device__ __forceinline__ uint32_t msm_last_le(const uint32_t *off, uint32_t K, uint32_t t) {
+    uint32_t lo = 0, hi = K;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (off[mid] <= t) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// A key's len items are cut into np pieces of equal length (+-1), so the lanes of a wave run the same number of
+// additions instead of full pieces next to a short remainder: piece j is [msm_share(j), msm_share(j + 1)).
+__device__ __forceinline__ uint32_t msm_share(uint32_t len, uint32_t j, uint32_t np) { return (uint32_t)(((uint64_t)len * j) / np); }
+
+// Work-item r of an accumulate launch sums the items [b, e) of ONE key into row `slot` of pout (to_pout) or of the bucket
+// array.
+//   out_off != nullptr: t is a (key, piece) pair (key from perm_key or by binary search in out_off).  A key with ONE piece
+//                       is finished by this work-item: its sum goes to buckets[key]; the pieces of a longer key go to
+//                       pout[t] and are summed by the next round.
+//   out_off == nullptr: every key has <= CH items; t is the key; result (identity when the key is empty) -> buckets[key],
+//                       the dense bucket array.
+// key_len: the items of the whole key.  The kernels' early-out of later rounds (a key that is a single partial) tests it
+// themselves: decided in here, the compiler keeps the decision as a lane mask and every accumulate kernel needs 2 - 4 more SGPRs.
+struct MsmPiece {
+    uint32_t b, e, key_len;
+    size_t slot;
+    bool to_pout;
+};
+__device__ __forceinline__ MsmPiece msm_piece(uint32_t r, const uint32_t *perm_t, const uint32_t *perm_key, const uint32_t *out_off,
+                                              const uint32_t *seg_off, uint32_t K) {
+    // perm_t: pieces in descending order of length (msm_piece_order_kernel), so the lanes of a wave run equally long
+    const uint32_t t = perm_t ? perm_t[r] : r;
+    MsmPiece p;
+    p.slot = t;
+    p.to_pout = false;
+    if (out_off) {
+        const uint32_t key = perm_key ? perm_key[r] : msm_last_le(out_off, K, t);
+        const uint32_t s0 = seg_off[key], len = seg_off[key + 1] - s0, np = out_off[key + 1] - out_off[key], j = t - out_off[key];
+        p.b = s0 + msm_share(len, j, np);
+        p.e = s0 + msm_share(len, j + 1, np);
+        p.key_len = len;
+        if (np == 1) p.slot = key; else p.to_pout = true;
+    } else {
+        p.b = seg_off[t];
+        p.e = seg_off[t + 1];
+        p.key_len = p.e - p.b;
+    }
+    return p;
+}
+
 // ---------------------------------------------------------------- accumulate
 // All device point arrays (caller's points, partial sums, buckets, running-sum temporaries) use the reference
 // memory layout, so one load path serves every round.
@@ -21,13 +72,7 @@ __device__ __forceinline__ Point<C> pt_ld(const void *base, size_t i) { return p
 template <class C>
 __device__ __forceinline__ void pt_st(void *base, size_t i, const Point<C> &p) { pt_store<C>((char *)base + i * (3 * C::B::BYTES), p); }
 
-// Work-item t sums <= CH items of ONE key.
-//   out_off != nullptr: t is a (key, piece) pair (key from perm_key or by binary search in out_off).  A key with ONE piece
-//                       is finished by this work-item: its sum goes to buckets[key]; the pieces of a longer key go to
-//                       pout[t] and are summed by the next round.
-//   out_off == nullptr: every key has <= CH items; t is the key; result (identity when the key is empty) -> buckets[key],
-//                       the dense bucket array.
-//   later rounds (index == nullptr) skip keys whose segment is a single partial: an earlier round finished them.
+// Work-item r sums its piece (msm_piece: <= CH items of ONE key).
 // index != nullptr: item i is the point +-pts[index[i] & 0x7fffffff], negated when bit 31 is set (first round: the caller's
 // points through the sorted list of signed digits); otherwise item i is pts[i] (partial sums of the previous round).
 // AFFINE: the rows of `pts` are affine pairs of a pre-normalised SRS (lw_hip_srs_*): 2/3 of the bytes per gather and
@@ -39,33 +84,10 @@ __global__ __launch_bounds__(MSM_THREADS, WAVES) void msm_accumulate_kernel(cons
                                                                              uint32_t K, uint32_t total_items, void *pout, void *buckets) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= total_items) return;
-    // perm_t: pieces in descending order of length (msm_piece_order_kernel), so the lanes of a wave run equally long
-    const uint32_t t = perm_t ? perm_t[r] : r;
-    uint32_t b, e;
-    void *dst = buckets;
-    size_t slot = t;
-    if (out_off) {
-        uint32_t lo = 0, hi = K;   // largest key with out_off[key] <= t
-        if (perm_key) {
-            lo = perm_key[r];
-        } else {
-            while (hi - lo > 1) {
-                uint32_t mid = (lo + hi) >> 1;
-                if (out_off[mid] <= t) lo = mid; else hi = mid;
-            }
-        }
-        // the key's items are cut into np = ceil(len / CH) pieces of equal length (+-1), so the lanes of a wave run
-        // the same number of additions instead of full pieces next to a short remainder
-        const uint32_t s0 = seg_off[lo], len = seg_off[lo + 1] - s0, np = out_off[lo + 1] - out_off[lo], j = t - out_off[lo];
-        b = s0 + (uint32_t)(((uint64_t)len * j) / np);
-        e = s0 + (uint32_t)(((uint64_t)len * (j + 1)) / np);
-        if (!index && len <= 1) return;
-        if (np == 1) slot = lo; else dst = pout;
-    } else {
-        b = seg_off[t];
-        e = seg_off[t + 1];
-        if (!index && e - b <= 1) return;
-    }
+    const MsmPiece piece = msm_piece(r, perm_t, perm_key, out_off, seg_off, K);
+    if (!index && piece.key_len <= 1) return;   // a later round: the key is a single partial, an earlier round finished it
+    const uint32_t b = piece.b, e = piece.e;
+    void *dst = piece.to_pout ? pout : buckets;
     // The gather of a point (96-288 B from a random row) is a dependent chain index -> row.  The next index is
     // fetched one addition ahead, and the next row's cache lines are touched (one dword per 128 B, discarded) before
     // the current addition starts, so the real load at the top of the next iteration hits L2.
@@ -115,7 +137,7 @@ __global__ __launch_bounds__(MSM_THREADS, WAVES) void msm_accumulate_kernel(cons
         }
         asm volatile("" ::"v"(touch0), "v"(touch1), "v"(touch2));   // consume the touches after the MACs
     }
-    pt_st<C>(dst, slot, acc);
+    pt_st<C>(dst, piece.slot, acc);
 }
 
 // The same work-items on four lanes each: when the pieces do not fill the machine a work-item's
@@ -135,30 +157,10 @@ __global__ __launch_bounds__(MSM_THREADS) void msm_accumulate_quad_kernel(const 
     const uint32_t r = gt >> 2;
     if (r >= total_items) return;                // quads are never split
     const uint32_t s = (gt & 3) == 3 ? 0u : (gt & 3);
-    const uint32_t t = perm_t ? perm_t[r] : r;
-    uint32_t b, e;
-    void *dst = buckets;
-    size_t slot = t;
-    if (out_off) {
-        uint32_t lo = 0, hi = K;
-        if (perm_key) {
-            lo = perm_key[r];
-        } else {
-            while (hi - lo > 1) {
-                uint32_t mid = (lo + hi) >> 1;
-                if (out_off[mid] <= t) lo = mid; else hi = mid;
-            }
-        }
-        const uint32_t s0 = seg_off[lo], len = seg_off[lo + 1] - s0, np = out_off[lo + 1] - out_off[lo], j = t - out_off[lo];
-        b = s0 + (uint32_t)(((uint64_t)len * j) / np);
-        e = s0 + (uint32_t)(((uint64_t)len * (j + 1)) / np);
-        if (!index && len <= 1) return;
-        if (np == 1) slot = lo; else dst = pout;
-    } else {
-        b = seg_off[t];
-        e = seg_off[t + 1];
-        if (!index && e - b <= 1) return;
-    }
+    const MsmPiece piece = msm_piece(r, perm_t, perm_key, out_off, seg_off, K);
+    if (!index && piece.key_len <= 1) return;   // a later round: the key is a single partial, an earlier round finished it
+    const uint32_t b = piece.b, e = piece.e;
+    void *dst = piece.to_pout ? pout : buckets;
     const bool ylane = s == 1;
     auto fetch = [&](uint32_t i, bool &neg) {
         const uint32_t ix = index ? index[i] : i;
@@ -188,7 +190,7 @@ __global__ __launch_bounds__(MSM_THREADS) void msm_accumulate_quad_kernel(const 
             acc = pt_add_quad<C>(acc, q, s);
         }
     }
-    if ((gt & 3) != 3) B::store((char *)dst + slot * (3 * B::BYTES) + s * B::BYTES, acc);   // partial sums and buckets are projective rows
+    if ((gt & 3) != 3) B::store((char *)dst + piece.slot * (3 * B::BYTES) + s * B::BYTES, acc);   // partial sums and buckets are projective rows
 }
 
 // SRS preparation: projective rows -> affine pairs with Montgomery's batch inversion (the reference's
@@ -393,27 +395,6 @@ __global__ __launch_bounds__(MSM_THREADS) void msm_slice_sum_kernel(const void *
 }
 
 // ---------------------------------------------------------------- host orchestration
-struct Carver {   // bump allocator over the context workspace
-    char *base;
-    size_t cap, used = 0;
-    void *take(size_t bytes) {
-        used = (used + 255) & ~(size_t)255;
-        void *p = base ? base + used : nullptr;
-        used += bytes;
-        return p;
-    }
-    // true once a real (non-dry) carve-out has run past the workspace the dry run sized: checked before every launch
-    // that would touch the new pointers
-    bool overrun() const { return base && used > cap; }
-};
-#define LW_MSM_WS_CHECK(cv)                                                                                          \
-    do {                                                                                                             \
-        if ((cv).overrun()) {                                                                                        \
-            set_error("internal: MSM workspace of %zu bytes is too small (%zu needed so far)", (cv).cap, (cv).used); \
-            return LW_ERR_ALLOC;                                                                                     \
-        }                                                                                                            \
-    } while (0)
-
 // Window width c (signed digits, W = ceil(257 / c) windows of 2^(c-1) buckets): the bucket additions N * W fall with c, the
 // running sums over W * 2^(c-1) buckets (about three additions per bucket, latency-bound levels) grow with it.  Only widths
 // whose top window is either empty or well filled for 254/255-bit scalars are candidates — c = 8 and 16 (the window at
@@ -445,10 +426,7 @@ struct MsmRunner {
     Context &c;
     hipStream_t stream;
     uint32_t W;
-    bool affine = false;   // d_points are affine pairs (pre-normalised SRS)
-    uint32_t fold_c = 0;        // folded SRS (lw_hip_srs_*): window width the shifted copies were built for, and
-    uint64_t fold_stride = 0;   // rows per copy: d_points[w * fold_stride + i] = 2^(c w) * P_i
-    hipEvent_t points_ready = nullptr;   // recorded on a side stream once d_points is complete; joined before the first accumulation
+    MsmCall call = {};   // what the running MSM was called with (run, shard_accumulate)
 
     // SRS preparation (lw_hip_srs_create*): n projective rows -> n affine pairs
     int normalize(const void *d_in, size_t n, void *d_out) {
@@ -560,62 +538,24 @@ struct MsmRunner {
         return LW_OK;
     }
 
-    // The arrays of one sort over all W windows of an MSM, its bucket array and its running sums.
+    // The bucket array of an MSM and its running sums.
     struct Slice {
-        uint32_t NW = 0, K = 0, CB = 0;
-        uint32_t *coarse_cnt = nullptr, *coarse_cursor = nullptr, *maxlen_d = nullptr, *key_cnt = nullptr, *key_cursor = nullptr;
-        uint32_t *coarse_off = nullptr, *sub_off = nullptr, *off = nullptr, *scan_tmp = nullptr, *sorted = nullptr, *order_tmp = nullptr;
-        uint64_t *items = nullptr;
         char *buckets = nullptr, *S = nullptr, *A = nullptr;
-        volatile uint32_t *maxlen_h = nullptr;   // pinned host word the sort's longest bucket is copied to
     };
-
-    // carve-outs of the sort; with cv.base == nullptr only the sizes are added up
-    int carve_sort(Slice &sl, size_t n, uint32_t cbits, Carver &cv) {
-        sl.NW = fold_stride ? 1u : W;           // bucket sets: one per window, or one for all (folded SRS)
-        sl.K = sl.NW << (cbits - 1);            // signed digits: 2^(c-1) buckets per window, bucket j = multiplier j + 1
-        sl.CB = msm_sort_coarse_bins(cbits, sl.NW, fold_stride ? (uint64_t)W * fold_stride : n);
-        sl.coarse_cnt = (uint32_t *)cv.take(4 * (size_t)(sl.CB + 1));
-        sl.coarse_cursor = (uint32_t *)cv.take(4 * (size_t)(sl.CB + 1));
-        sl.maxlen_d = (uint32_t *)cv.take(256);
-        sl.key_cnt = (uint32_t *)cv.take(4 * (size_t)sl.K);        // zeroed with the counters above (contiguous)
-        sl.key_cursor = (uint32_t *)cv.take(4 * (size_t)sl.K);
-        sl.coarse_off = (uint32_t *)cv.take(4 * (size_t)(sl.CB + 1));
-        sl.sub_off = (uint32_t *)cv.take(4 * (size_t)(sl.CB + 1));
-        sl.off = (uint32_t *)cv.take(4 * (size_t)(sl.K + 1));
-        sl.scan_tmp = (uint32_t *)cv.take(msm_scan_scratch_bytes(sl.K));
-        sl.sorted = (uint32_t *)cv.take(4 * n * W);
-        sl.items = (uint64_t *)cv.take(8 * n * W);
-        sl.order_tmp = (uint32_t *)cv.take(msm_order_tmp_bytes());
-        sl.buckets = (char *)cv.take(PB * (size_t)sl.K);
-        LW_MSM_WS_CHECK(cv);
-        return LW_OK;
-    }
-
-    // sort of the digit matrix on stream `s`; the longest bucket lands in *sl.maxlen_h once `s` gets there
-    int launch_sort(Slice &sl, const uint32_t *dig, size_t n, uint32_t cbits, hipStream_t s) {
-        // coarse_cnt, coarse_cursor, maxlen, key_cnt and key_cursor are adjacent carve-outs: one memset clears them all
-        LW_HIP_CHECK(hipMemsetAsync(sl.coarse_cnt, 0, (size_t)((char *)sl.coarse_off - (char *)sl.coarse_cnt), s), LW_ERR_LAUNCH);
-        msm_launch_sort(c, dig, (uint64_t)n, cbits, W, sl.coarse_cnt, sl.coarse_off,
-                        sl.coarse_cursor, sl.items, sl.sorted, sl.off, sl.K, sl.maxlen_d, sl.scan_tmp, sl.sub_off, sl.key_cnt,
-                        sl.key_cursor, fold_stride, (uint64_t)0, s);
-        LW_HIP_CHECK(hipMemcpyAsync((void *)sl.maxlen_h, sl.maxlen_d, 4, hipMemcpyDeviceToHost, s), LW_ERR_LAUNCH);
-        return LW_OK;
-    }
 
     // accumulate rounds on stream `s`: while some bucket is longer than CH, cut every bucket into CH-sized pieces.
     // `maxlen`: the longest bucket (real run: from the sort; dry run: the worst case).
-    int accumulate(Slice &sl, const void *d_points, size_t n, uint32_t maxlen, Carver &cv, hipStream_t s) {
+    int accumulate(const MsmSortBufs &sb, char *buckets, const void *d_points, size_t n, uint32_t maxlen, Carver &cv, hipStream_t s) {
         const bool dry = cv.base == nullptr;
-        const uint32_t K = sl.K;
+        const uint32_t K = sb.K;
         const uint32_t CH = msm_ch((uint64_t)n * W);
-        const uint32_t *seg = sl.off;
+        const uint32_t *seg = sb.off;
         const void *pts = d_points;         // first round: the caller's points through the sorted index list
-        const uint32_t *index = sl.sorted;
+        const uint32_t *index = sb.sorted;
         uint64_t len = maxlen;             // longest segment
         uint64_t items_bound = (uint64_t)n * W;   // upper bound on items in this round
         bool first = true;                 // (the dry run has no pointers to tell the rounds apart)
-        char *buckets = sl.buckets;
+        const bool affine = call.affine != 0;
         auto launch = [&](const uint32_t *out_off, const uint32_t *perm_t, const uint32_t *perm_key, uint32_t total, void *pout,
                           const char *name) {
             const uint32_t blocks = (total + MSM_THREADS - 1) / MSM_THREADS;
@@ -645,7 +585,7 @@ struct MsmRunner {
             uint32_t *perm_key = first ? (uint32_t *)cv.take(4 * out_bound) : nullptr;
             LW_MSM_WS_CHECK(cv);
             if (!dry) {
-                msm_launch_scan(seg, out_off, K, (int)CH, sl.maxlen_d, sl.scan_tmp, s);
+                msm_launch_scan(seg, out_off, K, (int)CH, sb.maxlen_d, sb.scan_tmp, s);
                 uint32_t total = 0;
                 LW_HIP_CHECK(hipMemcpyAsync(&total, out_off + K, 4, hipMemcpyDeviceToHost, s), LW_ERR_LAUNCH);
                 LW_HIP_CHECK(hipStreamSynchronize(s), LW_ERR_LAUNCH);
@@ -653,7 +593,7 @@ struct MsmRunner {
                     set_error("internal: MSM partial count %u exceeds bound %llu", total, (unsigned long long)out_bound);
                     return LW_ERR_LAUNCH;
                 }
-                if (first) msm_launch_piece_order(c, seg, out_off, K, total, sl.order_tmp, perm_t, perm_key, s);
+                if (first) msm_launch_piece_order(c, seg, out_off, K, total, sb.order_tmp, perm_t, perm_key, s);
                 if (total) launch(out_off, perm_t, perm_key, total, (void *)pout, index ? "msm_accumulate_kernel" : "msm_accumulate_kernel<partials>");
             }
             seg = out_off;
@@ -667,10 +607,72 @@ struct MsmRunner {
             uint32_t *perm_t = first ? (uint32_t *)cv.take(4 * (size_t)K) : nullptr;
             LW_MSM_WS_CHECK(cv);
             if (!dry) {
-                if (first) msm_launch_piece_order(c, seg, nullptr, K, K, sl.order_tmp, perm_t, nullptr, s);
+                if (first) msm_launch_piece_order(c, seg, nullptr, K, K, sb.order_tmp, perm_t, nullptr, s);
                 launch(nullptr, perm_t, nullptr, K, nullptr, index ? "msm_accumulate_kernel" : "msm_accumulate_kernel<final>");
             }
         }
+        return LW_OK;
+    }
+
+    // What every MSM of n > 0 pairs shares, on `stream`: the workspace plan (every carve-out twice: dry, to size the
+    // workspace, then for real), digits and sort of the scalars, the call's after-sort work, and the accumulation into
+    // sl.buckets.  tail(cv): what the caller appends behind the accumulation in both passes (run: the bucket reduce).
+    template <class Tail>
+    int sort_accumulate(const uint64_t *d_scalars, const void *d_points, size_t n, uint32_t cbits, MsmSortBufs &sb, Slice &sl, Tail tail) {
+        const uint64_t fold_stride = call.fold_stride;
+        W = (64 * call.scalar_limbs + cbits) / cbits;   // 1 + floor(B / c): the signed recoding of a B-bit scalar never carries out of the top window
+        if (n >> 32) {
+            set_error("MSM of %zu points: index width is 32 bits", n);
+            return LW_ERR_BAD_ARG;
+        }
+        if (n >> 31) {
+            set_error("MSM of %zu points: the sorted list keeps the digit's sign in bit 31 of the index", n);
+            return LW_ERR_BAD_ARG;
+        }
+        if (fold_stride && (((uint64_t)W * fold_stride) >> 31)) {
+            set_error("folded SRS of %llu x %u rows overflows the 31-bit point index", (unsigned long long)fold_stride, W);
+            return LW_ERR_BAD_ARG;
+        }
+        if (((uint64_t)n * W) >> 32) {
+            set_error("MSM of %zu points x %u windows overflows 32-bit item offsets; shard the input", n, W);
+            return LW_ERR_BAD_ARG;
+        }
+        // size the workspace for the worst case: one bucket holding every item.  A folded SRS sorts the items of all W
+        // windows into one bucket set, so its longest bucket can hold n * W items (every scalar with the same digit in
+        // every window), which takes more rounds of partial sums than n items do.
+        const uint64_t worst_len = fold_stride ? (uint64_t)n * W : (uint64_t)n;
+        const uint32_t worst = (uint32_t)std::min<uint64_t>(worst_len, 0xffffffffu);
+        uint32_t *dig = nullptr;
+        auto plan = [&](Carver &cv) -> int {   // every carve-out that does not depend on the data
+            dig = (uint32_t *)cv.take(4 * (size_t)W * msm_sort_padded_points(n));
+            const int rc = msm_sort_carve(sb, n, cbits, W, fold_stride, cv);
+            sl.buckets = (char *)cv.take(PB * (size_t)sb.K);
+            LW_MSM_WS_CHECK(cv);
+            return rc;
+        };
+        Carver dry{nullptr, 0};
+        int rc = plan(dry);
+        if (!rc) rc = accumulate(sb, sl.buckets, nullptr, n, worst, dry, stream);
+        if (!rc) rc = tail(dry);
+        if (rc) return rc;
+        if (c.msm_ws.ensure(dry.used + 4096)) return LW_ERR_ALLOC;
+        if (!c.pinned_words) LW_HIP_CHECK(hipHostMalloc((void **)&c.pinned_words, 256, hipHostMallocDefault), LW_ERR_ALLOC);
+        Carver cv{(char *)c.msm_ws.p, c.msm_ws.bytes};
+        rc = plan(cv);
+        if (rc) return rc;
+        volatile uint32_t *maxlen_h = c.pinned_words;   // pinned host word the sort's longest bucket is copied to
+        *maxlen_h = 0;
+        // digits of all windows, then their sort, on the caller's stream
+        rc = msm_launch_digits(c, (const uint32_t *)d_scalars, (uint64_t)n, cbits, W, dig, stream, call.scalar_limbs);
+        if (!rc) rc = msm_launch_sort(c, sb, dig, (uint64_t)n, cbits, W, fold_stride, maxlen_h, stream);
+        if (!rc && call.after_sort) rc = call.after_sort();   // host-buffer call: the points are uploaded (and normalised) while the sort above runs
+        if (rc) return rc;
+        LW_HIP_CHECK(hipStreamSynchronize(stream), LW_ERR_LAUNCH);
+        if (call.points_ready) LW_HIP_CHECK(hipStreamWaitEvent(stream, call.points_ready, 0), LW_ERR_LAUNCH);   // normalised points
+        rc = accumulate(sb, sl.buckets, d_points, n, *maxlen_h, cv, stream);
+        if (!rc) rc = tail(cv);
+        if (rc) return rc;
+        LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
         return LW_OK;
     }
 
@@ -700,10 +702,8 @@ struct MsmRunner {
     // Phase 1: digits + sort + accumulation of the local pairs with the window width all ranks agreed on; leaves the dense
     // bucket array [W][2^(c-1)] in the context workspace (*buckets_out, valid until the next MSM on this context).
     int shard_accumulate(const uint64_t *d_scalars, const void *d_points, size_t n, uint32_t cbits, char **buckets_out) {
-        if ((n >> 31) || (((uint64_t)n * ((256 + cbits) / cbits)) >> 32)) { set_error("MSM shard of %zu points: index width", n); return LW_ERR_BAD_ARG; }
-        W = (256 + cbits) / cbits;
-        Slice sl;
         if (n == 0) {   // no pairs here: identity buckets (this rank still owns a slice of everybody's)
+            W = (256 + cbits) / cbits;
             const uint64_t K = (uint64_t)W << (cbits - 1);
             if (c.msm_ws.ensure(PB * K + 4096)) return LW_ERR_ALLOC;
             hipLaunchKernelGGL((msm_fill_identity_kernel<C>), dim3((uint32_t)((K + 255) / 256)), dim3(256), 0, stream, c.msm_ws.p, K);
@@ -711,27 +711,10 @@ struct MsmRunner {
             *buckets_out = (char *)c.msm_ws.p;
             return LW_OK;
         }
-        Carver dry{nullptr, 0};
-        uint32_t *dig = (uint32_t *)dry.take(4 * (size_t)W * msm_sort_padded_points(n));
-        int rc = carve_sort(sl, n, cbits, dry);
-        if (!rc) rc = accumulate(sl, nullptr, n, (uint32_t)std::min<size_t>(n, 0xffffffffu), dry, stream);
+        MsmSortBufs sb;
+        Slice sl;
+        const int rc = sort_accumulate(d_scalars, d_points, n, cbits, sb, sl, [](Carver &) { return (int)LW_OK; });
         if (rc) return rc;
-        if (c.msm_ws.ensure(dry.used + 4096)) return LW_ERR_ALLOC;
-        if (!c.pinned_words) LW_HIP_CHECK(hipHostMalloc((void **)&c.pinned_words, 256, hipHostMallocDefault), LW_ERR_ALLOC);
-        Carver cv{(char *)c.msm_ws.p, c.msm_ws.bytes};
-        dig = (uint32_t *)cv.take(4 * (size_t)W * msm_sort_padded_points(n));
-        rc = carve_sort(sl, n, cbits, cv);
-        if (rc) return rc;
-        sl.maxlen_h = c.pinned_words;
-        *sl.maxlen_h = 0;
-        rc = msm_launch_digits(c, (const uint32_t *)d_scalars, (uint64_t)n, cbits, W, dig, stream, 4);
-        if (!rc) rc = launch_sort(sl, dig, n, cbits, stream);
-        if (rc) return rc;
-        LW_HIP_CHECK(hipStreamSynchronize(stream), LW_ERR_LAUNCH);
-        if (points_ready) LW_HIP_CHECK(hipStreamWaitEvent(stream, points_ready, 0), LW_ERR_LAUNCH);
-        rc = accumulate(sl, d_points, n, *sl.maxlen_h, cv, stream);
-        if (rc) return rc;
-        LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
         *buckets_out = sl.buckets;
         return LW_OK;
     }
@@ -790,77 +773,27 @@ struct MsmRunner {
         pt_store<C>(out_host, result);
     }
 
-    // d_scalars: n x scalar_limbs u64 (1 .. 8), each an unsigned integer of B = 64 x scalar_limbs bits, MS limb first
-    int run(const uint64_t *d_scalars, const void *d_points, size_t n, void *out_host, uint32_t scalar_limbs) {
+    // d_scalars: n x call.scalar_limbs u64 (1 .. 8), each an unsigned integer of B = 64 x scalar_limbs bits, MS limb first
+    int run(const uint64_t *d_scalars, const void *d_points, size_t n, void *out_host) {
         Point<C> result = pt_identity<C>();
-        const uint32_t bits = 64 * scalar_limbs;
+        const uint32_t bits = 64 * call.scalar_limbs;
         if (n > 0) {
-            if (scalar_limbs < 1 || scalar_limbs > 8 || (fold_stride && bits != 256)) {   // folded SRS: 4-limb scalars only
-                set_error("MSM scalars of %u limbs", scalar_limbs);
+            if (call.scalar_limbs < 1 || call.scalar_limbs > 8 || (call.fold_stride && bits != 256)) {   // folded SRS: 4-limb scalars only
+                set_error("MSM scalars of %u limbs", call.scalar_limbs);
                 return LW_ERR_BAD_ARG;
             }
-            if (n >> 32) {
-                set_error("MSM of %zu points: index width is 32 bits", n);
-                return LW_ERR_BAD_ARG;
-            }
-            if (n >> 31) {
-                set_error("MSM of %zu points: the sorted list keeps the digit's sign in bit 31 of the index", n);
-                return LW_ERR_BAD_ARG;
-            }
-            const uint32_t cbits = fold_stride ? fold_c : pick_window(n, bits);
-            W = (bits + cbits) / cbits;   // 1 + floor(B / c): the signed recoding of a B-bit scalar never carries out of the top window
-            if (fold_stride && (((uint64_t)W * fold_stride) >> 31)) {
-                set_error("folded SRS of %llu x %u rows overflows the 31-bit point index", (unsigned long long)fold_stride, W);
-                return LW_ERR_BAD_ARG;
-            }
-            if (((uint64_t)n * W) >> 32) {
-                set_error("MSM of %zu points x %u windows overflows 32-bit item offsets; shard the input", n, W);
-                return LW_ERR_BAD_ARG;
-            }
+            const uint32_t cbits = call.fold_stride ? call.fold_c : pick_window(n, bits);
             // One sort and one set of running sums over all windows.  (Measured and dropped, profiles/r03_ab_msm_slices.txt:
             // the windows as two halves, the second half's sort and the first half's running sums on a high-priority side
             // stream under the other half's accumulation — 2^24 BLS12-381 G1 45.6 ms against 45.2-45.6, 2^22 15.6 against
             // 14.8: the accumulate kernel is bound by VALU issue, every wave slot the side kernels take comes out of it.)
+            MsmSortBufs sb;
             Slice sl;
-            // size the workspace for the worst case: one bucket holding every item.  A folded SRS sorts the items of all W
-            // windows into one bucket set, so its longest bucket can hold n * W items (every scalar with the same digit in
-            // every window), which takes more rounds of partial sums than n items do.
-            const uint64_t worst_len = fold_stride ? (uint64_t)n * W : (uint64_t)n;
-            const uint32_t worst = (uint32_t)std::min<uint64_t>(worst_len, 0xffffffffu);
-            auto plan = [&](Carver &cv, uint32_t **dig_out) -> int {   // every carve-out that does not depend on the data
-                *dig_out = (uint32_t *)cv.take(4 * (size_t)W * msm_sort_padded_points(n));
-                return carve_sort(sl, n, cbits, cv);
-            };
-            Carver dry{nullptr, 0};
-            uint32_t *dig = nullptr;
-            int rc = plan(dry, &dig);
-            if (!rc) rc = accumulate(sl, nullptr, n, worst, dry, stream);
-            if (!rc) rc = reduce(sl.buckets, 1u << (cbits - 1), sl.NW, dry, &sl.S, &sl.A, stream);
+            const int rc = sort_accumulate(d_scalars, d_points, n, cbits, sb, sl, [&](Carver &cv) {
+                return reduce(sl.buckets, 1u << (cbits - 1), sb.NW, cv, &sl.S, &sl.A, stream);
+            });
             if (rc) return rc;
-            if (c.msm_ws.ensure(dry.used + 4096)) return LW_ERR_ALLOC;
-            if (!c.pinned_words) LW_HIP_CHECK(hipHostMalloc((void **)&c.pinned_words, 256, hipHostMallocDefault), LW_ERR_ALLOC);
-            Carver cv{(char *)c.msm_ws.p, c.msm_ws.bytes};
-            rc = plan(cv, &dig);
-            if (rc) return rc;
-            sl.maxlen_h = c.pinned_words;
-            *sl.maxlen_h = 0;
-            // digits of all windows, then their sort, on the caller's stream
-            rc = msm_launch_digits(c, (const uint32_t *)d_scalars, (uint64_t)n, cbits, W, dig, stream, scalar_limbs);
-            if (!rc) rc = launch_sort(sl, dig, n, cbits, stream);
-            if (rc) return rc;
-            if (c.msm_after_sort) {   // host-buffer call: the points are uploaded (and normalised) while the sort above runs
-                auto hook = std::move(c.msm_after_sort);
-                c.msm_after_sort = nullptr;
-                rc = hook();
-                if (rc) return rc;
-            }
-            LW_HIP_CHECK(hipStreamSynchronize(stream), LW_ERR_LAUNCH);
-            if (points_ready) LW_HIP_CHECK(hipStreamWaitEvent(stream, points_ready, 0), LW_ERR_LAUNCH);   // normalised points
-            rc = accumulate(sl, d_points, n, *sl.maxlen_h, cv, stream);
-            if (!rc) rc = reduce(sl.buckets, 1u << (cbits - 1), sl.NW, cv, &sl.S, &sl.A, stream);
-            if (rc) return rc;
-            LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
-            const uint32_t NW = sl.NW;
+            const uint32_t NW = sb.NW;
             std::vector<char> S(PB * NW), A(PB * NW);
             LW_HIP_CHECK(hipMemcpyAsync(S.data(), sl.S, PB * NW, hipMemcpyDeviceToHost, stream), LW_ERR_LAUNCH);
             LW_HIP_CHECK(hipMemcpyAsync(A.data(), sl.A, PB * NW, hipMemcpyDeviceToHost, stream), LW_ERR_LAUNCH);
@@ -868,7 +801,7 @@ struct MsmRunner {
             // window sum = sum (j + 1) * bucket[j] = S_w + A_w
             std::vector<Point<C>> wsum(NW);
             for (uint32_t w = 0; w < NW; w++) wsum[w] = pt_add<C>(pt_load<C>(S.data() + PB * w), pt_load<C>(A.data() + PB * w));
-            result = fold_windows(wsum, pt_load<C>(A.data() + PB * (NW - 1)), cbits, W, fold_stride != 0, bits);
+            result = fold_windows(wsum, pt_load<C>(A.data() + PB * (NW - 1)), cbits, W, call.fold_stride != 0, bits);
         }
         result = pt_unmap_result<C>(pt_to_affine<C>(result));
         pt_store<C>(out_host, result);
@@ -884,57 +817,47 @@ static void sum_points_host_t(const void *pts, size_t n, void *out) {
     pt_store<C>(out, pt_to_affine<C>(acc));
 }
 
-// one translation unit per curve (they compile in parallel): the operations msm.hip dispatches to through msm_ops_SUFFIX
-#define LW_MSM_INSTANTIATE(CURVE, SUFFIX)                                                                                        \
-    static int msm_run_##SUFFIX(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_points, size_t n, void *out,  \
-                                int affine, hipEvent_t points_ready, uint32_t scalar_limbs) {                                     \
-        if (affine && IsoOf<CURVE>::has) {   /* normalised rows live on the isomorphic model (msm_to_affine_kernel) */           \
-            MsmRunner<typename IsoOf<CURVE>::type> ri{c, s, 0};                                                                    \
-            ri.affine = true;                                                                                                      \
-            ri.points_ready = points_ready;                                                                                        \
-            ri.fold_c = c.msm_fold_c;                                                                                              \
-            ri.fold_stride = c.msm_fold_stride;                                                                                    \
-            return ri.run(d_scalars, d_points, n, out, scalar_limbs);                                                              \
-        }                                                                                                                          \
-        MsmRunner<CURVE> r{c, s, 0};                                                                                               \
-        r.affine = affine != 0;                                                                                                    \
-        r.points_ready = points_ready;                                                                                             \
-        if (affine) {                                                                                                              \
-            r.fold_c = c.msm_fold_c;                                                                                               \
-            r.fold_stride = c.msm_fold_stride;                                                                                     \
-        }                                                                                                                          \
-        return r.run(d_scalars, d_points, n, out, scalar_limbs);                                                                   \
-    }                                                                                                                              \
-    static int msm_normalize_##SUFFIX(Context &c, hipStream_t s, const void *d_in, size_t n, void *d_out) {                        \
-        MsmRunner<CURVE> r{c, s, 0};                                                                                               \
-        return r.normalize(d_in, n, d_out);                                                                                        \
-    }                                                                                                                              \
-    static size_t msm_affine_bytes_##SUFFIX(size_t n) { return MsmRunner<CURVE>::affine_bytes(n); }                               \
-    static int msm_fold_build_##SUFFIX(Context &c, hipStream_t s, void *d_rows, size_t n, uint32_t cbits) {   /* rows live on IsoOf<CURVE> */ \
-        MsmRunner<typename IsoOf<CURVE>::type> r{c, s, 0};                                                                         \
-        return r.build_fold(d_rows, n, cbits);                                                                                     \
-    }                                      \
-    /* sharded MSM phases: always on the normalised (affine) rows, i.e. on IsoOf<CURVE> where the curve has a cheaper model */  \
-    static int msm_shard_accumulate_##SUFFIX(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_aff, size_t n,  \
-                                             uint32_t cbits, char **buckets) {                                                     \
-        MsmRunner<typename IsoOf<CURVE>::type> r{c, s, 0};                                                                         \
-        r.affine = true;                                                                                                           \
-        return r.shard_accumulate(d_scalars, d_aff, n, cbits, buckets);                                                            \
-    }                                                                                                                              \
-    static int msm_shard_reduce_##SUFFIX(Context &c, hipStream_t s, const char *recv, uint32_t G, uint32_t cbits, char *d_sa) {    \
-        MsmRunner<typename IsoOf<CURVE>::type> r{c, s, 0};                                                                         \
-        return r.shard_reduce(recv, G, cbits, d_sa);                                                                               \
-    }                                                                                                                              \
-    static void msm_shard_combine_##SUFFIX(const char *sa_all, uint32_t G, uint32_t cbits, void *out) {                            \
-        MsmRunner<typename IsoOf<CURVE>::type>::shard_combine_host(sa_all, G, cbits, out);                                         \
-    }                                                                                                                              \
-    static int ec_add_outer_##SUFFIX(Context &c, hipStream_t s, const void *d_rows, uint32_t m, const void *d_cols, uint32_t k,    \
-                                     void *d_out) {                                                                                \
-        MsmRunner<CURVE> r{c, s, 0};                                                                                               \
-        return r.add_outer(d_rows, m, d_cols, k, d_out);                                                                           \
-    }                                                                                                                              \
-    MsmCurveOps msm_ops_##SUFFIX = {msm_run_##SUFFIX,          msm_normalize_##SUFFIX,   msm_affine_bytes_##SUFFIX,        \
-                                          msm_fold_build_##SUFFIX,   msm_shard_accumulate_##SUFFIX, msm_shard_reduce_##SUFFIX,   \
-                                          msm_shard_combine_##SUFFIX, ec_add_outer_##SUFFIX, sum_points_host_t<CURVE>};
+// The operations msm.hip dispatches to through msm_ops(): msm_<curve>.hip defines msm_ops_<curve> = msm_curve_ops<Curve>().
+// Affine rows — a normalised input, an SRS, the sharded MSM's phases — live on IsoOf<C>::type, the cheaper isomorphic model
+// where the curve has one (msm_to_affine_kernel) and C itself otherwise; projective rows on C.
+template <class C>
+static int msm_run(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_points, size_t n, void *out, const MsmCall &call) {
+    if (call.affine) return MsmRunner<typename IsoOf<C>::type>{c, s, 0, call}.run(d_scalars, d_points, n, out);
+    return MsmRunner<C>{c, s, 0, call}.run(d_scalars, d_points, n, out);
+}
+template <class C>
+static int msm_normalize(Context &c, hipStream_t s, const void *d_in, size_t n, void *d_out) {
+    return MsmRunner<C>{c, s, 0}.normalize(d_in, n, d_out);
+}
+template <class C>
+static size_t msm_affine_bytes(size_t n) { return MsmRunner<C>::affine_bytes(n); }
+template <class C>
+static int msm_fold_build(Context &c, hipStream_t s, void *d_rows, size_t n, uint32_t cbits) {
+    return MsmRunner<typename IsoOf<C>::type>{c, s, 0}.build_fold(d_rows, n, cbits);
+}
+template <class C>
+static int msm_shard_accumulate_on(Context &c, hipStream_t s, const uint64_t *d_scalars, const void *d_aff, size_t n, uint32_t cbits,
+                                   char **buckets) {
+    MsmCall call;
+    call.affine = 1;
+    return MsmRunner<typename IsoOf<C>::type>{c, s, 0, call}.shard_accumulate(d_scalars, d_aff, n, cbits, buckets);
+}
+template <class C>
+static int msm_shard_reduce_on(Context &c, hipStream_t s, const char *recv, uint32_t G, uint32_t cbits, char *d_sa) {
+    return MsmRunner<typename IsoOf<C>::type>{c, s, 0}.shard_reduce(recv, G, cbits, d_sa);
+}
+template <class C>
+static void msm_shard_combine_on(const char *sa_all, uint32_t G, uint32_t cbits, void *out) {
+    MsmRunner<typename IsoOf<C>::type>::shard_combine_host(sa_all, G, cbits, out);
+}
+template <class C>
+static int ec_add_outer(Context &c, hipStream_t s, const void *d_rows, uint32_t m, const void *d_cols, uint32_t k, void *d_out) {
+    return MsmRunner<C>{c, s, 0}.add_outer(d_rows, m, d_cols, k, d_out);
+}
+template <class C>
+constexpr MsmCurveOps msm_curve_ops() {
+    return {msm_run<C>,           msm_normalize<C>,        msm_affine_bytes<C>, msm_fold_build<C>,   msm_shard_accumulate_on<C>,
+            msm_shard_reduce_on<C>, msm_shard_combine_on<C>, ec_add_outer<C>,     sum_points_host_t<C>};
+}
 
 }  // namespace lw

@@ -201,6 +201,23 @@ def test_folded_srs_single_bucket_holds_every_window(name, n, monkeypatch):
     srs.close()
 
 
+def test_fold_is_per_call(monkeypatch):
+    """Whether a call runs on the shifted copies is decided per call and handed down as an argument: a folded call, a prefix
+    below the quarter (plain schedule on copy 0), a folded call again and a plain msm() of the same points on the same lane,
+    each against the oracle — nothing of one call's fold may reach the next."""
+    from lambda_elliptic_curves_amd import msm
+    crv, oid = util.curve_pairs()["bls12_381_g1"]
+    n = 3000
+    scalars, points = util.msm_case(oid, n, 5150)
+    exp = {m: aff(oid, O.parallel_msm_with(oid, scalars[:m], points[:m], 8, 16)) for m in (n, n // 5)}
+    monkeypatch.setenv("LW_HIP_SRS_FOLD_MIN", "0")
+    srs = msm.Srs(crv, points)
+    for m in (n, n // 5, n):
+        assert aff(oid, srs.msm(scalars[:m])) == exp[m], f"prefix {m}"
+    assert aff(oid, msm.msm(crv, scalars, points)) == exp[n]
+    srs.close()
+
+
 def test_folded_srs_matches_oracle_at_default_threshold():
     """2^19 points: the smallest set that is folded by default (BLS12-381 G1), against the oracle."""
     from lambda_elliptic_curves_amd import msm
