@@ -440,6 +440,69 @@ int lw_stark_deep_composition_device(lw_field_t field, const void *const *d_poly
                                      const void *points, uint32_t m, const void *weights, void *d_out_coeffs,
                                      size_t *out_len_or_null, void *out_evals_host_or_null, void *hip_stream);
 
+/* ---- PLONK prover rounds 1-3 ----
+ * Prover::round_1 / round_2 / round_3 (provers/plonk/src/prover.rs:311-341, 343-381, 383-535) without the commitments:
+ * the blinded wire polynomials, the permutation grand product z and the quotient parts t_lo, t_mid, t_hi.  With
+ * lw_hip_msm_srs_fr_device for the commitments and lw_kzg_open_batch_device for rounds 4-5 the reference prover runs
+ * device-resident: only challenges, blinders and commitments cross the bus.
+ * Elements are as in lw_poly_*: 4 x u64, MS limb first, Montgomery form, canonical; field LW_FIELD_STARK252 or
+ * LW_FIELD_BLS12_381_FR, anything else LW_ERR_BAD_ARG.  Device buffers are 16-byte aligned (LW_ERR_BAD_ARG otherwise).
+ * Every argument is checked before any device work.  beta, gamma, alpha, k1, the blinders and the public input are host
+ * memory in the _device forms too.  Outputs overlap no input.  Stream contract as at the top of this header.
+ *
+ * The circuit handle is the device-side CommonPreprocessedInput (provers/plonk/src/setup.rs), built once per circuit like
+ * lw_srs_t, from host buffers: q_coeffs = ql | qr | qo | qm | qc and s_coeffs = s1 | s2 | s3 in coefficient form, n
+ * coefficients each (zero padded); s_lagrange = s1_lagrange | s2_lagrange | s3_lagrange, n values each.  n not a power
+ * of two: LW_ERR_INPUT_NOT_POW2; log2(4n) above the field's two-adicity: LW_ERR_ROOT_OF_UNITY.  On the coset
+ * k1 * <w_4n> the vanishing polynomial X^n - 1 takes the four values k1^n * i4^j - 1 (i4 = w_4n^n, j = 0 .. 3); if one of
+ * them is zero — or k1 is — the result is LW_ERR_INV_ZERO (round 3 divides by them).
+ * The handle keeps on the device: the three s_lagrange columns (3n elements), the evaluations of the eight polynomials
+ * and of l1 on the coset (9 x 4n), and the table x_i = k1 * w_4n^i (4n): 43 n elements = 1376 n bytes, 1.34 GiB at
+ * n = 2^20.  The inverse vanishing values, k1^n * i4^j, 1 / k1 and w_n are kept on the host side of the handle.
+ * A handle is read-only once created: any number of calls, threads and streams may share it.  Destroy it before
+ * lw_hip_init rebinds the device. */
+typedef struct lw_plonk_circuit lw_plonk_circuit_t;
+int lw_plonk_circuit_create(lw_field_t field, size_t n, const void *k1, const void *q_coeffs, const void *s_coeffs,
+                            const void *s_lagrange, lw_plonk_circuit_t **out);
+int lw_plonk_circuit_destroy(lw_plonk_circuit_t *circuit);
+
+/* Round 1: p_w = interpolate_fft(w) + (b0 + b1 X)(X^n - 1) for w = a, b, c.  witness: a | b | c, n values each.
+ * blinders_or_null: six host elements, b0 b1 of a, then of b, then of c (NULL: no blinding, the reference's test
+ * generator).  out_p_abc: three blocks of n + 2 coefficients (trailing zeros are not stripped).  The blinding is added as
+ * out[i] -= b_i, out[n + i] += b_i, which is the product for every n >= 1. */
+int lw_plonk_round1(const lw_plonk_circuit_t *circuit, const void *witness, const void *blinders_or_null, void *out_p_abc);
+int lw_plonk_round1_device(const lw_plonk_circuit_t *circuit, const void *d_witness, const void *blinders_or_null,
+                           void *d_out_p_abc, void *hip_stream);
+
+/* Round 2: z_0 = 1, z_{i+1} = z_i * num_i / den_i for i = 0 .. n-2 with num, den as prover.rs:360-363, then
+ * p_z = interpolate_fft(z) + (b0 + b1 X + b2 X^2)(X^n - 1).  blinders_or_null: three host elements.
+ * out_z_values_or_null: the n values z_i; out_p_z: n + 3 coefficients.  Row n-1 of the witness and of s_lagrange is never
+ * read.  A zero den_i with i <= n-2 is LW_ERR_INV_ZERO (the reference's division fails there); a zero num_i is legal and
+ * zeroes the rest of z.  The rows are not divided one by one: z_i = (prod_{j<i} num_j) (prod_{i<=j<=n-2} den_j) / (prod
+ * of all den_j), with one inversion per call, on the host, of the 32 bytes that also decide LW_ERR_INV_ZERO — so BOTH
+ * forms synchronise the stream once in mid-call; the _device form returns with the rest of its work enqueued. */
+int lw_plonk_round2(const lw_plonk_circuit_t *circuit, const void *witness, const void *beta, const void *gamma,
+                    const void *blinders_or_null, void *out_z_values_or_null, void *out_p_z);
+int lw_plonk_round2_device(const lw_plonk_circuit_t *circuit, const void *d_witness, const void *beta, const void *gamma,
+                           const void *blinders_or_null, void *d_out_z_values_or_null, void *d_out_p_z, void *hip_stream);
+
+/* Round 3: t = interpolate_offset_fft(p_eval / Z_H, k1) on the 4n-point coset with offset k1, p_eval as
+ * prover.rs:440-498, from round 1's p_abc (3 x (n + 2)) and round 2's p_z (n + 3).  public_input: n_pub host elements,
+ * zero padded to n (n_pub > n: LW_ERR_LENGTH_MISMATCH).  t is cut as the reference cuts it: zero padded to 3 (n + 2)
+ * where 4n is shorter (n <= 4), coefficients from 3 (n + 2) on dropped.  out_t: three blocks of n + 3 coefficients,
+ *   block 0 = t[0 .. n+2) then b_0,
+ *   block 1 = t[n+2 .. 2n+4) with b_0 subtracted from coefficient 0, then b_1,
+ *   block 2 = t[2n+4 .. 3n+6) with b_1 subtracted from coefficient 0, then 0,
+ * with blinders_or_null = b_0 b_1 (two host elements; NULL: zero).  Each block can go to lw_hip_msm_srs_fr_device and to
+ * lw_kzg_open_batch_device as it is.  Per call: one n-point inverse transform for the public input (none when
+ * n_pub = 0), one batch of low-degree extensions n -> 4n (a, b, c, z and the public input), one kernel over the 4n points,
+ * one 4n-point inverse transform.  The _device form enqueues and returns. */
+int lw_plonk_round3(const lw_plonk_circuit_t *circuit, const void *p_abc, const void *p_z, const void *public_input, size_t n_pub,
+                    const void *beta, const void *gamma, const void *alpha, const void *blinders_or_null, void *out_t);
+int lw_plonk_round3_device(const lw_plonk_circuit_t *circuit, const void *d_p_abc, const void *d_p_z, const void *public_input,
+                           size_t n_pub, const void *beta, const void *gamma, const void *alpha, const void *blinders_or_null,
+                           void *d_out_t, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,8 @@ EXPORTS = [
     "lw_poly_evaluate", "lw_poly_evaluate_device", "lw_poly_ruffini_division", "lw_poly_ruffini_division_device",
     "lw_kzg_open", "lw_kzg_open_device", "lw_kzg_open_batch", "lw_kzg_open_batch_device",
     "lw_stark_deep_composition", "lw_stark_deep_composition_device",
+    "lw_plonk_circuit_create", "lw_plonk_circuit_destroy", "lw_plonk_round1", "lw_plonk_round1_device",
+    "lw_plonk_round2", "lw_plonk_round2_device", "lw_plonk_round3", "lw_plonk_round3_device",
 ]
 
 
@@ -185,6 +187,22 @@ def lib():
     L.lw_stark_deep_composition.restype = i
     L.lw_stark_deep_composition_device.argtypes = [i, vp, vp, u32, vp, u32, vp, vp, C.POINTER(sz), vp, vp]
     L.lw_stark_deep_composition_device.restype = i
+    L.lw_plonk_circuit_create.argtypes = [i, sz, vp, vp, vp, vp, C.POINTER(vp)]
+    L.lw_plonk_circuit_create.restype = i
+    L.lw_plonk_circuit_destroy.argtypes = [vp]
+    L.lw_plonk_circuit_destroy.restype = i
+    L.lw_plonk_round1.argtypes = [vp, vp, vp, vp]
+    L.lw_plonk_round1.restype = i
+    L.lw_plonk_round1_device.argtypes = [vp, vp, vp, vp, vp]
+    L.lw_plonk_round1_device.restype = i
+    L.lw_plonk_round2.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.lw_plonk_round2.restype = i
+    L.lw_plonk_round2_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lw_plonk_round2_device.restype = i
+    L.lw_plonk_round3.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp]
+    L.lw_plonk_round3.restype = i
+    L.lw_plonk_round3_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp]
+    L.lw_plonk_round3_device.restype = i
     _lib = L
     return L
 

@@ -90,6 +90,11 @@ pub struct lw_profile_t {
 pub struct lw_srs_t {
     _private: [u8; 0],
 }
+/// opaque `lw_plonk_circuit_t`
+#[repr(C)]
+pub struct lw_plonk_circuit_t {
+    _private: [u8; 0],
+}
 
 extern "C" {
     // ---- context
@@ -220,6 +225,26 @@ extern "C" {
                                             points: *const c_void, m: u32, weights: *const c_void, d_out_coeffs: *mut c_void,
                                             out_len_or_null: *mut usize, out_evals_host_or_null: *mut c_void,
                                             hip_stream: *mut c_void) -> c_int;
+    // ---- PLONK rounds 1-3 (k1, challenges, blinders and the public input on the host)
+    pub fn lw_plonk_circuit_create(field: Field, n: usize, k1: *const c_void, q_coeffs: *const c_void, s_coeffs: *const c_void,
+                                   s_lagrange: *const c_void, out: *mut *mut lw_plonk_circuit_t) -> c_int;
+    pub fn lw_plonk_circuit_destroy(circuit: *mut lw_plonk_circuit_t) -> c_int;
+    pub fn lw_plonk_round1(circuit: *const lw_plonk_circuit_t, witness: *const c_void, blinders_or_null: *const c_void,
+                           out_p_abc: *mut c_void) -> c_int;
+    pub fn lw_plonk_round1_device(circuit: *const lw_plonk_circuit_t, d_witness: *const c_void, blinders_or_null: *const c_void,
+                                  d_out_p_abc: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_plonk_round2(circuit: *const lw_plonk_circuit_t, witness: *const c_void, beta: *const c_void, gamma: *const c_void,
+                           blinders_or_null: *const c_void, out_z_values_or_null: *mut c_void, out_p_z: *mut c_void) -> c_int;
+    pub fn lw_plonk_round2_device(circuit: *const lw_plonk_circuit_t, d_witness: *const c_void, beta: *const c_void,
+                                  gamma: *const c_void, blinders_or_null: *const c_void, d_out_z_values_or_null: *mut c_void,
+                                  d_out_p_z: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_plonk_round3(circuit: *const lw_plonk_circuit_t, p_abc: *const c_void, p_z: *const c_void, public_input: *const c_void,
+                           n_pub: usize, beta: *const c_void, gamma: *const c_void, alpha: *const c_void,
+                           blinders_or_null: *const c_void, out_t: *mut c_void) -> c_int;
+    pub fn lw_plonk_round3_device(circuit: *const lw_plonk_circuit_t, d_p_abc: *const c_void, d_p_z: *const c_void,
+                                  public_input: *const c_void, n_pub: usize, beta: *const c_void, gamma: *const c_void,
+                                  alpha: *const c_void, blinders_or_null: *const c_void, d_out_t: *mut c_void,
+                                  hip_stream: *mut c_void) -> c_int;
 }
 
 // The C structs above must keep the sizes the header gives them.

@@ -377,6 +377,95 @@ pub fn deep_composition(field: Field, polys: &[&[[u64; 4]]], points: &[[u64; 4]]
     Ok((out, evals))
 }
 
+/// The device-side `CommonPreprocessedInput` of a PLONK circuit (provers/plonk/src/setup.rs, `lw_plonk_circuit_*`) and the
+/// prover's rounds 1-3 on it (provers/plonk/src/prover.rs:311-535, without the commitments).  Elements are stored
+/// `FieldElement`s (Montgomery form); `field` is Stark252 or BLS12-381 Fr.
+pub struct PlonkCircuit {
+    handle: *mut ffi::lw_plonk_circuit_t,
+    n: usize,
+}
+
+// SAFETY: the handle is read-only after creation and only used through the library.
+unsafe impl Send for PlonkCircuit {}
+unsafe impl Sync for PlonkCircuit {}
+
+impl PlonkCircuit {
+    /// `q_coeffs`: ql, qr, qo, qm, qc; `s_coeffs`: s1, s2, s3 (coefficient form, n each, zero padded); `s_lagrange`:
+    /// the three permutation columns in evaluation form.
+    pub fn new(field: Field, n: usize, k1: &[u64; 4], q_coeffs: &[[u64; 4]], s_coeffs: &[[u64; 4]], s_lagrange: &[[u64; 4]])
+               -> Result<Self, HipError> {
+        if q_coeffs.len() != 5 * n || s_coeffs.len() != 3 * n || s_lagrange.len() != 3 * n {
+            return Err(HipError::BadArgument("q_coeffs, s_coeffs, s_lagrange must hold 5n, 3n, 3n elements".into()));
+        }
+        let mut handle: *mut ffi::lw_plonk_circuit_t = ptr::null_mut();
+        // SAFETY: every slice is valid for the length checked above; `handle` receives an owned handle on success.
+        let rc = unsafe {
+            ffi::lw_plonk_circuit_create(field, n, k1.as_ptr() as *const c_void, q_coeffs.as_ptr() as *const c_void,
+                                         s_coeffs.as_ptr() as *const c_void, s_lagrange.as_ptr() as *const c_void, &mut handle)
+        };
+        check(rc)?;
+        Ok(Self { handle, n })
+    }
+
+    fn blinders<const K: usize>(b: Option<&[[u64; 4]; K]>) -> *const c_void {
+        b.map_or(ptr::null(), |b| b.as_ptr() as *const c_void)
+    }
+
+    /// `round_1`: p_a | p_b | p_c, n + 2 coefficients each.  `witness`: a | b | c, n values each.
+    pub fn round1(&self, witness: &[[u64; 4]], blinders: Option<&[[u64; 4]; 6]>) -> Result<Vec<[u64; 4]>, HipError> {
+        if witness.len() != 3 * self.n {
+            return Err(HipError::BadArgument("witness must hold 3n values".into()));
+        }
+        let mut out = vec![[0u64; 4]; 3 * (self.n + 2)];
+        // SAFETY: the handle is live until drop; `out` holds 3 (n + 2) elements.
+        check(unsafe { ffi::lw_plonk_round1(self.handle, witness.as_ptr() as *const c_void, Self::blinders(blinders), out.as_mut_ptr() as *mut c_void) })?;
+        Ok(out)
+    }
+
+    /// `round_2`: (the n values z_i, p_z with n + 3 coefficients).
+    pub fn round2(&self, witness: &[[u64; 4]], beta: &[u64; 4], gamma: &[u64; 4], blinders: Option<&[[u64; 4]; 3]>)
+                  -> Result<(Vec<[u64; 4]>, Vec<[u64; 4]>), HipError> {
+        if witness.len() != 3 * self.n {
+            return Err(HipError::BadArgument("witness must hold 3n values".into()));
+        }
+        let mut z = vec![[0u64; 4]; self.n];
+        let mut p_z = vec![[0u64; 4]; self.n + 3];
+        // SAFETY: the handle is live until drop; `z` holds n elements and `p_z` n + 3.
+        check(unsafe {
+            ffi::lw_plonk_round2(self.handle, witness.as_ptr() as *const c_void, beta.as_ptr() as *const c_void, gamma.as_ptr() as *const c_void,
+                                 Self::blinders(blinders), z.as_mut_ptr() as *mut c_void, p_z.as_mut_ptr() as *mut c_void)
+        })?;
+        Ok((z, p_z))
+    }
+
+    /// `round_3`: t_lo | t_mid | t_hi, n + 3 coefficients each, from round 1's and round 2's outputs.
+    #[allow(clippy::too_many_arguments)]
+    pub fn round3(&self, p_abc: &[[u64; 4]], p_z: &[[u64; 4]], public_input: &[[u64; 4]], beta: &[u64; 4], gamma: &[u64; 4],
+                  alpha: &[u64; 4], blinders: Option<&[[u64; 4]; 2]>) -> Result<Vec<[u64; 4]>, HipError> {
+        if p_abc.len() != 3 * (self.n + 2) || p_z.len() != self.n + 3 {
+            return Err(HipError::BadArgument("p_abc must hold 3 (n + 2) coefficients and p_z n + 3".into()));
+        }
+        let mut out = vec![[0u64; 4]; 3 * (self.n + 3)];
+        // SAFETY: the handle is live until drop; the inputs have the lengths checked above; `out` holds 3 (n + 3) elements.
+        check(unsafe {
+            ffi::lw_plonk_round3(self.handle, p_abc.as_ptr() as *const c_void, p_z.as_ptr() as *const c_void,
+                                 public_input.as_ptr() as *const c_void, public_input.len(), beta.as_ptr() as *const c_void,
+                                 gamma.as_ptr() as *const c_void, alpha.as_ptr() as *const c_void, Self::blinders(blinders),
+                                 out.as_mut_ptr() as *mut c_void)
+        })?;
+        Ok(out)
+    }
+}
+
+impl Drop for PlonkCircuit {
+    fn drop(&mut self) {
+        // SAFETY: the handle came from lw_plonk_circuit_create and is destroyed exactly once.
+        unsafe {
+            ffi::lw_plonk_circuit_destroy(self.handle);
+        }
+    }
+}
+
 impl Drop for Srs {
     fn drop(&mut self) {
         // SAFETY: the handle came from lw_hip_srs_create and is destroyed exactly once.
