@@ -440,6 +440,59 @@ int lw_stark_deep_composition_device(lw_field_t field, const void *const *d_poly
                                      const void *points, uint32_t m, const void *weights, void *d_out_coeffs,
                                      size_t *out_len_or_null, void *out_evals_host_or_null, void *hip_stream);
 
+/* ---- STARK round 4 tail: grinding and query openings ----
+ * What round_4_compute_and_run_fri_on_the_deep_composition_polynomial does after fri::commit_phase
+ * (provers/stark/src/prover.rs:596-617), on the data the calls above left in HBM.
+ *
+ * Grinding, grinding::generate_nonce (provers/stark/src/grinding.rs:40-54, is_valid_nonce_for_inner_hash :58-68,
+ * get_inner_hash :72-80):
+ *   inner = Keccak256(01 23 45 67 89 ab cd ed || seed (32 bytes) || grinding_factor (1 byte))
+ *   valid(nonce) <=> u64_be(Keccak256(inner || nonce.to_be_bytes())[0..8]) < 2^(64 - grinding_factor)
+ * The result is the SMALLEST valid nonce in [first, last], which is what the reference's build without `parallel` returns
+ * for [0, u64::MAX) (its rayon build returns any valid nonce).  *out_found = 1 and *out_nonce set, or *out_found = 0 and
+ * *out_nonce untouched when the range holds none.  seed32 and the outputs are host memory in both forms.
+ * grinding_factor outside 1 .. 63 (the reference's 1 << (64 - g) is undefined there; 0 means "no grinding", which is the
+ * caller's decision), a null pointer, first > last: LW_ERR_BAD_ARG, before any device work.
+ * The range is searched in ascending windows of lw_stark_grinding_window(grinding_factor) candidates, one bounded kernel
+ * launch and one 8-byte read-back per window; both forms return after the window that holds the result. */
+uint64_t lw_stark_grinding_window(uint32_t grinding_factor);
+int lw_stark_grinding_nonce(const uint8_t *seed32, uint32_t grinding_factor, uint64_t first, uint64_t last, uint64_t *out_nonce,
+                            int *out_found);
+int lw_stark_grinding_nonce_device(const uint8_t *seed32, uint32_t grinding_factor, uint64_t first, uint64_t last,
+                                   uint64_t *out_nonce, int *out_found, void *hip_stream);
+
+/* Query openings: MerkleTree::get_proof_by_pos (crypto/src/merkle_tree/merkle.rs:58-91, sibling_index / parent_index
+ * utils.rs:7-21) and the committed rows under the opened leaves, for any number of device-resident trees in one call.
+ * The path of leaf position pos in a tree of L leaves: i = pos + L - 1; push nodes[sibling(i)], i = parent(i) until i = 0:
+ * log2 L nodes, bottom first, none for L = 1.  The three openers of round 4 are this primitive:
+ *   fri::query_phase (fri/mod.rs:77-113)            tree k = layer k: n_cols 1, rows_per_leaf 2, bit_reverse 0 (the layer's
+ *                                                   evaluation is stored permuted), position iota >> (k + 1); the leaf holds
+ *                                                   evaluation[index & ~1], evaluation[index | 1], index = iota >> k
+ *   open_trace_polys (prover.rs:794-820)            rows_per_leaf 1, bit_reverse 1, positions 2 iota and 2 iota + 1
+ *   open_composition_poly (prover.rs:752-789)       rows_per_leaf 2, bit_reverse 1, position iota
+ * The primitive reads `nodes` and the columns however they were made (lw_stark_commit_columns* hashes one row per leaf). */
+typedef struct {
+    lw_field_t field;          /* LW_FIELD_STARK252 or LW_FIELD_BLS12_381_FR (elements of 4 x u64) */
+    const void *d_columns;     /* n_cols columns, column c at element c * col_stride_elems; NULL: paths only */
+    uint32_t n_cols;
+    uint64_t col_stride_elems; /* 0 = dense (2^log2_rows) */
+    uint32_t log2_rows;        /* rows committed */
+    uint32_t rows_per_leaf;    /* 1 or 2: leaf p covers committed rows p * r .. p * r + r - 1 */
+    int bit_reverse;           /* committed row j is natural row bitrev(j, log2_rows), as in lw_stark_commit_columns */
+    const void *d_nodes;       /* (2 * leaves - 1) x 32 bytes, root first; leaves = 2^log2_rows / rows_per_leaf */
+} lw_stark_tree_t;
+/* Opens every tree at its own q leaf positions: positions[t * q + s] (host).  Outputs are host buffers, tree-major, then
+ * query:  out_values  per (t, s) rows_per_leaf * n_cols elements, row-major (row, then column); trees with
+ *                     d_columns == NULL contribute nothing;
+ *         out_paths   per (t, s) log2(leaves_t) x 32 bytes, bottom first.
+ * One gather kernel for all trees and queries, one upload (tree table and positions), one download; synchronises.
+ * Duplicate positions are legal.  q = 0 or n_trees = 0: LW_OK, nothing written, no device needed.  LW_ERR_BAD_ARG before
+ * any device work: a position >= leaves, rows_per_leaf not 1 or 2, log2_rows = 0 with rows_per_leaf = 2, log2_rows > 31,
+ * a field other than the two, null d_nodes, a device buffer that is not 16-byte aligned, a stride below the column
+ * length, n_cols = 0 with columns, a null output that would be written. */
+int lw_stark_open_trees_device(const lw_stark_tree_t *trees, uint32_t n_trees, const uint64_t *positions, uint32_t q,
+                               void *out_values, uint8_t *out_paths, void *hip_stream);
+
 /* ---- PLONK prover rounds 1-3 ----
  * Prover::round_1 / round_2 / round_3 (provers/plonk/src/prover.rs:311-341, 343-381, 383-535) without the commitments:
  * the blinded wire polynomials, the permutation grand product z and the quotient parts t_lo, t_mid, t_hi.  With

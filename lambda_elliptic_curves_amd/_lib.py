@@ -36,6 +36,7 @@ EXPORTS = [
     "lw_stark_deep_composition", "lw_stark_deep_composition_device",
     "lw_plonk_circuit_create", "lw_plonk_circuit_destroy", "lw_plonk_round1", "lw_plonk_round1_device",
     "lw_plonk_round2", "lw_plonk_round2_device", "lw_plonk_round3", "lw_plonk_round3_device",
+    "lw_stark_grinding_window", "lw_stark_grinding_nonce", "lw_stark_grinding_nonce_device", "lw_stark_open_trees_device",
 ]
 
 
@@ -46,6 +47,12 @@ class Timings(C.Structure):
 
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
+
+
+class StarkTree(C.Structure):
+    """lw_stark_tree_t"""
+    _fields_ = [("field", C.c_int), ("d_columns", C.c_void_p), ("n_cols", C.c_uint32), ("col_stride_elems", C.c_uint64),
+                ("log2_rows", C.c_uint32), ("rows_per_leaf", C.c_uint32), ("bit_reverse", C.c_int), ("d_nodes", C.c_void_p)]
 
 
 class Profile(C.Structure):
@@ -203,6 +210,14 @@ def lib():
     L.lw_plonk_round3.restype = i
     L.lw_plonk_round3_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp]
     L.lw_plonk_round3_device.restype = i
+    L.lw_stark_grinding_window.argtypes = [u32]
+    L.lw_stark_grinding_window.restype = C.c_uint64
+    L.lw_stark_grinding_nonce.argtypes = [vp, u32, C.c_uint64, C.c_uint64, u64p, C.POINTER(i)]
+    L.lw_stark_grinding_nonce.restype = i
+    L.lw_stark_grinding_nonce_device.argtypes = [vp, u32, C.c_uint64, C.c_uint64, u64p, C.POINTER(i), vp]
+    L.lw_stark_grinding_nonce_device.restype = i
+    L.lw_stark_open_trees_device.argtypes = [C.POINTER(StarkTree), u32, u64p, u32, vp, vp, vp]
+    L.lw_stark_open_trees_device.restype = i
     _lib = L
     return L
 

@@ -61,6 +61,10 @@ int groth16_h_device(Context &c, const void *d_l, const void *d_r, const void *d
                      hipStream_t stream);
 int stripped_length_device(const void *d_elems, uint64_t n, uint64_t *d_len, hipStream_t stream);
 
+// ---- poly.hip
+// the lane's pinned staging c.deep_pin, at least `bytes` long and no longer read by an earlier call's upload
+int deep_pin(Context &c, size_t bytes);
+
 // ---- comm.hip
 void comm_release(Context &c);
 

@@ -478,8 +478,9 @@ static bool elem_is_zero(const void *e) {
     return memcmp(e, z, 32) == 0;
 }
 
-// pinned host memory for the tables of a DEEP call; the previous call's upload has been read once deep_pin_read fires
-static int deep_pin(Context &c, size_t bytes) {
+// pinned host memory for the tables of a DEEP call (and of lw_stark_open_trees_device, stark_query.hip); the previous
+// call's upload has been read once deep_pin_read fires
+int deep_pin(Context &c, size_t bytes) {
     if (c.deep_pin_read) LW_HIP_CHECK(hipEventSynchronize(c.deep_pin_read), LW_ERR_LAUNCH);
     else LW_HIP_CHECK(hipEventCreateWithFlags(&c.deep_pin_read, hipEventDisableTiming), LW_ERR_ALLOC);
     if (c.deep_pin_bytes >= bytes) return LW_OK;

@@ -136,3 +136,55 @@ def fri_commit_phase_device(field, number_layers, t_p0, n_coeffs, sample_zeta, a
         append_root(root)
     t_last, _ = fri_fold_device(field, t_poly, n, sample_zeta())
     return t_last, layers
+
+
+class Tree:
+    """One device-resident tree for open_trees_device (lw_stark_tree_t): t_nodes holds (2 * leaves - 1) x 32 bytes, root
+    first, leaves = 2^log2_rows / rows_per_leaf; t_columns (None: paths only) holds n_cols columns of 4 x u64 elements,
+    col_stride_elems apart (0: dense); committed row j is natural row bitrev(j) when bit_reverse."""
+
+    def __init__(self, field, t_nodes, log2_rows, t_columns=None, n_cols=0, rows_per_leaf=1, bit_reverse=True, col_stride_elems=0):
+        self.field, self.t_nodes, self.log2_rows, self.t_columns = field, t_nodes, int(log2_rows), t_columns
+        self.n_cols, self.rows_per_leaf, self.bit_reverse = int(n_cols), int(rows_per_leaf), bool(bit_reverse)
+        self.col_stride_elems = int(col_stride_elems)
+
+    @property
+    def log2_leaves(self):
+        return self.log2_rows - (self.rows_per_leaf - 1)
+
+
+def open_trees_device(trees, positions, stream=None):
+    """MerkleTree::get_proof_by_pos (crypto/src/merkle_tree/merkle.rs:58-91) and the committed rows for every tree at its
+    own leaf positions, in one gather.  positions: (n_trees, q) leaf positions.
+    -> (values, paths): values[t] is (q, rows_per_leaf, n_cols, 4) uint64, or None for a tree without columns;
+    paths[t] is (q, log2 leaves, 32) uint8, bottom first."""
+    pos = np.ascontiguousarray(positions, dtype=np.uint64)
+    n_trees = len(trees)
+    q = pos.size // n_trees if n_trees else 0
+    pos = pos.reshape(n_trees, q)
+    tab = (L.StarkTree * max(n_trees, 1))()
+    n_val = n_path = 0
+    for k, t in enumerate(trees):
+        tab[k] = L.StarkTree(t.field.field, t.t_columns.data_ptr() if t.t_columns is not None else None, t.n_cols,
+                             t.col_stride_elems, t.log2_rows, t.rows_per_leaf, 1 if t.bit_reverse else 0, t.t_nodes.data_ptr())
+        n_val += q * t.rows_per_leaf * t.n_cols if t.t_columns is not None else 0
+        n_path += q * max(t.log2_leaves, 0)
+    values = np.zeros((max(n_val, 1), 4), np.uint64)
+    paths = np.zeros((max(n_path, 1), 32), np.uint8)
+    if stream is None and n_trees and q:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    check(L.lib().lw_stark_open_trees_device(tab, n_trees, pos.ctypes.data_as(C.POINTER(C.c_uint64)), q,
+                                             values.ctypes.data_as(C.c_void_p), paths.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
+    out_v, out_p, v0, p0 = [], [], 0, 0
+    for t in trees:
+        if t.t_columns is not None:
+            nv = q * t.rows_per_leaf * t.n_cols
+            out_v.append(values[v0:v0 + nv].reshape(q, t.rows_per_leaf, t.n_cols, 4).copy())
+            v0 += nv
+        else:
+            out_v.append(None)
+        npth = q * max(t.log2_leaves, 0)
+        out_p.append(paths[p0:p0 + npth].reshape(q, max(t.log2_leaves, 0), 32).copy())
+        p0 += npth
+    return out_v, out_p

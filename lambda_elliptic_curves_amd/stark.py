@@ -72,3 +72,90 @@ def deep_composition_poly_device(field, t_trace_polys, trace_lens, t_parts, part
     n, ev = poly.deep_composition_device(field, list(t_trace_polys) + list(t_parts), list(trace_lens) + list(part_lens), points,
                                          weights, t_out, stream=stream)
     return n, ev[:C_, :T].copy(), ev[C_:, T].copy()
+
+
+# ---- round 4 after fri::commit_phase (provers/stark/src/prover.rs:596-617): grinding and the query openings
+
+def grinding_window(grinding_factor):
+    """Candidates per launch of the grinding search (lw_stark_grinding_window)."""
+    return int(L.lib().lw_stark_grinding_window(int(grinding_factor)))
+
+
+def grinding_nonce(seed, grinding_factor, first=0, last=2**64 - 1, stream=None):
+    """grinding::generate_nonce (provers/stark/src/grinding.rs:40-53) on the device: the smallest nonce in [first, last] with
+    u64_be(Keccak256(Keccak256(PREFIX || seed || grinding_factor) || nonce_be)[0..8]) < 2^(64 - grinding_factor), or None.
+    stream: a HIP stream handle (lw_stark_grinding_nonce_device); None: the library's own stream."""
+    import ctypes as C
+    from .errors import check
+    seed = bytes(seed)
+    if len(seed) != 32:
+        from .errors import InputError
+        raise InputError(f"the seed is {len(seed)} bytes, not 32")
+    if not (0 <= int(first) < 2**64 and 0 <= int(last) < 2**64):
+        from .errors import InputError
+        raise InputError("nonces are 64-bit")
+    buf = (C.c_uint8 * 32).from_buffer_copy(seed)
+    nonce, found = C.c_uint64(0), C.c_int(0)
+    if stream is None:
+        check(L.lib().lw_stark_grinding_nonce(buf, int(grinding_factor), int(first), int(last), C.byref(nonce), C.byref(found)))
+    else:
+        check(L.lib().lw_stark_grinding_nonce_device(buf, int(grinding_factor), int(first), int(last), C.byref(nonce), C.byref(found),
+                                                     C.c_void_p(stream)))
+    return int(nonce.value) if found.value else None
+
+
+def fri_query_phase_device(field, layers, iotas, stream=None):
+    """fri::query_phase (provers/stark/src/fri/mod.rs:77-113) over the layers merkle.fri_commit_phase_device returned,
+    [(t_evaluation, t_nodes, root, domain_size)], all resident.  -> per iota (layers_evaluations_sym, layers_auth_paths):
+    the reference's FriDecommitment, evaluations as (n_layers, 4) uint64 and one (log2(domain/2), 32) uint8 path per layer."""
+    from . import merkle
+    iotas = [int(x) for x in iotas]
+    if not layers or not iotas:
+        return [] if not layers else [(np.zeros((0, 4), np.uint64), []) for _ in iotas]
+    trees = [merkle.Tree(field, t_nodes, int(domain).bit_length() - 1, t_columns=t_ev, n_cols=1, rows_per_leaf=2, bit_reverse=False)
+             for (t_ev, t_nodes, _root, domain) in layers]
+    pos = np.array([[iota >> (k + 1) for iota in iotas] for k in range(len(layers))], np.uint64)
+    values, paths = merkle.open_trees_device(trees, pos, stream=stream)
+    out = []
+    for s, iota in enumerate(iotas):
+        # the leaf holds evaluation[index & ~1], evaluation[index | 1] with index = iota >> k; the symmetric one is index ^ 1
+        sym = np.stack([values[k][s, ((iota >> k) & 1) ^ 1, 0] for k in range(len(layers))])
+        out.append((sym, [paths[k][s] for k in range(len(layers))]))
+    return out
+
+
+def open_deep_composition_poly_device(field, main, composition, iotas, aux=None, stream=None):
+    """open_deep_composition_poly (provers/stark/src/prover.rs:822-860) on resident LDE columns and trees.
+    main / aux: (t_columns, n_cols, log2_rows, t_nodes) as lw_stark_commit_columns_device committed them (one bit-reversed row
+    per leaf, open_trace_polys :794-820); composition: the same tuple for the tree over pairs of consecutive bit-reversed
+    rows (2^(log2_rows - 1) leaves, :398-420, open_composition_poly :752-789).
+    -> per iota a dict tree name -> dict(evaluations, evaluations_sym (each (n_cols, 4) uint64), proof, proof_sym
+    ((log2 leaves, 32) uint8)): the reference's PolynomialOpenings; for the composition tree proof_sym is proof."""
+    from . import merkle
+    iotas = [int(x) for x in iotas]
+    names = ["main", "composition"] + (["aux"] if aux is not None else [])
+    if not iotas:
+        return []
+    q = len(iotas)
+    trace_pos = [2 * x for x in iotas] + [2 * x + 1 for x in iotas]          # 2 q positions: index, then index_sym
+    comp_pos = iotas + iotas                                                  # padded to the same q (duplicates are legal)
+    trees, pos = [], []
+    for name, src in (("main", main), ("composition", composition), ("aux", aux)):
+        if src is None:
+            continue
+        t_cols, n_cols, log2_rows, t_nodes = src
+        trees.append(merkle.Tree(field, t_nodes, log2_rows, t_columns=t_cols, n_cols=n_cols,
+                                 rows_per_leaf=2 if name == "composition" else 1, bit_reverse=True))
+        pos.append(comp_pos if name == "composition" else trace_pos)
+    values, paths = merkle.open_trees_device(trees, np.array(pos, np.uint64), stream=stream)
+    out = []
+    for s in range(q):
+        entry = {}
+        for k, name in enumerate(names):
+            if name == "composition":   # the even / odd split of prover.rs:778-787
+                entry[name] = dict(evaluations=values[k][s, 0], evaluations_sym=values[k][s, 1], proof=paths[k][s], proof_sym=paths[k][s])
+            else:
+                entry[name] = dict(evaluations=values[k][s, 0], evaluations_sym=values[k][q + s, 0], proof=paths[k][s],
+                                   proof_sym=paths[k][q + s])
+        out.append(entry)
+    return out

@@ -70,6 +70,23 @@ pub struct lw_timings_t {
     pub scratch_bytes: u64,
 }
 
+/// lw_stark_tree_t: one device-resident Merkle tree and the columns it commits (lw_stark_open_trees_device)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct lw_stark_tree_t {
+    pub field: Field,
+    /// NULL: paths only
+    pub d_columns: *const c_void,
+    pub n_cols: u32,
+    /// 0 = dense
+    pub col_stride_elems: u64,
+    pub log2_rows: u32,
+    /// 1 or 2
+    pub rows_per_leaf: u32,
+    pub bit_reverse: c_int,
+    pub d_nodes: *const c_void,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct lw_kernel_time_t {
@@ -225,6 +242,14 @@ extern "C" {
                                             points: *const c_void, m: u32, weights: *const c_void, d_out_coeffs: *mut c_void,
                                             out_len_or_null: *mut usize, out_evals_host_or_null: *mut c_void,
                                             hip_stream: *mut c_void) -> c_int;
+    // ---- STARK round 4 tail: grinding nonce search and query openings (seed, positions and every result on the host)
+    pub fn lw_stark_grinding_window(grinding_factor: u32) -> u64;
+    pub fn lw_stark_grinding_nonce(seed32: *const u8, grinding_factor: u32, first: u64, last: u64, out_nonce: *mut u64,
+                                   out_found: *mut c_int) -> c_int;
+    pub fn lw_stark_grinding_nonce_device(seed32: *const u8, grinding_factor: u32, first: u64, last: u64, out_nonce: *mut u64,
+                                          out_found: *mut c_int, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_stark_open_trees_device(trees: *const lw_stark_tree_t, n_trees: u32, positions: *const u64, q: u32,
+                                      out_values: *mut c_void, out_paths: *mut u8, hip_stream: *mut c_void) -> c_int;
     // ---- PLONK rounds 1-3 (k1, challenges, blinders and the public input on the host)
     pub fn lw_plonk_circuit_create(field: Field, n: usize, k1: *const c_void, q_coeffs: *const c_void, s_coeffs: *const c_void,
                                    s_lagrange: *const c_void, out: *mut *mut lw_plonk_circuit_t) -> c_int;
@@ -251,3 +276,4 @@ extern "C" {
 const _: () = assert!(core::mem::size_of::<lw_timings_t>() == 48);
 const _: () = assert!(core::mem::size_of::<lw_kernel_time_t>() == 64);
 const _: () = assert!(core::mem::size_of::<lw_profile_t>() == 8 + 32 * 64);
+const _: () = assert!(core::mem::size_of::<lw_stark_tree_t>() == 56);

@@ -377,6 +377,41 @@ pub fn deep_composition(field: Field, polys: &[&[[u64; 4]]], points: &[[u64; 4]]
     Ok((out, evals))
 }
 
+/// `grinding::generate_nonce` (provers/stark/src/grinding.rs:40-53) on the device: the smallest nonce in `[first, last]`
+/// whose hash has `grinding_factor` (1 ..= 63) leading zero bits, or `None`.
+pub fn stark_grinding_nonce(seed: &[u8; 32], grinding_factor: u8, first: u64, last: u64) -> Result<Option<u64>, HipError> {
+    let (mut nonce, mut found) = (0u64, 0 as c_int);
+    // SAFETY: the seed is 32 bytes; both outputs are valid for one value.
+    let rc = unsafe { ffi::lw_stark_grinding_nonce(seed.as_ptr(), grinding_factor as u32, first, last, &mut nonce, &mut found) };
+    check(rc)?;
+    Ok(if found != 0 { Some(nonce) } else { None })
+}
+
+/// `MerkleTree::get_proof_by_pos` (crypto/src/merkle_tree/merkle.rs:58-91) and the committed rows of device-resident trees:
+/// every tree is opened at its own `q` leaf positions, `positions[t * q + s]`.  Returns `(values, paths)` packed tree-major,
+/// then query: per (t, s) `rows_per_leaf * n_cols` elements (none for a tree without columns) and `log2(leaves)` nodes,
+/// bottom first.
+///
+/// # Safety
+/// The device pointers of every tree must be valid for the sizes its fields describe; `stream` is a HIP stream or null.
+pub unsafe fn stark_open_trees_device(trees: &[ffi::lw_stark_tree_t], positions: &[u64], q: usize, stream: *mut c_void)
+                                      -> Result<(Vec<[u64; 4]>, Vec<[u8; 32]>), HipError> {
+    assert_eq!(positions.len(), trees.len() * q, "positions: q per tree");
+    let (mut n_val, mut n_path) = (0usize, 0usize);
+    for t in trees {
+        if !t.d_columns.is_null() {
+            n_val += q * (t.rows_per_leaf as usize) * (t.n_cols as usize);
+        }
+        n_path += q * (t.log2_rows as usize).saturating_sub((t.rows_per_leaf as usize).saturating_sub(1));
+    }
+    let mut values = vec![[0u64; 4]; n_val];
+    let mut paths = vec![[0u8; 32]; n_path];
+    let rc = ffi::lw_stark_open_trees_device(trees.as_ptr(), trees.len() as u32, positions.as_ptr(), q as u32,
+                                             values.as_mut_ptr() as *mut c_void, paths.as_mut_ptr() as *mut u8, stream);
+    check(rc)?;
+    Ok((values, paths))
+}
+
 /// The device-side `CommonPreprocessedInput` of a PLONK circuit (provers/plonk/src/setup.rs, `lw_plonk_circuit_*`) and the
 /// prover's rounds 1-3 on it (provers/plonk/src/prover.rs:311-535, without the commitments).  Elements are stored
 /// `FieldElement`s (Montgomery form); `field` is Stark252 or BLS12-381 Fr.
