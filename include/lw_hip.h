@@ -556,6 +556,47 @@ int lw_plonk_round3_device(const lw_plonk_circuit_t *circuit, const void *d_p_ab
                            size_t n_pub, const void *beta, const void *gamma, const void *alpha, const void *blinders_or_null,
                            void *d_out_t, void *hip_stream);
 
+/* ---- Starknet Poseidon (PoseidonCairoStark252, crypto/src/hash/poseidon/mod.rs) ----
+ * The Hades permutation over Stark252 with the public Starknet parameters (state 3, rate 2, x^3, 4 + 83 + 4 rounds; round
+ * keys derived from sha256("Hades" + index), tools/gen_poseidon_consts.py), the three hashes built on it and the two
+ * Poseidon Merkle trees of the reference, batched: one work-item per permutation chain.  Stark252 only, so no lw_field_t.
+ * Elements are as everywhere else: 4 x u64, most significant limb first, Montgomery form, canonical (< p); every output
+ * is canonical.  Each function has a host form (buffers in host memory, complete on return) and a _device form (16-byte
+ * aligned device pointers, work enqueued on hip_stream; misaligned: LW_ERR_BAD_ARG).  n = 0 / n_rows = 0: LW_OK, nothing is
+ * touched.  More than 2^36 inputs: LW_ERR_ALLOC.
+ *
+ *   permute      n states of 3 elements -> n states (hades_permutation, mod.rs:27-41); out may be states (in place)
+ *   hash         out[i] = hash(x[i], y[i]): word 0 of the permuted (x, y, 2)                                (mod.rs:59-64)
+ *   hash_single  out[i] = hash_single(x[i]): word 0 of the permuted (x, 0, 1)                              (mod.rs:66-71)
+ *   hash_many    n_rows row-major rows of row_len >= 0 elements -> one digest each: the row, a 1, zeros up to a multiple
+ *                of 2, absorbed two elements per permutation into words 0 and 1; row_len = 0 hashes the padding block
+ *                alone (rows may then be NULL)                                                               (mod.rs:73-96) */
+int lw_poseidon_permute(const void *states, size_t n, void *out);
+int lw_poseidon_permute_device(const void *d_states, size_t n, void *d_out, void *hip_stream);
+int lw_poseidon_hash(const void *x, const void *y, size_t n, void *out);
+int lw_poseidon_hash_device(const void *d_x, const void *d_y, size_t n, void *d_out, void *hip_stream);
+int lw_poseidon_hash_single(const void *x, size_t n, void *out);
+int lw_poseidon_hash_single_device(const void *d_x, size_t n, void *d_out, void *hip_stream);
+int lw_poseidon_hash_many(const void *rows, size_t n_rows, size_t row_len, void *out);
+int lw_poseidon_hash_many_device(const void *d_rows, size_t n_rows, size_t row_len, void *d_out, void *hip_stream);
+
+/* The Poseidon twin of lw_stark_commit_columns[_device]: the tree over the 2^log2n rows of n_cols columns, with
+ *   leaf_mode = LW_POSEIDON_LEAF_SINGLE  TreePoseidon (merkle_tree/backends/field_element.rs:53-76): leaf = hash_single(v);
+ *                                        n_cols must be 1 (else LW_ERR_BAD_ARG)
+ *   leaf_mode = LW_POSEIDON_LEAF_MANY    BatchPoseidonTree (backends/field_element_vector.rs:61-85): leaf = hash_many(row),
+ *                                        which for n_cols = 1 is NOT hash_single
+ * and parent = hash(left, right).  nodes: (2 * 2^log2n - 1) elements of 32 bytes in the layout above, root first and leaves
+ * last (merkle_tree/utils.rs:43-71), so lw_stark_open_trees_device reads such a tree as it is; out_root: the root element,
+ * 32 bytes.  bit_reverse and col_stride_elems (0: dense) as in the Keccak form: leaf i commits natural row bitrev(i), the
+ * gather and the transposition happen in the leaf kernel and nothing is copied.  Exactly 2^log2n leaves: completing a
+ * shorter list by repeating its last leaf (utils.rs:24-29) stays with the caller, as for the Keccak trees.  log2n > 31:
+ * LW_ERR_ALLOC.  The _device form synchronises the stream only when out_root is not NULL. */
+typedef enum { LW_POSEIDON_LEAF_SINGLE = 0, LW_POSEIDON_LEAF_MANY = 1 } lw_poseidon_leaf_t;
+int lw_poseidon_commit_columns(const void *columns, uint32_t n_cols, uint32_t log2n, int bit_reverse, int leaf_mode,
+                               uint8_t *out_root, uint8_t *out_nodes_or_null);
+int lw_poseidon_commit_columns_device(const void *d_columns, uint32_t n_cols, uint64_t col_stride_elems, uint32_t log2n,
+                                      int bit_reverse, int leaf_mode, void *d_nodes, uint8_t *out_root, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

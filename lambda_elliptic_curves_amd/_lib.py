@@ -14,6 +14,7 @@ FIELD_STARK252, FIELD_BLS12_381_FR, FIELD_BABYBEAR = 0, 1, 2
 LAYOUT_U64_LIMBS_MS_FIRST, LAYOUT_BABYBEAR_U32_R32, LAYOUT_BABYBEAR_U64_R64, LAYOUT_EXT4_INTERLEAVED = 0, 1, 2, 3
 DIR_FORWARD, DIR_INVERSE = 0, 1
 CURVE_BLS12_381_G1, CURVE_BN254_G1, CURVE_BN254_G2, CURVE_BLS12_381_G2 = 0, 1, 2, 3
+POSEIDON_LEAF_SINGLE, POSEIDON_LEAF_MANY = 0, 1   # lw_poseidon_leaf_t
 (OK, ERR_INPUT_NOT_POW2, ERR_ORDER_TOO_LARGE, ERR_ROOT_OF_UNITY, ERR_LENGTH_MISMATCH, ERR_NO_DEVICE, ERR_ALLOC,
  ERR_LAUNCH, ERR_COMM, ERR_BAD_ARG, ERR_INV_ZERO) = (0, -1, -2, -3, -4, -5, -6, -7, -8, -9, -10)
 
@@ -37,6 +38,9 @@ EXPORTS = [
     "lw_plonk_circuit_create", "lw_plonk_circuit_destroy", "lw_plonk_round1", "lw_plonk_round1_device",
     "lw_plonk_round2", "lw_plonk_round2_device", "lw_plonk_round3", "lw_plonk_round3_device",
     "lw_stark_grinding_window", "lw_stark_grinding_nonce", "lw_stark_grinding_nonce_device", "lw_stark_open_trees_device",
+    "lw_poseidon_permute", "lw_poseidon_permute_device", "lw_poseidon_hash", "lw_poseidon_hash_device",
+    "lw_poseidon_hash_single", "lw_poseidon_hash_single_device", "lw_poseidon_hash_many", "lw_poseidon_hash_many_device",
+    "lw_poseidon_commit_columns", "lw_poseidon_commit_columns_device",
 ]
 
 
@@ -218,6 +222,26 @@ def lib():
     L.lw_stark_grinding_nonce_device.restype = i
     L.lw_stark_open_trees_device.argtypes = [C.POINTER(StarkTree), u32, u64p, u32, vp, vp, vp]
     L.lw_stark_open_trees_device.restype = i
+    L.lw_poseidon_permute.argtypes = [vp, sz, vp]
+    L.lw_poseidon_permute.restype = i
+    L.lw_poseidon_permute_device.argtypes = [vp, sz, vp, vp]
+    L.lw_poseidon_permute_device.restype = i
+    L.lw_poseidon_hash.argtypes = [vp, vp, sz, vp]
+    L.lw_poseidon_hash.restype = i
+    L.lw_poseidon_hash_device.argtypes = [vp, vp, sz, vp, vp]
+    L.lw_poseidon_hash_device.restype = i
+    L.lw_poseidon_hash_single.argtypes = [vp, sz, vp]
+    L.lw_poseidon_hash_single.restype = i
+    L.lw_poseidon_hash_single_device.argtypes = [vp, sz, vp, vp]
+    L.lw_poseidon_hash_single_device.restype = i
+    L.lw_poseidon_hash_many.argtypes = [vp, sz, sz, vp]
+    L.lw_poseidon_hash_many.restype = i
+    L.lw_poseidon_hash_many_device.argtypes = [vp, sz, sz, vp, vp]
+    L.lw_poseidon_hash_many_device.restype = i
+    L.lw_poseidon_commit_columns.argtypes = [vp, u32, u32, i, i, vp, vp]
+    L.lw_poseidon_commit_columns.restype = i
+    L.lw_poseidon_commit_columns_device.argtypes = [vp, u32, C.c_uint64, u32, i, i, vp, vp, vp]
+    L.lw_poseidon_commit_columns_device.restype = i
     _lib = L
     return L
 

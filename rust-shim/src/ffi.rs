@@ -270,7 +270,28 @@ extern "C" {
                                   public_input: *const c_void, n_pub: usize, beta: *const c_void, gamma: *const c_void,
                                   alpha: *const c_void, blinders_or_null: *const c_void, d_out_t: *mut c_void,
                                   hip_stream: *mut c_void) -> c_int;
+    // ---- Starknet Poseidon over Stark252: batched permutations, hashes and Merkle trees
+    pub fn lw_poseidon_permute(states: *const c_void, n: usize, out: *mut c_void) -> c_int;
+    pub fn lw_poseidon_permute_device(d_states: *const c_void, n: usize, d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_poseidon_hash(x: *const c_void, y: *const c_void, n: usize, out: *mut c_void) -> c_int;
+    pub fn lw_poseidon_hash_device(d_x: *const c_void, d_y: *const c_void, n: usize, d_out: *mut c_void,
+                                   hip_stream: *mut c_void) -> c_int;
+    pub fn lw_poseidon_hash_single(x: *const c_void, n: usize, out: *mut c_void) -> c_int;
+    pub fn lw_poseidon_hash_single_device(d_x: *const c_void, n: usize, d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_poseidon_hash_many(rows: *const c_void, n_rows: usize, row_len: usize, out: *mut c_void) -> c_int;
+    pub fn lw_poseidon_hash_many_device(d_rows: *const c_void, n_rows: usize, row_len: usize, d_out: *mut c_void,
+                                        hip_stream: *mut c_void) -> c_int;
+    pub fn lw_poseidon_commit_columns(columns: *const c_void, n_cols: u32, log2n: u32, bit_reverse: c_int, leaf_mode: c_int,
+                                      out_root: *mut u8, out_nodes_or_null: *mut u8) -> c_int;
+    pub fn lw_poseidon_commit_columns_device(d_columns: *const c_void, n_cols: u32, col_stride_elems: u64, log2n: u32,
+                                             bit_reverse: c_int, leaf_mode: c_int, d_nodes: *mut c_void, out_root: *mut u8,
+                                             hip_stream: *mut c_void) -> c_int;
 }
+
+/// lw_poseidon_leaf_t: TreePoseidon (leaf = hash_single of one column)
+pub const LW_POSEIDON_LEAF_SINGLE: c_int = 0;
+/// lw_poseidon_leaf_t: BatchPoseidonTree (leaf = hash_many of the row)
+pub const LW_POSEIDON_LEAF_MANY: c_int = 1;
 
 // The C structs above must keep the sizes the header gives them.
 const _: () = assert!(core::mem::size_of::<lw_timings_t>() == 48);

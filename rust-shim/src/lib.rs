@@ -412,6 +412,59 @@ pub unsafe fn stark_open_trees_device(trees: &[ffi::lw_stark_tree_t], positions:
     Ok((values, paths))
 }
 
+/// `PoseidonCairoStark252::hades_permutation` (crypto/src/hash/poseidon/mod.rs:27-41) on a batch of states, in place.
+pub fn poseidon_permute(states: &mut [[[u64; 4]; 3]]) -> Result<(), HipError> {
+    let p = states.as_mut_ptr() as *mut c_void;
+    // SAFETY: `states` is valid for its length; the call may run in place.
+    check(unsafe { ffi::lw_poseidon_permute(p as *const c_void, states.len(), p) })
+}
+
+/// `PoseidonCairoStark252::hash(x[i], y[i])` (mod.rs:59-64) for every pair.
+pub fn poseidon_hash(x: &[[u64; 4]], y: &[[u64; 4]]) -> Result<Vec<[u64; 4]>, HipError> {
+    assert_eq!(x.len(), y.len(), "one y per x");
+    let mut out = vec![[0u64; 4]; x.len()];
+    // SAFETY: all three buffers hold x.len() elements.
+    check(unsafe { ffi::lw_poseidon_hash(x.as_ptr() as *const c_void, y.as_ptr() as *const c_void, x.len(), out.as_mut_ptr() as *mut c_void) })?;
+    Ok(out)
+}
+
+/// `PoseidonCairoStark252::hash_single(x[i])` (mod.rs:66-71) for every element.
+pub fn poseidon_hash_single(x: &[[u64; 4]]) -> Result<Vec<[u64; 4]>, HipError> {
+    let mut out = vec![[0u64; 4]; x.len()];
+    // SAFETY: both buffers hold x.len() elements.
+    check(unsafe { ffi::lw_poseidon_hash_single(x.as_ptr() as *const c_void, x.len(), out.as_mut_ptr() as *mut c_void) })?;
+    Ok(out)
+}
+
+/// `PoseidonCairoStark252::hash_many` (mod.rs:73-96) of every row of a row-major matrix with `row_len` columns
+/// (`row_len = 0`: `n_rows` digests of the empty input).
+pub fn poseidon_hash_many(rows: &[[u64; 4]], n_rows: usize, row_len: usize) -> Result<Vec<[u64; 4]>, HipError> {
+    assert_eq!(rows.len(), n_rows * row_len, "rows: n_rows x row_len elements");
+    let mut out = vec![[0u64; 4]; n_rows];
+    // SAFETY: `rows` holds n_rows x row_len elements, `out` n_rows.
+    check(unsafe { ffi::lw_poseidon_hash_many(rows.as_ptr() as *const c_void, n_rows, row_len, out.as_mut_ptr() as *mut c_void) })?;
+    Ok(out)
+}
+
+/// `MerkleTree<TreePoseidon<PoseidonCairoStark252>>::build` (`batch = false`, one column) or
+/// `MerkleTree<BatchPoseidonTree<PoseidonCairoStark252>>::build` (`batch = true`) over the rows of `columns`, each a
+/// natural-order column of the same power-of-two length; row `i` of the tree is natural row `bitrev(i)` when
+/// `bit_reverse`.  Returns the reference's `nodes` (root first, leaves last).
+pub fn poseidon_commit_columns(columns: &[&[[u64; 4]]], bit_reverse: bool, batch: bool) -> Result<Vec<[u64; 4]>, HipError> {
+    let n = columns.first().map_or(0, |c| c.len());
+    assert!(n.is_power_of_two() && columns.iter().all(|c| c.len() == n), "columns: one power-of-two length");
+    let flat: Vec<[u64; 4]> = columns.iter().flat_map(|c| c.iter().copied()).collect();
+    let mut nodes = vec![[0u64; 4]; 2 * n - 1];
+    let mut root = [0u64; 4];
+    let mode = if batch { ffi::LW_POSEIDON_LEAF_MANY } else { ffi::LW_POSEIDON_LEAF_SINGLE };
+    // SAFETY: `flat` holds n_cols x n elements, `nodes` 2n - 1 elements of 32 bytes, `root` 32 bytes.
+    check(unsafe {
+        ffi::lw_poseidon_commit_columns(flat.as_ptr() as *const c_void, columns.len() as u32, n.trailing_zeros(), bit_reverse as c_int,
+                                        mode, root.as_mut_ptr() as *mut u8, nodes.as_mut_ptr() as *mut u8)
+    })?;
+    Ok(nodes)
+}
+
 /// The device-side `CommonPreprocessedInput` of a PLONK circuit (provers/plonk/src/setup.rs, `lw_plonk_circuit_*`) and the
 /// prover's rounds 1-3 on it (provers/plonk/src/prover.rs:311-535, without the commitments).  Elements are stored
 /// `FieldElement`s (Montgomery form); `field` is Stark252 or BLS12-381 Fr.
