@@ -18,6 +18,8 @@
  *                                                in_place_bit_reverse_permute (math/src/fft/cpu/bit_reversing.rs:2-9)
  *   - lw_hip_msm / lw_hip_msm_device        <->  msm::pippenger::msm (math/src/msm/pippenger.rs:18-32)
  *   - lw_hip_msm_limbs[_device]             <->  the same for UnsignedInteger<NUM_LIMBS>, NUM_LIMBS = 1 .. 8
+ *   - lw_circle_evaluate_cfft / interpolate <->  evaluate_cfft / interpolate_cfft (math/src/circle/polynomial.rs:18-72),
+ *     lw_circle_get_twiddles                     get_twiddles (math/src/circle/twiddles.rs:13-58), over Mersenne31
  *   - lw_hip_init / lw_hip_shutdown         <->  CudaState::new (math/src/fft/gpu/cuda/state.rs:29-38); the
  *                                                reference builds and drops device state on every call, this
  *                                                library keeps one context (twiddle caches, scratch, streams)
@@ -596,6 +598,36 @@ int lw_poseidon_commit_columns(const void *columns, uint32_t n_cols, uint32_t lo
                                uint8_t *out_root, uint8_t *out_nodes_or_null);
 int lw_poseidon_commit_columns_device(const void *d_columns, uint32_t n_cols, uint64_t col_stride_elems, uint32_t log2n,
                                       int bit_reverse, int leaf_mode, void *d_nodes, uint8_t *out_root, void *hip_stream);
+
+/* ---- Circle FFT over Mersenne31 (math/src/circle/: evaluate_cfft, interpolate_cfft, get_twiddles) ----
+ * The transform between the 2^log2n coefficients of a polynomial in the basis {1, y, x, xy, 2x^2 - 1, ...} (coefficient k
+ * multiplies y^(k & 1) * prod_t pi^t(x)^(bit t+1 of k), pi(x) = 2x^2 - 1) and its values on the standard coset
+ * g_{2n} + i g_n, i = 0 .. n-1 in that order, of the circle group over p = 2^31 - 1 (polynomial.rs:18-72).  Mersenne31 only,
+ * one u32 per element and no Montgomery form, so no lw_field_t / lw_layout_t.  Every input word is read as from_base_type
+ * reads it, (w & p) + (w >> 31): any u32 is accepted and p means 0.  Every output word is the canonical residue (< p), which
+ * is what the reference's PartialEq compares.
+ *   log2n      1 .. 30 (g_{2n} must exist in a group of order 2^31); 0: LW_ERR_BAD_ARG; above 30: LW_ERR_ORDER_TOO_LARGE
+ *   batch      columns of n words, batch_stride words apart (0: n); the words between two columns are not touched
+ *   in place   out == in is allowed; any other overlap of the two is LW_ERR_BAD_ARG, like a NULL pointer, batch = 0 and a
+ *              stride below n.  All of this is decided before any device work.
+ * interpolate_cfft includes the factor n^-1.  The twiddle tables are generated on the device and cached (the x-layers once
+ * for every size, the y-layer per size); both permutations of each direction are folded into the first and last pass.
+ * The reference's own evaluate_cfft stops at 2^8 points (Coset::get_coset_points keeps the size in a u8). */
+int lw_circle_evaluate_cfft(const uint32_t *coeffs, uint32_t *out, uint32_t log2n, uint32_t batch, size_t batch_stride);
+int lw_circle_interpolate_cfft(const uint32_t *evals, uint32_t *out, uint32_t log2n, uint32_t batch, size_t batch_stride);
+int lw_circle_evaluate_cfft_device(const uint32_t *d_in, uint32_t *d_out, uint32_t log2n, uint32_t batch, size_t batch_stride,
+                                   void *hip_stream);
+int lw_circle_interpolate_cfft_device(const uint32_t *d_in, uint32_t *d_out, uint32_t log2n, uint32_t batch, size_t batch_stride,
+                                      void *hip_stream);
+/* out = evaluate_cfft(zero_pad(interpolate_cfft(evals), 2^log2_out)) per column: the basis does not depend on n, so zero
+ * padding is the embedding into the larger domain.  The coefficients stay on the device, the padding is never written and
+ * the evaluation layers that would only meet it are skipped.  log2_out < log2_in: LW_ERR_BAD_ARG; log2_out = log2_in
+ * returns the input reduced mod p.  Strides in words, 0: dense. */
+int lw_circle_lde_device(const uint32_t *d_evals, uint32_t log2_in, size_t in_stride, uint32_t *d_out, uint32_t log2_out,
+                         size_t out_stride, uint32_t batch, void *hip_stream);
+/* get_twiddles(Coset::new_standard(log2n), config) (twiddles.rs:13-58), the layers concatenated: n - 1 words to host memory.
+ * config 0 (Evaluation): lengths 1, 2, .., n/2; config 1 (Interpolation): the inverses, lengths n/2, .., 1. */
+int lw_circle_get_twiddles(uint32_t log2n, int config, uint32_t *out);
 
 #ifdef __cplusplus
 }

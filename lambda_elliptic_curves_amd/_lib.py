@@ -41,6 +41,8 @@ EXPORTS = [
     "lw_poseidon_permute", "lw_poseidon_permute_device", "lw_poseidon_hash", "lw_poseidon_hash_device",
     "lw_poseidon_hash_single", "lw_poseidon_hash_single_device", "lw_poseidon_hash_many", "lw_poseidon_hash_many_device",
     "lw_poseidon_commit_columns", "lw_poseidon_commit_columns_device",
+    "lw_circle_evaluate_cfft", "lw_circle_interpolate_cfft", "lw_circle_evaluate_cfft_device", "lw_circle_interpolate_cfft_device",
+    "lw_circle_lde_device", "lw_circle_get_twiddles",
 ]
 
 
@@ -242,6 +244,16 @@ def lib():
     L.lw_poseidon_commit_columns.restype = i
     L.lw_poseidon_commit_columns_device.argtypes = [vp, u32, C.c_uint64, u32, i, i, vp, vp, vp]
     L.lw_poseidon_commit_columns_device.restype = i
+    for name in ("lw_circle_evaluate_cfft", "lw_circle_interpolate_cfft"):
+        getattr(L, name).argtypes = [vp, vp, u32, u32, sz]
+        getattr(L, name).restype = i
+    for name in ("lw_circle_evaluate_cfft_device", "lw_circle_interpolate_cfft_device"):
+        getattr(L, name).argtypes = [vp, vp, u32, u32, sz, vp]
+        getattr(L, name).restype = i
+    L.lw_circle_lde_device.argtypes = [vp, u32, sz, vp, u32, sz, u32, vp]
+    L.lw_circle_lde_device.restype = i
+    L.lw_circle_get_twiddles.argtypes = [u32, i, vp]
+    L.lw_circle_get_twiddles.restype = i
     _lib = L
     return L
 

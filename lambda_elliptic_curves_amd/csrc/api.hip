@@ -93,6 +93,12 @@ static void release_everything() {
             sh.tw[f][d].buf.release();
             sh.tw[f][d].valid = false;
         }
+    sh.circle_x.buf.release();
+    sh.circle_x.valid = false;
+    for (TwiddleTable &t : sh.circle_y) {
+        t.buf.release();
+        t.valid = false;
+    }
 }
 // SharedState::rw held unique
 static int init_locked(const int *device_ids, int n_devices) {

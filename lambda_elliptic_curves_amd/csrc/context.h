@@ -65,6 +65,10 @@ struct ProfSpan {
 struct SharedState {
     std::shared_mutex rw;
     TwiddleTable tw[3][2];   // [field][dir]
+    // Circle FFT over Mersenne31 (circle.hip), same discipline (ensure_twiddle_table below).  Each buffer holds the
+    // evaluation twiddles in its first half and their inverses (interpolation) in the second.
+    TwiddleTable circle_x;       // the x-layers 0 .. log_n - 2, layer i at word 2^i - 1: they do not depend on the size
+    TwiddleTable circle_y[31];   // [log2n]: the last (y) layer of that size, 2^(log2n - 1) words
     bool initialised = false;
     int device = -1;
 };

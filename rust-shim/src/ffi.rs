@@ -286,6 +286,16 @@ extern "C" {
     pub fn lw_poseidon_commit_columns_device(d_columns: *const c_void, n_cols: u32, col_stride_elems: u64, log2n: u32,
                                              bit_reverse: c_int, leaf_mode: c_int, d_nodes: *mut c_void, out_root: *mut u8,
                                              hip_stream: *mut c_void) -> c_int;
+    // ---- circle FFT over Mersenne31: one u32 per element, canonical residues out
+    pub fn lw_circle_evaluate_cfft(coeffs: *const u32, out: *mut u32, log2n: u32, batch: u32, batch_stride: usize) -> c_int;
+    pub fn lw_circle_interpolate_cfft(evals: *const u32, out: *mut u32, log2n: u32, batch: u32, batch_stride: usize) -> c_int;
+    pub fn lw_circle_evaluate_cfft_device(d_in: *const u32, d_out: *mut u32, log2n: u32, batch: u32, batch_stride: usize,
+                                          hip_stream: *mut c_void) -> c_int;
+    pub fn lw_circle_interpolate_cfft_device(d_in: *const u32, d_out: *mut u32, log2n: u32, batch: u32, batch_stride: usize,
+                                             hip_stream: *mut c_void) -> c_int;
+    pub fn lw_circle_lde_device(d_evals: *const u32, log2_in: u32, in_stride: usize, d_out: *mut u32, log2_out: u32,
+                                out_stride: usize, batch: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_circle_get_twiddles(log2n: u32, config: c_int, out: *mut u32) -> c_int;
 }
 
 /// lw_poseidon_leaf_t: TreePoseidon (leaf = hash_single of one column)

@@ -620,3 +620,25 @@ impl Drop for Comm {
         }
     }
 }
+
+/// `evaluate_cfft` (math/src/circle/polynomial.rs:18-35) over Mersenne31: the values of the polynomial with these
+/// coefficients on the standard coset of the same (power-of-two, at least 2) size, as canonical residues.
+pub fn circle_evaluate_cfft(coeffs: &[u32]) -> Result<Vec<u32>, HipError> {
+    assert!(coeffs.len().is_power_of_two() && coeffs.len() >= 2, "coeffs: a power of two, at least 2");
+    let mut out = vec![0u32; coeffs.len()];
+    // SAFETY: both buffers hold coeffs.len() words.
+    check(unsafe { ffi::lw_circle_evaluate_cfft(coeffs.as_ptr(), out.as_mut_ptr(), coeffs.len().trailing_zeros(), 1, 0) })?;
+    Ok(out)
+}
+
+/// `interpolate_cfft` (polynomial.rs:42-72); an empty input gives an empty result, as there.
+pub fn circle_interpolate_cfft(evals: &[u32]) -> Result<Vec<u32>, HipError> {
+    if evals.is_empty() {
+        return Ok(Vec::new());
+    }
+    assert!(evals.len().is_power_of_two() && evals.len() >= 2, "evals: a power of two, at least 2");
+    let mut out = vec![0u32; evals.len()];
+    // SAFETY: both buffers hold evals.len() words.
+    check(unsafe { ffi::lw_circle_interpolate_cfft(evals.as_ptr(), out.as_mut_ptr(), evals.len().trailing_zeros(), 1, 0) })?;
+    Ok(out)
+}
