@@ -495,6 +495,77 @@ typedef struct {
 int lw_stark_open_trees_device(const lw_stark_tree_t *trees, uint32_t n_trees, const uint64_t *positions, uint32_t q,
                                void *out_values, uint8_t *out_paths, void *hip_stream);
 
+/* ---- Batch inversion ----
+ * FieldElement::inplace_batch_inverse (math/src/field/element.rs:47-65): out[i] = in[i]^-1, canonical, over
+ * LW_FIELD_STARK252 or LW_FIELD_BLS12_381_FR (anything else: LW_ERR_BAD_ARG).  in == out is legal.  n = 0: LW_OK, no
+ * device needed.  A zero element: LW_ERR_INV_ZERO (FieldError::InvZeroError), the output is then unspecified.  Both forms
+ * synchronise once, to learn whether there was a zero.  Device buffers are 16-byte aligned.
+ * lw_field_batch_inverse_block(): the elements one workgroup owns (a chunk per work-item, one inversion per chunk). */
+int lw_field_batch_inverse(lw_field_t field, const void *in, size_t n, void *out);
+int lw_field_batch_inverse_device(lw_field_t field, const void *d_in, size_t n, void *d_out, void *hip_stream);
+uint64_t lw_field_batch_inverse_block(void);
+
+/* ---- STARK round 2: the composition polynomial and its commitment ----
+ * round_2_compute_composition_polynomial (provers/stark/src/prover.rs:428-484) without the AIR's compute_transition:
+ * ConstraintEvaluator::evaluate (constraints/evaluator.rs:33-225), interpolate_offset_fft, break_in_parts, the LDE of the
+ * parts and commit_composition_polynomial (prover.rs:398-425).  Fields as above; elements as stored (Montgomery form,
+ * 4 x u64, most significant limb first); scalars are host values, vectors device pointers in the _device forms.
+ *
+ * n = 2^log2_trace, N = n * 2^log2_blowup, g and w the primitive n-th and N-th roots, h = coset_offset, x_i = h w^i.
+ * d_columns[c]: LDE column c, N elements, natural order (main columns first, then auxiliary ones; a boundary
+ * constraint's col indexes this table).  Row c of d_transition_evals, at c * transition_stride_elems (0 = N), holds T_c(i),
+ * compute_transition's value for constraint c at LDE row i.  For i in [0, N):
+ *     out[i] = sum_c coeff_c Zc[i] T_c(i)  +  sum_k coeff_k (col_k[i] - value_k) / (x_i - g^step_k)
+ *     Zc[i]  = cycle_c[i mod len_c] * prod_{k = 1 .. end_exemptions} (x_i - g^(n - k period))
+ * with zerofier_evaluations_on_extended_domain's cycle (constraints/transition.rs:108-205, integer divisions truncate):
+ *     exemptions_period == 0:  len = 2^log2_blowup * period,  cycle[e] = 1 / ((h w^e)^(n / period) - g^(offset n / period))
+ *     otherwise (ep):          len = 2^log2_blowup * ep,      cycle[e] = ((h w^e)^(n / ep) - g^(n peo / ep)) / (that denominator)
+ * n_boundary = 0 or n_transitions = 0 is legal (both: zeros).  LW_ERR_BAD_ARG: period = 0, col >= n_cols, log2_trace +
+ * log2_blowup beyond the NTT (34, or the field's two-adicity), end_exemptions * period > n (the reference's unsigned
+ * n - k period underflows), a null or misaligned buffer.  LW_ERR_INV_ZERO: a zero denominator — in the boundary part exactly
+ * when h^N = 1 (checked on the host), in a cycle table as the device finds it.  Synchronises once when n_transitions > 0. */
+typedef struct {
+    uint32_t col, reserved;
+    uint64_t step;
+    uint64_t value[4];
+    uint64_t coeff[4];
+} lw_stark_boundary_t;
+typedef struct {
+    uint64_t period, offset, end_exemptions;
+    uint64_t exemptions_period; /* 0: none */
+    uint64_t periodic_exemptions_offset;
+    uint64_t coeff[4];
+} lw_stark_transition_t;
+int lw_stark_constraint_evaluations_device(lw_field_t field, const void *const *d_columns, uint32_t n_cols, uint32_t log2_trace,
+                                           uint32_t log2_blowup, const void *coset_offset, const lw_stark_boundary_t *boundary,
+                                           uint32_t n_boundary, const lw_stark_transition_t *transitions, uint32_t n_transitions,
+                                           const void *d_transition_evals, uint64_t transition_stride_elems, void *d_out,
+                                           void *hip_stream);
+/* H = interpolate_offset_fft(d_evals, h) (N = 2^log2_lde coefficients); break_in_parts(n_parts)
+ * (math/src/polynomial/mod.rs:289-302): part j takes coefficients j, j + P, j + 2 P, ... into a zero-padded block of
+ * L = next_power_of_two(ceil(N / P)) elements, d_parts_coeffs is P x L; evaluate_polynomial_on_lde_domain of every part
+ * (prover.rs:150-166: its values at x_0 .. x_{N-1}, whatever the part's degree) into d_parts_lde, P x N, natural order
+ * (NULL: not wanted).  out_part_lens_or_null: the P stripped lengths, as lw_stark_deep_composition_device takes them;
+ * asking for them synchronises.  1 <= n_parts <= N, else LW_ERR_BAD_ARG.  d_evals is not modified. */
+int lw_stark_composition_parts_device(lw_field_t field, const void *d_evals, uint32_t log2_lde, const void *coset_offset,
+                                      uint32_t n_parts, void *d_parts_coeffs, void *d_parts_lde, size_t *out_part_lens_or_null,
+                                      void *hip_stream);
+/* commit_composition_polynomial: rows of n_parts elements, bit-reverse permuted, consecutive rows merged in pairs, then
+ * BatchedMerkleTree<Keccak256>: leaf i of N / 2 hashes [H_0 .. H_{P-1}](rho) || [H_0 .. H_{P-1}](rho + N / 2),
+ * rho = bitrev(i, log2_lde - 1).  Part j starts at element j * col_stride_elems (0 = N).  d_nodes: (N - 1) x 32 bytes, root
+ * first — the layout lw_stark_open_trees_device reads with rows_per_leaf = 2.  log2_lde = 0: LW_ERR_BAD_ARG.
+ * out_root_or_null: host, 32 bytes (synchronises when given). */
+int lw_stark_commit_composition_device(lw_field_t field, const void *d_parts_lde, uint32_t n_parts, uint64_t col_stride_elems,
+                                       uint32_t log2_lde, void *d_nodes, uint8_t *out_root_or_null, void *hip_stream);
+/* The three calls above on host arrays, through the library's staging: columns is n_cols x N, transition_evals
+ * n_transitions x N, both dense.  out_parts_coeffs: P x L; out_part_lens: P; out_root: 32 bytes; out_nodes_or_null:
+ * (N - 1) x 32 bytes; out_parts_lde_or_null: P x N. */
+int lw_stark_round2(lw_field_t field, const void *columns, uint32_t n_cols, uint32_t log2_trace, uint32_t log2_blowup,
+                    const void *coset_offset, const lw_stark_boundary_t *boundary, uint32_t n_boundary,
+                    const lw_stark_transition_t *transitions, uint32_t n_transitions, const void *transition_evals, uint32_t n_parts,
+                    void *out_parts_coeffs, size_t *out_part_lens, uint8_t *out_root, uint8_t *out_nodes_or_null,
+                    void *out_parts_lde_or_null);
+
 /* ---- PLONK prover rounds 1-3 ----
  * Prover::round_1 / round_2 / round_3 (provers/plonk/src/prover.rs:311-341, 343-381, 383-535) without the commitments:
  * the blinded wire polynomials, the permutation grand product z and the quotient parts t_lo, t_mid, t_hi.  With

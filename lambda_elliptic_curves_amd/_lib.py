@@ -43,6 +43,9 @@ EXPORTS = [
     "lw_poseidon_commit_columns", "lw_poseidon_commit_columns_device",
     "lw_circle_evaluate_cfft", "lw_circle_interpolate_cfft", "lw_circle_evaluate_cfft_device", "lw_circle_interpolate_cfft_device",
     "lw_circle_lde_device", "lw_circle_get_twiddles",
+    "lw_field_batch_inverse", "lw_field_batch_inverse_device", "lw_field_batch_inverse_block",
+    "lw_stark_constraint_evaluations_device", "lw_stark_composition_parts_device", "lw_stark_commit_composition_device",
+    "lw_stark_round2",
 ]
 
 
@@ -59,6 +62,18 @@ class StarkTree(C.Structure):
     """lw_stark_tree_t"""
     _fields_ = [("field", C.c_int), ("d_columns", C.c_void_p), ("n_cols", C.c_uint32), ("col_stride_elems", C.c_uint64),
                 ("log2_rows", C.c_uint32), ("rows_per_leaf", C.c_uint32), ("bit_reverse", C.c_int), ("d_nodes", C.c_void_p)]
+
+
+class StarkBoundary(C.Structure):
+    """lw_stark_boundary_t"""
+    _fields_ = [("col", C.c_uint32), ("reserved", C.c_uint32), ("step", C.c_uint64), ("value", C.c_uint64 * 4),
+                ("coeff", C.c_uint64 * 4)]
+
+
+class StarkTransition(C.Structure):
+    """lw_stark_transition_t"""
+    _fields_ = [("period", C.c_uint64), ("offset", C.c_uint64), ("end_exemptions", C.c_uint64), ("exemptions_period", C.c_uint64),
+                ("periodic_exemptions_offset", C.c_uint64), ("coeff", C.c_uint64 * 4)]
 
 
 class Profile(C.Structure):
@@ -254,6 +269,21 @@ def lib():
     L.lw_circle_lde_device.restype = i
     L.lw_circle_get_twiddles.argtypes = [u32, i, vp]
     L.lw_circle_get_twiddles.restype = i
+    L.lw_field_batch_inverse.argtypes = [i, vp, sz, vp]
+    L.lw_field_batch_inverse.restype = i
+    L.lw_field_batch_inverse_device.argtypes = [i, vp, sz, vp, vp]
+    L.lw_field_batch_inverse_device.restype = i
+    L.lw_field_batch_inverse_block.argtypes = []
+    L.lw_field_batch_inverse_block.restype = C.c_uint64
+    bp, tp = C.POINTER(StarkBoundary), C.POINTER(StarkTransition)
+    L.lw_stark_constraint_evaluations_device.argtypes = [i, vp, u32, u32, u32, vp, bp, u32, tp, u32, vp, C.c_uint64, vp, vp]
+    L.lw_stark_constraint_evaluations_device.restype = i
+    L.lw_stark_composition_parts_device.argtypes = [i, vp, u32, vp, u32, vp, vp, C.POINTER(sz), vp]
+    L.lw_stark_composition_parts_device.restype = i
+    L.lw_stark_commit_composition_device.argtypes = [i, vp, u32, C.c_uint64, u32, vp, vp, vp]
+    L.lw_stark_commit_composition_device.restype = i
+    L.lw_stark_round2.argtypes = [i, vp, u32, u32, u32, vp, bp, u32, tp, u32, vp, u32, vp, C.POINTER(sz), vp, vp, vp]
+    L.lw_stark_round2.restype = i
     _lib = L
     return L
 

@@ -49,7 +49,7 @@ int ntt_cross_device(Context &c, lw_field_t field, lw_layout_t layout, lw_dir_t 
 
 // ---- merkle.hip
 int merkle_commit_device(Context &c, const void *d_cols, uint32_t n_cols, uint64_t col_stride, uint32_t log2n, int bit_reverse,
-                         void *d_nodes, hipStream_t stream, uint32_t elem_bytes = 32);
+                         void *d_nodes, hipStream_t stream, uint32_t elem_bytes = 32, uint32_t rows_per_leaf = 1);
 
 // ---- fri.hip
 int fri_layer_device(Context &c, lw_field_t field, const void *d_coeffs, uint64_t n, const uint32_t *zeta, const void *offset_ref,

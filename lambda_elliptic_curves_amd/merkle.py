@@ -50,6 +50,21 @@ def commit_columns_layout_device(field, t_columns, n_cols, log2n, t_nodes, bit_r
     return root.tobytes()
 
 
+def commit_composition_device(field, t_parts_lde, n_parts, log2_lde, t_nodes, col_stride_elems=0, stream=None):
+    """commit_composition_polynomial (provers/stark/src/prover.rs:398-425) on the device-resident LDE of the parts
+    (n_parts columns of 2^log2_lde elements, col_stride_elems apart, 0 = dense): rows bit-reverse permuted and merged in
+    pairs, 2^(log2_lde - 1) leaves.  t_nodes: (2^log2_lde - 1) * 32 bytes, the tree Tree(..., rows_per_leaf=2) opens.
+    -> the 32-byte root."""
+    import torch
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    root = np.zeros(32, np.uint8)
+    check(L.lib().lw_stark_commit_composition_device(field.field, C.c_void_p(t_parts_lde.data_ptr()), int(n_parts), int(col_stride_elems),
+                                                     int(log2_lde), C.c_void_p(t_nodes.data_ptr()), root.ctypes.data_as(C.c_void_p),
+                                                     C.c_void_p(stream)))
+    return root.tobytes()
+
+
 def fri_layer(field, coeffs, zeta, coset_offset, domain_size, return_nodes=False):
     """One layer of commit_phase (provers/stark/src/fri/mod.rs:44-58): returns (p' = 2*fold(p, zeta) coefficients,
     bit-reversed evaluation of p' on coset_offset * <w_domain>, Merkle root [, nodes])."""

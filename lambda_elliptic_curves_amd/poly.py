@@ -70,6 +70,29 @@ def ruffini_division_device(field, t_coeffs, n, x, t_quotient, stream=None, rema
     return rem if remainder else None
 
 
+def batch_inverse(field, elems):
+    """FieldElement::inplace_batch_inverse (math/src/field/element.rs:47-65): (n, 4) array of the inverses; a zero element
+    raises FieldError."""
+    a = _elems(elems)
+    out = np.zeros_like(a)
+    check(L.lib().lw_field_batch_inverse(field.field, a.ctypes.data_as(C.c_void_p), a.shape[0], out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def batch_inverse_device(field, t_in, n, t_out=None, stream=None):
+    """batch_inverse() of the first n elements of a device-resident tensor into t_out (None: in place); synchronises
+    once.  -> t_out"""
+    t_out = t_in if t_out is None else t_out
+    check(L.lib().lw_field_batch_inverse_device(field.field, C.c_void_p(t_in.data_ptr()), int(n), C.c_void_p(t_out.data_ptr()),
+                                                _stream(stream)))
+    return t_out
+
+
+def batch_inverse_block():
+    """Elements one workgroup of the batch inversion owns (lw_field_batch_inverse_block)."""
+    return int(L.lib().lw_field_batch_inverse_block())
+
+
 def _weights(weights, k, m):
     w = np.ascontiguousarray(weights, dtype=np.uint64).reshape(-1, 4)
     if w.shape[0] != k * m:

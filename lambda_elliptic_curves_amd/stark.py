@@ -159,3 +159,119 @@ def open_deep_composition_poly_device(field, main, composition, iotas, aux=None,
                                    proof_sym=paths[k][q + s])
         out.append(entry)
     return out
+
+
+# ---- round 2 (provers/stark/src/prover.rs:428-484): constraint evaluations, the parts of H and their commitment
+
+def _boundary_table(boundary):
+    """[(col, step, value, coeff)] -> lw_stark_boundary_t array; col indexes the column table (main, then auxiliary)."""
+    tab = (L.StarkBoundary * max(1, len(boundary)))()
+    for k, (col, step, value, coeff) in enumerate(boundary):
+        tab[k].col, tab[k].step = int(col), int(step)
+        tab[k].value[:] = [int(x) for x in np.asarray(value, np.uint64).reshape(4)]
+        tab[k].coeff[:] = [int(x) for x in np.asarray(coeff, np.uint64).reshape(4)]
+    return tab
+
+
+def _transition_table(transitions):
+    """[dict(period, offset, end_exemptions, exemptions_period (None / 0: none), periodic_exemptions_offset, coeff)], the
+    TransitionConstraint accessors of constraints/transition.rs:24-82 -> lw_stark_transition_t array."""
+    tab = (L.StarkTransition * max(1, len(transitions)))()
+    for k, t in enumerate(transitions):
+        tab[k].period, tab[k].offset = int(t.get("period", 1)), int(t.get("offset", 0))
+        tab[k].end_exemptions = int(t.get("end_exemptions", 0))
+        tab[k].exemptions_period = int(t.get("exemptions_period") or 0)
+        tab[k].periodic_exemptions_offset = int(t.get("periodic_exemptions_offset") or 0)
+        tab[k].coeff[:] = [int(x) for x in np.asarray(t["coeff"], np.uint64).reshape(4)]
+    return tab
+
+
+def constraint_evaluations_device(field, t_columns, log2_trace, log2_blowup, coset_offset, boundary, transitions, t_transition_evals,
+                                  t_out=None, transition_stride_elems=0, stream=None):
+    """ConstraintEvaluator::evaluate (constraints/evaluator.rs:33-225) on resident LDE columns: t_columns is a list of
+    tensors, one natural-order column of N = 2^(log2_trace + log2_blowup) elements each (main columns, then auxiliary);
+    row c of t_transition_evals is compute_transition's value of constraint c at every LDE row, written by the caller.
+    -> t_out (N, 4), the evaluations of the composition polynomial on the LDE coset."""
+    import ctypes as C
+    import torch
+    from .errors import check
+    n_lde = 1 << (int(log2_trace) + int(log2_blowup))
+    ptrs = (C.c_void_p * max(1, len(t_columns)))(*[t.data_ptr() for t in t_columns])
+    off = np.ascontiguousarray(coset_offset, dtype=np.uint64).reshape(4)
+    dev = t_columns[0].device if len(t_columns) else t_transition_evals.device
+    if t_out is None:
+        t_out = torch.empty((n_lde, 4), dtype=torch.int64, device=dev)
+    check(L.lib().lw_stark_constraint_evaluations_device(
+        field.field, ptrs, len(t_columns), int(log2_trace), int(log2_blowup), off.ctypes.data_as(C.c_void_p),
+        _boundary_table(boundary), len(boundary), _transition_table(transitions), len(transitions),
+        C.c_void_p(t_transition_evals.data_ptr()) if t_transition_evals is not None else None, int(transition_stride_elems),
+        C.c_void_p(t_out.data_ptr()), poly._stream(stream)))
+    return t_out
+
+
+def part_block_len(log2_lde, n_parts):
+    """next_power_of_two(ceil(N / P)): the zero-padded block a part of H is stored in."""
+    per = -(-(1 << int(log2_lde)) // int(n_parts))
+    return 1 << (per - 1).bit_length()
+
+
+def composition_parts_device(field, t_evals, log2_lde, coset_offset, n_parts, lde=True, lens=True, stream=None):
+    """interpolate_offset_fft, break_in_parts (math/src/polynomial/mod.rs:289-302) and the LDE of every part.
+    -> (t_parts_coeffs (P, L, 4), part_lens (stripped, None when lens=False: nothing is waited for), t_parts_lde (P, N, 4) or None)."""
+    import ctypes as C
+    import torch
+    from .errors import check
+    P, n_lde = int(n_parts), 1 << int(log2_lde)
+    off = np.ascontiguousarray(coset_offset, dtype=np.uint64).reshape(4)
+    t_coeffs = torch.empty((max(P, 1), part_block_len(log2_lde, max(P, 1)), 4), dtype=torch.int64, device=t_evals.device)
+    t_lde = torch.empty((max(P, 1), n_lde, 4), dtype=torch.int64, device=t_evals.device) if lde else None
+    ln = (C.c_size_t * max(1, P))()
+    check(L.lib().lw_stark_composition_parts_device(field.field, C.c_void_p(t_evals.data_ptr()), int(log2_lde), off.ctypes.data_as(C.c_void_p),
+                                                    P, C.c_void_p(t_coeffs.data_ptr()), C.c_void_p(t_lde.data_ptr()) if lde else None,
+                                                    ln if lens else None, poly._stream(stream)))
+    return t_coeffs, ([int(x) for x in ln] if lens else None), t_lde
+
+
+def round2_device(field, t_columns, log2_trace, log2_blowup, coset_offset, boundary, transitions, t_transition_evals, n_parts,
+                  transition_stride_elems=0, stream=None):
+    """round_2_compute_composition_polynomial (provers/stark/src/prover.rs:428-484) on resident data.
+    -> (t_parts_coeffs: the P coefficient blocks (views of one tensor), part_lens, t_parts_lde (P, N, 4), t_nodes, root):
+    deep_composition_poly_device takes the first two as t_parts / part_lens, open_deep_composition_poly_device
+    (t_parts_lde, P, log2_lde, t_nodes) as its composition tuple."""
+    import torch
+    from . import merkle
+    log2_lde = int(log2_trace) + int(log2_blowup)
+    t_ev = constraint_evaluations_device(field, t_columns, log2_trace, log2_blowup, coset_offset, boundary, transitions, t_transition_evals,
+                                         transition_stride_elems=transition_stride_elems, stream=stream)
+    t_coeffs, lens, t_lde = composition_parts_device(field, t_ev, log2_lde, coset_offset, n_parts, stream=stream)
+    t_nodes = torch.empty((((1 << log2_lde) - 1) * 4,), dtype=torch.int64, device=t_ev.device)
+    root = merkle.commit_composition_device(field, t_lde, n_parts, log2_lde, t_nodes, stream=stream)
+    return [t_coeffs[j] for j in range(int(n_parts))], lens, t_lde, t_nodes, root
+
+
+def round2(field, columns, log2_trace, log2_blowup, coset_offset, boundary, transitions, transition_evals, n_parts,
+           return_nodes=False, return_lde=False):
+    """round2_device on host arrays (lw_stark_round2): columns (n_cols, N, 4), transition_evals (n_transitions, N, 4).
+    -> (parts_coeffs (P, L, 4), part_lens, root[, nodes (N - 1, 32)][, parts_lde (P, N, 4)])"""
+    import ctypes as C
+    from .errors import check
+    log2_lde = int(log2_trace) + int(log2_blowup)
+    n_lde, P = 1 << log2_lde, int(n_parts)
+    cols = np.ascontiguousarray(columns, dtype=np.uint64).reshape(-1, n_lde, 4)
+    tev = np.ascontiguousarray(transition_evals, dtype=np.uint64).reshape(-1, n_lde, 4)
+    off = np.ascontiguousarray(coset_offset, dtype=np.uint64).reshape(4)
+    coeffs = np.zeros((max(P, 1), part_block_len(log2_lde, max(P, 1)), 4), np.uint64)
+    ln = (C.c_size_t * max(1, P))()
+    root = np.zeros(32, np.uint8)
+    nodes = np.zeros((n_lde - 1, 32), np.uint8) if return_nodes else None
+    lde = np.zeros((max(P, 1), n_lde, 4), np.uint64) if return_lde else None
+    vp = lambda x: x.ctypes.data_as(C.c_void_p) if x is not None else None
+    check(L.lib().lw_stark_round2(field.field, vp(cols), cols.shape[0], int(log2_trace), int(log2_blowup), vp(off),
+                                  _boundary_table(boundary), len(boundary), _transition_table(transitions), len(transitions), vp(tev),
+                                  P, vp(coeffs), ln, vp(root), vp(nodes), vp(lde)))
+    out = (coeffs, [int(x) for x in ln], root.tobytes())
+    if return_nodes:
+        out += (nodes,)
+    if return_lde:
+        out += (lde,)
+    return out

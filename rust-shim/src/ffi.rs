@@ -296,6 +296,51 @@ extern "C" {
     pub fn lw_circle_lde_device(d_evals: *const u32, log2_in: u32, in_stride: usize, d_out: *mut u32, log2_out: u32,
                                 out_stride: usize, batch: u32, hip_stream: *mut c_void) -> c_int;
     pub fn lw_circle_get_twiddles(log2n: u32, config: c_int, out: *mut u32) -> c_int;
+    // ---- batch inversion and STARK round 2 (the coset offset, the constraint tables and every small result on the host)
+    pub fn lw_field_batch_inverse(field: Field, input: *const c_void, n: usize, out: *mut c_void) -> c_int;
+    pub fn lw_field_batch_inverse_device(field: Field, d_in: *const c_void, n: usize, d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_field_batch_inverse_block() -> u64;
+    pub fn lw_stark_constraint_evaluations_device(field: Field, d_columns: *const *const c_void, n_cols: u32, log2_trace: u32,
+                                                  log2_blowup: u32, coset_offset: *const c_void, boundary: *const lw_stark_boundary_t,
+                                                  n_boundary: u32, transitions: *const lw_stark_transition_t, n_transitions: u32,
+                                                  d_transition_evals: *const c_void, transition_stride_elems: u64, d_out: *mut c_void,
+                                                  hip_stream: *mut c_void) -> c_int;
+    pub fn lw_stark_composition_parts_device(field: Field, d_evals: *const c_void, log2_lde: u32, coset_offset: *const c_void,
+                                             n_parts: u32, d_parts_coeffs: *mut c_void, d_parts_lde: *mut c_void,
+                                             out_part_lens_or_null: *mut usize, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_stark_commit_composition_device(field: Field, d_parts_lde: *const c_void, n_parts: u32, col_stride_elems: u64,
+                                              log2_lde: u32, d_nodes: *mut c_void, out_root_or_null: *mut u8,
+                                              hip_stream: *mut c_void) -> c_int;
+    pub fn lw_stark_round2(field: Field, columns: *const c_void, n_cols: u32, log2_trace: u32, log2_blowup: u32,
+                           coset_offset: *const c_void, boundary: *const lw_stark_boundary_t, n_boundary: u32,
+                           transitions: *const lw_stark_transition_t, n_transitions: u32, transition_evals: *const c_void,
+                           n_parts: u32, out_parts_coeffs: *mut c_void, out_part_lens: *mut usize, out_root: *mut u8,
+                           out_nodes_or_null: *mut u8, out_parts_lde_or_null: *mut c_void) -> c_int;
+}
+
+/// lw_stark_boundary_t: one boundary constraint of lw_stark_constraint_evaluations_device
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct lw_stark_boundary_t {
+    /// index into the column table (main columns, then auxiliary ones)
+    pub col: u32,
+    pub reserved: u32,
+    pub step: u64,
+    pub value: [u64; 4],
+    pub coeff: [u64; 4],
+}
+
+/// lw_stark_transition_t: the zerofier parameters and the coefficient of one transition constraint
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct lw_stark_transition_t {
+    pub period: u64,
+    pub offset: u64,
+    pub end_exemptions: u64,
+    /// 0: none
+    pub exemptions_period: u64,
+    pub periodic_exemptions_offset: u64,
+    pub coeff: [u64; 4],
 }
 
 /// lw_poseidon_leaf_t: TreePoseidon (leaf = hash_single of one column)
@@ -308,3 +353,5 @@ const _: () = assert!(core::mem::size_of::<lw_timings_t>() == 48);
 const _: () = assert!(core::mem::size_of::<lw_kernel_time_t>() == 64);
 const _: () = assert!(core::mem::size_of::<lw_profile_t>() == 8 + 32 * 64);
 const _: () = assert!(core::mem::size_of::<lw_stark_tree_t>() == 56);
+const _: () = assert!(core::mem::size_of::<lw_stark_boundary_t>() == 80);
+const _: () = assert!(core::mem::size_of::<lw_stark_transition_t>() == 72);

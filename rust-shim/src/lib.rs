@@ -377,6 +377,52 @@ pub fn deep_composition(field: Field, polys: &[&[[u64; 4]]], points: &[[u64; 4]]
     Ok((out, evals))
 }
 
+/// `FieldElement::inplace_batch_inverse` (math/src/field/element.rs:47-65) on the device; a zero element is
+/// `FieldError::InvZeroError`.
+pub fn batch_inverse(field: Field, elems: &mut [[u64; 4]]) -> Result<(), HipError> {
+    let p = elems.as_mut_ptr() as *mut c_void;
+    // SAFETY: `elems` is valid for its length; the call may run in place.
+    check(unsafe { ffi::lw_field_batch_inverse(field, p as *const c_void, elems.len(), p) })
+}
+
+/// The parts of the composition polynomial and their commitment, as `stark_round2` returns them.
+pub struct Round2 {
+    /// `n_parts` blocks of `block_len` coefficients, zero padded
+    pub parts_coeffs: Vec<[u64; 4]>,
+    pub block_len: usize,
+    /// stripped length of every part
+    pub part_lens: Vec<usize>,
+    pub root: [u8; 32],
+    /// `(N - 1)` nodes, root first
+    pub nodes: Vec<[u8; 32]>,
+    /// `n_parts` columns of `N` evaluations on the LDE coset
+    pub parts_lde: Vec<[u64; 4]>,
+}
+
+/// `round_2_compute_composition_polynomial` (provers/stark/src/prover.rs:428-484) over host arrays: `columns` holds the LDE
+/// columns (`n_cols x N`, natural order), `transition_evals` the AIR's `compute_transition` values (`transitions.len() x N`).
+pub fn stark_round2(field: Field, columns: &[[u64; 4]], log2_trace: u32, log2_blowup: u32, coset_offset: &[u64; 4],
+                    boundary: &[ffi::lw_stark_boundary_t], transitions: &[ffi::lw_stark_transition_t],
+                    transition_evals: &[[u64; 4]], n_parts: usize) -> Result<Round2, HipError> {
+    let n_lde = 1usize << (log2_trace + log2_blowup);
+    assert_eq!(columns.len() % n_lde, 0, "columns: N elements each");
+    assert_eq!(transition_evals.len(), transitions.len() * n_lde, "transition_evals: N elements per constraint");
+    let parts = n_parts.max(1);
+    let block_len = ((n_lde + parts - 1) / parts).next_power_of_two();
+    let mut out = Round2 { parts_coeffs: vec![[0u64; 4]; parts * block_len], block_len, part_lens: vec![0usize; parts], root: [0u8; 32],
+                           nodes: vec![[0u8; 32]; n_lde - 1], parts_lde: vec![[0u64; 4]; parts * n_lde] };
+    // SAFETY: every input is valid for its length; the outputs hold P x L, P, 32 bytes, N - 1 nodes and P x N elements.
+    let rc = unsafe {
+        ffi::lw_stark_round2(field, columns.as_ptr() as *const c_void, (columns.len() / n_lde) as u32, log2_trace, log2_blowup,
+                             coset_offset.as_ptr() as *const c_void, boundary.as_ptr(), boundary.len() as u32, transitions.as_ptr(),
+                             transitions.len() as u32, transition_evals.as_ptr() as *const c_void, n_parts as u32,
+                             out.parts_coeffs.as_mut_ptr() as *mut c_void, out.part_lens.as_mut_ptr(), out.root.as_mut_ptr(),
+                             out.nodes.as_mut_ptr() as *mut u8, out.parts_lde.as_mut_ptr() as *mut c_void)
+    };
+    check(rc)?;
+    Ok(out)
+}
+
 /// `grinding::generate_nonce` (provers/stark/src/grinding.rs:40-53) on the device: the smallest nonce in `[first, last]`
 /// whose hash has `grinding_factor` (1 ..= 63) leading zero bits, or `None`.
 pub fn stark_grinding_nonce(seed: &[u8; 32], grinding_factor: u8, first: u64, last: u64) -> Result<Option<u64>, HipError> {
