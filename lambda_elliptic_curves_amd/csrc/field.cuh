@@ -449,6 +449,8 @@ struct lw_fused_columns {
 };
 template <class F, int K, bool A_LT_P>
 struct FusedCol;
+template <class F, int K>
+struct FusedColS;   // FusedCol<F, K, true> with a's limbs as the scalar operand of the a*b MACs (a wave-uniform a)
 #include "mac_chains.inc"
 
 // every limb of p in [LO, HI) is a literal (> 64, so not an inline constant and not zero): the whole m*p part of a
@@ -530,7 +532,9 @@ __device__ __forceinline__ void lw_redc_unit0(uint32_t &m, uint32_t &mid, uint32
 // PRECONDITION of A_LT_P = true: the first operand is canonical, a < p.  With a larger a[N-1] those columns drop a
 // carry and the product is silently wrong, so only fe_mul_lazy, whose contract already says a < p, sets it; fe_mul
 // takes arbitrary operands and keeps the bound-free columns.
-template <class F, int K, bool A_LT_P>
+// A_SGPR (with A_LT_P): a is also the same in every lane of the wavefront, and its limbs go into the MACs as their scalar
+// operand (FusedColS): a then takes no vector registers.  A lane-dependent a would be read from its first active lane.
+template <class F, int K, bool A_LT_P, bool A_SGPR = false>
 __device__ __forceinline__ void fips_fused(uint64_t init, const Fe<F> &a, const Fe<F> &b, uint32_t (&m)[F::N], uint32_t (&t)[F::N]) {
     constexpr int N = F::N;
     static_assert(F::p(0) == 1u && F::INV == 0xffffffffu, "fused columns need a unit low limb of the modulus");
@@ -539,25 +543,27 @@ __device__ __forceinline__ void fips_fused(uint64_t init, const Fe<F> &a, const 
     } else {
         uint64_t lo;
         uint32_t hi;
-        FusedCol<F, K, A_LT_P>::run(lo, hi, init, a, b, m);
+        static_assert(A_LT_P || !A_SGPR, "the scalar-operand columns exist for a < p only");
+        if constexpr (A_SGPR) FusedColS<F, K>::run(lo, hi, init, a, b, m);
+        else FusedCol<F, K, A_LT_P>::run(lo, hi, init, a, b, m);
         if constexpr (K < N) {
             uint32_t mid, top;
             if constexpr (K == 0) lw_redc_unit0(m[0], mid, top, (uint32_t)lo, (uint32_t)(lo >> 32));
             else lw_redc_unit(m[K], mid, top, (uint32_t)lo, (uint32_t)(lo >> 32), hi);
-            fips_fused<F, K + 1, A_LT_P>(((uint64_t)top << 32) | mid, a, b, m, t);
+            fips_fused<F, K + 1, A_LT_P, A_SGPR>(((uint64_t)top << 32) | mid, a, b, m, t);
         } else {
             t[K - N] = (uint32_t)lo;
-            fips_fused<F, K + 1, A_LT_P>((lo >> 32) | ((uint64_t)hi << 32), a, b, m, t);
+            fips_fused<F, K + 1, A_LT_P, A_SGPR>((lo >> 32) | ((uint64_t)hi << 32), a, b, m, t);
         }
     }
 }
 // a*b + m*p over all columns into t (t < 2p for a < p), by the fused columns where the field has them.
 // A_LT_P: the caller guarantees a < p (see fips_fused); fields without fused columns ignore it.
-template <class F, bool A_LT_P = false>
+template <class F, bool A_LT_P = false, bool A_SGPR = false>
 __device__ __forceinline__ void fips_product(const Fe<F> &a, const Fe<F> &b, uint32_t (&t)[F::N]) {
     uint32_t m[F::N];
     if constexpr (lw_fused_columns<F>::value) {
-        fips_fused<F, 0, A_LT_P>(0ull, a, b, m, t);
+        fips_fused<F, 0, A_LT_P, A_SGPR>(0ull, a, b, m, t);
     } else {
         const Fe<F> *const pa[1] = {&a}, *const pb[1] = {&b};
         fips_col<F, 1, 0>(0ull, pa, pb, m, t);
@@ -692,6 +698,23 @@ LW_HD Fe<F> fe_mul_lazy(const Fe<F> &a, const Fe<F> &b) {
     constexpr int N = F::N;
     uint32_t t[N];
     fips_product<F, true>(a, b, t);
+    Fe<F> r;
+#pragma unroll
+    for (int i = 0; i < N; i++) r.v[i] = t[i];
+    return r;
+#else
+    return fe_mul_portable<F>(a, b);
+#endif
+}
+// fe_mul_lazy for an a that is the same in every lane of the wavefront (a twiddle shared by a whole wave, fetched through
+// a uniform address): on the device a's limbs are the scalar operand of the MACs and stay out of the vector registers.
+// Same result as fe_mul_lazy, same precondition a < p; fields without fused columns take the ordinary product.
+template <class F>
+LW_HD Fe<F> fe_mul_lazy_uniform(const Fe<F> &a, const Fe<F> &b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int N = F::N;
+    uint32_t t[N];
+    fips_product<F, true, lw_fused_columns<F>::value>(a, b, t);
     Fe<F> r;
 #pragma unroll
     for (int i = 0; i < N; i++) r.v[i] = t[i];

@@ -123,17 +123,23 @@ def fused_col_plan(p, k, a_canonical=False):
     return dict(macs=macs, has_hi=has_hi, carry_in=carry_in, proof=proof, total=total)
 
 
-def fused_col(field, p, k, a_canonical=False):
+def fused_col(field, p, k, a_canonical=False, a_sgpr=False):
     """Column k of a*b + m*p as one statement: lo(64) / hi(32) = init + sum a[i]*b[k-i] + sum m[i]*p[k-i] over every
     MAC of the column except the unit limb's m[k]*p[0] (lw_redc_unit in field.cuh does that one without a multiply).
     Which MACs carry an add-with-carry, and why the others need none, is fused_col_plan's business.
 
     a_canonical: the variant FusedCol<F, K, true> for callers whose contract says a < p (fe_mul_lazy: the NTT's
-    twiddles and scale factors).  Where the bound on a's top limb changes nothing it inherits the general column."""
+    twiddles and scale factors).  Where the bound on a's top limb changes nothing it inherits the general column.
+
+    a_sgpr: the variant FusedColS<F, K> of the a < p columns for an a that is the same in every lane of the wavefront
+    (a twiddle shared by a whole wave): its limbs are the MACs' scalar operand, as p's limbs are in the m*p MACs (one
+    scalar operand per v_mad_u64_u32), so a occupies no vector registers.  Same MACs in the same order with the same
+    add-with-carry pattern as FusedCol<F, K, true>: the bounds do not depend on where an operand lives."""
     n = len(p)
     last = 2 * n - 2
+    assert a_canonical or not a_sgpr
     plan = fused_col_plan(p, k, a_canonical)
-    if a_canonical and plan["macs"] == fused_col_plan(p, k, False)["macs"]:
+    if a_canonical and not a_sgpr and plan["macs"] == fused_col_plan(p, k, False)["macs"]:
         return (f"template <>\n"
                 f"struct FusedCol<{field}, {k}, true> : FusedCol<{field}, {k}, false> {{}};   // a < p changes nothing here\n")
     has_hi = plan["has_hi"]
@@ -158,7 +164,7 @@ def fused_col(field, p, k, a_canonical=False):
             opn += 2
         else:
             macs.append((f"%{opn}", f"%{opn + 1}"))
-            ins.append(f'"v"(a.v[{i}])')
+            ins.append(f'"{"s" if a_sgpr else "v"}"(a.v[{i}])')
             ins.append(f'"v"(b.v[{j}])')
             opn += 2
     body, hi_live = [], False
@@ -186,8 +192,9 @@ def fused_col(field, p, k, a_canonical=False):
     else:
         why = f"    // addend <= 0x{plan['carry_in']:x}; every MAC can carry\n"
     sep = "\n            "
+    name = f"FusedColS<{field}, {k}>" if a_sgpr else f"FusedCol<{field}, {k}, {'true' if a_canonical else 'false'}>"
     return (f"template <>\n"
-            f"struct FusedCol<{field}, {k}, {'true' if a_canonical else 'false'}> {{   // {nab} a*b + {nmp} m*p MACs\n"
+            f"struct {name} {{   // {nab} a*b + {nmp} m*p MACs\n"
             f"{why}"
             f"    __device__ static __forceinline__ void run(uint64_t &lo, uint32_t &hi, uint64_t init, const Fe<{field}> &a, "
             f"const Fe<{field}> &b, const uint32_t (&m)[{n}]) {{\n"
@@ -210,6 +217,9 @@ def fused_field(field, p):
         out.append(fused_col(field, p, k))
     for k in range(2 * n - 1):
         out.append(fused_col(field, p, k, a_canonical=True))
+    out.append(f"// {field}: the a < p columns for a wave-uniform a, whose limbs are the scalar operand of the a*b MACs (fips_fused, A_SGPR).\n")
+    for k in range(2 * n - 1):
+        out.append(fused_col(field, p, k, a_canonical=True, a_sgpr=True))
     return out
 
 
