@@ -20,6 +20,10 @@
  *   - lw_hip_msm_limbs[_device]             <->  the same for UnsignedInteger<NUM_LIMBS>, NUM_LIMBS = 1 .. 8
  *   - lw_circle_evaluate_cfft / interpolate <->  evaluate_cfft / interpolate_cfft (math/src/circle/polynomial.rs:18-72),
  *     lw_circle_get_twiddles                     get_twiddles (math/src/circle/twiddles.rs:13-58), over Mersenne31
+ *   - lw_goldilocks_ntt[_device]            <->  the same backend arm of Polynomial::evaluate_fft / interpolate_fft and their
+ *     lw_goldilocks_lde_device                   offset forms (math/src/fft/polynomial.rs:25-127) over p = 2^64 - 2^32 + 1:
+ *     lw_goldilocks_gen_twiddles                 U64TestField (math/src/field/test_fields/u64_test_field.rs:98-104) and
+ *                                                Winterfell's Felt (math/src/field/fields/winterfell.rs:21-24)
  *   - lw_hip_init / lw_hip_shutdown         <->  CudaState::new (math/src/fft/gpu/cuda/state.rs:29-38); the
  *                                                reference builds and drops device state on every call, this
  *                                                library keeps one context (twiddle caches, scratch, streams)
@@ -699,6 +703,44 @@ int lw_circle_lde_device(const uint32_t *d_evals, uint32_t log2_in, size_t in_st
 /* get_twiddles(Coset::new_standard(log2n), config) (twiddles.rs:13-58), the layers concatenated: n - 1 words to host memory.
  * config 0 (Evaluation): lengths 1, 2, .., n/2; config 1 (Interpolation): the inverses, lengths n/2, .., 1. */
 int lw_circle_get_twiddles(uint32_t log2n, int config, uint32_t *out);
+
+/* ---- NTT over Goldilocks, p = 2^64 - 2^32 + 1 (U64TestField, u64_test_field.rs:98-104; Felt, winterfell.rs:21-24) ----
+ * One u64 per element in host byte order, the residue itself: no Montgomery form, no lw_field_t / lw_layout_t.  Every input
+ * word is read as from_base_type reads it (any u64, x >= p means x - p); every output word is the canonical residue (< p).
+ *   forward   out[i] = sum_j in[j] (h w^i)^j         evaluate_fft / evaluate_offset_fft (fft/polynomial.rs:25-82) on a slice
+ *                                                     that is already a power of two; w the primitive 2^log2n-th root, h the
+ *                                                     offset or 1
+ *   inverse   out[j] = h^-j n^-1 sum_i in[i] w^-ij   interpolate_fft / interpolate_offset_fft (fft/polynomial.rs:87-127)
+ * Input and output are in natural order.  The transform is linear: elements kept in Montgomery form with R = 2^64
+ * (U64GoldilocksPrimeField, Winterfell's BaseElement) come out in Montgomery form, provided the offset is passed as the
+ * plain residue.
+ *   two_adic_root   the primitive 2^32-th root g; the primitive 2^k-th root is g^(2^(32-k)) (traits.rs:82-94).  0 selects
+ *                   the reference's TWO_ADIC_PRIMITVE_ROOT_OF_UNITY = 1753635133440165772 = 7^((p-1)/2^32); any other value
+ *                   must be below p with g^(2^31) = p - 1, else LW_ERR_ROOT_OF_UNITY (a Winterfell-style Felt passes its own
+ *                   constant).  The twiddle tables are generated on the device and cached for one root at a time.
+ *   offset_or_null  one u64 in host memory, or NULL; a value = 0 mod p is LW_ERR_INV_ZERO in both directions
+ *   log2n           0 .. 30 (0: the reduced copy); 31 and 32: LW_ERR_ORDER_TOO_LARGE (32-bit word indices, a table of 2^(n-1)
+ *                   entries); above 32: LW_ERR_ROOT_OF_UNITY, the reference's error above TWO_ADICITY
+ *   batch           columns of n words, batch_stride words apart (0: n); the words between two columns are not touched
+ *   in place        out == in is allowed; any other overlap is LW_ERR_BAD_ARG, like a NULL pointer, batch = 0, a stride below
+ *                   the column length and an unknown dir.  All of this is decided before any device work.
+ * Stream and lane contract of the _device forms as for the other *_device entry points. */
+int lw_goldilocks_ntt(lw_dir_t dir, const uint64_t *in, uint64_t *out, uint32_t log2n, uint32_t batch, size_t batch_stride,
+                      const uint64_t *offset_or_null, uint64_t two_adic_root);
+int lw_goldilocks_ntt_device(lw_dir_t dir, const uint64_t *d_in, uint64_t *d_out, uint32_t log2n, uint32_t batch,
+                             size_t batch_stride, const uint64_t *offset_or_null, uint64_t two_adic_root, void *hip_stream);
+/* evaluate_offset_fft(poly, blowup, Some(domain), offset): the forward transform of the 2^log2_coeffs coefficients zero
+ * padded to 2^log2n, per column.  The padding is never written or read and the stages that would only meet it are skipped.
+ * log2_coeffs > log2n and any overlap of the two buffers: LW_ERR_BAD_ARG.  Strides in words, 0: dense. */
+int lw_goldilocks_lde_device(const uint64_t *d_coeffs, uint32_t log2_coeffs, size_t in_stride, uint64_t *d_out, uint32_t log2n,
+                             size_t out_stride, uint32_t batch, const uint64_t *offset_or_null, uint64_t two_adic_root,
+                             void *hip_stream);
+/* get_twiddles(order, config) (fft/cpu/roots_of_unity.rs:66-75): 2^order / 2 words to host memory.  config is RootsConfig
+ * as in lw_hip_gen_twiddles: 0 Natural, 1 NaturalInversed, 2 BitReverse, 3 BitReverseInversed.  order as log2n above. */
+int lw_goldilocks_gen_twiddles(uint64_t order, int config, uint64_t two_adic_root, uint64_t *out);
+/* out[i] = a[i] b[i] mod p, the step between evaluate_fft and interpolate_fft of a polynomial product.  Words as above.
+ * d_out == d_a and d_out == d_b are allowed, any other overlap of d_out with an operand is LW_ERR_BAD_ARG. */
+int lw_goldilocks_mul_device(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t n, void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,8 @@ EXPORTS = [
     "lw_poseidon_commit_columns", "lw_poseidon_commit_columns_device",
     "lw_circle_evaluate_cfft", "lw_circle_interpolate_cfft", "lw_circle_evaluate_cfft_device", "lw_circle_interpolate_cfft_device",
     "lw_circle_lde_device", "lw_circle_get_twiddles",
+    "lw_goldilocks_ntt", "lw_goldilocks_ntt_device", "lw_goldilocks_lde_device", "lw_goldilocks_gen_twiddles",
+    "lw_goldilocks_mul_device",
     "lw_field_batch_inverse", "lw_field_batch_inverse_device", "lw_field_batch_inverse_block",
     "lw_stark_constraint_evaluations_device", "lw_stark_composition_parts_device", "lw_stark_commit_composition_device",
     "lw_stark_round2",
@@ -269,6 +271,16 @@ def lib():
     L.lw_circle_lde_device.restype = i
     L.lw_circle_get_twiddles.argtypes = [u32, i, vp]
     L.lw_circle_get_twiddles.restype = i
+    L.lw_goldilocks_ntt.argtypes = [i, vp, vp, u32, u32, sz, vp, C.c_uint64]
+    L.lw_goldilocks_ntt.restype = i
+    L.lw_goldilocks_ntt_device.argtypes = [i, vp, vp, u32, u32, sz, vp, C.c_uint64, vp]
+    L.lw_goldilocks_ntt_device.restype = i
+    L.lw_goldilocks_lde_device.argtypes = [vp, u32, sz, vp, u32, sz, u32, vp, C.c_uint64, vp]
+    L.lw_goldilocks_lde_device.restype = i
+    L.lw_goldilocks_gen_twiddles.argtypes = [C.c_uint64, i, C.c_uint64, vp]
+    L.lw_goldilocks_gen_twiddles.restype = i
+    L.lw_goldilocks_mul_device.argtypes = [vp, vp, vp, sz, vp]
+    L.lw_goldilocks_mul_device.restype = i
     L.lw_field_batch_inverse.argtypes = [i, vp, sz, vp]
     L.lw_field_batch_inverse.restype = i
     L.lw_field_batch_inverse_device.argtypes = [i, vp, sz, vp, vp]

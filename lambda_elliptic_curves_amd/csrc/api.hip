@@ -99,6 +99,10 @@ static void release_everything() {
         t.buf.release();
         t.valid = false;
     }
+    for (TwiddleTable &t : sh.goldilocks) {
+        t.buf.release();
+        t.valid = false;
+    }
 }
 // SharedState::rw held unique
 static int init_locked(const int *device_ids, int n_devices) {
@@ -159,6 +163,7 @@ void Context::release_all() {
     msm_affine.release();
     msm_prefix.release();
     bb_coset.release();
+    gl_coset.release();
     shard_a.release();
     shard_b.release();
     shard_c.release();

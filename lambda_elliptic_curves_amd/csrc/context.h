@@ -69,6 +69,10 @@ struct SharedState {
     // evaluation twiddles in its first half and their inverses (interpolation) in the second.
     TwiddleTable circle_x;       // the x-layers 0 .. log_n - 2, layer i at word 2^i - 1: they do not depend on the size
     TwiddleTable circle_y[31];   // [log2n]: the last (y) layer of that size, 2^(log2n - 1) words
+    // Goldilocks NTT (goldilocks.hip), same discipline: [dir], T[g] = w^bitrev(g) for the primitive 2^32-th root
+    // goldilocks_root (0: none yet).  One root at a time: a call with another root invalidates both tables.
+    TwiddleTable goldilocks[2];
+    uint64_t goldilocks_root = 0;
     bool initialised = false;
     int device = -1;
 };
@@ -96,6 +100,7 @@ struct Context {
     TwiddleTable (&tw)[3][2] = shared_state().tw;   // shared by all lanes; rebuilt only under SharedState::rw held unique
     std::shared_lock<std::shared_mutex> *call_lock = nullptr;   // the running call's shared hold on SharedState::rw (Entry)
     DeviceBuf bb_coset;      // two-level power tables of the current BabyBear coset offset (rebuilt per call: 8192 exponentiations)
+    DeviceBuf gl_coset;      // the same for the current Goldilocks coset offset (goldilocks.hip), u64 entries
     DeviceBuf scratch;
     DeviceBuf small;         // staging for small power tables
     CosetCache coset[3];     // forward coset, inverse coset, multi-GPU cross-step twiddle base

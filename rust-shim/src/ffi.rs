@@ -296,6 +296,16 @@ extern "C" {
     pub fn lw_circle_lde_device(d_evals: *const u32, log2_in: u32, in_stride: usize, d_out: *mut u32, log2_out: u32,
                                 out_stride: usize, batch: u32, hip_stream: *mut c_void) -> c_int;
     pub fn lw_circle_get_twiddles(log2n: u32, config: c_int, out: *mut u32) -> c_int;
+    // ---- NTT over Goldilocks (p = 2^64 - 2^32 + 1): one u64 per element, the residue itself, canonical residues out
+    pub fn lw_goldilocks_ntt(dir: c_int, input: *const u64, out: *mut u64, log2n: u32, batch: u32, batch_stride: usize,
+                             offset_or_null: *const u64, two_adic_root: u64) -> c_int;
+    pub fn lw_goldilocks_ntt_device(dir: c_int, d_in: *const u64, d_out: *mut u64, log2n: u32, batch: u32, batch_stride: usize,
+                                    offset_or_null: *const u64, two_adic_root: u64, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_goldilocks_lde_device(d_coeffs: *const u64, log2_coeffs: u32, in_stride: usize, d_out: *mut u64, log2n: u32,
+                                    out_stride: usize, batch: u32, offset_or_null: *const u64, two_adic_root: u64,
+                                    hip_stream: *mut c_void) -> c_int;
+    pub fn lw_goldilocks_gen_twiddles(order: u64, config: c_int, two_adic_root: u64, out: *mut u64) -> c_int;
+    pub fn lw_goldilocks_mul_device(d_a: *const u64, d_b: *const u64, d_out: *mut u64, n: usize, hip_stream: *mut c_void) -> c_int;
     // ---- batch inversion and STARK round 2 (the coset offset, the constraint tables and every small result on the host)
     pub fn lw_field_batch_inverse(field: Field, input: *const c_void, n: usize, out: *mut c_void) -> c_int;
     pub fn lw_field_batch_inverse_device(field: Field, d_in: *const c_void, n: usize, d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;

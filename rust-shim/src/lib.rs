@@ -688,3 +688,28 @@ pub fn circle_interpolate_cfft(evals: &[u32]) -> Result<Vec<u32>, HipError> {
     check(unsafe { ffi::lw_circle_interpolate_cfft(evals.as_ptr(), out.as_mut_ptr(), evals.len().trailing_zeros(), 1, 0) })?;
     Ok(out)
 }
+
+/// `evaluate_fft` / `evaluate_offset_fft` (math/src/fft/polynomial.rs:25-82) over Goldilocks, p = 2^64 - 2^32 + 1, on a
+/// slice that is already a power of two: one u64 per element, the residue itself (`U64TestField`'s memory), canonical
+/// residues out.  `two_adic_root`: 0 for the reference's `TWO_ADIC_PRIMITVE_ROOT_OF_UNITY`, or the caller's own primitive
+/// 2^32-th root (a Winterfell-style `Felt`).
+pub fn evaluate_fft_goldilocks_hip(coeffs: &[u64], offset: Option<u64>, two_adic_root: u64) -> Result<Vec<u64>, HipError> {
+    goldilocks_ntt_hip(0, coeffs, offset, two_adic_root)
+}
+
+/// `interpolate_fft` / `interpolate_offset_fft` (polynomial.rs:87-127) over Goldilocks; arguments as
+/// `evaluate_fft_goldilocks_hip`.  All n coefficients are returned.
+pub fn interpolate_fft_goldilocks_hip(evals: &[u64], offset: Option<u64>, two_adic_root: u64) -> Result<Vec<u64>, HipError> {
+    goldilocks_ntt_hip(1, evals, offset, two_adic_root)
+}
+
+fn goldilocks_ntt_hip(dir: c_int, input: &[u64], offset: Option<u64>, two_adic_root: u64) -> Result<Vec<u64>, HipError> {
+    assert!(input.len().is_power_of_two(), "input: a power of two");
+    let mut out = vec![0u64; input.len()];
+    let off = offset.as_ref().map_or(core::ptr::null(), |h| h as *const u64);
+    // SAFETY: both buffers hold input.len() words; `off` is NULL or points at one u64 that outlives the call.
+    check(unsafe {
+        ffi::lw_goldilocks_ntt(dir, input.as_ptr(), out.as_mut_ptr(), input.len().trailing_zeros(), 1, 0, off, two_adic_root)
+    })?;
+    Ok(out)
+}
