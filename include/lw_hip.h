@@ -742,6 +742,41 @@ int lw_goldilocks_gen_twiddles(uint64_t order, int config, uint64_t two_adic_roo
  * d_out == d_a and d_out == d_b are allowed, any other overlap of d_out with an operand is LW_ERR_BAD_ARG. */
 int lw_goldilocks_mul_device(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t n, void *hip_stream);
 
+/* ---- Rescue Prime Optimized over Goldilocks (RescuePrimeOptimized, crypto/src/hash/rescue_prime/; ePrint 2022/1577) ----
+ * The permutation, the sponge `hash` of the reference and a Merkle tree built from it, batched: one work-item per
+ * permutation.  Words are Goldilocks elements as above: one u64, the residue itself; every input word is read as
+ * from_base_type reads it (any u64), every output word is the canonical residue.
+ *   level   LW_RPO_128: state 12, capacity 4, rate 8, digest 4 words (the hash of Miden);
+ *           LW_RPO_160: state 16, capacity 6, rate 10, digest 5 words.  Anything else: LW_ERR_BAD_ARG.
+ *   permute n states of 12 (16) words -> n states (permutation(), rescue_prime_optimized.rs:192-202); out may be states
+ *   hash    n_rows rows of row_len >= 0 words -> one digest of rate / 2 words each (hash(), :205-230): word 0 of the state is
+ *           1 iff row_len is no multiple of the rate, every block overwrites the rate part, a partial last block is
+ *           padded with a 1 and zeros; row_len = 0 runs no permutation and gives zeros (rows may then be NULL).  The host
+ *           form reads dense row-major rows; the _device form rows row_stride words apart (0: row_len; below row_len:
+ *           LW_ERR_BAD_ARG).  hash_bytes of the reference is bytes_to_field_elements on the host, then this.
+ * Each function has a host form (buffers in host memory, complete on return, no CPU fallback) and a _device form (16-byte
+ * aligned device pointers, work enqueued on hip_stream; misaligned: LW_ERR_BAD_ARG).  n = 0 / n_rows = 0: LW_OK, nothing is
+ * touched and no device is needed.  More than 2^36 inputs: LW_ERR_ALLOC.  Every check happens before any device work.
+ *
+ * commit_columns: the tree over the 2^log2n rows of n_cols columns of words.  Leaf j = hash(committed row j over all
+ * columns), a node = hash(left || right) (2 digests = one block: one permutation; for LW_RPO_128 this is Miden's 2-to-1
+ * merge).  The reference has no RPO Merkle backend: this tree is built from its hash in the layout of its other trees.
+ * nodes: (2 * 2^log2n - 1) digests, root first and leaves last (merkle_tree/utils.rs:43-71); for LW_RPO_128 a digest is 32
+ * bytes and lw_stark_open_trees_device reads the authentication paths of such a tree as it is (d_columns = NULL).  out_root:
+ * one digest.  bit_reverse and col_stride (in words, 0: dense, below 2^log2n: LW_ERR_BAD_ARG) as in the other commit calls:
+ * leaf j commits natural row bitrev(j), gathered in the leaf kernel.  log2n 0 .. 30, above: LW_ERR_ALLOC.  The _device form
+ * synchronises the stream only when out_root is not NULL. */
+typedef enum { LW_RPO_128 = 0, LW_RPO_160 = 1 } lw_rpo_level_t;
+int lw_rpo_permute(lw_rpo_level_t level, const uint64_t *states, size_t n, uint64_t *out);
+int lw_rpo_permute_device(lw_rpo_level_t level, const uint64_t *d_states, size_t n, uint64_t *d_out, void *hip_stream);
+int lw_rpo_hash(lw_rpo_level_t level, const uint64_t *rows, size_t n_rows, size_t row_len, uint64_t *out);
+int lw_rpo_hash_device(lw_rpo_level_t level, const uint64_t *d_rows, size_t n_rows, size_t row_len, size_t row_stride,
+                       uint64_t *d_out, void *hip_stream);
+int lw_rpo_commit_columns(lw_rpo_level_t level, const uint64_t *columns, uint32_t n_cols, uint32_t log2n, int bit_reverse,
+                          uint64_t *out_root, uint64_t *out_nodes_or_null);
+int lw_rpo_commit_columns_device(lw_rpo_level_t level, const uint64_t *d_columns, uint32_t n_cols, uint64_t col_stride,
+                                 uint32_t log2n, int bit_reverse, uint64_t *d_nodes, uint64_t *out_root_or_null, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

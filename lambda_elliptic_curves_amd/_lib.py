@@ -15,6 +15,7 @@ LAYOUT_U64_LIMBS_MS_FIRST, LAYOUT_BABYBEAR_U32_R32, LAYOUT_BABYBEAR_U64_R64, LAY
 DIR_FORWARD, DIR_INVERSE = 0, 1
 CURVE_BLS12_381_G1, CURVE_BN254_G1, CURVE_BN254_G2, CURVE_BLS12_381_G2 = 0, 1, 2, 3
 POSEIDON_LEAF_SINGLE, POSEIDON_LEAF_MANY = 0, 1   # lw_poseidon_leaf_t
+RPO_128, RPO_160 = 0, 1   # lw_rpo_level_t
 (OK, ERR_INPUT_NOT_POW2, ERR_ORDER_TOO_LARGE, ERR_ROOT_OF_UNITY, ERR_LENGTH_MISMATCH, ERR_NO_DEVICE, ERR_ALLOC,
  ERR_LAUNCH, ERR_COMM, ERR_BAD_ARG, ERR_INV_ZERO) = (0, -1, -2, -3, -4, -5, -6, -7, -8, -9, -10)
 
@@ -45,6 +46,8 @@ EXPORTS = [
     "lw_circle_lde_device", "lw_circle_get_twiddles",
     "lw_goldilocks_ntt", "lw_goldilocks_ntt_device", "lw_goldilocks_lde_device", "lw_goldilocks_gen_twiddles",
     "lw_goldilocks_mul_device",
+    "lw_rpo_permute", "lw_rpo_permute_device", "lw_rpo_hash", "lw_rpo_hash_device",
+    "lw_rpo_commit_columns", "lw_rpo_commit_columns_device",
     "lw_field_batch_inverse", "lw_field_batch_inverse_device", "lw_field_batch_inverse_block",
     "lw_stark_constraint_evaluations_device", "lw_stark_composition_parts_device", "lw_stark_commit_composition_device",
     "lw_stark_round2",
@@ -281,6 +284,18 @@ def lib():
     L.lw_goldilocks_gen_twiddles.restype = i
     L.lw_goldilocks_mul_device.argtypes = [vp, vp, vp, sz, vp]
     L.lw_goldilocks_mul_device.restype = i
+    L.lw_rpo_permute.argtypes = [i, vp, sz, vp]
+    L.lw_rpo_permute.restype = i
+    L.lw_rpo_permute_device.argtypes = [i, vp, sz, vp, vp]
+    L.lw_rpo_permute_device.restype = i
+    L.lw_rpo_hash.argtypes = [i, vp, sz, sz, vp]
+    L.lw_rpo_hash.restype = i
+    L.lw_rpo_hash_device.argtypes = [i, vp, sz, sz, sz, vp, vp]
+    L.lw_rpo_hash_device.restype = i
+    L.lw_rpo_commit_columns.argtypes = [i, vp, u32, u32, i, vp, vp]
+    L.lw_rpo_commit_columns.restype = i
+    L.lw_rpo_commit_columns_device.argtypes = [i, vp, u32, C.c_uint64, u32, i, vp, vp, vp]
+    L.lw_rpo_commit_columns_device.restype = i
     L.lw_field_batch_inverse.argtypes = [i, vp, sz, vp]
     L.lw_field_batch_inverse.restype = i
     L.lw_field_batch_inverse_device.argtypes = [i, vp, sz, vp, vp]

@@ -306,6 +306,17 @@ extern "C" {
                                     hip_stream: *mut c_void) -> c_int;
     pub fn lw_goldilocks_gen_twiddles(order: u64, config: c_int, two_adic_root: u64, out: *mut u64) -> c_int;
     pub fn lw_goldilocks_mul_device(d_a: *const u64, d_b: *const u64, d_out: *mut u64, n: usize, hip_stream: *mut c_void) -> c_int;
+    // ---- Rescue Prime Optimized over Goldilocks: batched permutations, hashes and Merkle trees; level is LW_RPO_128 / LW_RPO_160
+    pub fn lw_rpo_permute(level: c_int, states: *const u64, n: usize, out: *mut u64) -> c_int;
+    pub fn lw_rpo_permute_device(level: c_int, d_states: *const u64, n: usize, d_out: *mut u64, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_rpo_hash(level: c_int, rows: *const u64, n_rows: usize, row_len: usize, out: *mut u64) -> c_int;
+    pub fn lw_rpo_hash_device(level: c_int, d_rows: *const u64, n_rows: usize, row_len: usize, row_stride: usize, d_out: *mut u64,
+                              hip_stream: *mut c_void) -> c_int;
+    pub fn lw_rpo_commit_columns(level: c_int, columns: *const u64, n_cols: u32, log2n: u32, bit_reverse: c_int, out_root: *mut u64,
+                                 out_nodes_or_null: *mut u64) -> c_int;
+    pub fn lw_rpo_commit_columns_device(level: c_int, d_columns: *const u64, n_cols: u32, col_stride: u64, log2n: u32,
+                                        bit_reverse: c_int, d_nodes: *mut u64, out_root_or_null: *mut u64,
+                                        hip_stream: *mut c_void) -> c_int;
     // ---- batch inversion and STARK round 2 (the coset offset, the constraint tables and every small result on the host)
     pub fn lw_field_batch_inverse(field: Field, input: *const c_void, n: usize, out: *mut c_void) -> c_int;
     pub fn lw_field_batch_inverse_device(field: Field, d_in: *const c_void, n: usize, d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
@@ -357,6 +368,10 @@ pub struct lw_stark_transition_t {
 pub const LW_POSEIDON_LEAF_SINGLE: c_int = 0;
 /// lw_poseidon_leaf_t: BatchPoseidonTree (leaf = hash_many of the row)
 pub const LW_POSEIDON_LEAF_MANY: c_int = 1;
+/// lw_rpo_level_t: state 12, capacity 4, rate 8, digest 4 words
+pub const LW_RPO_128: c_int = 0;
+/// lw_rpo_level_t: state 16, capacity 6, rate 10, digest 5 words
+pub const LW_RPO_160: c_int = 1;
 
 // The C structs above must keep the sizes the header gives them.
 const _: () = assert!(core::mem::size_of::<lw_timings_t>() == 48);

@@ -713,3 +713,70 @@ fn goldilocks_ntt_hip(dir: c_int, input: &[u64], offset: Option<u64>, two_adic_r
     })?;
     Ok(out)
 }
+
+/// Security level of `RescuePrimeOptimized` (crypto/src/hash/rescue_prime/parameters.rs `SecurityLevel`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum RpoLevel {
+    Sec128,
+    Sec160,
+}
+
+impl RpoLevel {
+    fn code(self) -> c_int {
+        match self {
+            RpoLevel::Sec128 => ffi::LW_RPO_128,
+            RpoLevel::Sec160 => ffi::LW_RPO_160,
+        }
+    }
+    /// words of the state
+    pub fn width(self) -> usize {
+        match self {
+            RpoLevel::Sec128 => 12,
+            RpoLevel::Sec160 => 16,
+        }
+    }
+    /// words of a digest: rate / 2
+    pub fn digest_len(self) -> usize {
+        match self {
+            RpoLevel::Sec128 => 4,
+            RpoLevel::Sec160 => 5,
+        }
+    }
+}
+
+/// `RescuePrimeOptimized::permutation` (rescue_prime_optimized.rs:192-202) on a batch of states, in place: `states` holds
+/// `width()` Goldilocks words per state, the residues themselves.
+pub fn rpo_permute_hip(level: RpoLevel, states: &mut [u64]) -> Result<(), HipError> {
+    assert!(states.len() % level.width() == 0, "states: a whole number of states");
+    let p = states.as_mut_ptr();
+    // SAFETY: one buffer of states.len() words, read and written in place.
+    check(unsafe { ffi::lw_rpo_permute(level.code(), p as *const u64, states.len() / level.width(), p) })
+}
+
+/// `RescuePrimeOptimized::hash` (rescue_prime_optimized.rs:205-230) of every row of a row-major matrix with `row_len`
+/// columns: `digest_len()` words per row.
+pub fn rpo_hash_hip(level: RpoLevel, rows: &[u64], n_rows: usize, row_len: usize) -> Result<Vec<u64>, HipError> {
+    assert!(rows.len() == n_rows * row_len, "rows: n_rows * row_len words");
+    let mut out = vec![0u64; n_rows * level.digest_len()];
+    // SAFETY: rows holds n_rows * row_len words, out n_rows digests.
+    check(unsafe { ffi::lw_rpo_hash(level.code(), rows.as_ptr(), n_rows, row_len, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// The Merkle tree over the rows of `columns` (each a power-of-two column of the same length): leaf = `hash` of the row,
+/// node = `hash(left || right)`.  Returns the reference's `nodes`, root first, `digest_len()` words each.
+pub fn rpo_commit_columns_hip(level: RpoLevel, columns: &[&[u64]], bit_reverse: bool) -> Result<Vec<u64>, HipError> {
+    assert!(!columns.is_empty(), "columns: at least one");
+    let n = columns[0].len();
+    assert!(n.is_power_of_two() && columns.iter().all(|c| c.len() == n), "columns: one power-of-two length");
+    let flat: Vec<u64> = columns.iter().flat_map(|c| c.iter().copied()).collect();
+    let d = level.digest_len();
+    let mut root = vec![0u64; d];
+    let mut nodes = vec![0u64; (2 * n - 1) * d];
+    // SAFETY: flat holds columns.len() * n words, root one digest, nodes 2 n - 1 digests.
+    check(unsafe {
+        ffi::lw_rpo_commit_columns(level.code(), flat.as_ptr(), columns.len() as u32, n.trailing_zeros(), bit_reverse as c_int,
+                                   root.as_mut_ptr(), nodes.as_mut_ptr())
+    })?;
+    Ok(nodes)
+}

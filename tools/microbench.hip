@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <vector>
 #include "../lambda_elliptic_curves_amd/csrc/field.cuh"
+#include "../lambda_elliptic_curves_amd/csrc/goldilocks.cuh"
 using namespace lw;
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
@@ -90,6 +91,25 @@ __global__ void k_femul(uint32_t *io, int iters) {
         for (int i = 0; i < F::N; i++) s ^= a[c].v[i];
     io[4096 * 12 + tid] = s;
 }
+// the Goldilocks product of csrc/goldilocks.cuh, CH independent chains a work-item (the ceiling of tools/rpo_timing.py)
+template <int CH>
+__global__ void k_glmul(uint32_t *io, int iters) {
+    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t *w = (const uint64_t *)io;
+    uint64_t a[CH];
+#pragma unroll
+    for (int c = 0; c < CH; c++) a[c] = w[((size_t)tid * CH + c) % 4096];
+    const uint64_t b = w[(tid + 17) % 4096] | 1;
+    for (int it = 0; it < iters; it++) {
+#pragma unroll
+        for (int c = 0; c < CH; c++) a[c] = gl_mul(a[c], b);
+    }
+    uint64_t s = 0;
+#pragma unroll
+    for (int c = 0; c < CH; c++) s ^= a[c];
+    io[4096 * 12 + tid] = (uint32_t)s ^ (uint32_t)(s >> 32);
+}
+
 // correctness: device fe_mul / add / sub vs host portable code
 template <class F>
 __global__ void k_check(const uint32_t *in, uint32_t *out, int n) {
@@ -191,6 +211,8 @@ int main() {
         ms = time_ms([&] { hipLaunchKernelGGL((k_femul<F, 2>), dim3(blocks), dim3(threads), 0, 0, buf, it2); }); \
         printf("RATE fe_mul %-9s   %8.2f Gmul/s   (%.1f mad-equivalents/mul at the measured mad rate)\n", NAME, lanes * it2 * 2 / ms / 1e6, 0.0);
         FEMUL(Stark252, "Stark252") FEMUL(Fr381, "Fr381") FEMUL(Fp254, "Fp254") FEMUL(Fp381, "Fp381")
+        ms = time_ms([&] { hipLaunchKernelGGL((k_glmul<8>), dim3(blocks), dim3(threads), 0, 0, buf, it2 * 8); });
+        printf("RATE gl_mul Goldilocks   %8.2f Gmul/s   (8 chains a work-item, %d waves/CU)\n", lanes * it2 * 8 * 8 / ms / 1e6, blocks * threads / 64 / cus);
     }
     {
         const size_t bytes = (size_t)2 << 30;
