@@ -332,3 +332,21 @@ def profile_end():
 
 def last_error():
     return lib().lw_hip_last_error().decode("utf-8", "replace")
+
+
+# ---- argument helpers of the bindings that take both numpy arrays and torch tensors (poseidon.py, rpo.py)
+def host_ptr(a):
+    """numpy array -> void *; None or an empty array -> NULL"""
+    return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+
+
+def device_ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def stream_ptr(stream):
+    """a hipStream_t as an integer, or None for torch's current stream"""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    return C.c_void_p(stream)

@@ -1,33 +1,17 @@
 """Host-side mirror of the reference's Starknet Poseidon (crypto/src/hash/poseidon/mod.rs, PoseidonCairoStark252) and of
 the Merkle trees built on it (TreePoseidon, BatchPoseidonTree), batched on the device.  Elements are Stark252
 FieldElements as everywhere else: (…, 4) uint64, most significant limb first, Montgomery form, canonical."""
-import ctypes as C
-
 import numpy as np
 
 from . import _lib as L
+from ._lib import device_ptr as _dp, host_ptr as _vp, stream_ptr as _stream
 from .errors import InputError, check
 
 LEAF_SINGLE, LEAF_MANY = L.POSEIDON_LEAF_SINGLE, L.POSEIDON_LEAF_MANY
 
 
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
-
-
 def _elems(a, shape):
     return np.ascontiguousarray(a, dtype=np.uint64).reshape(shape)
-
-
-def _stream(stream):
-    if stream is None:
-        import torch
-        stream = torch.cuda.current_stream().cuda_stream
-    return C.c_void_p(stream)
-
-
-def _dp(t):
-    return C.c_void_p(t.data_ptr())
 
 
 def permute(states):

@@ -6,11 +6,10 @@ is the canonical residue.  `level` is LEVEL_128 (state 12, rate 8, digest 4 word
 16, rate 10, digest 5 words).  Host arrays are numpy uint64; the device entry points take torch int64 tensors of the same
 bytes, 16-byte aligned, and run on torch's current stream.
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _lib as L
+from ._lib import device_ptr as _dp, host_ptr as _vp, stream_ptr as _stream
 from .errors import InputError, check
 
 P = (1 << 64) - (1 << 32) + 1
@@ -34,21 +33,6 @@ def rate(level):
 
 def digest_len(level):
     return _params(level)[2] // 2
-
-
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
-
-
-def _stream(stream):
-    if stream is None:
-        import torch
-        stream = torch.cuda.current_stream().cuda_stream
-    return C.c_void_p(stream)
-
-
-def _dp(t):
-    return C.c_void_p(t.data_ptr())
 
 
 def permute(level, states):
