@@ -5,8 +5,6 @@ An element is one uint32.  Any word is accepted and read as (w & p) + (w >> 31) 
 word of a result is the canonical residue.  Host arrays are numpy, one transform or a batch `(batch, n)`; the device
 entry points take torch int32 tensors resident in HBM and run on torch's current stream.
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _lib as L
@@ -14,10 +12,6 @@ from .errors import InputError, check
 
 P = (1 << 31) - 1
 TWIDDLES_EVALUATION, TWIDDLES_INTERPOLATION = 0, 1   # TwiddlesConfig
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _log2_len(n):
@@ -34,7 +28,7 @@ def _host(entry, a):
     log2n = _log2_len(a.shape[-1])
     out = np.empty_like(a)
     if a.size:
-        check(entry(_ptr(a), _ptr(out), log2n, a.shape[0] if a.ndim == 2 else 1, 0))
+        check(entry(L.host_ptr(a), L.host_ptr(out), log2n, a.shape[0] if a.ndim == 2 else 1, 0))
     return out
 
 
@@ -57,35 +51,28 @@ def get_twiddles(log2n, config):
     """get_twiddles(Coset::new_standard(log2n), config): the list of layers, lengths 1, 2, .., n/2 for TWIDDLES_EVALUATION
     and n/2, .., 1 (the inverses) for TWIDDLES_INTERPOLATION."""
     flat = np.empty((1 << log2n) - 1 if 1 <= log2n <= 30 else 1, np.uint32)
-    check(L.lib().lw_circle_get_twiddles(log2n, config, _ptr(flat)))
+    check(L.lib().lw_circle_get_twiddles(log2n, config, L.host_ptr(flat)))
     lengths = [1 << i for i in range(log2n)]
     if config == TWIDDLES_INTERPOLATION:
         lengths.reverse()
     return np.split(flat, np.cumsum(lengths)[:-1])
 
 
-def _stream(stream):
-    if stream is None:
-        import torch
-        stream = torch.cuda.current_stream().cuda_stream
-    return C.c_void_p(stream)
-
-
 def evaluate_cfft_device(t_in, t_out, log2n, batch=1, batch_stride=0, stream=None):
     """Device-resident evaluate_cfft of `batch` columns of 2^log2n words, `batch_stride` words apart (0: dense);
     t_out may be t_in.  Asynchronous on `stream` (default: torch's current stream)."""
-    check(L.lib().lw_circle_evaluate_cfft_device(C.c_void_p(t_in.data_ptr()), C.c_void_p(t_out.data_ptr()), log2n, batch,
-                                                 batch_stride, _stream(stream)))
+    check(L.lib().lw_circle_evaluate_cfft_device(L.device_ptr(t_in), L.device_ptr(t_out), log2n, batch,
+                                                 batch_stride, L.stream_ptr(stream)))
 
 
 def interpolate_cfft_device(t_in, t_out, log2n, batch=1, batch_stride=0, stream=None):
     """Device-resident interpolate_cfft; arguments as evaluate_cfft_device."""
-    check(L.lib().lw_circle_interpolate_cfft_device(C.c_void_p(t_in.data_ptr()), C.c_void_p(t_out.data_ptr()), log2n, batch,
-                                                    batch_stride, _stream(stream)))
+    check(L.lib().lw_circle_interpolate_cfft_device(L.device_ptr(t_in), L.device_ptr(t_out), log2n, batch,
+                                                    batch_stride, L.stream_ptr(stream)))
 
 
 def lde_device(t_evals, log2_in, t_out, log2_out, batch=1, in_stride=0, out_stride=0, stream=None):
     """Device-resident low-degree extension: evaluate_cfft(zero_pad(interpolate_cfft(evals), 2^log2_out)) for `batch`
     columns, the coefficients staying on the device and the padding never written."""
-    check(L.lib().lw_circle_lde_device(C.c_void_p(t_evals.data_ptr()), log2_in, in_stride, C.c_void_p(t_out.data_ptr()),
-                                       log2_out, out_stride, batch, _stream(stream)))
+    check(L.lib().lw_circle_lde_device(L.device_ptr(t_evals), log2_in, in_stride, L.device_ptr(t_out),
+                                       log2_out, out_stride, batch, L.stream_ptr(stream)))

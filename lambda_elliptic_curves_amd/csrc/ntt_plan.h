@@ -1,5 +1,5 @@
-// Pass planning shared by the 256-bit-field NTT (ntt256.hip), the BabyBear NTT (ntt_bb.hip) and the circle FFT (circle.hip): how the stages of a
-// transform are cut into passes, how wide each pass's tile is and how a pass is split into register steps.
+// Pass planning shared by the 256-bit-field NTT (ntt256.hip), the BabyBear NTT (ntt_bb.hip) and, through tile_pass.cuh, the circle FFT
+// (circle.hip) and the Goldilocks NTT (goldilocks.hip): how the stages of a transform are cut into passes, how wide each pass's tile is and how a pass is split into register steps.
 // Host only, plain C++ (no HIP header): tests/test_ntt_plan_cpu.py compiles it with g++ and pins every plan.
 #pragma once
 #include <stdint.h>
@@ -18,8 +18,8 @@ struct NttPlan {
 // Stages [skip, L) of a transform of 2^L elements whose word array has Lw index bits (Lw = L for the 256-bit fields, one
 // word per element; Lw = L + lgV for BabyBear, 2^lgV components per element).  The first `skip` stages of a zero-padded
 // input only replicate it (see ntt256_run) and are not planned.  A workgroup's tile holds 2^tile_log words, a register
-// step runs at most kmax stages, a pass at most max_r (the circle transform's diagnostic switch lowers it to reach the
-// higher pass counts at small sizes, circle.hip).
+// step runs at most kmax stages, a pass at most max_r (the diagnostic switches of the circle transform and of the
+// Goldilocks NTT lower it to reach the higher pass counts at small sizes, tile_max_r in tile_pass.cuh).
 inline NttPlan plan_passes(uint32_t Lw, uint32_t L, uint32_t skip, uint32_t tile_log, uint32_t kmax, bool full_last_pass,
                            uint32_t max_r = NTT_MAX_R) {
     NttPlan pl{};

@@ -8,8 +8,6 @@ same bytes, resident in HBM, and run on torch's current stream.  `root` is the p
 domain is built from: 0 selects the reference's TWO_ADIC_PRIMITVE_ROOT_OF_UNITY, a field type with another constant
 passes its own.
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _lib as L
@@ -22,23 +20,12 @@ TWO_ADIC_PRIMITIVE_ROOT_OF_UNITY = 1753635133440165772   # 7^((p - 1) / 2^32)
 ROOTS_NATURAL, ROOTS_NATURAL_INVERSED, ROOTS_BIT_REVERSE, ROOTS_BIT_REVERSE_INVERSED = 0, 1, 2, 3
 
 
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
 def _words(a):
     return np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
 
 
 def _offset_arg(offset):
     return None if offset is None else np.array([int(offset) & ((1 << 64) - 1)], np.uint64)
-
-
-def _stream(stream):
-    if stream is None:
-        import torch
-        stream = torch.cuda.current_stream().cuda_stream
-    return C.c_void_p(stream)
 
 
 def ntt(data, inverse=False, log2n=None, batch=1, batch_stride=0, offset=None, root=0, out=None):
@@ -55,8 +42,8 @@ def ntt(data, inverse=False, log2n=None, batch=1, batch_stride=0, offset=None, r
     elif out.nbytes != a.nbytes or out.dtype != a.dtype or not out.flags.c_contiguous:
         raise ValueError("out must be a C-contiguous array of the input's size and type")
     off = _offset_arg(offset)
-    check(L.lib().lw_goldilocks_ntt(L.DIR_INVERSE if inverse else L.DIR_FORWARD, _ptr(a), _ptr(out), log2n, batch, batch_stride,
-                                    _ptr(off), root))
+    check(L.lib().lw_goldilocks_ntt(L.DIR_INVERSE if inverse else L.DIR_FORWARD, L.host_ptr(a), L.host_ptr(out), log2n, batch, batch_stride,
+                                    L.host_ptr(off), root))
     return out
 
 
@@ -105,7 +92,7 @@ def get_twiddles(order, config, root=0):
     bit-reversed."""
     count = (1 << order) // 2 if 0 <= order <= 30 else 0
     out = np.empty(count, np.uint64)
-    check(L.lib().lw_goldilocks_gen_twiddles(order, config, root, _ptr(out) if count else None))
+    check(L.lib().lw_goldilocks_gen_twiddles(order, config, root, L.host_ptr(out)))
     return out
 
 
@@ -113,19 +100,19 @@ def ntt_device(t_in, t_out, log2n, inverse=False, batch=1, batch_stride=0, offse
     """Device-resident transform of `batch` columns of 2^log2n words, `batch_stride` words apart (0: dense); t_out may be
     t_in.  Asynchronous on `stream` (default: torch's current stream)."""
     off = _offset_arg(offset)
-    check(L.lib().lw_goldilocks_ntt_device(L.DIR_INVERSE if inverse else L.DIR_FORWARD, C.c_void_p(t_in.data_ptr()),
-                                           C.c_void_p(t_out.data_ptr()), log2n, batch, batch_stride, _ptr(off), root, _stream(stream)))
+    check(L.lib().lw_goldilocks_ntt_device(L.DIR_INVERSE if inverse else L.DIR_FORWARD, L.device_ptr(t_in),
+                                           L.device_ptr(t_out), log2n, batch, batch_stride, L.host_ptr(off), root, L.stream_ptr(stream)))
 
 
 def lde_device(t_coeffs, log2_coeffs, t_out, log2n, batch=1, in_stride=0, out_stride=0, offset=None, root=0, stream=None):
     """Device-resident low-degree extension: evaluate_offset_fft(poly, blowup, Some(domain), offset) for `batch` blocks
     of 2^log2_coeffs coefficients -> 2^log2n evaluations each, without materialising the zero padding."""
     off = _offset_arg(offset)
-    check(L.lib().lw_goldilocks_lde_device(C.c_void_p(t_coeffs.data_ptr()), log2_coeffs, in_stride, C.c_void_p(t_out.data_ptr()),
-                                           log2n, out_stride, batch, _ptr(off), root, _stream(stream)))
+    check(L.lib().lw_goldilocks_lde_device(L.device_ptr(t_coeffs), log2_coeffs, in_stride, L.device_ptr(t_out),
+                                           log2n, out_stride, batch, L.host_ptr(off), root, L.stream_ptr(stream)))
 
 
 def mul_device(t_a, t_b, t_out, n=None, stream=None):
     """t_out[i] = t_a[i] * t_b[i] mod p for n words (default: all of t_a); t_out may be t_a or t_b."""
-    check(L.lib().lw_goldilocks_mul_device(C.c_void_p(t_a.data_ptr()), C.c_void_p(t_b.data_ptr()), C.c_void_p(t_out.data_ptr()),
-                                           t_a.numel() if n is None else n, _stream(stream)))
+    check(L.lib().lw_goldilocks_mul_device(L.device_ptr(t_a), L.device_ptr(t_b), L.device_ptr(t_out),
+                                           t_a.numel() if n is None else n, L.stream_ptr(stream)))

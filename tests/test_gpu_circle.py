@@ -225,3 +225,36 @@ def test_warm_cache_smaller_and_larger_sizes():
         w = words((1, 1 << L), 1300 + L)
         assert np.array_equal(dev_transform(w, False), R.np_evaluate_cfft(w))
         assert np.array_equal(dev_transform(w, True), R.np_interpolate_cfft(w))
+
+
+SPLIT_BATCH = 32768 + 3   # grid.y carries at most 32768 columns: a chunk of 32768 and one of 3
+_SPLIT = {}
+
+
+def split_case():
+    """the columns and both references, computed once"""
+    if not _SPLIT:
+        w = words((SPLIT_BATCH, 2), 1400)
+        marked = (0, 32767, 32768, SPLIT_BATCH - 1)   # either side of the chunk boundary and both ends
+        for k, col in enumerate(marked):
+            w[col] = (11 + k, 101 + 7 * k)
+        _SPLIT.update(w=w, ev=R.np_evaluate_cfft(w), co=R.np_interpolate_cfft(w))
+        for exp in (_SPLIT["ev"], _SPLIT["co"]):   # a chunk offset that is off by one cannot hide behind equal columns
+            assert len({tuple(exp[col]) for col in marked} | {tuple(exp[1]), tuple(exp[32766]), tuple(exp[32769])}) == 7
+    return _SPLIT
+
+
+@pytest.mark.parametrize("in_place", [False, True])
+@pytest.mark.parametrize("inverse", [False, True])
+def test_batch_split_above_32768_columns(inverse, in_place):
+    # 2^1 words per column, the smallest size: one pass, so in place is the copy through the work buffer, per chunk
+    import torch
+    from lambda_elliptic_curves_amd import circle
+    case = split_case()
+    t_in = to_dev(case["w"])
+    t_out = t_in if in_place else torch.zeros_like(t_in)
+    (circle.interpolate_cfft_device if inverse else circle.evaluate_cfft_device)(t_in, t_out, 1, batch=SPLIT_BATCH)
+    torch.cuda.synchronize()
+    assert np.array_equal(to_host(t_out), case["co" if inverse else "ev"])
+    if not in_place:
+        assert np.array_equal(to_host(t_in), case["w"])

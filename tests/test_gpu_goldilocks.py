@@ -288,3 +288,29 @@ def test_host_forms():
     G.mul_device(fa, fb, fa)
     torch.cuda.synchronize()
     assert G.interpolate_fft(_host(fa), strip=True).tolist() == [3, 7, 2]
+
+
+SPLIT_BATCH = 32768 + 3   # grid.y carries at most 32768 columns: a chunk of 32768 and one of 3
+_SPLIT = {}
+
+
+def _split_case():
+    """the columns and both references (coset offset 7), computed once"""
+    if not _SPLIT:
+        a = _rand((SPLIT_BATCH, 2), 1000)
+        marked = (0, 32767, 32768, SPLIT_BATCH - 1)   # either side of the chunk boundary and both ends
+        for k, col in enumerate(marked):
+            a[col] = (11 + k, 101 + 7 * k)
+        _SPLIT.update(a=a, fwd=_ref(a, False, 7), inv=_ref(a, True, 7))
+        for exp in (_SPLIT["fwd"], _SPLIT["inv"]):   # a chunk offset that is off by one cannot hide behind equal columns
+            assert len({tuple(exp[col]) for col in marked} | {tuple(exp[1]), tuple(exp[32766]), tuple(exp[32769])}) == 7
+    return _SPLIT
+
+
+@pytest.mark.parametrize("in_place", [False, True])
+@pytest.mark.parametrize("inverse", [False, True])
+def test_batch_split_above_32768_columns(inverse, in_place):
+    # 2^1 words per column: one pass, so in place is the copy through the work buffer, per chunk
+    case = _split_case()
+    got = _ntt(case["a"], 1, inverse=inverse, batch=SPLIT_BATCH, offset=7, in_place=in_place)
+    assert np.array_equal(got, case["inv" if inverse else "fwd"])
