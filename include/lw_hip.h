@@ -356,6 +356,24 @@ int lw_hip_msm_limbs_device(lw_curve_t curve, const uint64_t *d_scalars, uint32_
 int lw_hip_ec_add_outer_device(lw_curve_t curve, const void *d_rows, size_t m, const void *d_cols, size_t k, void *d_out,
                                void *hip_stream);
 
+/* The test seam of the group law: one formula of csrc/ec.cuh per row, exactly as the MSM kernels call it, so that a test
+ * chooses every operand of every field product.  The complete formulas (RCB16 Alg. 7, 8, 9) are polynomials in the
+ * coordinates: the rows need not be on the curve, and d_out receives the (X, Y, Z) the function returned, bit for bit —
+ * nothing is normalised and nothing is mapped back.
+ *   model   0: the caller's curve; 1: the isomorphic model the MSM runs normalised point sets on (BLS12-381 G1:
+ *           y^2 = x^3 + 2/3, BN254 G2: y^2 = x^3 + 9 + u); LW_ERR_BAD_ARG for the curves that have none.
+ *   d_a     n projective rows, reference layout (coordinates are canonical Montgomery residues, < p).
+ *   d_b     LW_EC_OP_ADD, LW_EC_OP_ADD_QUAD: n projective rows.  LW_EC_OP_ADD_MIXED: n dense affine rows (x, y), two
+ *           coordinates apart; a row (0, 0) is the identity and returns row a.  LW_EC_OP_DBL, LW_EC_OP_TO_AFFINE: NULL.
+ *   op      ADD_QUAD is ADD spread over the four lanes of a quad (pt_add_quad): same group element, same bytes.
+ *           TO_AFFINE is (X/Z : Y/Z : 1), Z = 0 -> (0 : 1 : 0).
+ * A bad curve, op or model, a NULL or misaligned buffer (16 bytes), a missing or a superfluous d_b: LW_ERR_BAD_ARG, before
+ * any device work.  n = 0 (checked after curve, op and model): LW_OK, nothing is touched.  d_out must not overlap d_a or
+ * d_b. */
+typedef enum { LW_EC_OP_ADD = 0, LW_EC_OP_ADD_MIXED = 1, LW_EC_OP_DBL = 2, LW_EC_OP_ADD_QUAD = 3, LW_EC_OP_TO_AFFINE = 4 } lw_ec_op_t;
+int lw_hip_ec_pointwise_device(lw_curve_t curve, int model, lw_ec_op_t op, const void *d_a, const void *d_b,
+                               size_t n, void *d_out, void *hip_stream);
+
 /* Fixed point set cached on the device in affine form (SURVEY 8f "next" #2, second half).  Every reference caller
  * multiplies against a structured reference string it built once: KZG commits with
  * msm(&coefficients, &srs.powers_main_group[..coefficients.len()]) (crypto/src/commitments/kzg.rs:159-163), Groth16 with

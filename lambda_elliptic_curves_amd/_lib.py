@@ -14,6 +14,7 @@ FIELD_STARK252, FIELD_BLS12_381_FR, FIELD_BABYBEAR = 0, 1, 2
 LAYOUT_U64_LIMBS_MS_FIRST, LAYOUT_BABYBEAR_U32_R32, LAYOUT_BABYBEAR_U64_R64, LAYOUT_EXT4_INTERLEAVED = 0, 1, 2, 3
 DIR_FORWARD, DIR_INVERSE = 0, 1
 CURVE_BLS12_381_G1, CURVE_BN254_G1, CURVE_BN254_G2, CURVE_BLS12_381_G2 = 0, 1, 2, 3
+EC_OP_ADD, EC_OP_ADD_MIXED, EC_OP_DBL, EC_OP_ADD_QUAD, EC_OP_TO_AFFINE = 0, 1, 2, 3, 4   # lw_ec_op_t
 POSEIDON_LEAF_SINGLE, POSEIDON_LEAF_MANY = 0, 1   # lw_poseidon_leaf_t
 RPO_128, RPO_160 = 0, 1   # lw_rpo_level_t
 (OK, ERR_INPUT_NOT_POW2, ERR_ORDER_TOO_LARGE, ERR_ROOT_OF_UNITY, ERR_LENGTH_MISMATCH, ERR_NO_DEVICE, ERR_ALLOC,
@@ -29,7 +30,7 @@ EXPORTS = [
     "lw_stark_commit_columns", "lw_stark_commit_columns_device", "lw_stark_commit_columns_layout_device", "lw_stark_fri_layer",
     "lw_hip_srs_create", "lw_hip_srs_create_device", "lw_hip_srs_destroy", "lw_hip_msm_srs", "lw_hip_msm_srs_device",
     "lw_hip_msm_srs_fr", "lw_hip_msm_srs_fr_device", "lw_stark_fri_layer_device", "lw_groth16_h_coefficients_device",
-    "lw_hip_ec_add_outer_device",
+    "lw_hip_ec_add_outer_device", "lw_hip_ec_pointwise_device",
     "lw_hip_comm_unique_id", "lw_hip_comm_init", "lw_hip_comm_shutdown", "lw_hip_comm_info",
     "lw_hip_ntt_sharded_device", "lw_hip_ntt_sharded_selftest_device", "lw_hip_ntt_sharded_selftest_steps_device",
     "lw_hip_msm_sharded_device", "lw_hip_msm_sharded_selftest_device",
@@ -183,6 +184,8 @@ def lib():
     L.lw_groth16_h_coefficients_device.restype = i
     L.lw_hip_ec_add_outer_device.argtypes = [i, vp, sz, vp, sz, vp, vp]
     L.lw_hip_ec_add_outer_device.restype = i
+    L.lw_hip_ec_pointwise_device.argtypes = [i, i, i, vp, vp, sz, vp, vp]
+    L.lw_hip_ec_pointwise_device.restype = i
     L.lw_hip_comm_unique_id.argtypes = [vp]
     L.lw_hip_comm_unique_id.restype = i
     L.lw_hip_comm_init.argtypes = [vp, i, i]

@@ -83,6 +83,19 @@ def msm_device(curve, t_scalars, t_points, n, stream=None, scalar_limbs=4):
     return out
 
 
+def ec_pointwise_device(curve, op, t_a, t_b, n, t_out, model=0, stream=None):
+    """The test seam of the group law (lw_hip_ec_pointwise_device): one formula of csrc/ec.cuh per row of device-resident
+    torch tensors, raw (X, Y, Z) into t_out.  op: L.EC_OP_*; t_b: None for EC_OP_DBL and EC_OP_TO_AFFINE; model 1: the
+    isomorphic model of the curve."""
+    import torch
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    check(L.lib().lw_hip_ec_pointwise_device(curve.curve, model, op, C.c_void_p(t_a.data_ptr()),
+                                             C.c_void_p(t_b.data_ptr()) if t_b is not None else None, n,
+                                             C.c_void_p(t_out.data_ptr()), C.c_void_p(stream)))
+    return t_out
+
+
 class Srs:
     """A fixed point set kept on the device in affine form (lw_hip_srs_*): what the reference's KZG
     `StructuredReferenceString.powers_main_group` (crypto/src/commitments/kzg.rs:159-163) or a Groth16 proving-key

@@ -205,6 +205,9 @@ extern "C" {
                                    out_point_host: *mut c_void, hip_stream: *mut c_void) -> c_int;
     pub fn lw_hip_ec_add_outer_device(curve: Curve, d_rows: *const c_void, m: usize, d_cols: *const c_void, k: usize,
                                       d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    /// The test seam of the group law: one formula of csrc/ec.cuh per row, raw (X, Y, Z) out.  op: LW_EC_OP_*.
+    pub fn lw_hip_ec_pointwise_device(curve: Curve, model: c_int, op: c_int, d_a: *const c_void, d_b: *const c_void, n: usize,
+                                      d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
     pub fn lw_hip_srs_create(curve: Curve, points: *const c_void, n_points: usize, out_srs: *mut *mut lw_srs_t) -> c_int;
     pub fn lw_hip_srs_create_device(curve: Curve, d_points: *const c_void, n_points: usize, hip_stream: *mut c_void,
                                     out_srs: *mut *mut lw_srs_t) -> c_int;
@@ -368,6 +371,13 @@ pub struct lw_stark_transition_t {
 pub const LW_POSEIDON_LEAF_SINGLE: c_int = 0;
 /// lw_poseidon_leaf_t: BatchPoseidonTree (leaf = hash_many of the row)
 pub const LW_POSEIDON_LEAF_MANY: c_int = 1;
+/// lw_ec_op_t
+pub const LW_EC_OP_ADD: c_int = 0;
+pub const LW_EC_OP_ADD_MIXED: c_int = 1;
+pub const LW_EC_OP_DBL: c_int = 2;
+pub const LW_EC_OP_ADD_QUAD: c_int = 3;
+pub const LW_EC_OP_TO_AFFINE: c_int = 4;
+
 /// lw_rpo_level_t: state 12, capacity 4, rate 8, digest 4 words
 pub const LW_RPO_128: c_int = 0;
 /// lw_rpo_level_t: state 16, capacity 6, rate 10, digest 5 words

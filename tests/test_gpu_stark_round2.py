@@ -74,6 +74,42 @@ def test_batch_inverse_matches_python_pow(name):
 
 
 @pytest.mark.parametrize("name", ["stark252", "fr381"])
+def test_batch_inverse_of_chosen_stored_values(name):
+    """fe_inv_fast on operands of our choosing.  field_batch_inverse_kernel gives work-item t the elements t + 256 j of a
+    block and inverts their product, so in the test above an edge value reaches the binary GCD multiplied into random
+    neighbours.  With n <= 256 every work-item owns exactly one element and the GCD sees the stored value itself: the
+    edge set, 2^k, 2^k +- 1 and p - 2^k for every bit k, and 2000 values with p's top two limbs (the Z families of
+    tests/test_gpu_ec_pointwise.py).  One launch of n = B has the chosen value at position t and R mod p (the stored one)
+    in the seven other places of its chunk.  Expected: pow(v R^-1, -1, p) R mod p."""
+    import torch
+    from lambda_elliptic_curves_amd import poly
+    from tests import ec_formulas_ref as E
+    p, F = MODULI[name], fld(name)
+    B, _sizes = inverse_sizes()
+    R = 1 << 256
+    vals = E.inverse_operands(p, 4, 31)
+    assert len(vals) > 2000 + 3 * p.bit_length() and all(0 < v < p for v in vals)
+    stored = O.ints_to_array(vals, 4)
+    want = O.ints_to_array([pow(v * pow(R, -1, p), -1, p) * R % p for v in vals], 4)
+    for at in range(0, len(vals), 256):
+        n = min(256, len(vals) - at)
+        t_in = cuda(stored[at:at + n])
+        t_out = torch.zeros_like(t_in)
+        poly.batch_inverse_device(F, t_in, n, t_out)
+        got = host(t_out)
+        assert all(v < p for v in O.array_to_ints(got)), (name, at)
+        assert np.array_equal(got, want[at:at + n]), (name, at, [hex(vals[at + i]) for i in np.nonzero((got != want[at:at + n]).any(axis=1))[0][:4]])
+    assert B % 256 == 0 and B > 256
+    one = O.ints_to_array([R % p], 4)
+    block_in, block_want = np.repeat(one, B, axis=0), np.repeat(one, B, axis=0)
+    block_in[:256], block_want[:256] = stored[:256], want[:256]      # the edge set and the first powers of two
+    t_in = cuda(block_in)
+    t_out = torch.zeros_like(t_in)
+    poly.batch_inverse_device(F, t_in, B, t_out)
+    assert np.array_equal(host(t_out), block_want), name
+
+
+@pytest.mark.parametrize("name", ["stark252", "fr381"])
 def test_batch_inverse_reports_a_zero_element(name):
     from lambda_elliptic_curves_amd import errors, poly
     p, F = MODULI[name], fld(name)

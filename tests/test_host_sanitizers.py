@@ -70,7 +70,58 @@ def test_product_host_limb_code_under_ubsan(tmp_path):
             }}
             return bad;
         }}
+        // fe_inv_fast at the operands a binary GCD can stumble on: inv(a) * a == 1 and inv(a) < p.  Families: 2^k and its
+        // neighbours, p - 2^k, limb patterns over {{0, 0xffffffff, 0x80000000, 1}}, values sharing p's top limbs.
+        template <class F> bool below_p(const Fe<F> &a) {{
+            Fe<F> d, pp;
+            for (int i = 0; i < F::N; i++) pp.v[i] = F::p(i);
+            return limbs_sub<F::N>(d.v, a.v, pp.v) != 0;
+        }}
+        template <class F> int chkinv(const Fe<F> &a, int &ran) {{
+            if (a.is_zero() || !below_p<F>(a)) return 0;
+            ran++;
+            const Fe<F> r = fe_inv_fast<F>(a);
+            return !(below_p<F>(r) && fe_mul<F>(r, a) == Fe<F>::one());
+        }}
+        template <class F> int cmpinv_adversarial(int &ran) {{
+            constexpr int N = F::N;
+            unsigned long long st = 0x13198A2E03707344ull;
+            auto next = [&]() {{ st = st * 6364136223846793005ull + 1442695040888963407ull; return (unsigned)(st >> 32); }};
+            int bad = 0;
+            Fe<F> pp, one_int = Fe<F>::zero();
+            for (int i = 0; i < N; i++) pp.v[i] = F::p(i);
+            one_int.v[0] = 1;
+            for (int k = 0; k < 32 * N; k++) {{
+                Fe<F> a = Fe<F>::zero(), b, c, d;
+                a.v[k / 32] = 1u << (k % 32);                          // 2^k
+                limbs_add<N>(b.v, a.v, one_int.v);                     // 2^k + 1
+                limbs_sub<N>(c.v, a.v, one_int.v);                     // 2^k - 1
+                limbs_sub<N>(d.v, pp.v, a.v);                          // p - 2^k (wraps above p when 2^k > p: refused by chkinv)
+                bad += chkinv<F>(a, ran) + chkinv<F>(b, ran) + chkinv<F>(c, ran) + chkinv<F>(d, ran);
+            }}
+            const unsigned sym[4] = {{0u, 0xffffffffu, 0x80000000u, 1u}};
+            for (int it = 0; it < 20000; it++) {{
+                Fe<F> a;
+                unsigned r = 0;
+                for (int i = 0; i < N; i++) {{ if (i % 16 == 0) r = next(); a.v[i] = sym[(r >> (2 * (i % 16))) & 3]; }}
+                if (!below_p<F>(a)) a.v[N - 1] = it & 1 ? F::p(N - 1) - 1 : sym[3 * ((it >> 1) & 1)];
+                bad += chkinv<F>(a, ran);
+            }}
+            for (int it = 0; it < 12000; it++) {{
+                Fe<F> a = pp;                                          // the top `keep` limbs are p's, the next one is smaller
+                const int keep = 1 + it % (N - 1), nxt = N - 1 - keep;
+                if (F::p(nxt) == 0) continue;
+                a.v[nxt] = it & 64 ? F::p(nxt) - 1 : next() % F::p(nxt);
+                for (int i = 0; i < nxt; i++) a.v[i] = (it >> (i % 6)) & 1 ? next() : 0u;
+                bad += chkinv<F>(a, ran);
+            }}
+            return bad;
+        }}
         int main() {{
+            int ran = 0;
+            printf("invadv %d\\n", cmpinv_adversarial<Stark252>(ran) + cmpinv_adversarial<Fr381>(ran) + cmpinv_adversarial<Fp381>(ran) +
+                                   cmpinv_adversarial<Fp254>(ran) + cmpinv_adversarial<Fr254>(ran));
+            printf("invadv_cases %d\\n", (int)(ran > 150000));
             printf("inv %d\\n", cmpinv<Stark252>() + cmpinv<Fr381>() + cmpinv<Fp381>() + cmpinv<Fp254>() + cmpinv<Fr254>());
             printf("mul64 %d\\n", cmp64<Stark252>() + cmp64<Fr381>() + cmp64<Fp381>() + cmp64<Fp254>() + cmp64<Fr254>());
             run<Stark252>("stark"); run<Fr381>("fr381"); run<Fp381>("fp381"); run<Fp254>("fp254");
@@ -89,4 +140,4 @@ def test_product_host_limb_code_under_ubsan(tmp_path):
                            "-o", str(exe), str(src)])
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr[-2000:]
-    assert out.stdout.split() == ["inv", "0", "mul64", "0", "stark", "1", "fr381", "1", "fp381", "1", "fp254", "1", "id", "1", "bb", "1", "rf", "1"], out.stdout
+    assert out.stdout.split() == ["invadv", "0", "invadv_cases", "1", "inv", "0", "mul64", "0", "stark", "1", "fr381", "1", "fp381", "1", "fp254", "1", "id", "1", "bb", "1", "rf", "1"], out.stdout
