@@ -11,6 +11,7 @@
 #include <vector>
 #include "field.cuh"
 #include "internal.h"
+#include "ntt_plan.h"
 
 namespace lw {
 
@@ -379,27 +380,19 @@ int ntt_device_locked(Context &c, lw_field_t field, lw_layout_t layout, lw_dir_t
         set_error("low-degree extension needs the forward direction and distinct buffers");
         return LW_ERR_BAD_ARG;
     }
-    // grid.y carries the batch: split very wide batches
-    const uint32_t max_batch = 32768;
-    if (batch > max_batch) {
-        const size_t eb = lw_hip_field_elem_bytes(field, layout);
-        const size_t s_out = stride ? stride : ((size_t)1 << log2n);
-        const size_t s_in = in_log2 < log2n ? ((size_t)1 << in_log2) : s_out;
-        for (uint32_t b0 = 0; b0 < batch; b0 += max_batch) {
-            const uint32_t nb = batch - b0 < max_batch ? batch - b0 : max_batch;
-            int rc2 = ntt_device_locked(c, field, layout, dir, (const char *)d_in + (size_t)b0 * s_in * eb,
-                                        (char *)d_out + (size_t)b0 * s_out * eb, log2n, nb, stride, coset, stream, in_log2);
-            if (rc2) return rc2;
-        }
-        return LW_OK;
-    }
-    if (in_log2 == 0 && log2n > 0)   // a constant polynomial: every evaluation is c_0 (times offset^0), no stage left to run
-        return broadcast_device(lw_hip_field_elem_bytes(field, layout), d_in, d_out, 1ull << log2n, batch,
-                                stride ? stride : ((uint64_t)1 << log2n), stream);
-    if (field == LW_FIELD_BABYBEAR) return ntt_bb_device(c, layout, dir, d_in, d_out, log2n, batch, stride, coset, stream, in_log2);
+    const size_t eb = lw_hip_field_elem_bytes(field, layout);
+    const size_t s_out = stride ? stride : ((size_t)1 << log2n);
+    const size_t s_in = in_log2 < log2n ? ((size_t)1 << in_log2) : s_out;   // a low-degree extension reads dense blocks
     uint32_t cw[8];
-    if (coset) words_from_ref(coset, cw);
-    return ntt256_device(c, (int)field, dir, d_in, d_out, log2n, batch, stride, coset ? cw : nullptr, stream, in_log2);
+    if (coset && field != LW_FIELD_BABYBEAR) words_from_ref(coset, cw);
+    return split_batch(batch, [&](uint32_t b0, uint32_t nb) {
+        const void *in = (const char *)d_in + (size_t)b0 * s_in * eb;
+        void *out = (char *)d_out + (size_t)b0 * s_out * eb;
+        if (in_log2 == 0 && log2n > 0)   // a constant polynomial: every evaluation is c_0 (times offset^0), no stage left to run
+            return broadcast_device(eb, in, out, 1ull << log2n, nb, s_out, stream);
+        if (field == LW_FIELD_BABYBEAR) return ntt_bb_device(c, layout, dir, in, out, log2n, nb, stride, coset, stream, in_log2);
+        return ntt256_device(c, (int)field, dir, in, out, log2n, nb, stride, coset ? cw : nullptr, stream, in_log2);
+    });
 }
 
 // ---- pinned result buffers (lw_hip_result_acquire / release) ----

@@ -188,17 +188,14 @@ static int circle_lde_device(Context &c, const uint32_t *d_evals, uint32_t Lin, 
     int rc = circle_ensure_twiddles(c, Lin, stream);
     if (!rc) rc = circle_ensure_twiddles(c, Lout, stream);
     if (rc) return rc;
-    const uint32_t chunk = batch < TILE_MAX_BATCH ? batch : TILE_MAX_BATCH;
+    const uint32_t chunk = batch < MAX_BATCH ? batch : MAX_BATCH;
     if (c.scratch.ensure((size_t)(nin + nout) * chunk * 4)) return LW_ERR_ALLOC;   // coefficients | what lies between two passes
     uint32_t *coeffs = (uint32_t *)c.scratch.p, *work = coeffs + nin * chunk;
     const NttPlan back = tile_plan<CirclePolicy>(Lin, Lin), out = tile_plan<CirclePolicy>(Lout, Lin);
-    for (uint32_t b0 = 0; b0 < batch; b0 += chunk) {
-        const uint32_t nb = batch - b0 < chunk ? batch - b0 : chunk;
-        rc = tile_run<CirclePolicy>(c, CircleCall{true}, back, d_evals + b0 * in_stride, in_stride, Lin, coeffs, nin, Lin, nb, work, stream);
-        if (!rc) rc = tile_run<CirclePolicy>(c, CircleCall{false}, out, coeffs, nin, Lin, d_out + b0 * out_stride, out_stride, Lout, nb, work, stream);
-        if (rc) return rc;
-    }
-    return LW_OK;
+    return split_batch(batch, [&](uint32_t b0, uint32_t nb) {
+        const int rc = tile_run<CirclePolicy>(c, CircleCall{true}, back, d_evals + b0 * in_stride, in_stride, Lin, coeffs, nin, Lin, nb, work, stream);
+        return rc ? rc : tile_run<CirclePolicy>(c, CircleCall{false}, out, coeffs, nin, Lin, d_out + b0 * out_stride, out_stride, Lout, nb, work, stream);
+    });
 }
 
 // ---- argument checks, before any device work

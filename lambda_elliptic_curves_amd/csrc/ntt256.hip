@@ -3,7 +3,7 @@
 #include <vector>
 #include "internal.h"
 #include "ntt_kernels.cuh"
-#include "ntt_plan.h"
+#include "pass_run.h"
 
 namespace lw {
 
@@ -172,7 +172,6 @@ static int ntt256_run(Context &c, int field, lw_dir_t dir, const void *d_in, voi
     uint32_t skip = 0;
     if (dir == LW_DIR_FORWARD && in_log2 >= 1 && in_log2 < log2n) skip = log2n - in_log2;
     const uint64_t in_mask = skip ? ((1ull << in_log2) - 1) : ~0ull;
-    const uint64_t in_stride_default = skip ? (1ull << in_log2) : n;
     if (log2n == 0) {   // N = 1: the transform (and N^-1 = 1, h^0 = 1) is the identity
         if (d_in != d_out)
             LW_HIP_CHECK(hipMemcpy2DAsync(d_out, stride * 32, d_in, stride * 32, 32, batch, hipMemcpyDeviceToDevice, stream),
@@ -184,12 +183,9 @@ static int ntt256_run(Context &c, int field, lw_dir_t dir, const void *d_in, voi
     const uint4 *tw = (const uint4 *)c.tw[field][dir].buf.p;
 
     const NttPlan pl = plan_passes(log2n, log2n, skip, NTT_TILE_LOG, NTT_KMAX, true);
-    const bool need_scratch = pl.npass > 1 || d_in == d_out;
-    if (need_scratch && c.scratch.ensure((size_t)n * batch * 32)) return LW_ERR_ALLOC;
+    if ((pl.npass > 1 || d_in == d_out) && c.scratch.ensure((size_t)n * batch * 32)) return LW_ERR_ALLOC;
     c.timings.scratch_bytes = c.scratch.bytes;
 
-    const void *src = d_in;
-    uint64_t src_stride = skip ? in_stride_default : stride;
     const uint4 *cos_lo = nullptr, *cos_hi = nullptr;
     const uint32_t cos_hbits = (log2n + 1) / 2;
     if (coset_words) {   // coset scaling is fused into the first pass's load / the last pass's store
@@ -197,65 +193,35 @@ static int ntt256_run(Context &c, int field, lw_dir_t dir, const void *d_in, voi
         rc = power_tables<F>(c, field, inv ? 1 : 0, coset_words, inv, cos_hbits, log2n - cos_hbits, stream, &cos_lo, &cos_hi, inv);
         if (rc) return rc;
     }
-
-    if (pl.npass == 1 && src == d_out && !skip) {
-        // single pass on aliased buffers: the last pass permutes across tiles, so stage the input first
-        LW_HIP_CHECK(hipMemcpy2DAsync(c.scratch.p, n * 32, d_in, stride * 32, n * 32, batch, hipMemcpyDeviceToDevice, stream),
-                     LW_ERR_LAUNCH);
-        src = c.scratch.p;
-        src_stride = n;
-    }
-
-    for (int i = 0; i < pl.npass; i++) {
-        const bool last = (i == pl.npass - 1);
+    return run_passes(c, schedule_passes(pl, false, d_in == d_out), log2n, d_in, skip ? (1ull << in_log2) : stride, d_out, stride, batch,
+                      c.scratch.p, 32, stream, [&](const PassStep &st, const void *in, void *out, uint64_t in_stride, uint64_t out_stride, dim3 grid) {
         NttPassParams p{};
         p.tw = tw;
-        p.lazy_in = (F::LAZY && i > 0) ? 1 : 0;
-        p.in_mask = i == 0 ? in_mask : ~0ull;
+        p.lazy_in = (F::LAZY && st.i > 0) ? 1 : 0;
+        p.in_mask = st.first ? in_mask : ~0ull;
         p.cos_lo = cos_lo;
         p.cos_hi = cos_hi;
         p.cos_hbits = cos_hbits;
-        p.cos_in = (coset_words && dir == LW_DIR_FORWARD && i == 0) ? 1 : 0;
-        p.cos_out = (coset_words && dir == LW_DIR_INVERSE && last) ? 1 : 0;
+        p.cos_in = (coset_words && dir == LW_DIR_FORWARD && st.first) ? 1 : 0;
+        p.cos_out = (coset_words && dir == LW_DIR_INVERSE && st.last) ? 1 : 0;
         p.L = log2n;
-        p.s0 = pl.s0[i];
-        p.r = pl.r[i];
-        p.logC = pl.logC[i];
-        if (p.r > NTT_MAX_R) {
-            set_error("internal: NTT pass of %u stages", p.r);
-            return LW_ERR_BAD_ARG;
+        p.s0 = st.s0;
+        p.r = st.r;
+        p.logC = st.logC;
+        p.nsteps = st.nsteps;
+        for (uint32_t q = 0; q < p.nsteps; q++) p.k[q] = st.k[q];
+        p.in = (const uint4 *)in;
+        p.in_batch_stride = in_stride;
+        p.out = (uint4 *)out;
+        p.out_batch_stride = out_stride;
+        if (st.last && dir == LW_DIR_INVERSE) {
+            Fe<F> ninv = fe_inv<F>(fe_from_u64<F>(n));   // FieldElement::from(len as u64).inv()
+            p.scale = 1;
+            for (int k = 0; k < 8; k++) p.sc[k] = ninv.v[k];
         }
-        p.nsteps = pl.nsteps[i];
-        for (uint32_t q = 0; q < p.nsteps; q++) p.k[q] = pl.k[i][q];
-        p.in = (const uint4 *)src;
-        p.in_batch_stride = src_stride;
-        if (last) {
-            if (src == d_out) {
-                set_error("internal: last NTT pass would run in place");
-                return LW_ERR_BAD_ARG;
-            }
-            p.out = (uint4 *)d_out;
-            p.out_batch_stride = stride;
-            if (dir == LW_DIR_INVERSE) {
-                Fe<F> ninv = fe_inv<F>(fe_from_u64<F>(n));   // FieldElement::from(len as u64).inv()
-                p.scale = 1;
-                for (int k = 0; k < 8; k++) p.sc[k] = ninv.v[k];
-            }
-        } else {
-            p.out = (uint4 *)c.scratch.p;
-            p.out_batch_stride = n;
-        }
-        const uint32_t blocks = 1u << (log2n - p.r - p.logC);
-        dim3 grid(blocks, batch);
-        hipEvent_t pe = c.prof_begin(stream);
-        launch_pass<F>(last, grid, stream, p);
-        c.prof_end(last ? "ntt_pass_kernel<last>" : "ntt_pass_kernel", pe, stream);
-        LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
-        src = p.out;
-        src_stride = p.out_batch_stride;
-    }
-
-    return LW_OK;
+        launch_pass<F>(st.last, grid, stream, p);
+        return st.last ? "ntt_pass_kernel<last>" : "ntt_pass_kernel";
+    });
 }
 
 // ---- helpers for the multi-GPU cross step (ntt_cross.hip)

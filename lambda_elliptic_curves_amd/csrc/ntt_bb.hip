@@ -11,7 +11,7 @@
 #include <vector>
 #include "internal.h"
 #include "field.cuh"
-#include "ntt_plan.h"
+#include "pass_run.h"
 
 namespace lw {
 
@@ -369,9 +369,7 @@ static int bb_run(Context &c, lw_dir_t dir, uint32_t lgV, const void *d_in, void
 
     // pass plan: the stages split evenly; logC columns x components fill the tile
     const NttPlan pl = plan_passes(log2n + lgV, log2n, skip, BB_TILE_LOG, BB_KMAX, false);
-    const int npass = pl.npass;
-    const bool need_scratch = npass > 1 || d_in == d_out;
-    if (need_scratch && c.scratch.ensure((size_t)nwords * batch * wbytes)) return LW_ERR_ALLOC;
+    if ((pl.npass > 1 || d_in == d_out) && c.scratch.ensure((size_t)nwords * batch * wbytes)) return LW_ERR_ALLOC;
     // coset factors: h^i fused into the first pass's load (forward), h^-i * N^-1 into the last pass's store (inverse) —
     // a separate kernel with one exponentiation per element cost more than the transform (0.59 ms against 0.48 at 4 x 2^24)
     // (a low-degree extension scales the 2^in_log2 coefficients only: zero padding happens after Polynomial::scale)
@@ -391,17 +389,10 @@ static int bb_run(Context &c, lw_dir_t dir, uint32_t lgV, const void *d_in, void
         LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
     }
 
-    const void *src = d_in;
-    uint64_t src_stride = lde ? ((uint64_t)1 << (in_log2 + lgV)) : stride;
-    bool src64 = W64;   // word type of `src`: the layout's in the caller's buffers, u32 in every intermediate this function writes
-    if (npass == 1 && src == d_out) {
-        LW_HIP_CHECK(hipMemcpy2DAsync(c.scratch.p, nwords * wbytes, d_in, stride * wbytes, nwords * wbytes, batch,
-                                      hipMemcpyDeviceToDevice, stream), LW_ERR_LAUNCH);
-        src = c.scratch.p;
-        src_stride = nwords;
-    }
-    for (int i = 0; i < npass; i++) {
-        const bool last = (i == npass - 1);
+    // word type of a pass's input / output: the layout's in the caller's buffers (and the staged copy of one), u32 in every intermediate
+    return run_passes(c, schedule_passes(pl, false, d_in == d_out), log2n + lgV, d_in, lde ? ((uint64_t)1 << (in_log2 + lgV)) : stride, d_out,
+                      stride, batch, c.scratch.p, wbytes, stream, [&](const PassStep &st, const void *in, void *out, uint64_t in_stride, uint64_t out_stride, dim3 grid) {
+        const bool last = st.last, src64 = W64 && st.src != PASS_WORK;
         BbPassParams p{};
         p.tw = (const uint32_t *)c.tw[LW_FIELD_BABYBEAR][dir].buf.p;
         {
@@ -410,34 +401,25 @@ static int bb_run(Context &c, lw_dir_t dir, uint32_t lgV, const void *d_in, void
         }
         p.L = log2n;
         p.lgV = lgV;
-        p.s0 = pl.s0[i];
-        p.r = pl.r[i];
-        p.logC = pl.logC[i];
-        p.nsteps = pl.nsteps[i];
-        for (uint32_t q = 0; q < p.nsteps; q++) p.k[q] = pl.k[i][q];
-        p.in = src;
-        p.in_batch_stride = src_stride;
+        p.s0 = st.s0;
+        p.r = st.r;
+        p.logC = st.logC;
+        p.nsteps = st.nsteps;
+        for (uint32_t q = 0; q < p.nsteps; q++) p.k[q] = st.k[q];
+        p.in = in;
+        p.in_batch_stride = in_stride;
+        p.out = out;
+        p.out_batch_stride = out_stride;
         p.cos_lo = cos_lo;
         p.cos_hi = cos_hi;
         p.cos_hbits = cos_hbits;
-        p.in_mask = (lde && i == 0) ? (uint32_t)(((uint64_t)1 << (in_log2 + lgV)) - 1) : 0xffffffffu;
-        p.cos_in = (coset && dir == LW_DIR_FORWARD && i == 0) ? 1u : 0u;
+        p.in_mask = (lde && st.first) ? (uint32_t)(((uint64_t)1 << (in_log2 + lgV)) - 1) : 0xffffffffu;
+        p.cos_in = (coset && dir == LW_DIR_FORWARD && st.first) ? 1u : 0u;
         p.cos_out = (coset && dir == LW_DIR_INVERSE && last) ? 1u : 0u;
-        if (last) {
-            if (src == d_out) { set_error("internal: last NTT pass would run in place"); return LW_ERR_BAD_ARG; }
-            p.out = d_out;
-            p.out_batch_stride = stride;
-            if (dir == LW_DIR_INVERSE && !coset) {   // with a coset offset N^-1 rides in the hi table
-                p.scale = 1;
-                p.sc = bb_inv(bb_mul((uint32_t)(n % BabyBear::P), BabyBear::R2));   // FieldElement::from(n).inv()
-            }
-        } else {
-            p.out = c.scratch.p;
-            p.out_batch_stride = nwords;
+        if (last && dir == LW_DIR_INVERSE && !coset) {   // with a coset offset N^-1 rides in the hi table
+            p.scale = 1;
+            p.sc = bb_inv(bb_mul((uint32_t)(n % BabyBear::P), BabyBear::R2));   // FieldElement::from(n).inv()
         }
-        const uint32_t blocks = 1u << (log2n + lgV - p.r - p.logC);
-        dim3 grid(blocks, batch);
-        hipEvent_t pe = c.prof_begin(stream);
         // (a 4-columns-per-lane variant of this kernel measured no faster — the pass is bound by butterfly issue and
         // LDS exchange, not by the width of its memory instructions)
         // full-size tiles (every pass of a transform of 2^18 words and more) take the kernels with the tile shape compiled in
@@ -464,14 +446,8 @@ static int bb_run(Context &c, lw_dir_t dir, uint32_t lgV, const void *d_in, void
         }
 #undef LW_BB_LAUNCH
 #undef LW_BB_LAUNCH_R
-        c.prof_end(last ? "bb_pass_kernel<last>" : "bb_pass_kernel", pe, stream);
-        LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
-        src = p.out;
-        src_stride = p.out_batch_stride;
-        src64 = last ? W64 : false;
-    }
-    LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
-    return LW_OK;
+        return last ? "bb_pass_kernel<last>" : "bb_pass_kernel";
+    });
 }
 
 // get_powers_of_primitive_root[_coset] for the BabyBear shapes: out[i] = scale * w^e(i) in the layout's base word

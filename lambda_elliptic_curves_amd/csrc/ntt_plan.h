@@ -1,6 +1,7 @@
 // Pass planning shared by the 256-bit-field NTT (ntt256.hip), the BabyBear NTT (ntt_bb.hip) and, through tile_pass.cuh, the circle FFT
-// (circle.hip) and the Goldilocks NTT (goldilocks.hip): how the stages of a transform are cut into passes, how wide each pass's tile is and how a pass is split into register steps.
-// Host only, plain C++ (no HIP header): tests/test_ntt_plan_cpu.py compiles it with g++ and pins every plan.
+// (circle.hip) and the Goldilocks NTT (goldilocks.hip): how the stages of a transform are cut into passes, how wide each pass's tile is and how a pass is split into register steps
+// (plan_passes); which buffer each pass of a plan reads and writes and in which order passes and steps run (schedule_passes, the data pass_run.h launches from); how a wide batch is cut (split_batch).
+// Host only, plain C++ (no HIP header): tests/test_ntt_plan_cpu.py compiles it with g++ and pins every plan and every schedule.
 #pragma once
 #include <stdint.h>
 
@@ -8,6 +9,7 @@ namespace lw {
 
 // stages per pass: the staged twiddles (ltw[2][256], 255 entries) and the 17p lazy bound both need r <= 8 (ntt_kernels.cuh)
 constexpr uint32_t NTT_MAX_R = 8;
+constexpr uint32_t MAX_BATCH = 32768;   // grid.y carries the batch: wider ones are split (split_batch)
 
 struct NttPlan {
     int npass;
@@ -70,6 +72,60 @@ inline NttPlan plan_passes(uint32_t Lw, uint32_t L, uint32_t skip, uint32_t tile
         s += r;
     }
     return pl;
+}
+
+// The passes of a transform in the order they run and the buffer each one reads and writes.  Only the first pass reads
+// the caller's input, only the last writes the caller's output, everything between lies in one work buffer: a pass other
+// than the plan's last (`lo`, which reorders across tiles) rewrites the words of its own tile, so it may run from the work
+// buffer into the work buffer.  A single pass on aliased buffers (d_in == d_out) reads a copy in the work buffer (`stage`).
+enum PassBuf { PASS_IN, PASS_STAGED, PASS_WORK, PASS_OUT };   // the caller's input, its copy in the work buffer, the work buffer, the caller's output
+struct PassStep {
+    int i;                          // index into the plan
+    bool first, last, lo;           // the first / last pass that runs; the plan's last pass
+    PassBuf src, dst;
+    uint32_t s0, r, logC;           // the plan's entry
+    uint32_t nsteps, k[8], t0[8];   // register steps in the order they run: stages t0 .. t0 + k - 1 of the pass
+};
+struct PassSchedule {
+    bool stage;
+    int npass;
+    PassStep step[8];
+};
+// `backward`: the passes, and the steps of each, run in reverse order (the backward butterfly of the circle interpolation)
+inline PassSchedule schedule_passes(const NttPlan &pl, bool backward, bool aliased) {
+    PassSchedule sc{};
+    sc.stage = pl.npass == 1 && aliased;
+    sc.npass = pl.npass;
+    for (int q = 0; q < pl.npass; q++) {
+        PassStep &st = sc.step[q];
+        const int i = st.i = backward ? pl.npass - 1 - q : q;
+        st.first = q == 0;
+        st.last = q == pl.npass - 1;
+        st.lo = i == pl.npass - 1;
+        st.src = !st.first ? PASS_WORK : sc.stage ? PASS_STAGED : PASS_IN;
+        st.dst = st.last ? PASS_OUT : PASS_WORK;
+        st.s0 = pl.s0[i];
+        st.r = pl.r[i];
+        st.logC = pl.logC[i];
+        st.nsteps = pl.nsteps[i];
+        uint32_t t0 = 0;
+        for (uint32_t j = 0; j < st.nsteps; j++) {
+            const uint32_t at = backward ? st.nsteps - 1 - j : j;
+            st.k[at] = pl.k[i][j];
+            st.t0[at] = t0;
+            t0 += pl.k[i][j];
+        }
+    }
+    return sc;
+}
+
+// f(b0, nb) over a batch in chunks of at most MAX_BATCH columns, until one returns an error
+template <class F> inline int split_batch(uint32_t batch, F f) {
+    for (uint32_t b0 = 0; b0 < batch; b0 += MAX_BATCH) {
+        const int rc = f(b0, batch - b0 < MAX_BATCH ? batch - b0 : MAX_BATCH);
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 }  // namespace lw

@@ -1,6 +1,6 @@
 // The LDS-tiled multi-stage pass of a radix-2 transform over one-word elements, written once for circle.hip (Mersenne31,
-// u32) and goldilocks.hip (u64): the pass kernel, the loop that launches the passes of a transform, the batch split and
-// the host-buffer entry body.  A field is a compile-time policy T, a struct of constants, types and static
+// u32) and goldilocks.hip (u64): the pass kernel, this family's side of the loop that launches the passes of a transform
+// (pass_run.h) and the host-buffer entry body.  A field is a compile-time policy T, a struct of constants, types and static
 // __device__ __forceinline__ functions, so every kernel holds a single inlined copy of T's arithmetic and addressing.
 //
 // Passes.  A transform of 2^L words takes ceil(L / 8) passes (plan_passes), each a tile of 2^r rows x 2^logC columns in
@@ -34,14 +34,12 @@
 // and on the host a call object: backward(), fill(fields, L, first, last) and kernel(lo, name), see tile_run.
 #pragma once
 #include <stdlib.h>
-#include "internal.h"
-#include "ntt_plan.h"
+#include "pass_run.h"
 
 namespace lw {
 
 constexpr int TILE_THREADS = 256;
 constexpr int TILE_KMAX = 4;                 // radix-16 register steps
-constexpr uint32_t TILE_MAX_BATCH = 32768;   // grid.y carries the batch: wider ones are split
 
 template <class T> struct TilePassParams {
     const typename T::word *in;
@@ -203,7 +201,7 @@ static bool spans_overlap(const void *a, size_t a_bytes, const void *b, size_t b
 // One transform of `batch` columns of 2^L words by the passes of `pl` (tile_plan(L, in_log2)); a forward one reads
 // 2^in_log2 words per column (in_log2 < L: zero padded).  `work` holds batch x 2^L words for what lies between two
 // passes and for the copy of an in-place single pass; it is only touched when there is more than one pass or
-// d_in == d_out.  The field's tables must be there.  `call` is the field's side of the loop:
+// d_in == d_out (run_passes).  The field's tables must be there.  `call` is the field's side of the loop:
 //   call.backward()                  the passes, and the steps of each, run in reverse order (the backward butterfly)
 //   call.fill(f, L, first, last)     the field's parameters of the first / last pass that runs, or one between
 //   call.kernel(lo, name)            the instantiation for an LO or HI pass and its line in lw_hip_profile_end
@@ -211,68 +209,42 @@ template <class T, class Call>
 static int tile_run(Context &c, const Call &call, const NttPlan &pl, const typename T::word *d_in, uint64_t in_stride, uint32_t in_log2,
                     typename T::word *d_out, uint64_t out_stride, uint32_t L, uint32_t batch, typename T::word *work, hipStream_t stream) {
     using word = typename T::word;
-    const uint64_t n = 1ull << L;
-    const bool back = call.backward();
-    const word *src = d_in;
-    uint64_t src_stride = in_stride;
-    if (pl.npass == 1 && d_in == d_out) {
-        LW_HIP_CHECK(hipMemcpy2DAsync(work, n * sizeof(word), d_in, in_stride * sizeof(word), n * sizeof(word), batch, hipMemcpyDeviceToDevice, stream),
-                     LW_ERR_LAUNCH);
-        src = work;
-        src_stride = n;
-    }
-    for (int q = 0; q < pl.npass; q++) {
-        const int i = back ? pl.npass - 1 - q : q;
-        const bool lo = i == pl.npass - 1, last = q == pl.npass - 1;
+    return run_passes(c, schedule_passes(pl, call.backward(), d_in == d_out), L, d_in, in_stride, d_out, out_stride, batch, work, sizeof(word), stream,
+                      [&](const PassStep &st, const void *in, void *out, uint64_t src_stride, uint64_t dst_stride, dim3 grid) {
         TilePassParams<T> p{};
-        p.in = src;
+        p.in = (const word *)in;
         p.in_stride = src_stride;
-        p.out = last ? d_out : work;
-        p.out_stride = last ? out_stride : n;
+        p.out = (word *)out;
+        p.out_stride = dst_stride;
         p.L = L;
-        p.s0 = pl.s0[i];
-        p.r = pl.r[i];
-        p.logC = pl.logC[i];
-        p.nsteps = pl.nsteps[i];
-        uint32_t t0 = 0;
+        p.s0 = st.s0;
+        p.r = st.r;
+        p.logC = st.logC;
+        p.nsteps = st.nsteps;
         for (uint32_t j = 0; j < p.nsteps; j++) {
-            const uint32_t at = back ? p.nsteps - 1 - j : j;
-            p.k[at] = pl.k[i][j];
-            p.t0[at] = t0;
-            t0 += pl.k[i][j];
+            p.k[j] = st.k[j];
+            p.t0[j] = st.t0[j];
         }
-        p.in_mask = q == 0 ? (uint32_t)((1ull << in_log2) - 1) : 0xffffffffu;
-        call.fill(p.f, L, q == 0, last);
+        p.in_mask = st.first ? (uint32_t)((1ull << in_log2) - 1) : 0xffffffffu;
+        call.fill(p.f, L, st.first, st.last);
         const char *name = nullptr;
-        void (*kernel)(TilePassParams<T>) = call.kernel(lo, name);
-        hipEvent_t pe = c.prof_begin(stream);
-        hipLaunchKernelGGL(kernel, dim3(1u << (L - p.r - p.logC), batch), dim3(TILE_THREADS), 0, stream, p);
-        c.prof_end(name, pe, stream);
-        LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
-        src = p.out;
-        src_stride = p.out_stride;
-    }
-    return LW_OK;
+        void (*kernel)(TilePassParams<T>) = call.kernel(st.lo, name);
+        hipLaunchKernelGGL(kernel, grid, dim3(TILE_THREADS), 0, stream, p);
+        return name;
+    });
 }
 
-// tile_run over a batch of any width, in chunks of TILE_MAX_BATCH columns, with the lane's scratch as `work`
+// tile_run over a batch of any width, with the lane's scratch as `work`
 template <class T, class Call>
 static int tile_transform_device(Context &c, const Call &call, const typename T::word *d_in, uint64_t in_stride, uint32_t in_log2,
                                  typename T::word *d_out, uint64_t out_stride, uint32_t L, uint32_t batch, hipStream_t stream) {
     using word = typename T::word;
     const NttPlan pl = tile_plan<T>(L, in_log2);
-    const uint32_t chunk = batch < TILE_MAX_BATCH ? batch : TILE_MAX_BATCH;
-    word *work = nullptr;
-    if (pl.npass > 1 || d_in == d_out) {
-        if (c.scratch.ensure(((size_t)chunk << L) * sizeof(word))) return LW_ERR_ALLOC;
-        work = (word *)c.scratch.p;
-    }
-    for (uint32_t b0 = 0; b0 < batch; b0 += chunk) {
-        const uint32_t nb = batch - b0 < chunk ? batch - b0 : chunk;
-        const int rc = tile_run<T>(c, call, pl, d_in + b0 * in_stride, in_stride, in_log2, d_out + b0 * out_stride, out_stride, L, nb, work, stream);
-        if (rc) return rc;
-    }
-    return LW_OK;
+    if ((pl.npass > 1 || d_in == d_out) && c.scratch.ensure(((size_t)(batch < MAX_BATCH ? batch : MAX_BATCH) << L) * sizeof(word))) return LW_ERR_ALLOC;
+    word *work = (word *)c.scratch.p;
+    return split_batch(batch, [&](uint32_t b0, uint32_t nb) {
+        return tile_run<T>(c, call, pl, d_in + b0 * in_stride, in_stride, in_log2, d_out + b0 * out_stride, out_stride, L, nb, work, stream);
+    });
 }
 
 // The body of a host-buffer entry after its argument checks: `batch` columns of 2^log2n words, `stride` words apart, go

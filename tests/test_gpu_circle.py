@@ -258,3 +258,23 @@ def test_batch_split_above_32768_columns(inverse, in_place):
     assert np.array_equal(to_host(t_out), case["co" if inverse else "ev"])
     if not in_place:
         assert np.array_equal(to_host(t_in), case["w"])
+
+
+def test_lde_batch_split_above_32768_columns():
+    # 2^1 evaluations into 2^2 per column, strided on both sides: past the split the input advances by its own stride
+    import torch
+    from lambda_elliptic_curves_amd import circle
+    four = words((4, 2), 1500)
+    exp4 = R.np_lde(four, 2)
+    assert len({tuple(r) for r in exp4}) == 4
+    sin, sout, canary = 3, 5, np.uint32(0xDEADBEEF)
+    pick = np.arange(SPLIT_BATCH) % 4
+    buf = np.full((SPLIT_BATCH, sin), canary, np.uint32)
+    buf[:, :2] = four[pick]
+    exp = np.full((SPLIT_BATCH, sout), canary, np.uint32)
+    exp[:, :4] = exp4[pick]
+    t_in, t_out = to_dev(buf.reshape(-1)), to_dev(np.full(SPLIT_BATCH * sout, canary, np.uint32))
+    circle.lde_device(t_in, 1, t_out, 2, batch=SPLIT_BATCH, in_stride=sin, out_stride=sout)
+    torch.cuda.synchronize()
+    assert np.array_equal(to_host(t_out).reshape(SPLIT_BATCH, sout), exp)
+    assert np.array_equal(to_host(t_in).reshape(SPLIT_BATCH, sin), buf)

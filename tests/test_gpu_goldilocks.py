@@ -314,3 +314,22 @@ def test_batch_split_above_32768_columns(inverse, in_place):
     case = _split_case()
     got = _ntt(case["a"], 1, inverse=inverse, batch=SPLIT_BATCH, offset=7, in_place=in_place)
     assert np.array_equal(got, case["inv" if inverse else "fwd"])
+
+
+def test_lde_batch_split_above_32768_columns():
+    # 2^1 coefficients into 2^2 evaluations per column, strided on both sides: past the split the input advances by its own stride
+    import torch
+    four = _rand((4, 2), 1100)
+    exp4 = R.np_evaluate_fft(four, 7, log2n=2)
+    assert len({tuple(r) for r in exp4}) == 4
+    sin, sout, canary = 3, 5, np.uint64(0xDEADBEEFCAFEF00D)
+    pick = np.arange(SPLIT_BATCH) % 4
+    buf = np.full((SPLIT_BATCH, sin), canary, np.uint64)
+    buf[:, :2] = four[pick]
+    exp = np.full((SPLIT_BATCH, sout), canary, np.uint64)
+    exp[:, :4] = exp4[pick]
+    t_c, t_out = _dev(buf.reshape(-1)), _dev(np.full(SPLIT_BATCH * sout, canary, np.uint64))
+    _gl().lde_device(t_c, 1, t_out, 2, batch=SPLIT_BATCH, in_stride=sin, out_stride=sout, offset=7)
+    torch.cuda.synchronize()
+    assert np.array_equal(_host(t_out).reshape(SPLIT_BATCH, sout), exp)
+    assert np.array_equal(_host(t_c).reshape(SPLIT_BATCH, sin), buf)

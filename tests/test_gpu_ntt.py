@@ -243,3 +243,21 @@ def test_get_powers_of_primitive_root_and_coset_variant(name):
     assert np.array_equal(got.reshape(-1), np.asarray(exp).reshape(-1))
     with pytest.raises(errors.RootOfUnityError):
         fft.get_powers_of_primitive_root(fld, fld.two_adicity + 1, 4, fft.ROOTS_NATURAL)
+
+
+@pytest.mark.parametrize("name", F256)
+@pytest.mark.parametrize("in_place", [False, True])
+@pytest.mark.parametrize("inverse", [False, True])
+def test_batch_split_above_32768_columns(name, inverse, in_place):
+    util.check_ntt_split(name, inverse, in_place)
+
+
+@pytest.mark.parametrize("name", F256)
+def test_lde_batch_split_above_32768_blocks(name):
+    util.check_ntt_lde_split(name)
+
+
+@pytest.mark.parametrize("name", F256)
+@pytest.mark.parametrize("log_n", [1, 5, 8, 9])
+def test_strided_columns_with_canaries_distinct_and_in_place(name, log_n):
+    util.check_ntt_strided(name, log_n)

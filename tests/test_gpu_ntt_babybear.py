@@ -136,3 +136,21 @@ def test_max_size_2_24_roundtrip_u32():
     s1 = int((int(canon[0::2].sum()) - int(canon[1::2].sum())) % p)
     assert O.elems_from_mont(oid, ev[:1])[0] == s0
     assert O.elems_from_mont(oid, ev[1 << 23:(1 << 23) + 1])[0] == s1
+
+
+@pytest.mark.parametrize("name", BB)
+@pytest.mark.parametrize("in_place", [False, True])
+@pytest.mark.parametrize("inverse", [False, True])
+def test_batch_split_above_32768_columns(name, inverse, in_place):
+    util.check_ntt_split(name, inverse, in_place)
+
+
+@pytest.mark.parametrize("name", BB)
+def test_lde_batch_split_above_32768_blocks(name):
+    util.check_ntt_lde_split(name)
+
+
+@pytest.mark.parametrize("name", BB)
+@pytest.mark.parametrize("log_n", [1, 5, 8, 9])
+def test_strided_columns_with_canaries_distinct_and_in_place(name, log_n):
+    util.check_ntt_strided(name, log_n)

@@ -125,3 +125,117 @@ def groth16_h_by_composition(l, r, o, gates):
     lc, rc, oc, tc = (O.elems_from_mont(f, x) for x in (le, re_, oe, t))
     h = [((a * b - c) * pow(d, -1, p)) % p for a, b, c, d in zip(lc, rc, oc, tc)]
     return O.interpolate_fft(f, O.elems_to_mont(f, h), off, strip=True)
+
+
+# ---- device-resident NTT cases shared by test_gpu_ntt.py and test_gpu_ntt_babybear.py: every buffer is a 2-d array of
+# the layout's words, one row per element
+def ntt_words(name, a):
+    return np.ascontiguousarray(a).reshape(np.shape(a)[0], -1)
+
+
+def ntt_columns(name, count, n, seed):
+    """`count` columns of n elements each, (count, n, words); the last coefficient of each is not zero, so that
+    Polynomial::new strips nothing"""
+    a = ntt_words(name, rand_elems(name, count * n, seed))
+    a = a.reshape(count, n, a.shape[1]).copy()
+    a[:, -1, -1] |= a.dtype.type(1)
+    return a
+
+
+def ntt_oracle(name, col, inverse=False, offset=None, log2n=None):
+    """one column through the oracle: evaluate_[offset_]fft (zero padded to 2^log2n if given) or interpolate_[offset_]fft"""
+    oid = field_pairs()[name][1]
+    col = col.reshape(-1) if name == "babybear_u32" else col
+    if inverse:
+        out = O.interpolate_fft(oid, col, offset)
+    elif log2n is None:
+        out = O.evaluate_fft(oid, col, 1, None, offset)
+    else:
+        out = O.evaluate_fft(oid, col, 1, 1 << log2n, offset)
+    out = ntt_words(name, out)
+    assert out.shape[0] == (col.shape[0] if log2n is None else 1 << log2n)
+    return out
+
+
+def _to_device(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.int32 if a.dtype == np.uint32 else np.int64).copy()).cuda()
+
+
+def ntt_on_device(name, a, log2n, batch, stride=0, inverse=False, offset=None, out=None, lde_from=None):
+    """lw_hip_ntt_device on device copies of `a` and `out` (None: in place), or lw_hip_ntt_lde_device from dense blocks of
+    2^lde_from coefficients; returns (the output buffer, the input buffer afterwards) as arrays like `out` and `a`"""
+    import torch
+    from lambda_elliptic_curves_amd import fft
+    fld = field_pairs()[name][0]
+    t_in = _to_device(a)
+    t_out = t_in if out is None else _to_device(out)
+    if lde_from is None:
+        fft.ntt_device(fld, t_in, t_out, log2n, inverse=inverse, batch=batch, batch_stride=stride, offset=offset)
+    else:
+        fft.lde_device(fld, t_in, lde_from, t_out, log2n, batch=batch, offset=offset)
+    torch.cuda.synchronize()
+    like = a if out is None else out
+    return t_out.cpu().numpy().view(like.dtype).reshape(like.shape), t_in.cpu().numpy().view(a.dtype).reshape(a.shape)
+
+
+SPLIT_BATCH = 32768 + 3   # grid.y carries at most 32768 columns: a chunk of 32768 and one of 3
+_NTT_SPLIT = {}
+
+
+def ntt_split_case(name):
+    """SPLIT_BATCH columns of 2^1 elements that cycle through four distinct inputs, and what the oracle makes of them
+    under offset 3: forward, inverse and extended to 2^2.  Computed once per field and left unchanged."""
+    if name not in _NTT_SPLIT:
+        four = ntt_columns(name, 4, 2, 1500)
+        off = offset_elem(name, 3)
+        tile = lambda cols: np.concatenate([cols[b % 4] for b in range(SPLIT_BATCH)])
+        case = {"off": off, "in": tile(four)}
+        for key, kw in (("fwd", {}), ("inv", {"inverse": True}), ("lde", {"log2n": 2})):
+            outs = [ntt_oracle(name, c, offset=off, **kw) for c in four]
+            assert len({o.tobytes() for o in outs}) == 4   # a chunk offset that is off by one cannot hide behind equal columns
+            case[key] = tile(outs)
+        for v in case.values():
+            v.setflags(write=False)
+        _NTT_SPLIT[name] = case
+    return _NTT_SPLIT[name]
+
+
+def check_ntt_split(name, inverse, in_place):
+    """SPLIT_BATCH columns of the smallest transform, one pass: in place is the copy through the work buffer, per chunk"""
+    case = ntt_split_case(name)
+    a = case["in"]
+    got, after = ntt_on_device(name, a, 1, SPLIT_BATCH, inverse=inverse, offset=case["off"], out=None if in_place else np.zeros_like(a))
+    assert got.tobytes() == case["inv" if inverse else "fwd"].tobytes()
+    assert in_place or after.tobytes() == a.tobytes()
+
+
+def check_ntt_lde_split(name):
+    """dense blocks of 2^1 coefficients into 2^2 evaluations each: past the split the input advances by 2, the output by 4"""
+    case = ntt_split_case(name)
+    a = case["in"]
+    got, after = ntt_on_device(name, a, 2, SPLIT_BATCH, offset=case["off"], out=np.zeros((2 * a.shape[0], a.shape[1]), a.dtype), lde_from=1)
+    assert got.tobytes() == case["lde"].tobytes() and after.tobytes() == a.tobytes()
+
+
+def check_ntt_strided(name, log2n):
+    """3 columns, n + 8 elements apart, canaries between them and behind the last: forward, inverse and coset forward,
+    into a second buffer and in place.  One pass up to 2^8 (in place: the staging copy), two at 2^9."""
+    n, batch = 1 << log2n, 3
+    stride = n + 8
+    cols = ntt_columns(name, batch, n, 1600 + log2n)
+    W, dt = cols.shape[2], cols.dtype
+    canary = dt.type(0xDEADBEEF if dt == np.uint32 else 0xDEADBEEFCAFEF00D)
+    a = np.full((batch, stride, W), canary, dt)
+    a[:, :n] = cols
+    a = a.reshape(batch * stride, W)
+    off = offset_elem(name, 3)
+    for inverse, offset in ((False, None), (True, None), (False, off)):
+        want = np.full((batch, stride, W), canary, dt)
+        for b in range(batch):
+            want[b, :n] = ntt_oracle(name, cols[b], inverse=inverse, offset=offset)
+        want = want.reshape(batch * stride, W)
+        got, after = ntt_on_device(name, a, log2n, batch, stride, inverse=inverse, offset=offset, out=np.full_like(a, canary))
+        assert got.tobytes() == want.tobytes() and after.tobytes() == a.tobytes(), (inverse, offset is not None, "distinct")
+        got, _ = ntt_on_device(name, a, log2n, batch, stride, inverse=inverse, offset=offset)
+        assert got.tobytes() == want.tobytes(), (inverse, offset is not None, "in place")
