@@ -374,6 +374,53 @@ typedef enum { LW_EC_OP_ADD = 0, LW_EC_OP_ADD_MIXED = 1, LW_EC_OP_DBL = 2, LW_EC
 int lw_hip_ec_pointwise_device(lw_curve_t curve, int model, lw_ec_op_t op, const void *d_a, const void *d_b,
                                size_t n, void *d_out, void *hip_stream);
 
+/* The test seam of the field arithmetic: one primitive of csrc/field.cuh per row (csrc/field_pointwise_ops.cuh holds the
+ * table, csrc/field_pointwise.hip the kernel), on operands the caller chooses, the returned limbs written back bit for
+ * bit.  Fields and ops have enums of their own: the seam reaches fields (the base fields, Fr254) and operand ranges that
+ * no transform takes, so lw_field_t and lw_layout_t are not involved.
+ *   rows    Multi-limb fields: an element is N/2 u64 limbs, most significant first (the reference layout), read and
+ *           written as stored: nothing is converted.  "a < p" below is about that stored integer.  BabyBear: u32 words,
+ *           except the u64 words REDUCE64 and FROM_R64 read and TO_R64 writes.
+ *   op      (out "canonical": < p; "raw": the limbs the primitive returned, see its comment in field.cuh)
+ *           ADD, SUB, NEG, DBL    fe_add, fe_sub, fe_neg, fe_dbl; a, b < p; canonical
+ *           MUL                   fe_mul; one operand < p, the other any N-limb value, in either order; canonical
+ *           SQR                   fe_sqr; a < p; canonical
+ *           MUL_LAZY              fe_mul_lazy; a < p, b any N-limb value; raw, in [0, 2p)
+ *           MUL_LAZY_UNIFORM      fe_mul_lazy_uniform; d_a holds ONE row, read by every work-item through the same address,
+ *                                 a < p; b any N-limb value; the bytes of MUL_LAZY
+ *           REDUCE_FULL           fe_reduce_full; Stark252: any 256-bit value, other fields: a < 2p; canonical
+ *           COND_SUB_P            fe_cond_sub_kp<F, 0>; any N-limb value; a - p if a >= p, else a
+ *           ADD_RAW               fe_add_raw; a + b < 2^(32N); a + b
+ *           ADD2P_SUB_RAW         fe_add2p_sub_raw; b <= a + 2p and a + 2p - b < 2^(32N); a + 2p - b
+ *           NEG_RAW, NEG_RAW_2P   fe_neg_raw, a <= p: p - a; fe_neg_raw_2p, a <= 2p: 2p - a
+ *           TO_MONT, FROM_MONT    fe_to_mont, fe_from_mont; a < p; canonical
+ *           DOT2, DOT4            fe_dot<F, 2>, fe_dot<F, 4>; rows of 2 / 4 elements in d_a and in d_b, each <= p (p itself
+ *                                 allowed); one element out, canonical.  LW_ERR_BAD_ARG for a field whose modulus leaves
+ *                                 fe_dot no room for that many products (DOT4 on Fr381)
+ *           INV                   fe_inv (Fermat); a < p, 0 -> 0; canonical
+ *           BabyBear only: MUL, ADD, SUB (bb_mul, bb_add, bb_sub; words < p); REDUCE64 (bb_reduce; a u64 below p * 2^32);
+ *           FROM_R64 (bb_from_r64; a u64 below p); TO_R64 (bb_to_r64; a word < p, a u64 out).  Every other pairing of
+ *           BabyBear, or of a multi-limb field, with an op: LW_ERR_BAD_ARG.
+ * Operands outside the stated domain are not detected: the result is whatever the primitive gives.
+ * One work-item per row; rows past n are never written.  A bad field or op, an op the field does not have, a NULL or
+ * misaligned buffer (16 bytes), a missing or a superfluous d_b: LW_ERR_BAD_ARG, before any device work.  n = 0 (checked
+ * after field and op): LW_OK, nothing is touched.  d_out may be exactly d_a or exactly d_b where the rows of that operand
+ * are as long as the output's (not DOT2 / DOT4, not the single row of MUL_LAZY_UNIFORM, not across word sizes); any other
+ * overlap of d_out with an operand is LW_ERR_BAD_ARG. */
+typedef enum {
+    LW_PW_FIELD_STARK252 = 0, LW_PW_FIELD_FR381 = 1, LW_PW_FIELD_FR254 = 2, LW_PW_FIELD_FP381 = 3, LW_PW_FIELD_FP254 = 4,
+    LW_PW_FIELD_BABYBEAR = 5
+} lw_pw_field_t;
+typedef enum {
+    LW_FIELD_OP_ADD = 0, LW_FIELD_OP_SUB = 1, LW_FIELD_OP_NEG = 2, LW_FIELD_OP_DBL = 3, LW_FIELD_OP_MUL = 4, LW_FIELD_OP_SQR = 5,
+    LW_FIELD_OP_MUL_LAZY = 6, LW_FIELD_OP_MUL_LAZY_UNIFORM = 7, LW_FIELD_OP_REDUCE_FULL = 8, LW_FIELD_OP_COND_SUB_P = 9,
+    LW_FIELD_OP_ADD_RAW = 10, LW_FIELD_OP_ADD2P_SUB_RAW = 11, LW_FIELD_OP_NEG_RAW = 12, LW_FIELD_OP_NEG_RAW_2P = 13,
+    LW_FIELD_OP_TO_MONT = 14, LW_FIELD_OP_FROM_MONT = 15, LW_FIELD_OP_DOT2 = 16, LW_FIELD_OP_DOT4 = 17, LW_FIELD_OP_INV = 18,
+    LW_FIELD_OP_REDUCE64 = 19, LW_FIELD_OP_FROM_R64 = 20, LW_FIELD_OP_TO_R64 = 21
+} lw_field_op_t;
+int lw_hip_field_pointwise_device(lw_pw_field_t field, lw_field_op_t op, const void *d_a, const void *d_b, size_t n, void *d_out,
+                                  void *hip_stream);
+
 /* Fixed point set cached on the device in affine form (SURVEY 8f "next" #2, second half).  Every reference caller
  * multiplies against a structured reference string it built once: KZG commits with
  * msm(&coefficients, &srs.powers_main_group[..coefficients.len()]) (crypto/src/commitments/kzg.rs:159-163), Groth16 with

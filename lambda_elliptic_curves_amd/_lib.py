@@ -15,6 +15,11 @@ LAYOUT_U64_LIMBS_MS_FIRST, LAYOUT_BABYBEAR_U32_R32, LAYOUT_BABYBEAR_U64_R64, LAY
 DIR_FORWARD, DIR_INVERSE = 0, 1
 CURVE_BLS12_381_G1, CURVE_BN254_G1, CURVE_BN254_G2, CURVE_BLS12_381_G2 = 0, 1, 2, 3
 EC_OP_ADD, EC_OP_ADD_MIXED, EC_OP_DBL, EC_OP_ADD_QUAD, EC_OP_TO_AFFINE = 0, 1, 2, 3, 4   # lw_ec_op_t
+PW_FIELD_STARK252, PW_FIELD_FR381, PW_FIELD_FR254, PW_FIELD_FP381, PW_FIELD_FP254, PW_FIELD_BABYBEAR = range(6)   # lw_pw_field_t
+(FIELD_OP_ADD, FIELD_OP_SUB, FIELD_OP_NEG, FIELD_OP_DBL, FIELD_OP_MUL, FIELD_OP_SQR, FIELD_OP_MUL_LAZY, FIELD_OP_MUL_LAZY_UNIFORM,
+ FIELD_OP_REDUCE_FULL, FIELD_OP_COND_SUB_P, FIELD_OP_ADD_RAW, FIELD_OP_ADD2P_SUB_RAW, FIELD_OP_NEG_RAW, FIELD_OP_NEG_RAW_2P,
+ FIELD_OP_TO_MONT, FIELD_OP_FROM_MONT, FIELD_OP_DOT2, FIELD_OP_DOT4, FIELD_OP_INV, FIELD_OP_REDUCE64, FIELD_OP_FROM_R64,
+ FIELD_OP_TO_R64) = range(22)   # lw_field_op_t
 POSEIDON_LEAF_SINGLE, POSEIDON_LEAF_MANY = 0, 1   # lw_poseidon_leaf_t
 RPO_128, RPO_160 = 0, 1   # lw_rpo_level_t
 (OK, ERR_INPUT_NOT_POW2, ERR_ORDER_TOO_LARGE, ERR_ROOT_OF_UNITY, ERR_LENGTH_MISMATCH, ERR_NO_DEVICE, ERR_ALLOC,
@@ -30,7 +35,7 @@ EXPORTS = [
     "lw_stark_commit_columns", "lw_stark_commit_columns_device", "lw_stark_commit_columns_layout_device", "lw_stark_fri_layer",
     "lw_hip_srs_create", "lw_hip_srs_create_device", "lw_hip_srs_destroy", "lw_hip_msm_srs", "lw_hip_msm_srs_device",
     "lw_hip_msm_srs_fr", "lw_hip_msm_srs_fr_device", "lw_stark_fri_layer_device", "lw_groth16_h_coefficients_device",
-    "lw_hip_ec_add_outer_device", "lw_hip_ec_pointwise_device",
+    "lw_hip_ec_add_outer_device", "lw_hip_ec_pointwise_device", "lw_hip_field_pointwise_device",
     "lw_hip_comm_unique_id", "lw_hip_comm_init", "lw_hip_comm_shutdown", "lw_hip_comm_info",
     "lw_hip_ntt_sharded_device", "lw_hip_ntt_sharded_selftest_device", "lw_hip_ntt_sharded_selftest_steps_device",
     "lw_hip_msm_sharded_device", "lw_hip_msm_sharded_selftest_device",
@@ -186,6 +191,8 @@ def lib():
     L.lw_hip_ec_add_outer_device.restype = i
     L.lw_hip_ec_pointwise_device.argtypes = [i, i, i, vp, vp, sz, vp, vp]
     L.lw_hip_ec_pointwise_device.restype = i
+    L.lw_hip_field_pointwise_device.argtypes = [i, i, vp, vp, sz, vp, vp]
+    L.lw_hip_field_pointwise_device.restype = i
     L.lw_hip_comm_unique_id.argtypes = [vp]
     L.lw_hip_comm_unique_id.restype = i
     L.lw_hip_comm_init.argtypes = [vp, i, i]

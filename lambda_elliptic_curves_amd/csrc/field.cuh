@@ -288,8 +288,9 @@ LW_HD Fe<F> fe_dbl(const Fe<F> &a) { return fe_add<F>(a, a); }
 // inline asm, several MACs per statement (hipcc pads one wait state after every asm statement).
 // Multiplications by the modulus limbs are resolved at compile time: zero limbs vanish, small limbs
 // become inline constants, the rest are SGPR literals (Stark252: p = 2^251 + 17*2^192 + 1, INV = -1).
+// (a*b + m*p) / R before the final subtraction: in [0, 2p) for a < p and any b, the same integer the device columns form
 template <class F>
-LW_HD Fe<F> fe_mul_portable(const Fe<F> &a, const Fe<F> &b) {
+LW_HD Fe<F> fe_mul_portable_raw(const Fe<F> &a, const Fe<F> &b) {
     constexpr int N = F::N;
     uint32_t t[N];
 #pragma unroll
@@ -318,8 +319,10 @@ LW_HD Fe<F> fe_mul_portable(const Fe<F> &a, const Fe<F> &b) {
     Fe<F> r;
 #pragma unroll
     for (int i = 0; i < N; i++) r.v[i] = t[i];
-    return reduce_once<F>(r);
+    return r;
 }
+template <class F>
+LW_HD Fe<F> fe_mul_portable(const Fe<F> &a, const Fe<F> &b) { return reduce_once<F>(fe_mul_portable_raw<F>(a, b)); }
 
 #if !defined(__HIP_DEVICE_COMPILE__) && defined(__SIZEOF_INT128__)
 // Host build on a 64-bit machine: the same CIOS over 64-bit limbs with 128-bit products (4-5x the 32-bit loop above).
@@ -703,7 +706,7 @@ LW_HD Fe<F> fe_mul_lazy(const Fe<F> &a, const Fe<F> &b) {
     for (int i = 0; i < N; i++) r.v[i] = t[i];
     return r;
 #else
-    return fe_mul_portable<F>(a, b);
+    return fe_mul_portable_raw<F>(a, b);   // unreduced on the host too: the same limbs as the device
 #endif
 }
 // fe_mul_lazy for an a that is the same in every lane of the wavefront (a twiddle shared by a whole wave, fetched through
@@ -720,7 +723,7 @@ LW_HD Fe<F> fe_mul_lazy_uniform(const Fe<F> &a, const Fe<F> &b) {
     for (int i = 0; i < N; i++) r.v[i] = t[i];
     return r;
 #else
-    return fe_mul_portable<F>(a, b);
+    return fe_mul_portable_raw<F>(a, b);   // unreduced on the host too: the same limbs as the device
 #endif
 }
 

@@ -208,6 +208,10 @@ extern "C" {
     /// The test seam of the group law: one formula of csrc/ec.cuh per row, raw (X, Y, Z) out.  op: LW_EC_OP_*.
     pub fn lw_hip_ec_pointwise_device(curve: Curve, model: c_int, op: c_int, d_a: *const c_void, d_b: *const c_void, n: usize,
                                       d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    /// The test seam of the field arithmetic: one primitive of csrc/field.cuh per row, the returned limbs out.
+    /// field: LW_PW_FIELD_*, op: LW_FIELD_OP_*.
+    pub fn lw_hip_field_pointwise_device(field: c_int, op: c_int, d_a: *const c_void, d_b: *const c_void, n: usize, d_out: *mut c_void,
+                                         hip_stream: *mut c_void) -> c_int;
     pub fn lw_hip_srs_create(curve: Curve, points: *const c_void, n_points: usize, out_srs: *mut *mut lw_srs_t) -> c_int;
     pub fn lw_hip_srs_create_device(curve: Curve, d_points: *const c_void, n_points: usize, hip_stream: *mut c_void,
                                     out_srs: *mut *mut lw_srs_t) -> c_int;
@@ -377,6 +381,36 @@ pub const LW_EC_OP_ADD_MIXED: c_int = 1;
 pub const LW_EC_OP_DBL: c_int = 2;
 pub const LW_EC_OP_ADD_QUAD: c_int = 3;
 pub const LW_EC_OP_TO_AFFINE: c_int = 4;
+/// lw_pw_field_t
+pub const LW_PW_FIELD_STARK252: c_int = 0;
+pub const LW_PW_FIELD_FR381: c_int = 1;
+pub const LW_PW_FIELD_FR254: c_int = 2;
+pub const LW_PW_FIELD_FP381: c_int = 3;
+pub const LW_PW_FIELD_FP254: c_int = 4;
+pub const LW_PW_FIELD_BABYBEAR: c_int = 5;
+/// lw_field_op_t
+pub const LW_FIELD_OP_ADD: c_int = 0;
+pub const LW_FIELD_OP_SUB: c_int = 1;
+pub const LW_FIELD_OP_NEG: c_int = 2;
+pub const LW_FIELD_OP_DBL: c_int = 3;
+pub const LW_FIELD_OP_MUL: c_int = 4;
+pub const LW_FIELD_OP_SQR: c_int = 5;
+pub const LW_FIELD_OP_MUL_LAZY: c_int = 6;
+pub const LW_FIELD_OP_MUL_LAZY_UNIFORM: c_int = 7;
+pub const LW_FIELD_OP_REDUCE_FULL: c_int = 8;
+pub const LW_FIELD_OP_COND_SUB_P: c_int = 9;
+pub const LW_FIELD_OP_ADD_RAW: c_int = 10;
+pub const LW_FIELD_OP_ADD2P_SUB_RAW: c_int = 11;
+pub const LW_FIELD_OP_NEG_RAW: c_int = 12;
+pub const LW_FIELD_OP_NEG_RAW_2P: c_int = 13;
+pub const LW_FIELD_OP_TO_MONT: c_int = 14;
+pub const LW_FIELD_OP_FROM_MONT: c_int = 15;
+pub const LW_FIELD_OP_DOT2: c_int = 16;
+pub const LW_FIELD_OP_DOT4: c_int = 17;
+pub const LW_FIELD_OP_INV: c_int = 18;
+pub const LW_FIELD_OP_REDUCE64: c_int = 19;
+pub const LW_FIELD_OP_FROM_R64: c_int = 20;
+pub const LW_FIELD_OP_TO_R64: c_int = 21;
 
 /// lw_rpo_level_t: state 12, capacity 4, rate 8, digest 4 words
 pub const LW_RPO_128: c_int = 0;

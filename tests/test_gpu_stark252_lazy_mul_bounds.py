@@ -9,7 +9,8 @@ same extremes reach the real kernels:
   * a: the last pass of interpolate_offset_fft multiplies natural output i by h^-i * N^-1 with that factor as a.  The
     offset h is chosen so that the factor of output 1 is, limb for limb, a chosen Montgomery-form value: the largest
     canonical value with a[7] = 2^27 (a[6] = 16, a[0..5] = 0xffffffff), p - 1, and 2^251 - 1.  (A twiddle w^k with
-    a[7] = 2^27 has probability 2^-55, so the twiddle tables never get there by themselves.)"""
+    a[7] = 2^27 has probability 2^-55, so the twiddle tables never get there by themselves.)
+fe_mul_lazy and fe_mul_lazy_uniform take the same first operands directly, one product per row, in tests/test_gpu_field_pointwise.py."""
 import numpy as np
 import pytest
 

@@ -1,7 +1,8 @@
 """Stark252 NTTs that drive the fused Montgomery column chains (field.cuh fips_fused, mac_chains.inc FusedCol) through
 their edges, bit-exact against the CPU oracle: inputs of all zeros (every column sum and every t_k is 0, so the unit-limb
 step runs with no borrow), all p - 1 (the largest canonical limbs), and values whose low u64 limb is 0 (t_0 = t_1 = 0 in
-the first products of the first pass); then random inputs at 2^8, 2^16 and 2^20, forward and inverse, plain and coset."""
+the first products of the first pass); then random inputs at 2^8, 2^16 and 2^20, forward and inverse, plain and coset.
+The same columns run on chosen operand pairs, one product per row, in tests/test_gpu_field_pointwise.py."""
 import numpy as np
 import pytest
 
