@@ -739,6 +739,33 @@ int lw_poseidon_commit_columns(const void *columns, uint32_t n_cols, uint32_t lo
 int lw_poseidon_commit_columns_device(const void *d_columns, uint32_t n_cols, uint64_t col_stride_elems, uint32_t log2n,
                                       int bit_reverse, int leaf_mode, void *d_nodes, uint8_t *out_root, void *hip_stream);
 
+/* ---- Starknet Pedersen hash over the Stark curve (PedersenStarkCurve::hash, crypto/src/hash/pedersen/mod.rs) ----
+ * The Stark curve is y^2 = x^3 + x + b over the Stark252 prime; it is not an lw_curve_t (nothing else here runs on it).
+ * Elements, host and _device forms, alignment, n = 0 and the 2^36 limit as for Poseidon above.
+ *   hash           out[i] = hash(x[i], y[i]): the affine x of P0 + sum of table points chosen by the nibbles of the
+ *                  canonical integers x[i], y[i] (mod.rs:43-54); one work-item per hash, about 117 curve additions and one
+ *                  inversion each
+ *   commit_leaves  the 2-to-1 tree over 2^log2n leaf VALUES (Starknet's Pedersen trees): the reference's MerkleTree with
+ *                  hash_new_parent = hash and identity leaves.  nodes, out_root, bit_reverse, log2n > 31 and the
+ *                  synchronisation of the _device form as lw_poseidon_commit_columns[_device]; n_cols is the number of
+ *                  columns offered and must be 1 (else LW_ERR_BAD_ARG: a leaf is one element)
+ *   table          host only, no device needed: the 1 890 affine points of the lookup tables T1 || T2 || T3 || T4
+ *                  (930 + 15 + 930 + 15; T1[15 i + k - 1] = k 2^(4 i) P1, T2[k - 1] = k P2, T3, T4 from P3, P4), as they are
+ *                  generated from StarkWare's five published points: (x, y), 8 u64 each, 120 960 bytes
+ *   add_affine     test seam of the group law, device form only: out[i] = p[i] + q[i] for affine points (x, y) of 8 u64,
+ *                  (0, 0) standing for the point at infinity in p and out.  p[i] is lifted to the hash kernel's Jacobian
+ *                  accumulator and rescaled by z[i] != 0 ((X, Y, Z) -> (X z^2, Y z^3, Z z)), q[i] is added with the
+ *                  device function the hash calls and the sum is normalised by the hash's own code path, so doubling
+ *                  (p = q), p = -q and p = infinity are reachable with chosen operands */
+int lw_pedersen_hash(const void *x, const void *y, size_t n, void *out);
+int lw_pedersen_hash_device(const void *d_x, const void *d_y, size_t n, void *d_out, void *hip_stream);
+int lw_pedersen_commit_leaves(const void *leaves, uint32_t n_cols, uint32_t log2n, int bit_reverse, uint8_t *out_root,
+                              uint8_t *out_nodes_or_null);
+int lw_pedersen_commit_leaves_device(const void *d_leaves, uint32_t n_cols, uint32_t log2n, int bit_reverse, void *d_nodes,
+                                     uint8_t *out_root, void *hip_stream);
+int lw_pedersen_table(void *out);
+int lw_pedersen_add_affine_device(const void *d_p, const void *d_z, const void *d_q, size_t n, void *d_out, void *hip_stream);
+
 /* ---- Circle FFT over Mersenne31 (math/src/circle/: evaluate_cfft, interpolate_cfft, get_twiddles) ----
  * The transform between the 2^log2n coefficients of a polynomial in the basis {1, y, x, xy, 2x^2 - 1, ...} (coefficient k
  * multiplies y^(k & 1) * prod_t pi^t(x)^(bit t+1 of k), pi(x) = 2x^2 - 1) and its values on the standard coset

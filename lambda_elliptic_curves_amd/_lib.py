@@ -48,6 +48,8 @@ EXPORTS = [
     "lw_poseidon_permute", "lw_poseidon_permute_device", "lw_poseidon_hash", "lw_poseidon_hash_device",
     "lw_poseidon_hash_single", "lw_poseidon_hash_single_device", "lw_poseidon_hash_many", "lw_poseidon_hash_many_device",
     "lw_poseidon_commit_columns", "lw_poseidon_commit_columns_device",
+    "lw_pedersen_hash", "lw_pedersen_hash_device", "lw_pedersen_commit_leaves", "lw_pedersen_commit_leaves_device",
+    "lw_pedersen_table", "lw_pedersen_add_affine_device",
     "lw_circle_evaluate_cfft", "lw_circle_interpolate_cfft", "lw_circle_evaluate_cfft_device", "lw_circle_interpolate_cfft_device",
     "lw_circle_lde_device", "lw_circle_get_twiddles",
     "lw_goldilocks_ntt", "lw_goldilocks_ntt_device", "lw_goldilocks_lde_device", "lw_goldilocks_gen_twiddles",
@@ -274,6 +276,18 @@ def lib():
     L.lw_poseidon_commit_columns.restype = i
     L.lw_poseidon_commit_columns_device.argtypes = [vp, u32, C.c_uint64, u32, i, i, vp, vp, vp]
     L.lw_poseidon_commit_columns_device.restype = i
+    L.lw_pedersen_hash.argtypes = [vp, vp, sz, vp]
+    L.lw_pedersen_hash.restype = i
+    L.lw_pedersen_hash_device.argtypes = [vp, vp, sz, vp, vp]
+    L.lw_pedersen_hash_device.restype = i
+    L.lw_pedersen_commit_leaves.argtypes = [vp, u32, u32, i, vp, vp]
+    L.lw_pedersen_commit_leaves.restype = i
+    L.lw_pedersen_commit_leaves_device.argtypes = [vp, u32, u32, i, vp, vp, vp]
+    L.lw_pedersen_commit_leaves_device.restype = i
+    L.lw_pedersen_table.argtypes = [vp]
+    L.lw_pedersen_table.restype = i
+    L.lw_pedersen_add_affine_device.argtypes = [vp, vp, vp, sz, vp, vp]
+    L.lw_pedersen_add_affine_device.restype = i
     for name in ("lw_circle_evaluate_cfft", "lw_circle_interpolate_cfft"):
         getattr(L, name).argtypes = [vp, vp, u32, u32, sz]
         getattr(L, name).restype = i

@@ -73,6 +73,8 @@ struct SharedState {
     // goldilocks_root (0: none yet).  One root at a time: a call with another root invalidates both tables.
     TwiddleTable goldilocks[2];
     uint64_t goldilocks_root = 0;
+    // Pedersen lookup tables (pedersen.hip): a __device__ array of the library, filled once per device under rw held unique
+    bool pedersen_table_ready = false;
     bool initialised = false;
     int device = -1;
 };

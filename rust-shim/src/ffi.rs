@@ -293,6 +293,17 @@ extern "C" {
     pub fn lw_poseidon_commit_columns_device(d_columns: *const c_void, n_cols: u32, col_stride_elems: u64, log2n: u32,
                                              bit_reverse: c_int, leaf_mode: c_int, d_nodes: *mut c_void, out_root: *mut u8,
                                              hip_stream: *mut c_void) -> c_int;
+    // ---- Starknet Pedersen hash over the Stark curve: batched hashes, the tree over leaf values, the tables, the group-law seam
+    pub fn lw_pedersen_hash(x: *const c_void, y: *const c_void, n: usize, out: *mut c_void) -> c_int;
+    pub fn lw_pedersen_hash_device(d_x: *const c_void, d_y: *const c_void, n: usize, d_out: *mut c_void,
+                                   hip_stream: *mut c_void) -> c_int;
+    pub fn lw_pedersen_commit_leaves(leaves: *const c_void, n_cols: u32, log2n: u32, bit_reverse: c_int, out_root: *mut u8,
+                                     out_nodes_or_null: *mut u8) -> c_int;
+    pub fn lw_pedersen_commit_leaves_device(d_leaves: *const c_void, n_cols: u32, log2n: u32, bit_reverse: c_int,
+                                            d_nodes: *mut c_void, out_root: *mut u8, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_pedersen_table(out: *mut c_void) -> c_int;
+    pub fn lw_pedersen_add_affine_device(d_p: *const c_void, d_z: *const c_void, d_q: *const c_void, n: usize,
+                                         d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
     // ---- circle FFT over Mersenne31: one u32 per element, canonical residues out
     pub fn lw_circle_evaluate_cfft(coeffs: *const u32, out: *mut u32, log2n: u32, batch: u32, batch_stride: usize) -> c_int;
     pub fn lw_circle_interpolate_cfft(evals: *const u32, out: *mut u32, log2n: u32, batch: u32, batch_stride: usize) -> c_int;
