@@ -25,7 +25,7 @@ namespace lw {
 // p(i), one(i), r2(i): 32-bit limb i (LS first) of the modulus, R mod p, R^2 mod p.  INV = -p^-1 mod 2^32.
 struct Stark252 {   // math/src/field/fields/fft_friendly/stark_252_prime_field.rs:13-24
     static constexpr int N = 8;
-    // p < 2^252: 2^256 / p ~ 32, so NTT butterflies can carry values in [0, 24p) between reductions
+    // p < 2^252: 2^256 / p ~ 32, so NTT butterflies can carry values up to 30p between reductions
     static constexpr bool LAZY = true;
     static constexpr uint32_t INV = 0xffffffffu;
     static constexpr uint32_t TWO_ADICITY = 192;
@@ -690,6 +690,53 @@ LW_HD Fe<F> fe_add2p_sub_raw(const Fe<F> &a, const Fe<F> &b) {   // a + 2p - b, 
     limbs_add<N>(r.v, d.v, kp);
     return r;
 }
+// ---- offset form of the lazy helpers (ntt_bound_plan.h: a pass adds C*p once, on load, instead of 2p per butterfly) ----
+// limbs of C*p for p = 2^251 + 17*2^192 + 1, as chain operands; C <= 15 keeps every limb inside 32 bits
+template <int C>
+LW_HD void limbs_cp_stark(uint32_t (&k)[8]) {
+    static_assert(C >= 1 && C <= 15, "C*p limb by limb: 17C and C << 27 must fit their limbs");
+    const uint32_t z = lw_k(0u);
+    k[0] = lw_k((uint32_t)C); k[1] = z; k[2] = z; k[3] = z; k[4] = z; k[5] = z;
+    k[6] = lw_k(17u * (uint32_t)C); k[7] = lw_k((uint32_t)C << 27);
+}
+// x - (x >> 251)*p mod 2^256 for any 256-bit x: the subtraction of fe_reduce_full.  As an integer the difference lies in
+// (-2^202, p], so the result is only meaningful once a multiple of p has been added back (fe_add_cp).
+LW_HD Fe<Stark252> fe_sub_qp(const Fe<Stark252> &x) {
+    const uint32_t q = x.v[7] >> 27;
+    const uint32_t z = lw_k(0u);
+    const uint32_t sub[8] = {q, z, z, z, z, z, 17u * q, q << 27};
+    Fe<Stark252> d;
+    limbs_sub<8>(d.v, x.v, sub);
+    return d;
+}
+// x + C*p mod 2^256: the offset alone, for a value that is already below p (the input of a first pass)
+template <int C>
+LW_HD Fe<Stark252> fe_add_cp(const Fe<Stark252> &x) {
+    uint32_t cp[8];
+    limbs_cp_stark<C>(cp);
+    Fe<Stark252> r;
+    limbs_add<8>(r.v, x.v, cp);
+    return r;
+}
+// x - (x >> 251)*p + C*p for any 256-bit x: fe_reduce_full with an unconditional add of a constant in place of the masked
+// + p.  Result in (C*p - 2^202, (C + 1)*p], congruent to x.
+template <int C>
+LW_HD Fe<Stark252> fe_reduce_offset(const Fe<Stark252> &x) { return fe_add_cp<C>(fe_sub_qp(x)); }
+// One lazy butterfly's add/sub network: a <- a + t, t <- a - t (FREE: the caller guarantees a >= t, ntt_bound_plan.h) or
+// a + 2p - t.  The caller guarantees that a + t, and a + 2p when it is added, fit N limbs.
+template <class F, bool FREE>
+LW_HD void fe_butterfly_raw(Fe<F> &a, Fe<F> &t) {
+    const Fe<F> a0 = a;
+    a = fe_add_raw<F>(a0, t);
+    if (FREE) {
+        Fe<F> d;
+        limbs_sub<F::N>(d.v, a0.v, t.v);
+        t = d;
+    } else {
+        t = fe_add2p_sub_raw<F>(a0, t);
+    }
+}
+
 // Montgomery product without the final conditional subtraction: result in [0, 2p) whenever a < p
 // (b may be any N-limb value): (a*b + m*p) / R < a*b/R + p < 2p.
 // a < p is a hard precondition on the device, not only the source of the 2p bound: the fused columns use a[N-1] <= p[N-1]

@@ -6,8 +6,8 @@
 // every field op returns the canonical residue, results are byte-identical to the reference however
 // the stages are scheduled; here they are scheduled for the GPU:
 //
-//   * log2(N) stages are cut into passes of r <= 8 stages (the staged twiddles ltw[2][256] and the 17p lazy bound
-//     both need r <= 8; plan_passes, ntt_plan.h, never plans more).  One workgroup owns a tile of 2^r "rows"
+//   * log2(N) stages are cut into passes of r <= 8 stages (the staged twiddles ltw[2][256] and the lazy bounds, 17p and
+//     the 30p of ntt_bound_plan.h, all need r <= 8; plan_passes, ntt_plan.h, never plans more).  One workgroup owns a tile of 2^r "rows"
 //     (the index bits the pass's stages touch) x C adjacent "columns" (contiguous elements), stages it in
 //     LDS once and runs all r stages there: a pass costs one HBM read + one HBM write of the vector,
 //     versus one round trip per stage in the reference's CUDA path (math/src/fft/gpu/cuda/ops.rs:28-38).
@@ -23,10 +23,14 @@
 //     work-items walk columns fastest, so the lanes of a row already hold one contiguous run of the output (256 B for an
 //     8-stage tile).  Only the last pass goes back through LDS, for the transpose that turns its bit-reversed rows into
 //     coalesced runs.
-//   * lazy values (< 17p) handed from pass to pass are reduced on load only where the first stage adds them (half of the
-//     elements of a work-item); the other half enters a Montgomery product, which takes any 256-bit operand (ntt_item).
+//   * lazy values (< 17p, at most 30p behind a full-size tile) handed from pass to pass are reduced on load only where the
+//     first stage adds them (half of the elements of a work-item); the other half enters a Montgomery product, which takes
+//     any 256-bit operand (ntt_item).
+//   * over full-size tiles that reduction leaves c*p in place (c = 13 or 15, ntt_bound_plan.h), which lets the butterflies
+//     of the first six or seven stages of the pass subtract without adding 2p first (ntt_butterflies).
 #pragma once
 #include "field.cuh"
+#include "ntt_bound_plan.h"
 
 namespace lw {
 
@@ -58,7 +62,7 @@ struct NttPassParams {
     uint32_t cos_in;       // first pass: multiply element e by h^e on load (Polynomial::scale, polynomial/mod.rs:259-271)
     uint32_t cos_out;      // last pass of an inverse transform: multiply natural output i by h^-i * N^-1 (folded into cos_hi)
     uint64_t in_mask;      // first pass of a low-degree extension: element g is read from in[g & in_mask] (see ntt256.hip)
-    uint32_t lazy_in;      // input of this pass may be non-canonical (< 24p): a previous lazy pass wrote it
+    uint32_t lazy_in;      // input of this pass may be non-canonical (any 256-bit value; <= 30p in fact): a previous lazy pass wrote it
     uint32_t wave_sync;    // WL kernels: bit s set = the exchange before register step s stays inside a wavefront (no workgroup barrier)
     uint32_t scale;        // multiply outputs by sc (last pass of an inverse transform)
     uint32_t sc[8];
@@ -229,7 +233,7 @@ __device__ __forceinline__ Fe<F> ntt_fetch_tw(const NttPassParams &p, const NttI
 // PF: fetch the next twiddle under the current group's butterflies (eight more live VGPRs; see ntt_waves_per_simd).
 // UNI: the step's twiddles are the same for the whole wavefront (g.m_high is wave-uniform and the pass is not the last):
 // they come from the table through scalar loads, all E - 1 up front, and feed the products from SGPRs.
-template <class F, int K, bool LAST, bool WL, bool PF, bool UNI = false>
+template <class F, int K, bool LAST, bool WL, bool PF, bool UNI = false, int FX = 0>
 __device__ __forceinline__ void ntt_butterflies(const NttPassParams &p, const NttItemGeo &g, uint4 (*ltw)[NTT_LTW], uint32_t t0, bool first,
                                                 Fe<F> *x) {
     constexpr int E = 1 << K;
@@ -243,7 +247,25 @@ __device__ __forceinline__ void ntt_butterflies(const NttPassParams &p, const Nt
     // returns t < 2p (the unit branch reduces its operand itself).  After the stage x'[j] = x + t < 3p and
     // x'[j + E/2] = x + 2p - t < 3p with x < p, the same p + 2p per stage as if all E had been reduced.
     // Every result is still the unique canonical residue when it leaves the transform, so parity is unaffected.
-    if (F::LAZY && first && p.lazy_in) {
+    //
+    // Full-size tiles (FX stages, known here) go one step further, by the bound plan of ntt_bound_plan.h: the elements
+    // the first stage adds get BP.c * p on load, with the reduction where the input is lazy (the masked + p becomes a
+    // constant) and as a plain add in a first pass, whose inputs are below p (so are the canonical products of a coset
+    // load).  In exchange the stages below BP.nfree subtract without adding 2p, 8 instructions less per butterfly; values
+    // then ride in (0, 30p] and a pass hands on anything below 2^256, which the next pass's reduction and products take.
+    // The run-time-shape kernels (FX = 0) keep [0, 17p) and the + 2p in every butterfly.
+    constexpr bool OFFSET = F::LAZY && FX != 0;
+    constexpr NttBoundPlan BP = ntt_bound_plan(FX ? FX : 1);
+    if constexpr (OFFSET) {
+        if (first) {
+            if (p.lazy_in) {   // launch-uniform; with the add below this is fe_reduce_offset
+#pragma unroll
+                for (int j = 0; j < E / 2; j++) x[j] = fe_sub_qp(x[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < E / 2; j++) x[j] = fe_add_cp<BP.c>(x[j]);
+        }
+    } else if (F::LAZY && first && p.lazy_in) {
 #pragma unroll
         for (int j = 0; j < E / 2; j++) x[j] = fe_reduce_full(x[j]);
     }
@@ -273,14 +295,15 @@ __device__ __forceinline__ void ntt_butterflies(const NttPassParams &p, const Nt
         // quarter of the first pass's products).  The reference multiplies anyway (fft.rs:40-43); the product
         // by the Montgomery one is the identity on canonical residues, so skipping it changes no byte.
         const bool unit = (jt == 0) && (g.hi_c == 0) && (m_high == 0);
+        const bool free_stage = OFFSET && t0 + (uint32_t)u < (uint32_t)BP.nfree;   // t0 is a literal at every FX call site
 #pragma unroll
         for (int jl = 0; jl < half; jl++) {
             const int j = (jt << (K - u)) | jl;
             if (F::LAZY) {
                 Fe<F> wb = unit ? fe_reduce_full(x[j + half]) : UNI ? fe_mul_lazy_uniform<F>(tw, x[j + half]) : fe_mul_lazy<F>(tw, x[j + half]);
-                Fe<F> a = x[j];
-                x[j] = fe_add_raw<F>(a, wb);
-                x[j + half] = fe_add2p_sub_raw<F>(a, wb);
+                if (free_stage) fe_butterfly_raw<F, true>(x[j], wb);
+                else fe_butterfly_raw<F, false>(x[j], wb);
+                x[j + half] = wb;
             } else {
                 Fe<F> wb = unit ? x[j + half] : fe_mul<F>(tw, x[j + half]);
                 Fe<F> a = x[j];
@@ -364,7 +387,7 @@ __device__ __forceinline__ void ntt_item(const NttPassParams &p, uint4 (*lds)[NT
         ntt_tw_stage_store(ltw, r, tq0, tq1);
         __syncthreads();
     }
-    ntt_butterflies<F, K, LAST, WL, true>(p, g, ltw, t0, step == 0, x);
+    ntt_butterflies<F, K, LAST, WL, true, false, FX>(p, g, ltw, t0, step == 0, x);
     if (last_step) ntt_finish<F, K, LAST, EXTRA, FX>(p, g, x);
     if (!LAST && last_step) {
         ntt_store_global<F, K>(g, gout, lgS, x);
@@ -443,15 +466,15 @@ __device__ __forceinline__ void ntt_tile_fx(const NttPassParams &p, uint4 *lds, 
     ntt_load_global<F, 2, false, EXTRA>(p, g, gin, lgS, x);
     // no barrier of its own: the barriers of the first hand-over order these stores before step 2 reads the table
     ntt_tw_stage_store(ltw, FX, tq0, tq1);
-    ntt_butterflies<F, 2, false, false, PF, true>(p, g, ltw, 0u, true, x);
+    ntt_butterflies<F, 2, false, false, PF, true, FX>(p, g, ltw, 0u, true, x);
     ntt_item_slots<2, FX>(g, so);
 #pragma unroll
     for (uint32_t s = 1; s < FX / 2; s++) {
         g = ntt_item_geo<2, false, false, FX>(p, tid, s, 2 * s, base, hi_uniform, 0u);
         ntt_item_slots<2, FX>(g, si);
         ntt_exchange<F>(lds, so, si, x);
-        if (s == 1) ntt_butterflies<F, 2, false, false, PF, true>(p, g, ltw, 2 * s, false, x);
-        else ntt_butterflies<F, 2, false, false, PF>(p, g, ltw, 2 * s, false, x);
+        if (s == 1) ntt_butterflies<F, 2, false, false, PF, true, FX>(p, g, ltw, 2 * s, false, x);
+        else ntt_butterflies<F, 2, false, false, PF, false, FX>(p, g, ltw, 2 * s, false, x);
 #pragma unroll
         for (int j = 0; j < 4; j++) so[j] = si[j];
     }
@@ -461,8 +484,8 @@ __device__ __forceinline__ void ntt_tile_fx(const NttPassParams &p, uint4 *lds, 
         ntt_item_slots<1, FX>(ga, si);
         ntt_item_slots<1, FX>(gb, si + 2);
         ntt_exchange<F>(lds, so, si, x);
-        ntt_butterflies<F, 1, false, false, PF>(p, ga, ltw, FX - 1, false, x);
-        ntt_butterflies<F, 1, false, false, PF>(p, gb, ltw, FX - 1, false, x + 2);
+        ntt_butterflies<F, 1, false, false, PF, false, FX>(p, ga, ltw, FX - 1, false, x);
+        ntt_butterflies<F, 1, false, false, PF, false, FX>(p, gb, ltw, FX - 1, false, x + 2);
         ntt_finish<F, 1, false, EXTRA, FX>(p, ga, x);
         ntt_finish<F, 1, false, EXTRA, FX>(p, gb, x + 2);
         ntt_store_global<F, 1>(ga, gout, lgS, x);
