@@ -766,6 +766,36 @@ int lw_pedersen_commit_leaves_device(const void *d_leaves, uint32_t n_cols, uint
 int lw_pedersen_table(void *out);
 int lw_pedersen_add_affine_device(const void *d_p, const void *d_z, const void *d_q, size_t n, void *d_out, void *hip_stream);
 
+/* ---- dense multilinear polynomials and the sumcheck prover's round ----
+ * DenseMultilinearPolynomial::evaluate / fix_variables (math/src/polynomial/dense_multilinear_poly.rs) and the round
+ * polynomial of a sumcheck over a product of K tables.  Elements are as in lw_poly_*: 4 x u64, MS limb first, Montgomery
+ * form, canonical in and out; field LW_FIELD_STARK252 or LW_FIELD_BLS12_381_FR.  point, r and r_prev are host memory in
+ * both forms.
+ * A table T of 2^n_vars elements is a polynomial in x_0 .. x_{n-1}, x_0 on the MOST significant bit of the index (the
+ * order of the reference's chis table).  eq(r, 1) = r, eq(r, 0) = 1 - r.
+ *   evaluate       out[kk] = sum_i tables[kk][i] * prod_j eq(point[j], bit_{n-1-j}(i)) for k >= 1 tables at one point;
+ *                  n_vars = 0 returns tables[kk][0] (the host form then needs no device).  Synchronises once.
+ *   fix_variables  out[j] = sum_{b < 2^t} eq(r[0..t), b) * table[b * 2^(n-t) + j], 2^(n-t) elements: t = n is evaluate,
+ *                  t = 0 a copy.  The _device form enqueues and returns; for t > 0 d_out must not overlap d_table.
+ *   sumcheck_round out_round[u] = g(u) = sum_{j<h} prod_k (T_k[j] + u * (T_k[j+h] - T_k[j])), u = 0 .. k, h = 2^(n-1):
+ *                  k + 1 elements, g(0) + g(1) = the sum of the product over the cube.  k is 1, 2 or 3.  With r_prev
+ *                  (fused form, n_vars >= 2) every table is first replaced IN PLACE by fix_variables(T_k, [r_prev]) - its
+ *                  first 2^(n-1) elements hold the bound table, the rest is unspecified afterwards - and g is taken over
+ *                  the n - 1 remaining variables; a round then reads every table once.  Synchronises once.
+ * LW_ERR_BAD_ARG, decided before any device work: a field other than the two, a null pointer where data is needed,
+ * n_vars > 30, k = 0, k > 3 for a round, t > n_vars, a round with n_vars = 0, a fused round with n_vars < 2, a device
+ * pointer that is not 16-byte aligned, two tables of a round that overlap, a d_out that overlaps d_table when t > 0. */
+int lw_multilinear_evaluate(lw_field_t field, const void *const *tables, uint32_t k, uint32_t n_vars, const void *point, void *out);
+int lw_multilinear_evaluate_device(lw_field_t field, const void *const *d_tables, uint32_t k, uint32_t n_vars, const void *point,
+                                   void *out_host, void *hip_stream);
+int lw_multilinear_fix_variables(lw_field_t field, const void *table, uint32_t n_vars, const void *r, uint32_t t, void *out);
+int lw_multilinear_fix_variables_device(lw_field_t field, const void *d_table, uint32_t n_vars, const void *r, uint32_t t,
+                                        void *d_out, void *hip_stream);
+int lw_sumcheck_round(lw_field_t field, void *const *tables, uint32_t k, uint32_t n_vars, const void *r_prev_or_null,
+                      void *out_round);
+int lw_sumcheck_round_device(lw_field_t field, void *const *d_tables, uint32_t k, uint32_t n_vars, const void *r_prev_or_null,
+                             void *out_round_host, void *hip_stream);
+
 /* ---- Circle FFT over Mersenne31 (math/src/circle/: evaluate_cfft, interpolate_cfft, get_twiddles) ----
  * The transform between the 2^log2n coefficients of a polynomial in the basis {1, y, x, xy, 2x^2 - 1, ...} (coefficient k
  * multiplies y^(k & 1) * prod_t pi^t(x)^(bit t+1 of k), pi(x) = 2x^2 - 1) and its values on the standard coset

@@ -59,6 +59,8 @@ EXPORTS = [
     "lw_field_batch_inverse", "lw_field_batch_inverse_device", "lw_field_batch_inverse_block",
     "lw_stark_constraint_evaluations_device", "lw_stark_composition_parts_device", "lw_stark_commit_composition_device",
     "lw_stark_round2",
+    "lw_multilinear_evaluate", "lw_multilinear_evaluate_device", "lw_multilinear_fix_variables",
+    "lw_multilinear_fix_variables_device", "lw_sumcheck_round", "lw_sumcheck_round_device",
 ]
 
 
@@ -335,6 +337,18 @@ def lib():
     L.lw_stark_commit_composition_device.restype = i
     L.lw_stark_round2.argtypes = [i, vp, u32, u32, u32, vp, bp, u32, tp, u32, vp, u32, vp, C.POINTER(sz), vp, vp, vp]
     L.lw_stark_round2.restype = i
+    L.lw_multilinear_evaluate.argtypes = [i, vp, u32, u32, vp, vp]
+    L.lw_multilinear_evaluate.restype = i
+    L.lw_multilinear_evaluate_device.argtypes = [i, vp, u32, u32, vp, vp, vp]
+    L.lw_multilinear_evaluate_device.restype = i
+    L.lw_multilinear_fix_variables.argtypes = [i, vp, u32, vp, u32, vp]
+    L.lw_multilinear_fix_variables.restype = i
+    L.lw_multilinear_fix_variables_device.argtypes = [i, vp, u32, vp, u32, vp, vp]
+    L.lw_multilinear_fix_variables_device.restype = i
+    L.lw_sumcheck_round.argtypes = [i, vp, u32, u32, vp, vp]
+    L.lw_sumcheck_round.restype = i
+    L.lw_sumcheck_round_device.argtypes = [i, vp, u32, u32, vp, vp, vp]
+    L.lw_sumcheck_round_device.restype = i
     _lib = L
     return L
 

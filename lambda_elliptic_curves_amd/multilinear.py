@@ -1,0 +1,154 @@
+"""DenseMultilinearPolynomial::evaluate / fix_variables (math/src/polynomial/dense_multilinear_poly.rs) and the prover's
+round of a sumcheck over a product of K tables, on the device, over Stark252 and BLS12-381 Fr.  A table is a (2^n, 4)
+uint64 array in the reference's memory form (Montgomery, MS limb first); variable x_0 is the MOST significant bit of the
+index.  Points and challenges are host values in every form.  The transcript stays with the caller."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from .errors import check
+
+MODULI = {
+    L.FIELD_STARK252: 0x800000000000011000000000000000000000000000000000000000000000001,
+    L.FIELD_BLS12_381_FR: 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001,
+}
+
+
+def _elems(a):
+    return np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
+
+
+def _vp(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _opt(r):
+    """one optional host element -> (array kept alive, pointer or None)"""
+    if r is None:
+        return None, None
+    a = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1)[:4].copy()
+    return a, _vp(a)
+
+
+def _stream(stream):
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    return C.c_void_p(stream)
+
+
+def _n_vars(table):
+    n = table.shape[0]
+    if n == 0 or n & (n - 1):
+        from .errors import InputError
+        raise InputError(f"a multilinear table has 2^n elements, not {n}")
+    return n.bit_length() - 1
+
+
+def _point(point, n):
+    p = _elems(point) if n else np.zeros((1, 4), np.uint64)
+    if n and p.shape[0] != n:
+        from .errors import LengthMismatch
+        raise LengthMismatch(f"{p.shape[0]} coordinates for {n} variables")
+    return p
+
+
+def evaluate(field, tables, point):
+    """(K, 4): tables[k] at `point` (n elements for tables of 2^n); every table has the same size."""
+    ts = [_elems(t) for t in tables]
+    n = _n_vars(ts[0]) if ts else 0
+    p = _point(point, n)
+    out = np.zeros((len(ts), 4), np.uint64)
+    ptrs = (C.c_void_p * max(1, len(ts)))(*[t.ctypes.data for t in ts])
+    check(L.lib().lw_multilinear_evaluate(field.field, ptrs, len(ts), n, _vp(p), _vp(out)))
+    return out
+
+
+def evaluate_device(field, t_tables, n_vars, point, stream=None):
+    """evaluate() on device-resident torch tensors of at least 2^n_vars elements each."""
+    p = _point(point, n_vars)
+    out = np.zeros((len(t_tables), 4), np.uint64)
+    ptrs = (C.c_void_p * max(1, len(t_tables)))(*[t.data_ptr() for t in t_tables])
+    check(L.lib().lw_multilinear_evaluate_device(field.field, ptrs, len(t_tables), n_vars, _vp(p), _vp(out), _stream(stream)))
+    return out
+
+
+def fix_variables(field, table, r):
+    """(2^(n - t), 4): the table with its first t = len(r) variables bound to r."""
+    a = _elems(table)
+    n = _n_vars(a)
+    rr = _elems(r) if len(r) else np.zeros((0, 4), np.uint64)
+    t = rr.shape[0]
+    out = np.zeros((1 << max(0, n - t), 4), np.uint64)
+    check(L.lib().lw_multilinear_fix_variables(field.field, _vp(a), n, _vp(rr) if t else None, t, _vp(out)))
+    return out
+
+
+def fix_variables_device(field, t_table, n_vars, r, t_out, stream=None):
+    """fix_variables() of a device-resident tensor into t_out (2^(n_vars - len(r)) elements, not overlapping t_table);
+    nothing is waited for.  -> t_out"""
+    rr = _elems(r) if len(r) else np.zeros((0, 4), np.uint64)
+    t = rr.shape[0]
+    check(L.lib().lw_multilinear_fix_variables_device(field.field, C.c_void_p(t_table.data_ptr()), n_vars, _vp(rr) if t else None, t,
+                                                      C.c_void_p(t_out.data_ptr()), _stream(stream)))
+    return t_out
+
+
+def sumcheck_round(field, tables, r_prev=None):
+    """(K + 1, 4): g(0) .. g(K) of the round over K = 1, 2 or 3 tables of 2^n elements.  With r_prev the tables (which
+    must then be writable (2^n, 4) uint64 arrays) are first bound to it in place - their first halves hold the bound
+    tables afterwards - and the round runs over the n - 1 remaining variables."""
+    ts = [_elems(t) for t in tables]
+    inplace = lambda u: isinstance(u, np.ndarray) and u.dtype == np.uint64 and u.flags.c_contiguous and u.flags.writeable
+    if r_prev is not None and not all(inplace(u) for u in tables):
+        from .errors import InputError
+        raise InputError("a fused round binds in place: pass C-contiguous uint64 arrays")
+    n = _n_vars(ts[0]) if ts else 0
+    out = np.zeros((len(ts) + 1, 4), np.uint64)
+    keep, rp = _opt(r_prev)
+    ptrs = (C.c_void_p * max(1, len(ts)))(*[t.ctypes.data for t in ts])
+    check(L.lib().lw_sumcheck_round(field.field, ptrs, len(ts), n, rp, _vp(out)))
+    return out
+
+
+def sumcheck_round_device(field, t_tables, n_vars, r_prev=None, stream=None):
+    """sumcheck_round() on device-resident torch tensors; with r_prev they are bound in place."""
+    out = np.zeros((len(t_tables) + 1, 4), np.uint64)
+    keep, rp = _opt(r_prev)
+    ptrs = (C.c_void_p * max(1, len(t_tables)))(*[t.data_ptr() for t in t_tables])
+    check(L.lib().lw_sumcheck_round_device(field.field, ptrs, len(t_tables), n_vars, rp, _vp(out), _stream(stream)))
+    return out
+
+
+def _add(field, a, b):
+    """a + b of two stored elements (addition is the same in Montgomery form)"""
+    to_int = lambda x: int.from_bytes(np.ascontiguousarray(x, dtype=np.uint64).astype(">u8").tobytes(), "big")
+    s = (to_int(a) + to_int(b)) % MODULI[field.field]
+    return np.frombuffer(s.to_bytes(32, "big"), dtype=">u8").astype(np.uint64)
+
+
+def sumcheck_prove_device(field, t_tables, n_vars, challenge, stream=None):
+    """The prover's side of a sumcheck of prod_k t_tables[k] over the cube of n_vars >= 1 variables, the tables resident
+    on the device and consumed in place.  challenge: a callable from a round's (K + 1, 4) array to the next r (4 uint64),
+    the seam for the caller's transcript.  One plain round, n_vars - 1 fused rounds (bind the previous challenge, then
+    sum), and a final fix_variables of the last variable.
+    -> (claimed_sum (4,), rounds [n_vars arrays (K + 1, 4)], point (n_vars, 4), final_evals (K, 4))"""
+    import torch
+    rounds, point = [], []
+    r = None
+    for i in range(n_vars):
+        g = sumcheck_round_device(field, t_tables, n_vars - max(0, i - 1), r, stream)
+        rounds.append(g)
+        r = np.ascontiguousarray(challenge(g), dtype=np.uint64).reshape(-1)[:4].copy()
+        point.append(r)
+    claimed = _add(field, rounds[0][0], rounds[0][1])
+    t_fin = torch.empty((len(t_tables), 4), dtype=torch.int64, device=t_tables[0].device)
+    for k, t in enumerate(t_tables):
+        fix_variables_device(field, t, 1, r.reshape(1, 4), t_fin[k], stream)
+    if stream is None:
+        torch.cuda.current_stream().synchronize()
+    else:
+        torch.cuda.synchronize()
+    final = t_fin.cpu().numpy().view(np.uint64)
+    return claimed, rounds, np.stack(point), final

@@ -304,6 +304,19 @@ extern "C" {
     pub fn lw_pedersen_table(out: *mut c_void) -> c_int;
     pub fn lw_pedersen_add_affine_device(d_p: *const c_void, d_z: *const c_void, d_q: *const c_void, n: usize,
                                          d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    // ---- dense multilinear polynomials and the sumcheck round (4 x u64 Montgomery elements; point, r, r_prev on the host)
+    pub fn lw_multilinear_evaluate(field: Field, tables: *const *const c_void, k: u32, n_vars: u32, point: *const c_void,
+                                   out: *mut c_void) -> c_int;
+    pub fn lw_multilinear_evaluate_device(field: Field, d_tables: *const *const c_void, k: u32, n_vars: u32, point: *const c_void,
+                                          out_host: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_multilinear_fix_variables(field: Field, table: *const c_void, n_vars: u32, r: *const c_void, t: u32,
+                                        out: *mut c_void) -> c_int;
+    pub fn lw_multilinear_fix_variables_device(field: Field, d_table: *const c_void, n_vars: u32, r: *const c_void, t: u32,
+                                               d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_sumcheck_round(field: Field, tables: *const *mut c_void, k: u32, n_vars: u32, r_prev_or_null: *const c_void,
+                             out_round: *mut c_void) -> c_int;
+    pub fn lw_sumcheck_round_device(field: Field, d_tables: *const *mut c_void, k: u32, n_vars: u32, r_prev_or_null: *const c_void,
+                                    out_round_host: *mut c_void, hip_stream: *mut c_void) -> c_int;
     // ---- circle FFT over Mersenne31: one u32 per element, canonical residues out
     pub fn lw_circle_evaluate_cfft(coeffs: *const u32, out: *mut u32, log2n: u32, batch: u32, batch_stride: usize) -> c_int;
     pub fn lw_circle_interpolate_cfft(evals: *const u32, out: *mut u32, log2n: u32, batch: u32, batch_stride: usize) -> c_int;

@@ -385,6 +385,67 @@ pub fn batch_inverse(field: Field, elems: &mut [[u64; 4]]) -> Result<(), HipErro
     check(unsafe { ffi::lw_field_batch_inverse(field, p as *const c_void, elems.len(), p) })
 }
 
+/// log2 of the common length of multilinear tables; the length must be a power of two (the reference pads, the caller does here).
+fn multilinear_vars(len: usize) -> Result<u32, HipError> {
+    if !len.is_power_of_two() {
+        return Err(HipError::BadArgument("a multilinear table has 2^n elements".into()));
+    }
+    Ok(len.trailing_zeros())
+}
+
+/// `DenseMultilinearPolynomial::evaluate` (math/src/polynomial/dense_multilinear_poly.rs:54-80) of every table at one
+/// point: tables of `2^n` elements, `point` of `n`, variable 0 on the most significant bit of the index.
+pub fn multilinear_evaluate(field: Field, tables: &[&[[u64; 4]]], point: &[[u64; 4]]) -> Result<Vec<[u64; 4]>, HipError> {
+    let n = multilinear_vars(tables.first().map_or(1, |t| t.len()))?;
+    if tables.iter().any(|t| t.len() != 1usize << n) || point.len() != n as usize {
+        return Err(HipError::BadArgument("tables of 2^n elements and a point of n coordinates".into()));
+    }
+    let ptrs: Vec<*const c_void> = tables.iter().map(|t| t.as_ptr() as *const c_void).collect();
+    let mut out = vec![[0u64; 4]; tables.len()];
+    // SAFETY: every table is valid for 2^n elements, `point` for n, `out` for one element per table.
+    let rc = unsafe {
+        ffi::lw_multilinear_evaluate(field, ptrs.as_ptr(), tables.len() as u32, n, point.as_ptr() as *const c_void,
+                                     out.as_mut_ptr() as *mut c_void)
+    };
+    check(rc)?;
+    Ok(out)
+}
+
+/// `DenseMultilinearPolynomial::fix_variables`: the table with its first `r.len()` variables bound to `r`.
+pub fn multilinear_fix_variables(field: Field, table: &[[u64; 4]], r: &[[u64; 4]]) -> Result<Vec<[u64; 4]>, HipError> {
+    let n = multilinear_vars(table.len())?;
+    if r.len() > n as usize {
+        return Err(HipError::BadArgument("more values than variables".into()));
+    }
+    let mut out = vec![[0u64; 4]; table.len() >> r.len()];
+    // SAFETY: `table` is valid for 2^n elements, `r` for t, `out` for 2^(n - t).
+    let rc = unsafe {
+        ffi::lw_multilinear_fix_variables(field, table.as_ptr() as *const c_void, n, r.as_ptr() as *const c_void, r.len() as u32,
+                                          out.as_mut_ptr() as *mut c_void)
+    };
+    check(rc)?;
+    Ok(out)
+}
+
+/// The prover's round of a sumcheck over the product of 1, 2 or 3 tables: `g(0) .. g(K)`.  With `r_prev` every table is
+/// first bound to it in place (its first half holds the bound table afterwards) and the round runs over the remaining
+/// variables.
+pub fn sumcheck_round(field: Field, tables: &mut [&mut [[u64; 4]]], r_prev: Option<&[u64; 4]>) -> Result<Vec<[u64; 4]>, HipError> {
+    let n = multilinear_vars(tables.first().map_or(1, |t| t.len()))?;
+    if tables.iter().any(|t| t.len() != 1usize << n) {
+        return Err(HipError::BadArgument("tables of one length".into()));
+    }
+    let ptrs: Vec<*mut c_void> = tables.iter_mut().map(|t| t.as_mut_ptr() as *mut c_void).collect();
+    let mut out = vec![[0u64; 4]; tables.len() + 1];
+    // SAFETY: every table is valid and exclusively borrowed for 2^n elements; `out` holds K + 1 elements.
+    let rc = unsafe {
+        ffi::lw_sumcheck_round(field, ptrs.as_ptr(), tables.len() as u32, n, r_prev.map_or(core::ptr::null(), |r| r.as_ptr() as *const c_void),
+                               out.as_mut_ptr() as *mut c_void)
+    };
+    check(rc)?;
+    Ok(out)
+}
+
 /// The parts of the composition polynomial and their commitment, as `stark_round2` returns them.
 pub struct Round2 {
     /// `n_parts` blocks of `block_len` coefficients, zero padded
