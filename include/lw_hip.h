@@ -899,6 +899,49 @@ int lw_rpo_commit_columns(lw_rpo_level_t level, const uint64_t *columns, uint32_
 int lw_rpo_commit_columns_device(lw_rpo_level_t level, const uint64_t *d_columns, uint32_t n_cols, uint64_t col_stride,
                                  uint32_t log2n, int bit_reverse, uint64_t *d_nodes, uint64_t *out_root_or_null, void *hip_stream);
 
+/* ---- Monolith over Mersenne31 (crypto/src/hash/monolith/: MonolithMersenne31<WIDTH, NUM_FULL_ROUNDS>, from Plonky3) ----
+ * The permutation, batched (one work-item per state), and for width 16 a hash, a 2-to-1 compression and a Merkle tree
+ * built from it.  Words are Mersenne31 elements as in the circle FFT: one u32; every input word is read mod p = 2^31 - 1
+ * (any u32), every output word is the canonical residue.
+ *   width    8, 12, 16, 20 or 24; rounds (NUM_FULL_ROUNDS) 1 .. 15, the reference tests 5.  Anything else: LW_ERR_BAD_ARG.
+ *   permute  n states of `width` words -> n states (permutation(), mod.rs:91-102); out may be states
+ *   hash     n_rows rows of row_len >= 0 words -> 8 words each.  Plonky3's PaddingFreeSponge<16, 8, 8> over the width-16
+ *            permutation: the state starts as 16 zeros; every chunk of up to 8 words overwrites state[0 .. chunk length),
+ *            the rest stays, then the state is permuted; the digest is state[0 .. 8).  row_len = 0 gives zeros and runs no
+ *            permutation.  There is NO padding: rows of different lengths can collide ([a] and [a, 0] have the same
+ *            digest), so the hash is only meant for rows of one fixed length, as a tree's leaves are.
+ *            row_stride in words, 0: dense, below row_len: LW_ERR_BAD_ARG.
+ *   compress n pairs of 8-word digests -> permute(left || right)[0 .. 8), Plonky3's TruncatedPermutation<2, 8, 16>
+ * The reference ships the permutation only; the two modes are specified by the lines above.
+ * NULL buffers and _device buffers that are not 16-byte aligned are LW_ERR_BAD_ARG once there is work; n = 0 (n_rows = 0)
+ * touches nothing and needs no device.  More than 2^36 inputs: LW_ERR_ALLOC.  Every check happens before any device work.
+ *
+ * commit_columns: the tree over the 2^log2n rows of n_cols columns of words.  Leaf j = hash(committed row j over all
+ * columns), a node = compress(left, right).  nodes: (2 * 2^log2n - 1) digests of 32 bytes, root first and leaves last
+ * (merkle_tree/utils.rs:43-71): lw_stark_open_trees_device reads the authentication paths of such a tree as it is
+ * (d_columns = NULL).  bit_reverse, col_stride (in words), log2n 0 .. 30 and the synchronisation as lw_rpo_commit_columns.
+ *
+ * constants: the round constants (rounds x width words) and the matrix of Concrete (width x width words, row-major; for
+ * width 16 the circulant written out) of one instance, generated from their SHAKE128 rule (mod.rs:47-55, 109-116).  No device.
+ * layer_device: a test seam.  One layer per state, through the function the permutation inlines: words are read mod p,
+ * the layer is applied, canonical words are written.  Bars changes the first 8 words of a state. */
+typedef enum { LW_MONOLITH_CONCRETE = 0, LW_MONOLITH_BARS = 1, LW_MONOLITH_BRICKS = 2 } lw_monolith_layer_t;
+int lw_monolith_permute(uint32_t width, uint32_t rounds, const uint32_t *states, size_t n, uint32_t *out);
+int lw_monolith_permute_device(uint32_t width, uint32_t rounds, const uint32_t *d_states, size_t n, uint32_t *d_out, void *hip_stream);
+int lw_monolith_hash(uint32_t rounds, const uint32_t *rows, size_t n_rows, size_t row_len, uint32_t *out);
+int lw_monolith_hash_device(uint32_t rounds, const uint32_t *d_rows, size_t n_rows, size_t row_len, size_t row_stride, uint32_t *d_out,
+                            void *hip_stream);
+int lw_monolith_compress(uint32_t rounds, const uint32_t *left, const uint32_t *right, size_t n, uint32_t *out);
+int lw_monolith_compress_device(uint32_t rounds, const uint32_t *d_left, const uint32_t *d_right, size_t n, uint32_t *d_out,
+                                void *hip_stream);
+int lw_monolith_commit_columns(uint32_t rounds, const uint32_t *columns, uint32_t n_cols, uint32_t log2n, int bit_reverse,
+                               uint32_t *out_root, uint32_t *out_nodes_or_null);
+int lw_monolith_commit_columns_device(uint32_t rounds, const uint32_t *d_columns, uint32_t n_cols, uint64_t col_stride, uint32_t log2n,
+                                      int bit_reverse, uint32_t *d_nodes, uint32_t *out_root_or_null, void *hip_stream);
+int lw_monolith_constants(uint32_t width, uint32_t rounds, uint32_t *out_round_constants, uint32_t *out_mds);
+int lw_monolith_layer_device(uint32_t width, uint32_t rounds, lw_monolith_layer_t layer, const uint32_t *d_states, size_t n,
+                             uint32_t *d_out, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@ PW_FIELD_STARK252, PW_FIELD_FR381, PW_FIELD_FR254, PW_FIELD_FP381, PW_FIELD_FP25
  FIELD_OP_TO_R64) = range(22)   # lw_field_op_t
 POSEIDON_LEAF_SINGLE, POSEIDON_LEAF_MANY = 0, 1   # lw_poseidon_leaf_t
 RPO_128, RPO_160 = 0, 1   # lw_rpo_level_t
+MONOLITH_CONCRETE, MONOLITH_BARS, MONOLITH_BRICKS = 0, 1, 2   # lw_monolith_layer_t
 (OK, ERR_INPUT_NOT_POW2, ERR_ORDER_TOO_LARGE, ERR_ROOT_OF_UNITY, ERR_LENGTH_MISMATCH, ERR_NO_DEVICE, ERR_ALLOC,
  ERR_LAUNCH, ERR_COMM, ERR_BAD_ARG, ERR_INV_ZERO) = (0, -1, -2, -3, -4, -5, -6, -7, -8, -9, -10)
 
@@ -56,6 +57,9 @@ EXPORTS = [
     "lw_goldilocks_mul_device",
     "lw_rpo_permute", "lw_rpo_permute_device", "lw_rpo_hash", "lw_rpo_hash_device",
     "lw_rpo_commit_columns", "lw_rpo_commit_columns_device",
+    "lw_monolith_permute", "lw_monolith_permute_device", "lw_monolith_hash", "lw_monolith_hash_device",
+    "lw_monolith_compress", "lw_monolith_compress_device", "lw_monolith_commit_columns", "lw_monolith_commit_columns_device",
+    "lw_monolith_constants", "lw_monolith_layer_device",
     "lw_field_batch_inverse", "lw_field_batch_inverse_device", "lw_field_batch_inverse_block",
     "lw_stark_constraint_evaluations_device", "lw_stark_composition_parts_device", "lw_stark_commit_composition_device",
     "lw_stark_round2",
@@ -322,6 +326,26 @@ def lib():
     L.lw_rpo_commit_columns.restype = i
     L.lw_rpo_commit_columns_device.argtypes = [i, vp, u32, C.c_uint64, u32, i, vp, vp, vp]
     L.lw_rpo_commit_columns_device.restype = i
+    L.lw_monolith_permute.argtypes = [u32, u32, vp, sz, vp]
+    L.lw_monolith_permute.restype = i
+    L.lw_monolith_permute_device.argtypes = [u32, u32, vp, sz, vp, vp]
+    L.lw_monolith_permute_device.restype = i
+    L.lw_monolith_hash.argtypes = [u32, vp, sz, sz, vp]
+    L.lw_monolith_hash.restype = i
+    L.lw_monolith_hash_device.argtypes = [u32, vp, sz, sz, sz, vp, vp]
+    L.lw_monolith_hash_device.restype = i
+    L.lw_monolith_compress.argtypes = [u32, vp, vp, sz, vp]
+    L.lw_monolith_compress.restype = i
+    L.lw_monolith_compress_device.argtypes = [u32, vp, vp, sz, vp, vp]
+    L.lw_monolith_compress_device.restype = i
+    L.lw_monolith_commit_columns.argtypes = [u32, vp, u32, u32, i, vp, vp]
+    L.lw_monolith_commit_columns.restype = i
+    L.lw_monolith_commit_columns_device.argtypes = [u32, vp, u32, C.c_uint64, u32, i, vp, vp, vp]
+    L.lw_monolith_commit_columns_device.restype = i
+    L.lw_monolith_constants.argtypes = [u32, u32, vp, vp]
+    L.lw_monolith_constants.restype = i
+    L.lw_monolith_layer_device.argtypes = [u32, u32, i, vp, sz, vp, vp]
+    L.lw_monolith_layer_device.restype = i
     L.lw_field_batch_inverse.argtypes = [i, vp, sz, vp]
     L.lw_field_batch_inverse.restype = i
     L.lw_field_batch_inverse_device.argtypes = [i, vp, sz, vp, vp]

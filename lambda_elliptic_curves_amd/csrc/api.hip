@@ -105,6 +105,7 @@ static void release_everything() {
         t.valid = false;
     }
     sh.pedersen_table_ready = false;   // the next device has a __device__ array of its own
+    sh.monolith_table_ready = false;   // ... and a __constant__ table of its own
 }
 // SharedState::rw held unique
 static int init_locked(const int *device_ids, int n_devices) {

@@ -75,6 +75,8 @@ struct SharedState {
     uint64_t goldilocks_root = 0;
     // Pedersen lookup tables (pedersen.hip): a __device__ array of the library, filled once per device under rw held unique
     bool pedersen_table_ready = false;
+    // Monolith constants (monolith.hip): a __constant__ table of the library for every (width, rounds), same discipline
+    bool monolith_table_ready = false;
     bool initialised = false;
     int device = -1;
 };

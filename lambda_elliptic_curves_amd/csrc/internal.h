@@ -61,6 +61,9 @@ int groth16_h_device(Context &c, const void *d_l, const void *d_r, const void *d
                      hipStream_t stream);
 int stripped_length_device(const void *d_elems, uint64_t n, uint64_t *d_len, hipStream_t stream);
 
+// ---- stark_query.hip
+void keccak_f1600_host(uint64_t (&a)[25]);   // Keccak-f[1600] on the host: the grinding seed, the SHAKE128 of monolith.hip
+
 // ---- poly.hip
 // the lane's pinned staging c.deep_pin, at least `bytes` long and no longer read by an earlier call's upload
 int deep_pin(Context &c, size_t bytes);

@@ -13,8 +13,8 @@ namespace lw {
 
 // ---- grinding
 
-// Keccak-f[1600] on the host: one permutation per call, for the inner hash
-static void keccak_f1600_host(uint64_t (&a)[25]) {
+// Keccak-f[1600] on the host: one permutation per call, for the inner hash (and for monolith.hip's SHAKE128)
+void keccak_f1600_host(uint64_t (&a)[25]) {
     static const uint64_t RC[24] = {
         0x0000000000000001ULL, 0x0000000000008082ULL, 0x800000000000808aULL, 0x8000000080008000ULL, 0x000000000000808bULL,
         0x0000000080000001ULL, 0x8000000080008081ULL, 0x8000000000008009ULL, 0x000000000000008aULL, 0x0000000000000088ULL,

@@ -348,6 +348,24 @@ extern "C" {
     pub fn lw_rpo_commit_columns_device(level: c_int, d_columns: *const u64, n_cols: u32, col_stride: u64, log2n: u32,
                                         bit_reverse: c_int, d_nodes: *mut u64, out_root_or_null: *mut u64,
                                         hip_stream: *mut c_void) -> c_int;
+    // ---- Monolith over Mersenne31: batched permutations (width 8 .. 24, rounds 1 .. 15); hash, compression and Merkle tree over width 16
+    pub fn lw_monolith_permute(width: u32, rounds: u32, states: *const u32, n: usize, out: *mut u32) -> c_int;
+    pub fn lw_monolith_permute_device(width: u32, rounds: u32, d_states: *const u32, n: usize, d_out: *mut u32,
+                                      hip_stream: *mut c_void) -> c_int;
+    pub fn lw_monolith_hash(rounds: u32, rows: *const u32, n_rows: usize, row_len: usize, out: *mut u32) -> c_int;
+    pub fn lw_monolith_hash_device(rounds: u32, d_rows: *const u32, n_rows: usize, row_len: usize, row_stride: usize, d_out: *mut u32,
+                                   hip_stream: *mut c_void) -> c_int;
+    pub fn lw_monolith_compress(rounds: u32, left: *const u32, right: *const u32, n: usize, out: *mut u32) -> c_int;
+    pub fn lw_monolith_compress_device(rounds: u32, d_left: *const u32, d_right: *const u32, n: usize, d_out: *mut u32,
+                                       hip_stream: *mut c_void) -> c_int;
+    pub fn lw_monolith_commit_columns(rounds: u32, columns: *const u32, n_cols: u32, log2n: u32, bit_reverse: c_int, out_root: *mut u32,
+                                      out_nodes_or_null: *mut u32) -> c_int;
+    pub fn lw_monolith_commit_columns_device(rounds: u32, d_columns: *const u32, n_cols: u32, col_stride: u64, log2n: u32,
+                                             bit_reverse: c_int, d_nodes: *mut u32, out_root_or_null: *mut u32,
+                                             hip_stream: *mut c_void) -> c_int;
+    pub fn lw_monolith_constants(width: u32, rounds: u32, out_round_constants: *mut u32, out_mds: *mut u32) -> c_int;
+    pub fn lw_monolith_layer_device(width: u32, rounds: u32, layer: c_int, d_states: *const u32, n: usize, d_out: *mut u32,
+                                    hip_stream: *mut c_void) -> c_int;
     // ---- batch inversion and STARK round 2 (the coset offset, the constraint tables and every small result on the host)
     pub fn lw_field_batch_inverse(field: Field, input: *const c_void, n: usize, out: *mut c_void) -> c_int;
     pub fn lw_field_batch_inverse_device(field: Field, d_in: *const c_void, n: usize, d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
@@ -440,6 +458,11 @@ pub const LW_FIELD_OP_TO_R64: c_int = 21;
 pub const LW_RPO_128: c_int = 0;
 /// lw_rpo_level_t: state 16, capacity 6, rate 10, digest 5 words
 pub const LW_RPO_160: c_int = 1;
+
+/// lw_monolith_layer_t: the layer lw_monolith_layer_device applies
+pub const LW_MONOLITH_CONCRETE: c_int = 0;
+pub const LW_MONOLITH_BARS: c_int = 1;
+pub const LW_MONOLITH_BRICKS: c_int = 2;
 
 // The C structs above must keep the sizes the header gives them.
 const _: () = assert!(core::mem::size_of::<lw_timings_t>() == 48);

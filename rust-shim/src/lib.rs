@@ -841,3 +841,48 @@ pub fn rpo_commit_columns_hip(level: RpoLevel, columns: &[&[u64]], bit_reverse: 
     })?;
     Ok(nodes)
 }
+
+/// `MonolithMersenne31::<WIDTH, NUM_FULL_ROUNDS>::permutation` (crypto/src/hash/monolith/mod.rs:91-102) on a batch of
+/// states, in place: `states` holds `width` Mersenne31 words per state, read mod p, canonical on return.
+pub fn monolith_permute_hip(width: usize, rounds: usize, states: &mut [u32]) -> Result<(), HipError> {
+    assert!(width != 0 && states.len() % width == 0, "states: a whole number of states");
+    let p = states.as_mut_ptr();
+    // SAFETY: one buffer of states.len() words, read and written in place.
+    check(unsafe { ffi::lw_monolith_permute(width as u32, rounds as u32, p as *const u32, states.len() / width, p) })
+}
+
+/// The 8-word digest of every row of a row-major matrix with `row_len` columns, over the width-16 permutation: every chunk
+/// of up to 8 words overwrites the front of the state.  No padding: only for rows of one fixed length.
+pub fn monolith_hash_hip(rounds: usize, rows: &[u32], n_rows: usize, row_len: usize) -> Result<Vec<u32>, HipError> {
+    assert!(rows.len() == n_rows * row_len, "rows: n_rows * row_len words");
+    let mut out = vec![0u32; n_rows * 8];
+    // SAFETY: rows holds n_rows * row_len words, out n_rows digests.
+    check(unsafe { ffi::lw_monolith_hash(rounds as u32, rows.as_ptr(), n_rows, row_len, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// `permute(left || right)[0..8]` for every pair of 8-word digests.
+pub fn monolith_compress_hip(rounds: usize, left: &[u32], right: &[u32]) -> Result<Vec<u32>, HipError> {
+    assert!(left.len() % 8 == 0 && left.len() == right.len(), "left, right: the same number of 8-word digests");
+    let mut out = vec![0u32; left.len()];
+    // SAFETY: the three buffers hold left.len() / 8 digests each.
+    check(unsafe { ffi::lw_monolith_compress(rounds as u32, left.as_ptr(), right.as_ptr(), left.len() / 8, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// The Merkle tree over the rows of `columns` (each a power-of-two column of the same length): leaf = the hash of the row,
+/// node = the compression of its children.  Returns the reference's `nodes`, root first, 8 words each.
+pub fn monolith_commit_columns_hip(rounds: usize, columns: &[&[u32]], bit_reverse: bool) -> Result<Vec<u32>, HipError> {
+    assert!(!columns.is_empty(), "columns: at least one");
+    let n = columns[0].len();
+    assert!(n.is_power_of_two() && columns.iter().all(|c| c.len() == n), "columns: one power-of-two length");
+    let flat: Vec<u32> = columns.iter().flat_map(|c| c.iter().copied()).collect();
+    let mut root = vec![0u32; 8];
+    let mut nodes = vec![0u32; (2 * n - 1) * 8];
+    // SAFETY: flat holds columns.len() * n words, root one digest, nodes 2 n - 1 digests.
+    check(unsafe {
+        ffi::lw_monolith_commit_columns(rounds as u32, flat.as_ptr(), columns.len() as u32, n.trailing_zeros(), bit_reverse as c_int,
+                                        root.as_mut_ptr(), nodes.as_mut_ptr())
+    })?;
+    Ok(nodes)
+}
