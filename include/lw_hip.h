@@ -796,6 +796,37 @@ int lw_sumcheck_round(lw_field_t field, void *const *tables, uint32_t k, uint32_
 int lw_sumcheck_round_device(lw_field_t field, void *const *d_tables, uint32_t k, uint32_t n_vars, const void *r_prev_or_null,
                              void *out_round_host, void *hip_stream);
 
+/* ---- the table of eq(point, .) and the sumcheck round over an eq-weighted sum of products ----
+ * The shape of Spartan's two sumchecks, of a GKR layer and of HyperPlonk's zero check:
+ * sum_x E(x) * sum_t c_t * prod_{m in S_t} T_m(x), E the table of eq(tau, .).  Fields, element form, variable order and
+ * n_vars <= 30 are those of lw_multilinear_* above; point, masks, coefficients and r_prev are host memory in both forms.
+ *   eq_table     out[i] = prod_j eq(point[j], bit_{n-1-j}(i)), i < 2^n_vars, canonical residues: the reference's chis table,
+ *                bit for bit.  n_vars = 0 writes the element one (the host form then needs no device).  The _device form
+ *                enqueues and returns; nothing in flight reads caller memory.
+ *   terms_round  out_round[u] = g(u) = sum_{j<h} E_j(u) * sum_t c_t * prod_{m in mask_t} T_m,j(u), u = 0 .. D, with
+ *                X_j(u) = X[j] + u * (X[j+h] - X[j]) and h = 2^(n-1).  Bit m of term_masks[t] puts tables[m] into term t;
+ *                D = max_t popcount(term_masks[t]) + (eq ? 1 : 0), and D + 1 elements are written.  Without eq the factor E
+ *                is absent.  term_coeffs_or_null holds n_terms elements; NULL means every coefficient is one.  The
+ *                coefficients one and minus one cost no product.  With r_prev (fused form, n_vars >= 2) every table and
+ *                the eq table is first replaced IN PLACE by its binding to r_prev, exactly as in sumcheck_round: the first
+ *                2^(n-1) elements hold the bound table, the rest is unspecified, g is taken over the n - 1 remaining
+ *                variables, and a round reads every table once.  Synchronises once.
+ * Limits: 1 <= n_tables <= 4 not counting eq, 1 <= n_terms <= 8, every mask non-zero, within n_tables bits and of at most
+ * three bits, so D <= 4.  A power of one table (A^2) and more than four tables are out of scope: the pair of every table
+ * and the D + 1 running sums of a thread live in registers, and a fifth table would not fit beside them.
+ * LW_ERR_BAD_ARG, decided before any device work: a field other than the two, a null pointer where data is needed,
+ * n_tables or n_terms out of range, a mask that is zero, has a bit at or above n_tables or more than three bits,
+ * n_vars > 30, a round with n_vars = 0, a fused round with n_vars < 2, a device pointer that is not 16-byte aligned, any
+ * two of the tables and eq that overlap. */
+int lw_multilinear_eq_table(lw_field_t field, const void *point, uint32_t n_vars, void *out);
+int lw_multilinear_eq_table_device(lw_field_t field, const void *point, uint32_t n_vars, void *d_out, void *hip_stream);
+int lw_sumcheck_terms_round(lw_field_t field, void *const *tables, uint32_t n_tables, void *eq_or_null,
+                            const uint32_t *term_masks, const void *term_coeffs_or_null, uint32_t n_terms, uint32_t n_vars,
+                            const void *r_prev_or_null, void *out_round);
+int lw_sumcheck_terms_round_device(lw_field_t field, void *const *d_tables, uint32_t n_tables, void *d_eq_or_null,
+                                   const uint32_t *term_masks, const void *term_coeffs_or_null, uint32_t n_terms,
+                                   uint32_t n_vars, const void *r_prev_or_null, void *out_round_host, void *hip_stream);
+
 /* ---- Circle FFT over Mersenne31 (math/src/circle/: evaluate_cfft, interpolate_cfft, get_twiddles) ----
  * The transform between the 2^log2n coefficients of a polynomial in the basis {1, y, x, xy, 2x^2 - 1, ...} (coefficient k
  * multiplies y^(k & 1) * prod_t pi^t(x)^(bit t+1 of k), pi(x) = 2x^2 - 1) and its values on the standard coset

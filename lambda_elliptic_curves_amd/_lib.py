@@ -65,6 +65,7 @@ EXPORTS = [
     "lw_stark_round2",
     "lw_multilinear_evaluate", "lw_multilinear_evaluate_device", "lw_multilinear_fix_variables",
     "lw_multilinear_fix_variables_device", "lw_sumcheck_round", "lw_sumcheck_round_device",
+    "lw_multilinear_eq_table", "lw_multilinear_eq_table_device", "lw_sumcheck_terms_round", "lw_sumcheck_terms_round_device",
 ]
 
 
@@ -373,6 +374,14 @@ def lib():
     L.lw_sumcheck_round.restype = i
     L.lw_sumcheck_round_device.argtypes = [i, vp, u32, u32, vp, vp, vp]
     L.lw_sumcheck_round_device.restype = i
+    L.lw_multilinear_eq_table.argtypes = [i, vp, u32, vp]
+    L.lw_multilinear_eq_table.restype = i
+    L.lw_multilinear_eq_table_device.argtypes = [i, vp, u32, vp, vp]
+    L.lw_multilinear_eq_table_device.restype = i
+    L.lw_sumcheck_terms_round.argtypes = [i, vp, u32, vp, vp, vp, u32, u32, vp, vp]
+    L.lw_sumcheck_terms_round.restype = i
+    L.lw_sumcheck_terms_round_device.argtypes = [i, vp, u32, vp, vp, vp, u32, u32, vp, vp, vp]
+    L.lw_sumcheck_terms_round_device.restype = i
     _lib = L
     return L
 

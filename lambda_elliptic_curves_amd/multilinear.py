@@ -152,3 +152,120 @@ def sumcheck_prove_device(field, t_tables, n_vars, challenge, stream=None):
         torch.cuda.synchronize()
     final = t_fin.cpu().numpy().view(np.uint64)
     return claimed, rounds, np.stack(point), final
+
+
+# ---- the table of eq(point, .) and the round over an eq-weighted sum of products ----
+MAX_TERM_TABLES = 4
+MAX_TERMS = 8
+MAX_TERM_FACTORS = 3
+
+
+def eq_table(field, point):
+    """(2^n, 4): out[i] = prod_j eq(point[j], bit_{n-1-j}(i)) for a point of n coordinates, the reference's chis table."""
+    n = len(point)
+    p = _point(point, n)
+    out = np.zeros((1 << n, 4), np.uint64)
+    check(L.lib().lw_multilinear_eq_table(field.field, _vp(p), n, _vp(out)))
+    return out
+
+
+def eq_table_device(field, point, t_out=None, stream=None):
+    """eq_table() into the device-resident tensor t_out (at least 2^n elements; a new (2^n, 4) int64 tensor when None);
+    nothing is waited for.  -> t_out"""
+    n = len(point)
+    p = _point(point, n)
+    if t_out is None:
+        import torch
+        t_out = torch.empty((1 << n, 4), dtype=torch.int64, device="cuda")
+    if t_out.numel() * t_out.element_size() < 32 << n or not t_out.is_contiguous():
+        from .errors import LengthMismatch
+        raise LengthMismatch(f"the output holds fewer than 2^{n} contiguous elements")
+    check(L.lib().lw_multilinear_eq_table_device(field.field, _vp(p), n, C.c_void_p(t_out.data_ptr()), _stream(stream)))
+    return t_out
+
+
+def _terms(field, terms, has_eq):
+    """terms [(coeff or None, (table indices ...)), ...] -> (masks, coefficient array or None, D)"""
+    from .errors import InputError
+    masks = np.zeros(max(1, len(terms)), np.uint32)
+    coeffs, deg = [], 0
+    for t, (c, idx) in enumerate(terms):
+        idx = [int(m) for m in idx]
+        if len(set(idx)) != len(idx) or any(m < 0 or m >= 32 for m in idx):
+            raise InputError(f"term {t}: every table at most once (no powers), indices from 0")
+        masks[t] = sum(1 << m for m in idx)
+        deg = max(deg, len(idx))
+        coeffs.append(c)
+    carr = None
+    if any(c is not None for c in coeffs):
+        one = np.frombuffer(((1 << 256) % MODULI[field.field]).to_bytes(32, "big"), dtype=">u8").astype(np.uint64)
+        carr = np.stack([one if c is None else np.ascontiguousarray(c, dtype=np.uint64).reshape(-1)[:4] for c in coeffs])
+        carr = np.ascontiguousarray(carr)
+    return masks, carr, deg + (1 if has_eq else 0)
+
+
+def sumcheck_terms_round(field, tables, terms, eq=None, r_prev=None):
+    """(D + 1, 4): g(0) .. g(D) of the round of sum_x E(x) sum_t c_t prod_{m in S_t} T_m(x) over at most 4 tables of 2^n
+    elements.  terms: a list of (coeff_or_None, (table indices ...)), at most 8, each over at most 3 distinct tables; None
+    is the coefficient one.  eq: the table E or None.  D = the most tables in a term, plus one with eq.  With r_prev the
+    tables and eq (which must then be writable (2^n, 4) uint64 arrays) are first bound to it in place, as in
+    sumcheck_round."""
+    every = list(tables) + ([eq] if eq is not None else [])
+    ts = [_elems(t) for t in every]
+    inplace = lambda u: isinstance(u, np.ndarray) and u.dtype == np.uint64 and u.flags.c_contiguous and u.flags.writeable
+    if r_prev is not None and not all(inplace(u) for u in every):
+        from .errors import InputError
+        raise InputError("a fused round binds in place: pass C-contiguous uint64 arrays")
+    n = _n_vars(ts[0]) if ts else 0
+    masks, carr, deg = _terms(field, terms, eq is not None)
+    out = np.zeros((deg + 1, 4), np.uint64)
+    keep, rp = _opt(r_prev)
+    k = len(tables)
+    ptrs = (C.c_void_p * max(1, k))(*[t.ctypes.data for t in ts[:k]])
+    check(L.lib().lw_sumcheck_terms_round(field.field, ptrs, k, _vp(ts[k]) if eq is not None else None, _vp(masks),
+                                          _vp(carr) if carr is not None else None, len(terms), n, rp, _vp(out)))
+    return out
+
+
+def sumcheck_terms_round_device(field, t_tables, terms, n_vars, t_eq=None, r_prev=None, stream=None):
+    """sumcheck_terms_round() on device-resident torch tensors; with r_prev they are bound in place."""
+    masks, carr, deg = _terms(field, terms, t_eq is not None)
+    for t in list(t_tables) + ([t_eq] if t_eq is not None else []):
+        if 0 <= n_vars <= 30 and t.numel() * t.element_size() < 32 << n_vars:
+            from .errors import LengthMismatch
+            raise LengthMismatch(f"a table holds fewer than 2^{n_vars} elements")
+    out = np.zeros((deg + 1, 4), np.uint64)
+    keep, rp = _opt(r_prev)
+    ptrs = (C.c_void_p * max(1, len(t_tables)))(*[t.data_ptr() for t in t_tables])
+    check(L.lib().lw_sumcheck_terms_round_device(field.field, ptrs, len(t_tables), C.c_void_p(t_eq.data_ptr()) if t_eq is not None else None,
+                                                 _vp(masks), _vp(carr) if carr is not None else None, len(terms), n_vars, rp, _vp(out),
+                                                 _stream(stream)))
+    return out
+
+
+def sumcheck_terms_prove_device(field, t_tables, terms, n_vars, challenge, t_eq=None, stream=None):
+    """The prover's side of a sumcheck of sum_x E(x) sum_t c_t prod_{m in S_t} T_m(x) over the cube of n_vars >= 1
+    variables, the tables and t_eq resident on the device and consumed in place.  challenge: a callable from a round's
+    (D + 1, 4) array to the next r (4 uint64), the seam for the caller's transcript.  The loop of sumcheck_prove_device: one
+    plain round, n_vars - 1 fused rounds, and a final fix_variables of the last variable.
+    -> (claimed_sum (4,), rounds [n_vars arrays (D + 1, 4)], point (n_vars, 4), final_evals (K, 4) or (K + 1, 4) with
+    the eq table's value last)"""
+    import torch
+    rounds, point = [], []
+    r = None
+    for i in range(n_vars):
+        g = sumcheck_terms_round_device(field, t_tables, terms, n_vars - max(0, i - 1), t_eq, r, stream)
+        rounds.append(g)
+        r = np.ascontiguousarray(challenge(g), dtype=np.uint64).reshape(-1)[:4].copy()
+        point.append(r)
+    claimed = _add(field, rounds[0][0], rounds[0][1])
+    every = list(t_tables) + ([t_eq] if t_eq is not None else [])
+    t_fin = torch.empty((len(every), 4), dtype=torch.int64, device=every[0].device)
+    for k, t in enumerate(every):
+        fix_variables_device(field, t, 1, r.reshape(1, 4), t_fin[k], stream)
+    if stream is None:
+        torch.cuda.current_stream().synchronize()
+    else:
+        torch.cuda.synchronize()
+    final = t_fin.cpu().numpy().view(np.uint64)
+    return claimed, rounds, np.stack(point), final

@@ -317,6 +317,17 @@ extern "C" {
                              out_round: *mut c_void) -> c_int;
     pub fn lw_sumcheck_round_device(field: Field, d_tables: *const *mut c_void, k: u32, n_vars: u32, r_prev_or_null: *const c_void,
                                     out_round_host: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    // ---- the table of eq(point, .) and the round over an eq-weighted sum of products (masks, coefficients on the host)
+    pub fn lw_multilinear_eq_table(field: Field, point: *const c_void, n_vars: u32, out: *mut c_void) -> c_int;
+    pub fn lw_multilinear_eq_table_device(field: Field, point: *const c_void, n_vars: u32, d_out: *mut c_void,
+                                          hip_stream: *mut c_void) -> c_int;
+    pub fn lw_sumcheck_terms_round(field: Field, tables: *const *mut c_void, n_tables: u32, eq_or_null: *mut c_void,
+                                   term_masks: *const u32, term_coeffs_or_null: *const c_void, n_terms: u32, n_vars: u32,
+                                   r_prev_or_null: *const c_void, out_round: *mut c_void) -> c_int;
+    pub fn lw_sumcheck_terms_round_device(field: Field, d_tables: *const *mut c_void, n_tables: u32, d_eq_or_null: *mut c_void,
+                                          term_masks: *const u32, term_coeffs_or_null: *const c_void, n_terms: u32, n_vars: u32,
+                                          r_prev_or_null: *const c_void, out_round_host: *mut c_void,
+                                          hip_stream: *mut c_void) -> c_int;
     // ---- circle FFT over Mersenne31: one u32 per element, canonical residues out
     pub fn lw_circle_evaluate_cfft(coeffs: *const u32, out: *mut u32, log2n: u32, batch: u32, batch_stride: usize) -> c_int;
     pub fn lw_circle_interpolate_cfft(evals: *const u32, out: *mut u32, log2n: u32, batch: u32, batch_stride: usize) -> c_int;

@@ -446,6 +446,68 @@ pub fn sumcheck_round(field: Field, tables: &mut [&mut [[u64; 4]]], r_prev: Opti
     Ok(out)
 }
 
+/// The table of `eq(point, .)`: `out[i] = prod_j eq(point[j], bit_{n-1-j}(i))`, `2^n` elements for a point of `n`
+/// coordinates (the `chis` table of `DenseMultilinearPolynomial::evaluate`).
+pub fn multilinear_eq_table(field: Field, point: &[[u64; 4]]) -> Result<Vec<[u64; 4]>, HipError> {
+    if point.len() > 30 {
+        return Err(HipError::BadArgument("at most 30 variables".into()));
+    }
+    let mut out = vec![[0u64; 4]; 1usize << point.len()];
+    // SAFETY: `point` is valid for n elements, `out` for 2^n.
+    let rc = unsafe {
+        ffi::lw_multilinear_eq_table(field, point.as_ptr() as *const c_void, point.len() as u32, out.as_mut_ptr() as *mut c_void)
+    };
+    check(rc)?;
+    Ok(out)
+}
+
+/// One term of a composed sumcheck: `coeff * prod_{m in tables} T_m`; `None` is the coefficient one.  Every table at most
+/// once, at most three tables.
+pub struct SumcheckTerm<'a> {
+    pub coeff: Option<[u64; 4]>,
+    pub tables: &'a [u32],
+}
+
+/// The prover's round of a sumcheck over `sum_x E(x) * sum_t c_t * prod_{m in S_t} T_m(x)`: `g(0) .. g(D)` with
+/// `D` = the most tables in a term, plus one with `eq`.  At most 4 tables, 8 terms.  `one` is the field's Montgomery one,
+/// the coefficient of a term that names none.  With `r_prev` every table and `eq` is first bound to it in place, as in
+/// `sumcheck_round`.
+pub fn sumcheck_terms_round(field: Field, tables: &mut [&mut [[u64; 4]]], eq: Option<&mut [[u64; 4]]>, terms: &[SumcheckTerm],
+                            one: &[u64; 4], r_prev: Option<&[u64; 4]>) -> Result<Vec<[u64; 4]>, HipError> {
+    let n = multilinear_vars(tables.first().map_or(1, |t| t.len()))?;
+    if tables.iter().any(|t| t.len() != 1usize << n) || eq.as_ref().map_or(false, |e| e.len() != 1usize << n) {
+        return Err(HipError::BadArgument("tables of one length".into()));
+    }
+    let mut masks = Vec::with_capacity(terms.len());
+    let mut coeffs = Vec::with_capacity(terms.len());
+    let mut deg = 0usize;
+    for t in terms {
+        let mut mask = 0u32;
+        for &m in t.tables {
+            if m >= 32 || mask & (1 << m) != 0 {
+                return Err(HipError::BadArgument("a term names every table at most once".into()));
+            }
+            mask |= 1 << m;
+        }
+        masks.push(mask);
+        coeffs.push(t.coeff.unwrap_or(*one));
+        deg = deg.max(t.tables.len());
+    }
+    let all_one = terms.iter().all(|t| t.coeff.is_none());
+    let ptrs: Vec<*mut c_void> = tables.iter_mut().map(|t| t.as_mut_ptr() as *mut c_void).collect();
+    let mut out = vec![[0u64; 4]; deg + 1 + eq.is_some() as usize];
+    let eq_ptr = eq.map_or(core::ptr::null_mut(), |e| e.as_mut_ptr() as *mut c_void);
+    // SAFETY: every table and `eq` is valid and exclusively borrowed for 2^n elements; `masks` and `coeffs` hold one entry
+    // per term; `out` holds D + 1 elements, D as the library computes it from the masks.
+    let rc = unsafe {
+        ffi::lw_sumcheck_terms_round(field, ptrs.as_ptr(), tables.len() as u32, eq_ptr, masks.as_ptr(),
+                                     if all_one { core::ptr::null() } else { coeffs.as_ptr() as *const c_void }, terms.len() as u32, n,
+                                     r_prev.map_or(core::ptr::null(), |r| r.as_ptr() as *const c_void), out.as_mut_ptr() as *mut c_void)
+    };
+    check(rc)?;
+    Ok(out)
+}
+
 /// The parts of the composition polynomial and their commitment, as `stark_round2` returns them.
 pub struct Round2 {
     /// `n_parts` blocks of `block_len` coefficients, zero padded
