@@ -827,6 +827,52 @@ int lw_sumcheck_terms_round_device(lw_field_t field, void *const *d_tables, uint
                                    const uint32_t *term_masks, const void *term_coeffs_or_null, uint32_t n_terms,
                                    uint32_t n_vars, const void *r_prev_or_null, void *out_round_host, void *hip_stream);
 
+/* ---- a rank-one constraint system on the device: A z, B z, C z, the row-bound matrix, Groth16's h from a witness ----
+ * The handle keeps the three sparse matrices A, B, C of an R1CS (n_rows constraints over n_cols variables) resident, built
+ * once per circuit like lw_plonk_circuit_t.  Fields and element form are those of lw_multilinear_*: LW_FIELD_STARK252 or
+ * LW_FIELD_BLS12_381_FR, 4 x u64, MS limb first, Montgomery form, canonical.
+ *   create       three CSR matrices in host memory: row_ptr[m] has n_rows + 1 entries, col_idx[m] and values[m] have
+ *                nnz_m = row_ptr[m][n_rows] (< 2^32).  1 <= n_rows, n_cols <= 2^30.  A matrix may be empty (its col_idx and
+ *                values may then be NULL), rows may be empty, the columns of a row need no order, a repeated (row, column)
+ *                is summed, explicit zeros are allowed.  LW_ERR_BAD_ARG, decided on the host before any device work: a field
+ *                other than the two, NULL where data is needed, n_rows or n_cols out of range, row_ptr[m][0] != 0 or a
+ *                decreasing row_ptr, a column index >= n_cols, a value >= p.  The handle holds the CSR arrays, the
+ *                transposed index, a class per entry (one, minus one, general: the first two cost no product) and the plan
+ *                of the lists longer than lw_r1cs_split_length() entries, which are cut into pieces of that length.
+ *   matvec       every requested output receives n_out >= n_rows elements: (M z)[i] for i < n_rows, zero above, whatever
+ *                the buffer held.  z holds n_cols elements.  n_out is the padded table or gate-domain length (<= 2^34).
+ *   bind_rows    out[j] = sum_i e[i] * (c_A A[i,j] + c_B B[i,j] + c_C C[i,j]) for j < n_cols, zero for n_cols <= j < n_out.
+ *                e holds n_rows elements; coeffs3 = (c_A, c_B, c_C) is host memory in both forms.  With e the table of
+ *                eq(r_x, .) this is the table of Spartan's second sumcheck.
+ *   first_unsatisfied  *out_row = the smallest i with (A z)_i (B z)_i != (C z)_i, or -1.  Synchronises.
+ *   The _device forms take 16-byte aligned device pointers and enqueue on hip_stream; matvec and bind_rows wait for nothing.
+ *   LW_ERR_BAD_ARG before any device work: a NULL handle or vector, n_out below the rows (columns) or above 2^34, a
+ *   misaligned device pointer, an output that overlaps the input vector or another output.
+ *   lw_r1cs_lazy_terms(): the terms a Stark252 sum carries between two full reductions (the bound is in csrc/r1cs.hip).
+ *   h_from_witness  QuadraticArithmeticProgram::calculate_h_coefficients from the witness w (n_cols elements) of a system
+ *                over LW_FIELD_BLS12_381_FR (else LW_ERR_BAD_ARG): A w, B w, C w padded to num_gates, their interpolations
+ *                over the gate domain (what scale_and_accumulate_variable_polynomials sums on the host,
+ *                provers/groth16/src/qap.rs:44-66), then lw_groth16_h_coefficients, bit for bit.  num_gates: a power of two
+ *                (else LW_ERR_INPUT_NOT_POW2) >= n_rows (else LW_ERR_BAD_ARG).  out_h and coeff_len_or_null as there. */
+typedef struct lw_r1cs lw_r1cs_t;
+int lw_r1cs_create(lw_field_t field, uint32_t n_rows, uint32_t n_cols, const uint32_t *const row_ptr[3],
+                   const uint32_t *const col_idx[3], const void *const values[3], lw_r1cs_t **out);
+int lw_r1cs_destroy(lw_r1cs_t *r1cs);
+uint32_t lw_r1cs_split_length(void);
+uint32_t lw_r1cs_lazy_terms(void);
+int lw_r1cs_matvec(const lw_r1cs_t *r1cs, const void *z, size_t n_out, void *out_az_or_null, void *out_bz_or_null,
+                   void *out_cz_or_null);
+int lw_r1cs_matvec_device(const lw_r1cs_t *r1cs, const void *d_z, size_t n_out, void *d_out_az_or_null, void *d_out_bz_or_null,
+                          void *d_out_cz_or_null, void *hip_stream);
+int lw_r1cs_bind_rows(const lw_r1cs_t *r1cs, const void *e, const void *coeffs3, size_t n_out, void *out);
+int lw_r1cs_bind_rows_device(const lw_r1cs_t *r1cs, const void *d_e, const void *coeffs3, size_t n_out, void *d_out,
+                             void *hip_stream);
+int lw_r1cs_first_unsatisfied(const lw_r1cs_t *r1cs, const void *z, int64_t *out_row);
+int lw_r1cs_first_unsatisfied_device(const lw_r1cs_t *r1cs, const void *d_z, int64_t *out_row, void *hip_stream);
+int lw_groth16_h_from_witness(const lw_r1cs_t *r1cs, const void *w, size_t num_gates, void *out_h, size_t *coeff_len_or_null);
+int lw_groth16_h_from_witness_device(const lw_r1cs_t *r1cs, const void *d_w, size_t num_gates, void *d_out_h,
+                                     size_t *coeff_len_or_null, void *hip_stream);
+
 /* ---- Circle FFT over Mersenne31 (math/src/circle/: evaluate_cfft, interpolate_cfft, get_twiddles) ----
  * The transform between the 2^log2n coefficients of a polynomial in the basis {1, y, x, xy, 2x^2 - 1, ...} (coefficient k
  * multiplies y^(k & 1) * prod_t pi^t(x)^(bit t+1 of k), pi(x) = 2x^2 - 1) and its values on the standard coset

@@ -66,6 +66,9 @@ EXPORTS = [
     "lw_multilinear_evaluate", "lw_multilinear_evaluate_device", "lw_multilinear_fix_variables",
     "lw_multilinear_fix_variables_device", "lw_sumcheck_round", "lw_sumcheck_round_device",
     "lw_multilinear_eq_table", "lw_multilinear_eq_table_device", "lw_sumcheck_terms_round", "lw_sumcheck_terms_round_device",
+    "lw_r1cs_create", "lw_r1cs_destroy", "lw_r1cs_split_length", "lw_r1cs_lazy_terms", "lw_r1cs_matvec", "lw_r1cs_matvec_device",
+    "lw_r1cs_bind_rows", "lw_r1cs_bind_rows_device", "lw_r1cs_first_unsatisfied", "lw_r1cs_first_unsatisfied_device",
+    "lw_groth16_h_from_witness", "lw_groth16_h_from_witness_device",
 ]
 
 
@@ -382,6 +385,30 @@ def lib():
     L.lw_sumcheck_terms_round.restype = i
     L.lw_sumcheck_terms_round_device.argtypes = [i, vp, u32, vp, vp, vp, u32, u32, vp, vp, vp]
     L.lw_sumcheck_terms_round_device.restype = i
+    L.lw_r1cs_create.argtypes = [i, u32, u32, vp, vp, vp, C.POINTER(vp)]
+    L.lw_r1cs_create.restype = i
+    L.lw_r1cs_destroy.argtypes = [vp]
+    L.lw_r1cs_destroy.restype = i
+    L.lw_r1cs_split_length.argtypes = []
+    L.lw_r1cs_split_length.restype = u32
+    L.lw_r1cs_lazy_terms.argtypes = []
+    L.lw_r1cs_lazy_terms.restype = u32
+    L.lw_r1cs_matvec.argtypes = [vp, vp, sz, vp, vp, vp]
+    L.lw_r1cs_matvec.restype = i
+    L.lw_r1cs_matvec_device.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+    L.lw_r1cs_matvec_device.restype = i
+    L.lw_r1cs_bind_rows.argtypes = [vp, vp, vp, sz, vp]
+    L.lw_r1cs_bind_rows.restype = i
+    L.lw_r1cs_bind_rows_device.argtypes = [vp, vp, vp, sz, vp, vp]
+    L.lw_r1cs_bind_rows_device.restype = i
+    L.lw_r1cs_first_unsatisfied.argtypes = [vp, vp, C.POINTER(C.c_int64)]
+    L.lw_r1cs_first_unsatisfied.restype = i
+    L.lw_r1cs_first_unsatisfied_device.argtypes = [vp, vp, C.POINTER(C.c_int64), vp]
+    L.lw_r1cs_first_unsatisfied_device.restype = i
+    L.lw_groth16_h_from_witness.argtypes = [vp, vp, sz, vp, C.POINTER(sz)]
+    L.lw_groth16_h_from_witness.restype = i
+    L.lw_groth16_h_from_witness_device.argtypes = [vp, vp, sz, vp, C.POINTER(sz), vp]
+    L.lw_groth16_h_from_witness_device.restype = i
     _lib = L
     return L
 

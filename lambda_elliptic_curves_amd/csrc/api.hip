@@ -1115,6 +1115,56 @@ int lw_groth16_h_coefficients(const void *l_coeffs, const void *r_coeffs, const 
     return download(out_h, c.host_io_b.p, n * 32, io);
 }
 
+// h straight from a witness: the accumulation of the variable polynomials (scale_and_accumulate_variable_polynomials,
+// provers/groth16/src/qap.rs:44-66) is the interpolation of A w, B w, C w over the gate domain, so the three products and
+// three inverse transforms run on the device in front of the pipeline above.  Tables in c.poly_q: [Aw | Bw | Cw | l | r | o].
+static int groth16_witness_entry(const lw_r1cs_t *h, const void *w, size_t num_gates, void *out_h, size_t *coeff_len, void *hip_stream,
+                                 bool device) {
+    if (!h || !w || !out_h) { set_error("null argument"); return LW_ERR_BAD_ARG; }
+    if (r1cs_field(h) != LW_FIELD_BLS12_381_FR) { set_error("Groth16 runs over BLS12_381_FR"); return LW_ERR_BAD_ARG; }
+    int rc = check_pow2(num_gates, 1);
+    if (rc) return rc;
+    if (num_gates < r1cs_rows(h)) { set_error("%zu gates for %u constraints", num_gates, r1cs_rows(h)); return LW_ERR_BAD_ARG; }
+    const uint32_t lg = ceil_log2(num_gates);
+    rc = check_root(LW_FIELD_BLS12_381_FR, lg + 1);
+    if (rc) return rc;
+    if (device && ((((uintptr_t)w) | ((uintptr_t)out_h)) & 15)) { set_error("device buffers must be 16-byte aligned"); return LW_ERR_BAD_ARG; }
+    Entry en(hip_stream);
+    if (en.rc) return en.rc;
+    Context &c = en.c;
+    hipStream_t s = en.stream;
+    const void *d_w = w;
+    void *d_out = out_h;
+    const size_t n = 2 * num_gates, tb = num_gates * 32;
+    if (!device) {
+        s = en.use_lane_stream();
+        if (!s) return en.rc;
+        const size_t wb = (size_t)r1cs_cols(h) * 32;
+        if (c.host_io_a.ensure(wb) || c.host_io_b.ensure(n * 32)) return LW_ERR_ALLOC;
+        LW_HIP_CHECK(hipMemcpyAsync(c.host_io_a.p, w, wb, hipMemcpyHostToDevice, s), LW_ERR_LAUNCH);
+        d_w = c.host_io_a.p;
+        d_out = c.host_io_b.p;
+    }
+    if (c.poly_q.ensure(6 * tb)) return LW_ERR_ALLOC;   // the lane's grow-only buffer: a second call of this size allocates nothing
+    char *t = (char *)c.poly_q.p;
+    void *const prod[3] = {t, t + tb, t + 2 * tb};
+    rc = r1cs_matvec_locked(c, h, d_w, num_gates, prod, s);
+    if (rc) return rc;
+    rc = ntt_device_locked(c, LW_FIELD_BLS12_381_FR, LW_LAYOUT_U64_LIMBS_MS_FIRST, LW_DIR_INVERSE, t, t + 3 * tb, lg, 3, 0, nullptr, s);
+    if (rc) return rc;
+    const void *src[3] = {t + 3 * tb, t + 4 * tb, t + 5 * tb};
+    rc = groth16_h_locked(c, src, num_gates, num_gates, lg, d_out, coeff_len, s);
+    if (rc || device) return rc;
+    return download(out_h, d_out, n * 32, s);
+}
+int lw_groth16_h_from_witness(const lw_r1cs_t *r1cs, const void *w, size_t num_gates, void *out_h, size_t *coeff_len_or_null) {
+    return groth16_witness_entry(r1cs, w, num_gates, out_h, coeff_len_or_null, nullptr, false);
+}
+int lw_groth16_h_from_witness_device(const lw_r1cs_t *r1cs, const void *d_w, size_t num_gates, void *d_out_h, size_t *coeff_len_or_null,
+                                     void *hip_stream) {
+    return groth16_witness_entry(r1cs, d_w, num_gates, d_out_h, coeff_len_or_null, hip_stream, true);
+}
+
 // One body for the host and device MSM forms: the host form stages the scalars and hands msm_device the points to upload
 static int msm_entry(lw_curve_t curve, const uint64_t *scalars, size_t n_scalars, const void *points, size_t n_points, void *out_point,
                      void *hip_stream, int mont, uint32_t limbs, bool device) {

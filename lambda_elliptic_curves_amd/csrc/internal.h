@@ -61,6 +61,13 @@ int groth16_h_device(Context &c, const void *d_l, const void *d_r, const void *d
                      hipStream_t stream);
 int stripped_length_device(const void *d_elems, uint64_t n, uint64_t *d_len, hipStream_t stream);
 
+// ---- r1cs.hip
+lw_field_t r1cs_field(const lw_r1cs_t *h);
+uint32_t r1cs_rows(const lw_r1cs_t *h);
+uint32_t r1cs_cols(const lw_r1cs_t *h);
+// A z, B z, C z of a device-resident z into the requested d_out (n_out >= rows elements each, zero past the rows)
+int r1cs_matvec_locked(Context &c, const lw_r1cs_t *h, const void *d_z, size_t n_out, void *const (&d_out)[3], hipStream_t s);
+
 // ---- stark_query.hip
 void keccak_f1600_host(uint64_t (&a)[25]);   // Keccak-f[1600] on the host: the grinding seed, the SHAKE128 of monolith.hip
 

@@ -113,6 +113,12 @@ pub struct lw_plonk_circuit_t {
     _private: [u8; 0],
 }
 
+/// opaque `lw_r1cs_t`
+#[repr(C)]
+pub struct lw_r1cs_t {
+    _private: [u8; 0],
+}
+
 extern "C" {
     // ---- context
     pub fn lw_hip_init(device_ids: *const c_int, n_devices: c_int) -> c_int;
@@ -328,6 +334,27 @@ extern "C" {
                                           term_masks: *const u32, term_coeffs_or_null: *const c_void, n_terms: u32, n_vars: u32,
                                           r_prev_or_null: *const c_void, out_round_host: *mut c_void,
                                           hip_stream: *mut c_void) -> c_int;
+    // ---- a rank-one constraint system on the device: A z, B z, C z, the row-bound matrix, Groth16's h from a witness
+    pub fn lw_r1cs_create(field: Field, n_rows: u32, n_cols: u32, row_ptr: *const *const u32, col_idx: *const *const u32,
+                          values: *const *const c_void, out: *mut *mut lw_r1cs_t) -> c_int;
+    pub fn lw_r1cs_destroy(r1cs: *mut lw_r1cs_t) -> c_int;
+    pub fn lw_r1cs_split_length() -> u32;
+    pub fn lw_r1cs_lazy_terms() -> u32;
+    pub fn lw_r1cs_matvec(r1cs: *const lw_r1cs_t, z: *const c_void, n_out: usize, out_az_or_null: *mut c_void,
+                          out_bz_or_null: *mut c_void, out_cz_or_null: *mut c_void) -> c_int;
+    pub fn lw_r1cs_matvec_device(r1cs: *const lw_r1cs_t, d_z: *const c_void, n_out: usize, d_out_az_or_null: *mut c_void,
+                                 d_out_bz_or_null: *mut c_void, d_out_cz_or_null: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_r1cs_bind_rows(r1cs: *const lw_r1cs_t, e: *const c_void, coeffs3: *const c_void, n_out: usize,
+                             out: *mut c_void) -> c_int;
+    pub fn lw_r1cs_bind_rows_device(r1cs: *const lw_r1cs_t, d_e: *const c_void, coeffs3: *const c_void, n_out: usize,
+                                    d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_r1cs_first_unsatisfied(r1cs: *const lw_r1cs_t, z: *const c_void, out_row: *mut i64) -> c_int;
+    pub fn lw_r1cs_first_unsatisfied_device(r1cs: *const lw_r1cs_t, d_z: *const c_void, out_row: *mut i64,
+                                            hip_stream: *mut c_void) -> c_int;
+    pub fn lw_groth16_h_from_witness(r1cs: *const lw_r1cs_t, w: *const c_void, num_gates: usize, out_h: *mut c_void,
+                                     coeff_len_or_null: *mut usize) -> c_int;
+    pub fn lw_groth16_h_from_witness_device(r1cs: *const lw_r1cs_t, d_w: *const c_void, num_gates: usize, d_out_h: *mut c_void,
+                                            coeff_len_or_null: *mut usize, hip_stream: *mut c_void) -> c_int;
     // ---- circle FFT over Mersenne31: one u32 per element, canonical residues out
     pub fn lw_circle_evaluate_cfft(coeffs: *const u32, out: *mut u32, log2n: u32, batch: u32, batch_stride: usize) -> c_int;
     pub fn lw_circle_interpolate_cfft(evals: *const u32, out: *mut u32, log2n: u32, batch: u32, batch_stride: usize) -> c_int;

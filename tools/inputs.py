@@ -37,6 +37,40 @@ def rand_elems(name, n, seed):
     raise KeyError(name)
 
 
+def r1cs_system(name, n_rows, n_cols, skewed, seed):
+    """A synthetic R1CS for tools/r1cs_timing.py: three CSR matrices (row_ptr, col_idx, values) as arrays.
+    skewed: the row and column profile of the circom Poseidon circuit as the timing asks for it - every row one entry, one
+    row in 512 a long one of 58 entries (about 1.11 entries a row), and in C the constant column 0 as the entry of 30 % of
+    the rows.  Otherwise the same number of entries spread evenly: one a row, the rest as second entries of rows picked
+    at random, every column drawn uniformly.  Values: 45 % one, 45 % minus one, 10 % general."""
+    p = P_STARK252 if name == "stark252" else P_FR381
+    word = lambda v: np.array([(v >> (64 * (3 - k))) & ((1 << 64) - 1) for k in range(4)], dtype=np.uint64)
+    one, minus_one = word((1 << 256) % p), word(p - (1 << 256) % p)
+    rng = np.random.default_rng(seed)
+    mats = []
+    for m in range(3):
+        long_rows = rng.permutation(n_rows)[:n_rows // 512]
+        extra = 57 * long_rows.shape[0]
+        lens = np.ones(n_rows, np.int64)
+        if skewed:
+            lens[long_rows] = 58
+        else:
+            lens[rng.permutation(n_rows)[:extra]] += 1
+        row_ptr = np.zeros(n_rows + 1, np.uint32)
+        row_ptr[1:] = np.cumsum(lens)
+        nnz = int(row_ptr[-1])
+        cols = rng.integers(0, n_cols, nnz, dtype=np.uint32)
+        if skewed and m == 2:
+            first = row_ptr[:-1][rng.random(n_rows) < 0.3]
+            cols[first] = 0
+        values = rand_elems(name, nnz, seed + 10 + m)
+        kind = rng.random(nnz)
+        values[kind < 0.45] = one
+        values[(kind >= 0.45) & (kind < 0.9)] = minus_one
+        mats.append((row_ptr, cols, values))
+    return mats
+
+
 def offset_elem(name, h):
     """Coset offset h (small canonical int) as one domain-field element in memory (Montgomery) form"""
     if name == "babybear_u32":
