@@ -18,13 +18,15 @@
 //                   (ml_round_kernel<K, FUSED>).  FUSED first binds the leading variable to the previous challenge in place:
 //                   with h = 2^(n-1) and q = h / 2 a thread owns the indices j, j + q, j + h, j + h + q of every table,
 //                   stores the bound values at j and j + q and feeds them to the products, so that a round reads every
-//                   table once and no thread reads what another one writes.  The values at t >= 2 come from adding
-//                   b - a; only the products multiply.  Blocks reduce in LDS, ml_sum_finish_kernel adds up their partials.
+//                   table once and no thread reads what another one writes (ml_load_pair).  The values at t >= 2 come from
+//                   adding b - a; only the products multiply.  Blocks reduce in LDS, ml_sum_finish_kernel adds up their
+//                   partials.
 // Every stored value is a canonical residue (fe_add / fe_sub / fe_mul / fe_dot of canonical operands), and field addition
 // is exact, so the order of the reductions does not show in the result.  Small operands (eq tables, weights, challenges,
 // table pointers) travel as kernel arguments: a call without a host result leaves nothing in flight that reads caller
 // memory; a call with one synchronises once (ml_result).
-// The block reduction, the finish kernel and the host helpers that sumcheck_terms.hip uses as well are in multilinear.cuh.
+// What the composed round of sumcheck_terms.hip uses as well is in multilinear.cuh: the pair loader, the epilogue and the
+// finish kernel of a round, its driver (ml_round_plan, ml_round_finish) and the helpers of the entry points (MlTables).
 #include "multilinear.cuh"
 
 namespace lw {
@@ -109,24 +111,12 @@ __global__ __launch_bounds__(ML_THREADS) void ml_round_kernel(const MlRoundArgs<
     Fe<F> acc[K + 1];
 #pragma unroll
     for (int t = 0; t <= K; t++) acc[t] = Fe<F>::zero();
-    const uint64_t q = a.q, h = 2 * q, step = (uint64_t)gridDim.x * ML_THREADS;
+    const uint64_t q = a.q, step = (uint64_t)gridDim.x * ML_THREADS;
 #pragma unroll 1
     for (uint64_t j = (uint64_t)blockIdx.x * ML_THREADS + threadIdx.x; j < q; j += step) {
         Fe<F> v[K], d[K];
 #pragma unroll
-        for (int k = 0; k < K; k++) {
-            char *p = a.tab[k] + j * 32;
-            Fe<F> lo = fe_load<F>(p), hi = fe_load<F>(p + q * 32);
-            if (FUSED) {   // bind the leading variable: x + r (y - x), the halves are h apart
-                const Fe<F> lo1 = fe_load<F>(p + h * 32), hi1 = fe_load<F>(p + (h + q) * 32);
-                lo = fe_add<F>(lo, fe_mul<F>(a.r, fe_sub<F>(lo1, lo)));
-                hi = fe_add<F>(hi, fe_mul<F>(a.r, fe_sub<F>(hi1, hi)));
-                fe_store<F>(p, lo);
-                fe_store<F>(p + q * 32, hi);
-            }
-            v[k] = lo;
-            d[k] = fe_sub<F>(hi, lo);
-        }
+        for (int k = 0; k < K; k++) ml_load_pair<F, FUSED>(a.tab[k] + j * 32, q, FUSED ? &a.r : nullptr, v[k], d[k]);
 #pragma unroll
         for (int t = 0; t <= K; t++) {
             Fe<F> prod = v[0];
@@ -140,10 +130,7 @@ __global__ __launch_bounds__(ML_THREADS) void ml_round_kernel(const MlRoundArgs<
         }
     }
 #pragma unroll
-    for (int t = 0; t <= K; t++) {
-        const Fe<F> s = ml_block_sum<F>(acc[t], lds);
-        if (threadIdx.x == 0) fe_store<F>(a.partials + ((uint64_t)t * gridDim.x + blockIdx.x) * 32, s);
-    }
+    for (int t = 0; t <= K; t++) ml_store_partial<F>(acc[t], lds, a.partials, t);
 }
 
 // ---- host side ----
@@ -247,25 +234,19 @@ static void ml_round_launch(Context &c, const MlRoundArgs<F> &a, bool fused, uin
 // the round polynomial's K + 1 values -> out_host; with r_prev the tables are first bound in place.  Synchronises.
 template <class F>
 static int ml_round_locked(Context &c, void *const *tabs, uint32_t k, uint32_t n, const void *r_prev, void *out_host, hipStream_t s) {
+    MlRoundPlan plan;
+    int rc = ml_round_plan(c, n, r_prev, k + 1, plan);
+    if (rc) return rc;
     MlRoundArgs<F> a;
     memset(&a, 0, sizeof(a));
     for (uint32_t i = 0; i < k; i++) a.tab[i] = (char *)tabs[i];
-    a.q = (uint64_t)1 << (n - (r_prev ? 2 : 1));
+    a.partials = plan.partials;
+    a.q = plan.q;
     if (r_prev) a.r = ml_load<F>(r_prev);
-    const uint64_t want = (a.q + ML_THREADS - 1) / ML_THREADS;
-    const uint32_t blocks = want < ML_ROUND_BLOCKS ? (uint32_t)want : ML_ROUND_BLOCKS;
-    // workspace: [values | partials]
-    if (c.poly_ws.ensure(256 + (size_t)(k + 1) * blocks * 32)) return LW_ERR_ALLOC;
-    char *vals = (char *)c.poly_ws.p;
-    a.partials = vals + 256;
-    if (k == 1) ml_round_launch<F, 1>(c, a, r_prev != nullptr, blocks, s);
-    else if (k == 2) ml_round_launch<F, 2>(c, a, r_prev != nullptr, blocks, s);
-    else ml_round_launch<F, 3>(c, a, r_prev != nullptr, blocks, s);
-    hipEvent_t pe = c.prof_begin(s);
-    hipLaunchKernelGGL((ml_sum_finish_kernel<F>), dim3(k + 1), dim3(ML_THREADS), 0, s, (const char *)a.partials, blocks, vals);
-    c.prof_end("ml_sum_finish_kernel", pe, s);
-    LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
-    return ml_result(c, vals, (size_t)(k + 1) * 32, out_host, s);
+    if (k == 1) ml_round_launch<F, 1>(c, a, r_prev != nullptr, plan.blocks, s);
+    else if (k == 2) ml_round_launch<F, 2>(c, a, r_prev != nullptr, plan.blocks, s);
+    else ml_round_launch<F, 3>(c, a, r_prev != nullptr, plan.blocks, s);
+    return ml_round_finish<F>(c, plan, k + 1, out_host, s);
 }
 
 }  // namespace lw
@@ -278,10 +259,10 @@ static int ml_evaluate_entry(lw_field_t field, const void *const *tabs, uint32_t
                              void *hip_stream, bool device) {
     if (!ml_field_ok(field)) return LW_ERR_BAD_ARG;
     if (k == 0) { set_error("no table"); return LW_ERR_BAD_ARG; }
-    if (n > ML_MAX_VARS) { set_error("%u variables: at most %u", n, ML_MAX_VARS); return LW_ERR_BAD_ARG; }
+    if (!ml_vars_ok(n)) return LW_ERR_BAD_ARG;
     if (!tabs || !out || (n && !point)) { set_error("null argument"); return LW_ERR_BAD_ARG; }
-    for (uint32_t i = 0; i < k; i++)
-        if (!tabs[i] || (device && !ml_aligned16(tabs[i]))) { set_error("table %u: null or misaligned buffer", i); return LW_ERR_BAD_ARG; }
+    MlTables t = {(void *const *)tabs, k, n, device};   // only read here, so two may be the same table
+    if (!t.ok(false)) return LW_ERR_BAD_ARG;
     if (n == 0 && !device) {   // a constant: no device needed
         for (uint32_t i = 0; i < k; i++) memcpy((char *)out + (size_t)i * 32, tabs[i], 32);
         return LW_OK;
@@ -295,16 +276,9 @@ static int ml_evaluate_entry(lw_field_t field, const void *const *tabs, uint32_t
         LW_HIP_CHECK(hipStreamSynchronize(s), LW_ERR_LAUNCH);
         return LW_OK;
     }
-    std::vector<void *> staged;
-    if (!device) {
-        s = en.use_lane_stream();
-        if (!s) return en.rc;
-        int rc = ml_stage(c, tabs, k, n, staged, s);
-        if (rc) return rc;
-        tabs = staged.data();
-    }
-    return field == LW_FIELD_STARK252 ? ml_evaluate_locked<Stark252>(c, tabs, k, n, point, out, s)
-                                      : ml_evaluate_locked<Fr381>(c, tabs, k, n, point, out, s);
+    int rc = t.stage(en, s);
+    if (rc) return rc;
+    return ml_with_field(field, [&](auto F) { return ml_evaluate_locked<decltype(F)>(c, t.on_device(), k, n, point, out, s); });
 }
 int lw_multilinear_evaluate(lw_field_t field, const void *const *tables, uint32_t k, uint32_t n_vars, const void *point, void *out) {
     return ml_evaluate_entry(field, tables, k, n_vars, point, out, nullptr, false);
@@ -317,7 +291,7 @@ int lw_multilinear_evaluate_device(lw_field_t field, const void *const *d_tables
 static int ml_fix_entry(lw_field_t field, const void *table, uint32_t n, const void *r, uint32_t t, void *out, void *hip_stream,
                         bool device) {
     if (!ml_field_ok(field)) return LW_ERR_BAD_ARG;
-    if (n > ML_MAX_VARS) { set_error("%u variables: at most %u", n, ML_MAX_VARS); return LW_ERR_BAD_ARG; }
+    if (!ml_vars_ok(n)) return LW_ERR_BAD_ARG;
     if (t > n) { set_error("%u variables to bind of %u", t, n); return LW_ERR_BAD_ARG; }
     if (!table || !out || (t && !r)) { set_error("null argument"); return LW_ERR_BAD_ARG; }
     const size_t in_b = (size_t)32 << n, out_b = (size_t)32 << (n - t);
@@ -334,24 +308,19 @@ static int ml_fix_entry(lw_field_t field, const void *table, uint32_t n, const v
     if (!device) {
         s = en.use_lane_stream();
         if (!s) return en.rc;
-        std::vector<void *> staged;
-        int rc = ml_stage(c, &table, 1, n, staged, s);
+        int rc = ml_upload(c.host_io_a, table, in_b, s);
         if (rc) return rc;
-        d_table = staged[0];
+        d_table = c.host_io_a.p;
         if (c.host_io_b.ensure(out_b)) return LW_ERR_ALLOC;
         d_out = c.host_io_b.p;
     }
     if (t == 0) {
         if (d_out != d_table) LW_HIP_CHECK(hipMemcpyAsync(d_out, d_table, in_b, hipMemcpyDeviceToDevice, s), LW_ERR_LAUNCH);
     } else {
-        int rc = field == LW_FIELD_STARK252 ? ml_fix_locked<Stark252>(c, d_table, n, r, t, d_out, s)
-                                            : ml_fix_locked<Fr381>(c, d_table, n, r, t, d_out, s);
+        int rc = ml_with_field(field, [&](auto F) { return ml_fix_locked<decltype(F)>(c, d_table, n, r, t, d_out, s); });
         if (rc) return rc;
     }
-    if (device) return LW_OK;
-    LW_HIP_CHECK(hipMemcpyAsync(out, d_out, out_b, hipMemcpyDeviceToHost, s), LW_ERR_LAUNCH);
-    LW_HIP_CHECK(hipStreamSynchronize(s), LW_ERR_LAUNCH);
-    return LW_OK;
+    return device ? LW_OK : ml_download(out, d_out, out_b, s);
 }
 int lw_multilinear_fix_variables(lw_field_t field, const void *table, uint32_t n_vars, const void *r, uint32_t t, void *out) {
     return ml_fix_entry(field, table, n_vars, r, t, out, nullptr, false);
@@ -365,35 +334,17 @@ static int ml_round_entry(lw_field_t field, void *const *tabs, uint32_t k, uint3
                           bool device) {
     if (!ml_field_ok(field)) return LW_ERR_BAD_ARG;
     if (k == 0 || k > 3) { set_error("%u tables: a round takes 1, 2 or 3", k); return LW_ERR_BAD_ARG; }
-    if (n > ML_MAX_VARS) { set_error("%u variables: at most %u", n, ML_MAX_VARS); return LW_ERR_BAD_ARG; }
-    if (n < (r_prev ? 2u : 1u)) { set_error("%u variables: a round needs 1, a fused round 2", n); return LW_ERR_BAD_ARG; }
+    if (!ml_vars_ok(n) || !ml_round_vars_ok(n, r_prev)) return LW_ERR_BAD_ARG;
     if (!tabs || !out) { set_error("null argument"); return LW_ERR_BAD_ARG; }
-    const size_t bytes = (size_t)32 << n;
-    for (uint32_t i = 0; i < k; i++) {
-        if (!tabs[i] || (device && !ml_aligned16(tabs[i]))) { set_error("table %u: null or misaligned buffer", i); return LW_ERR_BAD_ARG; }
-        for (uint32_t j = 0; j < i; j++)
-            if (ml_overlap(tabs[i], bytes, tabs[j], bytes)) { set_error("tables %u and %u overlap", j, i); return LW_ERR_BAD_ARG; }
-    }
+    MlTables t = {tabs, k, n, device};
+    if (!t.ok(true)) return LW_ERR_BAD_ARG;
     Entry en(hip_stream);
     if (en.rc) return en.rc;
-    Context &c = en.c;
     hipStream_t s = en.stream;
-    std::vector<void *> staged;
-    void *const *d_tabs = tabs;
-    if (!device) {
-        s = en.use_lane_stream();
-        if (!s) return en.rc;
-        int rc = ml_stage(c, tabs, k, n, staged, s);
-        if (rc) return rc;
-        d_tabs = staged.data();
-    }
-    int rc = field == LW_FIELD_STARK252 ? ml_round_locked<Stark252>(c, d_tabs, k, n, r_prev, out, s)
-                                        : ml_round_locked<Fr381>(c, d_tabs, k, n, r_prev, out, s);
-    if (rc || device || !r_prev) return rc;
-    for (uint32_t i = 0; i < k; i++)   // the bound tables go back to the caller's first halves
-        LW_HIP_CHECK(hipMemcpyAsync(tabs[i], d_tabs[i], bytes / 2, hipMemcpyDeviceToHost, s), LW_ERR_LAUNCH);
-    LW_HIP_CHECK(hipStreamSynchronize(s), LW_ERR_LAUNCH);
-    return LW_OK;
+    int rc = t.stage(en, s);
+    if (rc) return rc;
+    rc = ml_with_field(field, [&](auto F) { return ml_round_locked<decltype(F)>(en.c, t.on_device(), k, n, r_prev, out, s); });
+    return rc || device || !r_prev ? rc : t.return_bound(s);
 }
 int lw_sumcheck_round(lw_field_t field, void *const *tables, uint32_t k, uint32_t n_vars, const void *r_prev_or_null, void *out_round) {
     return ml_round_entry(field, tables, k, n_vars, r_prev_or_null, out_round, nullptr, false);

@@ -511,16 +511,13 @@ static int matvec_entry(const lw_r1cs_t *h, const void *z, size_t n_out, void *a
     }
     hipStream_t s = en.use_lane_stream();
     if (!s) return en.rc;
-    if (c.host_io_a.ensure(zb) || c.host_io_b.ensure(3 * ob)) return LW_ERR_ALLOC;
-    LW_HIP_CHECK(hipMemcpyAsync(c.host_io_a.p, z, zb, hipMemcpyHostToDevice, s), LW_ERR_LAUNCH);
+    if (c.host_io_b.ensure(3 * ob)) return LW_ERR_ALLOC;   // both buffers before any copy from caller memory
+    int rc = ml_upload(c.host_io_a, z, zb, s);
+    if (rc) return rc;
     char *o = (char *)c.host_io_b.p;
     void *const d[3] = {az ? o : nullptr, bz ? o + ob : nullptr, cz ? o + 2 * ob : nullptr};
-    int rc = r1cs_matvec_locked(c, h, c.host_io_a.p, n_out, d, s);
-    if (rc) return rc;
-    for (int m = 0; m < 3; m++)
-        if (outs[m]) LW_HIP_CHECK(hipMemcpyAsync(outs[m], d[m], ob, hipMemcpyDeviceToHost, s), LW_ERR_LAUNCH);
-    LW_HIP_CHECK(hipStreamSynchronize(s), LW_ERR_LAUNCH);
-    return LW_OK;
+    rc = r1cs_matvec_locked(c, h, c.host_io_a.p, n_out, d, s);
+    return rc ? rc : ml_download_each(outs, d, 3, ob, s);
 }
 int lw_r1cs_matvec(const lw_r1cs_t *r1cs, const void *z, size_t n_out, void *out_az_or_null, void *out_bz_or_null, void *out_cz_or_null) {
     return matvec_entry(r1cs, z, n_out, out_az_or_null, out_bz_or_null, out_cz_or_null, nullptr, false);
@@ -542,13 +539,11 @@ static int bind_entry(const lw_r1cs_t *h, const void *e, const void *coeffs3, si
     if (device) return r1cs_bind_locked(c, h, e, coeffs3, n_out, out, en.stream);
     hipStream_t s = en.use_lane_stream();
     if (!s) return en.rc;
-    if (c.host_io_a.ensure(eb) || c.host_io_b.ensure(ob)) return LW_ERR_ALLOC;
-    LW_HIP_CHECK(hipMemcpyAsync(c.host_io_a.p, e, eb, hipMemcpyHostToDevice, s), LW_ERR_LAUNCH);
-    int rc = r1cs_bind_locked(c, h, c.host_io_a.p, coeffs3, n_out, c.host_io_b.p, s);
+    if (c.host_io_b.ensure(ob)) return LW_ERR_ALLOC;   // both buffers before any copy from caller memory
+    int rc = ml_upload(c.host_io_a, e, eb, s);
     if (rc) return rc;
-    LW_HIP_CHECK(hipMemcpyAsync(out, c.host_io_b.p, ob, hipMemcpyDeviceToHost, s), LW_ERR_LAUNCH);
-    LW_HIP_CHECK(hipStreamSynchronize(s), LW_ERR_LAUNCH);
-    return LW_OK;
+    rc = r1cs_bind_locked(c, h, c.host_io_a.p, coeffs3, n_out, c.host_io_b.p, s);
+    return rc ? rc : ml_download(out, c.host_io_b.p, ob, s);
 }
 int lw_r1cs_bind_rows(const lw_r1cs_t *r1cs, const void *e, const void *coeffs3, size_t n_out, void *out) {
     return bind_entry(r1cs, e, coeffs3, n_out, out, nullptr, false);
@@ -566,10 +561,8 @@ static int check_entry(const lw_r1cs_t *h, const void *z, int64_t *out_row, void
     if (device) return r1cs_check_locked(c, h, z, out_row, en.stream);
     hipStream_t s = en.use_lane_stream();
     if (!s) return en.rc;
-    const size_t zb = (size_t)h->n_cols * 32;
-    if (c.host_io_a.ensure(zb)) return LW_ERR_ALLOC;
-    LW_HIP_CHECK(hipMemcpyAsync(c.host_io_a.p, z, zb, hipMemcpyHostToDevice, s), LW_ERR_LAUNCH);
-    return r1cs_check_locked(c, h, c.host_io_a.p, out_row, s);
+    int rc = ml_upload(c.host_io_a, z, (size_t)h->n_cols * 32, s);
+    return rc ? rc : r1cs_check_locked(c, h, c.host_io_a.p, out_row, s);
 }
 int lw_r1cs_first_unsatisfied(const lw_r1cs_t *r1cs, const void *z, int64_t *out_row) {
     return check_entry(r1cs, z, out_row, nullptr, false);

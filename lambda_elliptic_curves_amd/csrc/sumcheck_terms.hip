@@ -9,13 +9,14 @@
 //              variable is the single element one, so n = 0 and n = 1 take the same path.
 //   round      g(u) = sum_{j<h} E_j(u) * sum_t c_t * prod_{m in mask_t} T_m,j(u), u = 0 .. D, X_j(u) = X[j] + u (X[j+h] - X[j]),
 //              h = 2^(n-1), D = max_t popcount(mask_t) + (eq ? 1 : 0)  (ml_terms_round_kernel<F, M, HAS_EQ, FUSED>).
-//              The M tables and the eq table of a pair are loaded once into v[m], d[m] = hi - lo exactly as ml_round_kernel
-//              loads them, the fused bind of four indices per table included; u walks by adding d[m].  The terms are a
-//              runtime loop over wave-uniform masks in the kernel's argument, the tables of a term an unrolled loop behind a
-//              uniform test of the mask's bit, so that no register array is indexed by a runtime value.  Per u the bracket
-//              sum_t c_t prod is formed first and E multiplies it once.  A coefficient one costs no product and minus one is
-//              a subtraction: the host compares the coefficients with both and passes a kind per term.  The accumulators are
-//              per u.  Blocks reduce with ml_block_sum, ml_sum_finish_kernel adds up their partials (multilinear.cuh).
+//              The M tables and the eq table of a pair are loaded once into v[m], d[m] = hi - lo by ml_load_pair
+//              (multilinear.cuh), the loader of ml_round_kernel, which also does the fused bind of four indices per table; u
+//              walks by adding d[m].  The terms are a runtime loop over wave-uniform masks in the kernel's argument, the tables
+//              of a term an unrolled loop behind a uniform test of the mask's bit, so that no register array is indexed by a
+//              runtime value.  Per u the bracket sum_t c_t prod is formed first and E multiplies it once.  A coefficient one
+//              costs no product and minus one is a subtraction: the host compares the coefficients with both and passes a
+//              kind per term.  The accumulators are per u.  Blocks reduce and store with ml_store_partial, and the round is
+//              planned and finished by the driver of the product round (ml_round_plan, ml_round_finish).
 // Every stored value is a canonical residue, so neither the order of the products nor that of the sums shows in a result.
 #include "multilinear.cuh"
 
@@ -114,25 +115,13 @@ __global__ __launch_bounds__(ML_THREADS) void ml_terms_round_kernel(const MlTerm
     Fe<F> acc[DMAX + 1];
 #pragma unroll
     for (int u = 0; u <= DMAX; u++) acc[u] = Fe<F>::zero();
-    const uint64_t q = a.q, h = 2 * q, step = (uint64_t)gridDim.x * ML_THREADS;
+    const uint64_t q = a.q, step = (uint64_t)gridDim.x * ML_THREADS;
     const uint32_t n_terms = a.n_terms, deg = a.deg;
 #pragma unroll 1
     for (uint64_t j = (uint64_t)blockIdx.x * ML_THREADS + threadIdx.x; j < q; j += step) {
         Fe<F> v[MT], d[MT];
 #pragma unroll
-        for (int k = 0; k < MT; k++) {
-            char *p = a.tab[k < M ? k : (int)MLT_MAX_TABLES] + j * 32;
-            Fe<F> lo = fe_load<F>(p), hi = fe_load<F>(p + q * 32);
-            if (FUSED) {   // bind the leading variable: x + r (y - x), the halves are h apart
-                const Fe<F> lo1 = fe_load<F>(p + h * 32), hi1 = fe_load<F>(p + (h + q) * 32);
-                lo = fe_add<F>(lo, fe_mul<F>(a.r, fe_sub<F>(lo1, lo)));
-                hi = fe_add<F>(hi, fe_mul<F>(a.r, fe_sub<F>(hi1, hi)));
-                fe_store<F>(p, lo);
-                fe_store<F>(p + q * 32, hi);
-            }
-            v[k] = lo;
-            d[k] = fe_sub<F>(hi, lo);
-        }
+        for (int k = 0; k < MT; k++) ml_load_pair<F, FUSED>(a.tab[k < M ? k : (int)MLT_MAX_TABLES] + j * 32, q, FUSED ? &a.r : nullptr, v[k], d[k]);
         // u = 0 .. DMAX written out: the loop's own unrolling is not left to the optimiser, since acc[] indexed by a loop
         // counter would go to scratch.  D >= 1 always.
         mlt_point<F, M, HAS_EQ, false>(a, n_terms, v, d, acc[0]);
@@ -149,10 +138,7 @@ __global__ __launch_bounds__(ML_THREADS) void ml_terms_round_kernel(const MlTerm
     }
 #pragma unroll
     for (int u = 0; u <= DMAX; u++) {
-        if ((uint32_t)u <= deg) {   // uniform: every thread of the block reaches the barriers or none does
-            const Fe<F> s = ml_block_sum<F>(acc[u], lds);
-            if (threadIdx.x == 0) fe_store<F>(a.partials + ((uint64_t)u * gridDim.x + blockIdx.x) * 32, s);
-        }
+        if ((uint32_t)u <= deg) ml_store_partial<F>(acc[u], lds, a.partials, u);   // uniform: every thread reaches the barriers or none does
     }
 }
 
@@ -206,11 +192,15 @@ static void mlt_launch_m(Context &c, const MlTermsArgs<F> &a, uint32_t m, bool f
 // the round polynomial's deg + 1 values -> out_host; with r_prev the tables are first bound in place.  Synchronises.
 template <class F>
 static int mlt_round_locked(Context &c, void *const *tabs, void *eq, const MltCall &call, void *out_host, hipStream_t s) {
+    MlRoundPlan plan;
+    int rc = ml_round_plan(c, call.n, call.r_prev, call.deg + 1, plan);
+    if (rc) return rc;
     MlTermsArgs<F> a;
     memset(&a, 0, sizeof(a));
     for (uint32_t i = 0; i < call.n_tables; i++) a.tab[i] = (char *)tabs[i];
     a.tab[MLT_MAX_TABLES] = (char *)eq;
-    a.q = (uint64_t)1 << (call.n - (call.r_prev ? 2 : 1));
+    a.partials = plan.partials;
+    a.q = plan.q;
     if (call.r_prev) a.r = ml_load<F>(call.r_prev);
     a.n_terms = call.n_terms;
     a.deg = call.deg;
@@ -220,19 +210,9 @@ static int mlt_round_locked(Context &c, void *const *tabs, void *eq, const MltCa
         a.coeff[t] = call.coeffs ? ml_load<F>((const char *)call.coeffs + (size_t)t * 32) : one;
         a.kind[t] = a.coeff[t] == one ? MLT_COEFF_ONE : a.coeff[t] == minus_one ? MLT_COEFF_MINUS_ONE : MLT_COEFF_GENERAL;
     }
-    const uint64_t want = (a.q + ML_THREADS - 1) / ML_THREADS;
-    const uint32_t blocks = want < ML_ROUND_BLOCKS ? (uint32_t)want : ML_ROUND_BLOCKS;
-    // workspace: [values | partials]
-    if (c.poly_ws.ensure(256 + (size_t)(call.deg + 1) * blocks * 32)) return LW_ERR_ALLOC;
-    char *vals = (char *)c.poly_ws.p;
-    a.partials = vals + 256;
-    if (eq) mlt_launch_m<F, true>(c, a, call.n_tables, call.r_prev != nullptr, blocks, s);
-    else mlt_launch_m<F, false>(c, a, call.n_tables, call.r_prev != nullptr, blocks, s);
-    hipEvent_t pe = c.prof_begin(s);
-    hipLaunchKernelGGL((ml_sum_finish_kernel<F>), dim3(call.deg + 1), dim3(ML_THREADS), 0, s, (const char *)a.partials, blocks, vals);
-    c.prof_end("ml_sum_finish_kernel", pe, s);
-    LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
-    return ml_result(c, vals, (size_t)(call.deg + 1) * 32, out_host, s);
+    if (eq) mlt_launch_m<F, true>(c, a, call.n_tables, call.r_prev != nullptr, plan.blocks, s);
+    else mlt_launch_m<F, false>(c, a, call.n_tables, call.r_prev != nullptr, plan.blocks, s);
+    return ml_round_finish<F>(c, plan, call.deg + 1, out_host, s);
 }
 
 }  // namespace lw
@@ -243,13 +223,12 @@ extern "C" {
 
 static int mlt_eq_entry(lw_field_t field, const void *point, uint32_t n, void *out, void *hip_stream, bool device) {
     if (!ml_field_ok(field)) return LW_ERR_BAD_ARG;
-    if (n > ML_MAX_VARS) { set_error("%u variables: at most %u", n, ML_MAX_VARS); return LW_ERR_BAD_ARG; }
+    if (!ml_vars_ok(n)) return LW_ERR_BAD_ARG;
     if (!out || (n && !point)) { set_error("null argument"); return LW_ERR_BAD_ARG; }
     if (device && !ml_aligned16(out)) { set_error("device buffers must be 16-byte aligned"); return LW_ERR_BAD_ARG; }
     if (n == 0 && !device) {   // the element one: no device needed
         alignas(16) uint64_t w[4];
-        if (field == LW_FIELD_STARK252) fe_store<Stark252>(w, Fe<Stark252>::one());
-        else fe_store<Fr381>(w, Fe<Fr381>::one());
+        ml_with_field(field, [&](auto F) { fe_store<decltype(F)>(w, Fe<decltype(F)>::one()); });
         memcpy(out, w, 32);
         return LW_OK;
     }
@@ -265,11 +244,8 @@ static int mlt_eq_entry(lw_field_t field, const void *point, uint32_t n, void *o
         if (c.host_io_a.ensure(bytes)) return LW_ERR_ALLOC;
         d_out = c.host_io_a.p;
     }
-    int rc = field == LW_FIELD_STARK252 ? mlt_eq_locked<Stark252>(c, point, n, d_out, s) : mlt_eq_locked<Fr381>(c, point, n, d_out, s);
-    if (rc || device) return rc;
-    LW_HIP_CHECK(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, s), LW_ERR_LAUNCH);
-    LW_HIP_CHECK(hipStreamSynchronize(s), LW_ERR_LAUNCH);
-    return LW_OK;
+    int rc = ml_with_field(field, [&](auto F) { return mlt_eq_locked<decltype(F)>(c, point, n, d_out, s); });
+    return rc || device ? rc : ml_download(out, d_out, bytes, s);
 }
 int lw_multilinear_eq_table(lw_field_t field, const void *point, uint32_t n_vars, void *out) {
     return mlt_eq_entry(field, point, n_vars, out, nullptr, false);
@@ -283,8 +259,7 @@ static int mlt_round_entry(lw_field_t field, void *const *tabs, uint32_t n_table
     if (!ml_field_ok(field)) return LW_ERR_BAD_ARG;
     if (n_tables == 0 || n_tables > MLT_MAX_TABLES) { set_error("%u tables: a composed round takes 1 to %u", n_tables, MLT_MAX_TABLES); return LW_ERR_BAD_ARG; }
     if (n_terms == 0 || n_terms > MLT_MAX_TERMS) { set_error("%u terms: a composed round takes 1 to %u", n_terms, MLT_MAX_TERMS); return LW_ERR_BAD_ARG; }
-    if (n > ML_MAX_VARS) { set_error("%u variables: at most %u", n, ML_MAX_VARS); return LW_ERR_BAD_ARG; }
-    if (n < (r_prev ? 2u : 1u)) { set_error("%u variables: a round needs 1, a fused round 2", n); return LW_ERR_BAD_ARG; }
+    if (!ml_vars_ok(n) || !ml_round_vars_ok(n, r_prev)) return LW_ERR_BAD_ARG;
     if (!tabs || !masks || !out) { set_error("null argument"); return LW_ERR_BAD_ARG; }
     uint32_t deg = 0;
     for (uint32_t t = 0; t < n_terms; t++) {
@@ -296,38 +271,22 @@ static int mlt_round_entry(lw_field_t field, void *const *tabs, uint32_t n_table
         if (bits > deg) deg = bits;
     }
     if (eq) deg++;
-    const size_t bytes = (size_t)32 << n;
-    void *all[MLT_MAX_TABLES + 1];
+    void *all[MLT_MAX_TABLES + 1];   // the tables, then the eq table: the indices that the messages name
     uint32_t n_all = 0;
     for (uint32_t i = 0; i < n_tables; i++) all[n_all++] = tabs[i];
     if (eq) all[n_all++] = eq;
-    for (uint32_t i = 0; i < n_all; i++) {
-        if (!all[i] || (device && !ml_aligned16(all[i]))) { set_error("table %u: null or misaligned buffer", i); return LW_ERR_BAD_ARG; }
-        for (uint32_t j = 0; j < i; j++)
-            if (ml_overlap(all[i], bytes, all[j], bytes)) { set_error("tables %u and %u overlap", j, i); return LW_ERR_BAD_ARG; }
-    }
+    MlTables t = {all, n_all, n, device};
+    if (!t.ok(true)) return LW_ERR_BAD_ARG;
     Entry en(hip_stream);
     if (en.rc) return en.rc;
-    Context &c = en.c;
     hipStream_t s = en.stream;
-    std::vector<void *> staged;
-    void *const *d_all = all;
-    if (!device) {
-        s = en.use_lane_stream();
-        if (!s) return en.rc;
-        int rc = ml_stage(c, all, n_all, n, staged, s);
-        if (rc) return rc;
-        d_all = staged.data();
-    }
+    int rc = t.stage(en, s);
+    if (rc) return rc;
     const MltCall call = {n_tables, n_terms, n, deg, masks, coeffs, r_prev};
+    void *const *d_all = t.on_device();
     void *d_eq = eq ? d_all[n_tables] : nullptr;
-    int rc = field == LW_FIELD_STARK252 ? mlt_round_locked<Stark252>(c, d_all, d_eq, call, out, s)
-                                        : mlt_round_locked<Fr381>(c, d_all, d_eq, call, out, s);
-    if (rc || device || !r_prev) return rc;
-    for (uint32_t i = 0; i < n_all; i++)   // the bound tables go back to the caller's first halves
-        LW_HIP_CHECK(hipMemcpyAsync(all[i], d_all[i], bytes / 2, hipMemcpyDeviceToHost, s), LW_ERR_LAUNCH);
-    LW_HIP_CHECK(hipStreamSynchronize(s), LW_ERR_LAUNCH);
-    return LW_OK;
+    rc = ml_with_field(field, [&](auto F) { return mlt_round_locked<decltype(F)>(en.c, d_all, d_eq, call, out, s); });
+    return rc || device || !r_prev ? rc : t.return_bound(s);
 }
 int lw_sumcheck_terms_round(lw_field_t field, void *const *tables, uint32_t n_tables, void *eq_or_null, const uint32_t *term_masks,
                             const void *term_coeffs_or_null, uint32_t n_terms, uint32_t n_vars, const void *r_prev_or_null, void *out_round) {

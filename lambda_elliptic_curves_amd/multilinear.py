@@ -19,23 +19,25 @@ def _elems(a):
     return np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
 
 
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 def _opt(r):
     """one optional host element -> (array kept alive, pointer or None)"""
     if r is None:
         return None, None
     a = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1)[:4].copy()
-    return a, _vp(a)
+    return a, L.host_ptr(a)
 
 
-def _stream(stream):
-    if stream is None:
-        import torch
-        stream = torch.cuda.current_stream().cuda_stream
-    return C.c_void_p(stream)
+def _ptrs(addresses):
+    """the pointer array of a call's tables (one slot even for none: the library reports the count itself)"""
+    return (C.c_void_p * max(1, len(addresses)))(*addresses)
+
+
+def _bound_in_place(r_prev, arrays):
+    """a fused host round writes the bound tables into the caller's arrays, so they must be what the library is given"""
+    ok = lambda u: isinstance(u, np.ndarray) and u.dtype == np.uint64 and u.flags.c_contiguous and u.flags.writeable
+    if r_prev is not None and not all(ok(u) for u in arrays):
+        from .errors import InputError
+        raise InputError("a fused round binds in place: pass C-contiguous uint64 arrays")
 
 
 def _n_vars(table):
@@ -60,8 +62,7 @@ def evaluate(field, tables, point):
     n = _n_vars(ts[0]) if ts else 0
     p = _point(point, n)
     out = np.zeros((len(ts), 4), np.uint64)
-    ptrs = (C.c_void_p * max(1, len(ts)))(*[t.ctypes.data for t in ts])
-    check(L.lib().lw_multilinear_evaluate(field.field, ptrs, len(ts), n, _vp(p), _vp(out)))
+    check(L.lib().lw_multilinear_evaluate(field.field, _ptrs([t.ctypes.data for t in ts]), len(ts), n, L.host_ptr(p), L.host_ptr(out)))
     return out
 
 
@@ -69,8 +70,8 @@ def evaluate_device(field, t_tables, n_vars, point, stream=None):
     """evaluate() on device-resident torch tensors of at least 2^n_vars elements each."""
     p = _point(point, n_vars)
     out = np.zeros((len(t_tables), 4), np.uint64)
-    ptrs = (C.c_void_p * max(1, len(t_tables)))(*[t.data_ptr() for t in t_tables])
-    check(L.lib().lw_multilinear_evaluate_device(field.field, ptrs, len(t_tables), n_vars, _vp(p), _vp(out), _stream(stream)))
+    check(L.lib().lw_multilinear_evaluate_device(field.field, _ptrs([t.data_ptr() for t in t_tables]), len(t_tables), n_vars, L.host_ptr(p),
+                                                 L.host_ptr(out), L.stream_ptr(stream)))
     return out
 
 
@@ -81,7 +82,7 @@ def fix_variables(field, table, r):
     rr = _elems(r) if len(r) else np.zeros((0, 4), np.uint64)
     t = rr.shape[0]
     out = np.zeros((1 << max(0, n - t), 4), np.uint64)
-    check(L.lib().lw_multilinear_fix_variables(field.field, _vp(a), n, _vp(rr) if t else None, t, _vp(out)))
+    check(L.lib().lw_multilinear_fix_variables(field.field, L.host_ptr(a), n, L.host_ptr(rr), t, L.host_ptr(out)))
     return out
 
 
@@ -89,9 +90,8 @@ def fix_variables_device(field, t_table, n_vars, r, t_out, stream=None):
     """fix_variables() of a device-resident tensor into t_out (2^(n_vars - len(r)) elements, not overlapping t_table);
     nothing is waited for.  -> t_out"""
     rr = _elems(r) if len(r) else np.zeros((0, 4), np.uint64)
-    t = rr.shape[0]
-    check(L.lib().lw_multilinear_fix_variables_device(field.field, C.c_void_p(t_table.data_ptr()), n_vars, _vp(rr) if t else None, t,
-                                                      C.c_void_p(t_out.data_ptr()), _stream(stream)))
+    check(L.lib().lw_multilinear_fix_variables_device(field.field, L.device_ptr(t_table), n_vars, L.host_ptr(rr), rr.shape[0],
+                                                      L.device_ptr(t_out), L.stream_ptr(stream)))
     return t_out
 
 
@@ -100,15 +100,11 @@ def sumcheck_round(field, tables, r_prev=None):
     must then be writable (2^n, 4) uint64 arrays) are first bound to it in place - their first halves hold the bound
     tables afterwards - and the round runs over the n - 1 remaining variables."""
     ts = [_elems(t) for t in tables]
-    inplace = lambda u: isinstance(u, np.ndarray) and u.dtype == np.uint64 and u.flags.c_contiguous and u.flags.writeable
-    if r_prev is not None and not all(inplace(u) for u in tables):
-        from .errors import InputError
-        raise InputError("a fused round binds in place: pass C-contiguous uint64 arrays")
+    _bound_in_place(r_prev, tables)
     n = _n_vars(ts[0]) if ts else 0
     out = np.zeros((len(ts) + 1, 4), np.uint64)
     keep, rp = _opt(r_prev)
-    ptrs = (C.c_void_p * max(1, len(ts)))(*[t.ctypes.data for t in ts])
-    check(L.lib().lw_sumcheck_round(field.field, ptrs, len(ts), n, rp, _vp(out)))
+    check(L.lib().lw_sumcheck_round(field.field, _ptrs([t.ctypes.data for t in ts]), len(ts), n, rp, L.host_ptr(out)))
     return out
 
 
@@ -116,8 +112,8 @@ def sumcheck_round_device(field, t_tables, n_vars, r_prev=None, stream=None):
     """sumcheck_round() on device-resident torch tensors; with r_prev they are bound in place."""
     out = np.zeros((len(t_tables) + 1, 4), np.uint64)
     keep, rp = _opt(r_prev)
-    ptrs = (C.c_void_p * max(1, len(t_tables)))(*[t.data_ptr() for t in t_tables])
-    check(L.lib().lw_sumcheck_round_device(field.field, ptrs, len(t_tables), n_vars, rp, _vp(out), _stream(stream)))
+    check(L.lib().lw_sumcheck_round_device(field.field, _ptrs([t.data_ptr() for t in t_tables]), len(t_tables), n_vars, rp, L.host_ptr(out),
+                                           L.stream_ptr(stream)))
     return out
 
 
@@ -128,23 +124,21 @@ def _add(field, a, b):
     return np.frombuffer(s.to_bytes(32, "big"), dtype=">u8").astype(np.uint64)
 
 
-def sumcheck_prove_device(field, t_tables, n_vars, challenge, stream=None):
-    """The prover's side of a sumcheck of prod_k t_tables[k] over the cube of n_vars >= 1 variables, the tables resident
-    on the device and consumed in place.  challenge: a callable from a round's (K + 1, 4) array to the next r (4 uint64),
-    the seam for the caller's transcript.  One plain round, n_vars - 1 fused rounds (bind the previous challenge, then
-    sum), and a final fix_variables of the last variable.
-    -> (claimed_sum (4,), rounds [n_vars arrays (K + 1, 4)], point (n_vars, 4), final_evals (K, 4))"""
+def _prove_device(field, round_fn, t_finish, n_vars, challenge, stream):
+    """The prover's loop: round_fn(n, r_prev) for one plain round and n_vars - 1 fused rounds (bind the previous challenge,
+    then sum), then fix_variables of the last variable of every tensor of t_finish.
+    -> (claimed_sum (4,), rounds, point (n_vars, 4), final_evals (len(t_finish), 4))"""
     import torch
     rounds, point = [], []
     r = None
     for i in range(n_vars):
-        g = sumcheck_round_device(field, t_tables, n_vars - max(0, i - 1), r, stream)
+        g = round_fn(n_vars - max(0, i - 1), r)
         rounds.append(g)
         r = np.ascontiguousarray(challenge(g), dtype=np.uint64).reshape(-1)[:4].copy()
         point.append(r)
     claimed = _add(field, rounds[0][0], rounds[0][1])
-    t_fin = torch.empty((len(t_tables), 4), dtype=torch.int64, device=t_tables[0].device)
-    for k, t in enumerate(t_tables):
+    t_fin = torch.empty((len(t_finish), 4), dtype=torch.int64, device=t_finish[0].device)
+    for k, t in enumerate(t_finish):
         fix_variables_device(field, t, 1, r.reshape(1, 4), t_fin[k], stream)
     if stream is None:
         torch.cuda.current_stream().synchronize()
@@ -152,6 +146,15 @@ def sumcheck_prove_device(field, t_tables, n_vars, challenge, stream=None):
         torch.cuda.synchronize()
     final = t_fin.cpu().numpy().view(np.uint64)
     return claimed, rounds, np.stack(point), final
+
+
+def sumcheck_prove_device(field, t_tables, n_vars, challenge, stream=None):
+    """The prover's side of a sumcheck of prod_k t_tables[k] over the cube of n_vars >= 1 variables, the tables resident
+    on the device and consumed in place.  challenge: a callable from a round's (K + 1, 4) array to the next r (4 uint64),
+    the seam for the caller's transcript.  One plain round, n_vars - 1 fused rounds (bind the previous challenge, then
+    sum), and a final fix_variables of the last variable.
+    -> (claimed_sum (4,), rounds [n_vars arrays (K + 1, 4)], point (n_vars, 4), final_evals (K, 4))"""
+    return _prove_device(field, lambda n, r: sumcheck_round_device(field, t_tables, n, r, stream), t_tables, n_vars, challenge, stream)
 
 
 # ---- the table of eq(point, .) and the round over an eq-weighted sum of products ----
@@ -165,7 +168,7 @@ def eq_table(field, point):
     n = len(point)
     p = _point(point, n)
     out = np.zeros((1 << n, 4), np.uint64)
-    check(L.lib().lw_multilinear_eq_table(field.field, _vp(p), n, _vp(out)))
+    check(L.lib().lw_multilinear_eq_table(field.field, L.host_ptr(p), n, L.host_ptr(out)))
     return out
 
 
@@ -180,7 +183,7 @@ def eq_table_device(field, point, t_out=None, stream=None):
     if t_out.numel() * t_out.element_size() < 32 << n or not t_out.is_contiguous():
         from .errors import LengthMismatch
         raise LengthMismatch(f"the output holds fewer than 2^{n} contiguous elements")
-    check(L.lib().lw_multilinear_eq_table_device(field.field, _vp(p), n, C.c_void_p(t_out.data_ptr()), _stream(stream)))
+    check(L.lib().lw_multilinear_eq_table_device(field.field, L.host_ptr(p), n, L.device_ptr(t_out), L.stream_ptr(stream)))
     return t_out
 
 
@@ -212,18 +215,15 @@ def sumcheck_terms_round(field, tables, terms, eq=None, r_prev=None):
     sumcheck_round."""
     every = list(tables) + ([eq] if eq is not None else [])
     ts = [_elems(t) for t in every]
-    inplace = lambda u: isinstance(u, np.ndarray) and u.dtype == np.uint64 and u.flags.c_contiguous and u.flags.writeable
-    if r_prev is not None and not all(inplace(u) for u in every):
-        from .errors import InputError
-        raise InputError("a fused round binds in place: pass C-contiguous uint64 arrays")
+    _bound_in_place(r_prev, every)
     n = _n_vars(ts[0]) if ts else 0
     masks, carr, deg = _terms(field, terms, eq is not None)
     out = np.zeros((deg + 1, 4), np.uint64)
     keep, rp = _opt(r_prev)
     k = len(tables)
-    ptrs = (C.c_void_p * max(1, k))(*[t.ctypes.data for t in ts[:k]])
-    check(L.lib().lw_sumcheck_terms_round(field.field, ptrs, k, _vp(ts[k]) if eq is not None else None, _vp(masks),
-                                          _vp(carr) if carr is not None else None, len(terms), n, rp, _vp(out)))
+    check(L.lib().lw_sumcheck_terms_round(field.field, _ptrs([t.ctypes.data for t in ts[:k]]), k,
+                                          C.c_void_p(ts[k].ctypes.data) if eq is not None else None,   # an eq given stays one, even empty
+                                          L.host_ptr(masks), L.host_ptr(carr), len(terms), n, rp, L.host_ptr(out)))
     return out
 
 
@@ -236,10 +236,9 @@ def sumcheck_terms_round_device(field, t_tables, terms, n_vars, t_eq=None, r_pre
             raise LengthMismatch(f"a table holds fewer than 2^{n_vars} elements")
     out = np.zeros((deg + 1, 4), np.uint64)
     keep, rp = _opt(r_prev)
-    ptrs = (C.c_void_p * max(1, len(t_tables)))(*[t.data_ptr() for t in t_tables])
-    check(L.lib().lw_sumcheck_terms_round_device(field.field, ptrs, len(t_tables), C.c_void_p(t_eq.data_ptr()) if t_eq is not None else None,
-                                                 _vp(masks), _vp(carr) if carr is not None else None, len(terms), n_vars, rp, _vp(out),
-                                                 _stream(stream)))
+    check(L.lib().lw_sumcheck_terms_round_device(field.field, _ptrs([t.data_ptr() for t in t_tables]), len(t_tables),
+                                                 L.device_ptr(t_eq) if t_eq is not None else None, L.host_ptr(masks), L.host_ptr(carr),
+                                                 len(terms), n_vars, rp, L.host_ptr(out), L.stream_ptr(stream)))
     return out
 
 
@@ -250,22 +249,6 @@ def sumcheck_terms_prove_device(field, t_tables, terms, n_vars, challenge, t_eq=
     plain round, n_vars - 1 fused rounds, and a final fix_variables of the last variable.
     -> (claimed_sum (4,), rounds [n_vars arrays (D + 1, 4)], point (n_vars, 4), final_evals (K, 4) or (K + 1, 4) with
     the eq table's value last)"""
-    import torch
-    rounds, point = [], []
-    r = None
-    for i in range(n_vars):
-        g = sumcheck_terms_round_device(field, t_tables, terms, n_vars - max(0, i - 1), t_eq, r, stream)
-        rounds.append(g)
-        r = np.ascontiguousarray(challenge(g), dtype=np.uint64).reshape(-1)[:4].copy()
-        point.append(r)
-    claimed = _add(field, rounds[0][0], rounds[0][1])
     every = list(t_tables) + ([t_eq] if t_eq is not None else [])
-    t_fin = torch.empty((len(every), 4), dtype=torch.int64, device=every[0].device)
-    for k, t in enumerate(every):
-        fix_variables_device(field, t, 1, r.reshape(1, 4), t_fin[k], stream)
-    if stream is None:
-        torch.cuda.current_stream().synchronize()
-    else:
-        torch.cuda.synchronize()
-    final = t_fin.cpu().numpy().view(np.uint64)
-    return claimed, rounds, np.stack(point), final
+    return _prove_device(field, lambda n, r: sumcheck_terms_round_device(field, t_tables, terms, n, t_eq, r, stream), every, n_vars,
+                         challenge, stream)

@@ -8,7 +8,8 @@ import numpy as np
 
 from . import _lib as L
 from .errors import check
-from .multilinear import MODULI, _elems, _stream, _vp
+from ._lib import device_ptr, host_ptr, stream_ptr
+from .multilinear import MODULI, _elems
 
 
 def __getattr__(name):
@@ -122,7 +123,7 @@ class R1cs:
         zz = self._vec(z, self.n_cols, "z")
         n = self._n_out(n_out, self.n_rows)
         outs = [np.empty((max(n, 0), 4), np.uint64) if w else None for w in which]
-        check(L.lib().lw_r1cs_matvec(self._h, _vp(zz), n, *[_vp(o) if o is not None else None for o in outs]))
+        check(L.lib().lw_r1cs_matvec(self._h, host_ptr(zz), n, *[host_ptr(o) for o in outs]))
         return outs
 
     def bind_rows(self, e, coeffs3, n_out=None):
@@ -131,14 +132,15 @@ class R1cs:
         cc = self._vec(coeffs3, 3, "coeffs3")
         n = self._n_out(n_out, self.n_cols)
         out = np.empty((max(n, 0), 4), np.uint64)
-        check(L.lib().lw_r1cs_bind_rows(self._h, _vp(ee), _vp(cc), n, _vp(out)))
+        # an output of no element still has an address: n_out is what the library reports, not a null argument
+        check(L.lib().lw_r1cs_bind_rows(self._h, host_ptr(ee), host_ptr(cc), n, C.c_void_p(out.ctypes.data)))
         return out
 
     def first_unsatisfied(self, z):
         """the smallest row i with (A z)_i (B z)_i != (C z)_i, or -1"""
         zz = self._vec(z, self.n_cols, "z")
         row = C.c_int64(0)
-        check(L.lib().lw_r1cs_first_unsatisfied(self._h, _vp(zz), C.byref(row)))
+        check(L.lib().lw_r1cs_first_unsatisfied(self._h, host_ptr(zz), C.byref(row)))
         return int(row.value)
 
     # ---- device-resident tensors
@@ -149,8 +151,8 @@ class R1cs:
         n = self._n_out(n_out, self.n_rows)
         outs = [(t if t is not None else torch.empty((n, 4), dtype=torch.int64, device=t_z.device)) if w else None
                 for t, w in zip(t_out, which)]
-        check(L.lib().lw_r1cs_matvec_device(self._h, C.c_void_p(t_z.data_ptr()), n,
-                                            *[C.c_void_p(o.data_ptr()) if o is not None else None for o in outs], _stream(stream)))
+        check(L.lib().lw_r1cs_matvec_device(self._h, device_ptr(t_z), n, *[device_ptr(o) if o is not None else None for o in outs],
+                                            stream_ptr(stream)))
         return outs
 
     def bind_rows_device(self, t_e, coeffs3, n_out=None, t_out=None, stream=None):
@@ -160,11 +162,10 @@ class R1cs:
         n = self._n_out(n_out, self.n_cols)
         if t_out is None:
             t_out = torch.empty((n, 4), dtype=torch.int64, device=t_e.device)
-        check(L.lib().lw_r1cs_bind_rows_device(self._h, C.c_void_p(t_e.data_ptr()), _vp(cc), n, C.c_void_p(t_out.data_ptr()),
-                                               _stream(stream)))
+        check(L.lib().lw_r1cs_bind_rows_device(self._h, device_ptr(t_e), host_ptr(cc), n, device_ptr(t_out), stream_ptr(stream)))
         return t_out
 
     def first_unsatisfied_device(self, t_z, stream=None):
         row = C.c_int64(0)
-        check(L.lib().lw_r1cs_first_unsatisfied_device(self._h, C.c_void_p(t_z.data_ptr()), C.byref(row), _stream(stream)))
+        check(L.lib().lw_r1cs_first_unsatisfied_device(self._h, device_ptr(t_z), C.byref(row), stream_ptr(stream)))
         return int(row.value)

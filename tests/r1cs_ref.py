@@ -8,21 +8,9 @@ import os
 import numpy as np
 
 from tests.multilinear_ref import MODULI, Fld  # noqa: F401
+from tests.util import to_arr, to_ints  # noqa: F401
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def to_ints(a):
-    a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
-    b = a.astype(">u8").tobytes()
-    return [int.from_bytes(b[32 * i:32 * i + 32], "big") for i in range(a.shape[0])]
-
-
-def to_arr(vals):
-    if not len(vals):
-        return np.zeros((0, 4), np.uint64)
-    b = b"".join(int(v).to_bytes(32, "big") for v in vals)
-    return np.frombuffer(b, dtype=">u8").astype(np.uint64).reshape(-1, 4)
 
 
 def csr(n_rows, entries):

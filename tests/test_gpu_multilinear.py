@@ -18,45 +18,11 @@ import numpy as np
 import pytest
 
 from tests import multilinear_ref as M
+from tests.util import dev, fld, host, rand_elems, to_arr, to_ints
 
 pytestmark = pytest.mark.gpu
 FIELDS = ["stark252", "fr381"]
 F_REF = {name: M.Fld(M.MODULI[name], True) for name in FIELDS}
-
-
-def fld(name):
-    from lambda_elliptic_curves_amd import fft
-    return {"stark252": fft.Stark252PrimeField, "fr381": fft.FrField}[name]
-
-
-def to_ints(a):
-    a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
-    b = a.astype(">u8").tobytes()
-    return [int.from_bytes(b[32 * i:32 * i + 32], "big") for i in range(a.shape[0])]
-
-
-def to_arr(vals):
-    if not len(vals):
-        return np.zeros((0, 4), np.uint64)
-    b = b"".join(int(v).to_bytes(32, "big") for v in vals)
-    return np.frombuffer(b, dtype=">u8").astype(np.uint64).reshape(-1, 4)
-
-
-def rand_elems(name, n, seed):
-    """n canonical residues: any value below 2^251 (Stark252) / 2^254 (Fr381) is below p"""
-    rng = np.random.default_rng(seed)
-    a = rng.integers(0, 1 << 63, size=(n, 4), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, size=(n, 4), dtype=np.uint64)
-    a[:, 0] &= np.uint64((1 << (59 if name == "stark252" else 62)) - 1)
-    return a
-
-
-def dev(arr):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(arr).view(np.int64)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy().view(np.uint64)
 
 
 @functools.lru_cache(maxsize=None)

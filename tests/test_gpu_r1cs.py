@@ -20,6 +20,8 @@ import pytest
 
 from tests import multilinear_ref as M
 from tests import r1cs_ref as R
+from tests import util
+from tests.util import dev, fld
 
 pytestmark = pytest.mark.gpu
 FIELDS = ["stark252", "fr381"]
@@ -28,25 +30,16 @@ BLOCK = 256   # outputs per block of r1cs_lists_kernel, work-items of a block of
 FEW = 8       # R1CS_FEW: an output with at most this many pieces per matrix is added up by one work-item, not by a block
 
 
-def fld(name):
-    from lambda_elliptic_curves_amd import fft
-    return {"stark252": fft.Stark252PrimeField, "fr381": fft.FrField}[name]
-
-
 def consts():
     from lambda_elliptic_curves_amd import r1cs
     return r1cs.SPLIT, r1cs.TERMS
 
 
-def dev(arr):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(arr).view(np.int64).copy()).cuda()
-
-
 def host(t):
+    """util.host after the whole device has finished, whichever stream the call used"""
     import torch
     torch.cuda.synchronize()
-    return t.cpu().numpy().view(np.uint64)
+    return util.host(t)
 
 
 def ones_dev(n):

@@ -153,3 +153,34 @@ def test_eq_table_of_no_variable_needs_no_device_and_nothing_else_falls_back():
         multilinear.sumcheck_terms_round(F, [tab], [(None, (0,))])
     with pytest.raises(errors.HipError):
         multilinear.sumcheck_terms_round(F, [tab], [(tab[0], (0,))], eq=tab2, r_prev=tab[0])
+
+
+def test_both_rounds_report_bad_tables_alike():
+    """lw_sumcheck_round and lw_sumcheck_terms_round check their tables with one helper: the same bad arguments give both
+    the same status and message, host and device forms.  The texts are the ones the two entry points had when each still
+    carried its own copy of the checks."""
+    from lambda_elliptic_curves_amd import _lib
+    L = C.CDLL(_lib.LIB_PATH)
+    L.lw_hip_last_error.restype = C.c_char_p
+    buf = np.zeros(8192, np.uint8)
+    base = (buf.ctypes.data + 63) & ~63
+    at = lambda off: C.c_void_p(base + off)
+    A, B, NEAR, Q, OUT, N = at(0), at(512), at(64), at(2560), at(3072), C.c_void_p(None)   # NEAR: inside 2^2 elements at A
+    u32, S = C.c_uint32, C.c_int(0)
+    arr = lambda *ps: (C.c_void_p * len(ps))(*[p.value for p in ps])
+    one_term = (C.c_uint32 * 1)(3)   # the product of both tables
+    cases = [   # tables, n_vars, r_prev, message
+        (arr(A, N), 2, N, b"table 1: null or misaligned buffer"),
+        (arr(A, NEAR), 2, N, b"tables 0 and 1 overlap"),
+        (arr(A, B), 31, N, b"31 variables: at most 30"),
+        (arr(A, B), 1, Q, b"1 variables: a round needs 1, a fused round 2"),
+    ]
+    for tabs, n, rp, msg in cases:
+        calls = [
+            lambda: L.lw_sumcheck_round(S, tabs, u32(2), u32(n), rp, OUT),
+            lambda: L.lw_sumcheck_round_device(S, tabs, u32(2), u32(n), rp, OUT, N),
+            lambda: L.lw_sumcheck_terms_round(S, tabs, u32(2), N, one_term, N, u32(1), u32(n), rp, OUT),
+            lambda: L.lw_sumcheck_terms_round_device(S, tabs, u32(2), N, one_term, N, u32(1), u32(n), rp, OUT, N),
+        ]
+        for i, call in enumerate(calls):
+            assert (call(), L.lw_hip_last_error()) == (_lib.ERR_BAD_ARG, msg), (msg, i)

@@ -15,6 +15,11 @@ def field_pairs():
     }
 
 
+def fld(name):
+    """the product Field of a name"""
+    return field_pairs()[name][0]
+
+
 P_BABYBEAR = 2013265921
 
 
@@ -38,6 +43,31 @@ def rand_elems(name, n, seed):
     if name == "babybear_ext4":
         return rng.integers(0, P_BABYBEAR, size=(n, 4), dtype=np.uint64)
     raise KeyError(name)
+
+
+def to_ints(a):
+    """stored 256-bit elements, (n, 4) uint64 MS limb first -> Python integers"""
+    a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
+    b = a.astype(">u8").tobytes()
+    return [int.from_bytes(b[32 * i:32 * i + 32], "big") for i in range(a.shape[0])]
+
+
+def to_arr(vals):
+    """Python integers below 2^256 -> (n, 4) uint64, MS limb first"""
+    if not len(vals):
+        return np.zeros((0, 4), np.uint64)
+    b = b"".join(int(v).to_bytes(32, "big") for v in vals)
+    return np.frombuffer(b, dtype=">u8").astype(np.uint64).reshape(-1, 4)
+
+
+def dev(arr):
+    """a (n, 4) uint64 array -> an int64 tensor on the device (a copy: read-only arrays are welcome)"""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(arr).view(np.int64).copy()).cuda()
+
+
+def host(t):
+    return t.cpu().numpy().view(np.uint64)
 
 
 def offset_elem(name, h):
