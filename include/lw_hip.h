@@ -575,7 +575,8 @@ int lw_field_batch_inverse_device(lw_field_t field, const void *d_in, size_t n, 
 uint64_t lw_field_batch_inverse_block(void);
 
 /* ---- STARK round 2: the composition polynomial and its commitment ----
- * round_2_compute_composition_polynomial (provers/stark/src/prover.rs:428-484) without the AIR's compute_transition:
+ * round_2_compute_composition_polynomial (provers/stark/src/prover.rs:428-484) without the AIR's compute_transition
+ * (for an AIR given as data, lw_stark_transition_evaluations_device below writes the table this section reads):
  * ConstraintEvaluator::evaluate (constraints/evaluator.rs:33-225), interpolate_offset_fft, break_in_parts, the LDE of the
  * parts and commit_composition_polynomial (prover.rs:398-425).  Fields as above; elements as stored (Montgomery form,
  * 4 x u64, most significant limb first); scalars are host values, vectors device pointers in the _device forms.
@@ -634,6 +635,59 @@ int lw_stark_round2(lw_field_t field, const void *columns, uint32_t n_cols, uint
                     const lw_stark_transition_t *transitions, uint32_t n_transitions, const void *transition_evals, uint32_t n_parts,
                     void *out_parts_coeffs, size_t *out_part_lens, uint8_t *out_root, uint8_t *out_nodes_or_null,
                     void *out_parts_lde_or_null);
+
+/* ---- STARK transition constraints from an AIR given as data ----
+ * The AIR's compute_transition (provers/stark/src/traits.rs) as a straight-line program that the device runs at every LDE
+ * row: it writes the T_c rows lw_stark_constraint_evaluations_device reads.  Fields and elements as above.
+ *
+ * An accumulator machine with one field element acc and LW_STARK_AIR_MAX_TMPS temporaries; one instruction is 8 bytes:
+ *     LOAD  acc = s        ADD  acc += s        SUB  acc -= s        MUL  acc *= s        NEG  acc = -acc
+ *     STORE tmp[index] = acc                    EMIT T_index[i] = acc
+ * s, for LOAD / ADD / SUB / MUL, by src:
+ *     CELL   column `index` at trace-row offset `row`: at LDE row i, col[(i + row * 2^log2_blowup) mod len_col]
+ *            (Frame::read_from_lde with the rows of a step flattened: row = offset * STEP_SIZE + row_in_step)
+ *     CONST  consts[index]          TMP  tmp[index]
+ * len_col = 2^col_log2_len[c] <= N; a NULL table: every column has N elements.  A periodic column is a short one: its LDE
+ * has period * 2^log2_blowup elements and is stored once.  consts: n_consts host elements (the RAP challenges and the AIR's
+ * literals), per call.  A field an instruction does not use (src and row of STORE and EMIT, row of a CONST or TMP operand,
+ * all three of NEG) must be 0.
+ *
+ * Every check runs on the host before any device work; a failure is LW_ERR_BAD_ARG and lw_hip_last_error names the op:
+ * an unknown op or src; a column, constant, temporary or constraint index out of range; row >= n; a non-zero unused field;
+ * acc read (by anything but LOAD) before the first LOAD; a TMP read before its STORE; a constraint emitted twice or never;
+ * more than LW_STARK_AIR_MAX_OPS ops or LW_STARK_AIR_MAX_CONSTS constants; col_log2_len[c] > log2_trace + log2_blowup;
+ * a field other than the two; an LDE domain beyond the NTT; a null or misaligned buffer; 0 < out_stride_elems < N with
+ * more than one constraint.  n_transitions = 0 with n_ops = 0 is legal and writes nothing. */
+#define LW_STARK_AIR_MAX_OPS 4096
+#define LW_STARK_AIR_MAX_TMPS 8
+#define LW_STARK_AIR_MAX_CONSTS 256
+typedef enum {
+    LW_STARK_AIR_LOAD = 0,
+    LW_STARK_AIR_ADD = 1,
+    LW_STARK_AIR_SUB = 2,
+    LW_STARK_AIR_MUL = 3,
+    LW_STARK_AIR_NEG = 4,
+    LW_STARK_AIR_STORE = 5,
+    LW_STARK_AIR_EMIT = 6
+} lw_stark_air_opcode_t;
+typedef enum { LW_STARK_AIR_CELL = 0, LW_STARK_AIR_CONST = 1, LW_STARK_AIR_TMP = 2 } lw_stark_air_src_t;
+typedef struct {
+    uint8_t op, src;
+    uint16_t index;
+    uint32_t row;
+} lw_stark_air_op_t;
+/* d_columns: host array of n_cols device pointers, 16-byte aligned.  Row c of d_out starts at element c * out_stride_elems
+ * (0 = N) and takes N elements; the rest of a stride is not written.  ops and consts are copied into the library's
+ * staging before the call returns.  Enqueues on hip_stream and returns: no synchronisation. */
+int lw_stark_transition_evaluations_device(lw_field_t field, const lw_stark_air_op_t *ops, uint32_t n_ops, const void *consts,
+                                           uint32_t n_consts, const void *const *d_columns, const uint32_t *col_log2_len_or_null,
+                                           uint32_t n_cols, uint32_t log2_trace, uint32_t log2_blowup, uint32_t n_transitions,
+                                           void *d_out, uint64_t out_stride_elems, void *hip_stream);
+/* The same on host arrays through the library's staging: columns holds the n_cols columns back to back, each with its
+ * own 2^col_log2_len[c] (or N) elements; out is n_transitions x N, dense. */
+int lw_stark_transition_evaluations(lw_field_t field, const lw_stark_air_op_t *ops, uint32_t n_ops, const void *consts,
+                                    uint32_t n_consts, const void *columns, const uint32_t *col_log2_len_or_null, uint32_t n_cols,
+                                    uint32_t log2_trace, uint32_t log2_blowup, uint32_t n_transitions, void *out);
 
 /* ---- PLONK prover rounds 1-3 ----
  * Prover::round_1 / round_2 / round_3 (provers/plonk/src/prover.rs:311-341, 343-381, 383-535) without the commitments:

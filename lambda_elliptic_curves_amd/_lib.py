@@ -23,6 +23,9 @@ PW_FIELD_STARK252, PW_FIELD_FR381, PW_FIELD_FR254, PW_FIELD_FP381, PW_FIELD_FP25
 POSEIDON_LEAF_SINGLE, POSEIDON_LEAF_MANY = 0, 1   # lw_poseidon_leaf_t
 RPO_128, RPO_160 = 0, 1   # lw_rpo_level_t
 MONOLITH_CONCRETE, MONOLITH_BARS, MONOLITH_BRICKS = 0, 1, 2   # lw_monolith_layer_t
+AIR_LOAD, AIR_ADD, AIR_SUB, AIR_MUL, AIR_NEG, AIR_STORE, AIR_EMIT = range(7)   # lw_stark_air_opcode_t
+AIR_CELL, AIR_CONST, AIR_TMP = 0, 1, 2   # lw_stark_air_src_t
+AIR_MAX_OPS, AIR_MAX_TMPS, AIR_MAX_CONSTS = 4096, 8, 256   # LW_STARK_AIR_MAX_*
 (OK, ERR_INPUT_NOT_POW2, ERR_ORDER_TOO_LARGE, ERR_ROOT_OF_UNITY, ERR_LENGTH_MISMATCH, ERR_NO_DEVICE, ERR_ALLOC,
  ERR_LAUNCH, ERR_COMM, ERR_BAD_ARG, ERR_INV_ZERO) = (0, -1, -2, -3, -4, -5, -6, -7, -8, -9, -10)
 
@@ -62,7 +65,7 @@ EXPORTS = [
     "lw_monolith_constants", "lw_monolith_layer_device",
     "lw_field_batch_inverse", "lw_field_batch_inverse_device", "lw_field_batch_inverse_block",
     "lw_stark_constraint_evaluations_device", "lw_stark_composition_parts_device", "lw_stark_commit_composition_device",
-    "lw_stark_round2",
+    "lw_stark_round2", "lw_stark_transition_evaluations_device", "lw_stark_transition_evaluations",
     "lw_multilinear_evaluate", "lw_multilinear_evaluate_device", "lw_multilinear_fix_variables",
     "lw_multilinear_fix_variables_device", "lw_sumcheck_round", "lw_sumcheck_round_device",
     "lw_multilinear_eq_table", "lw_multilinear_eq_table_device", "lw_sumcheck_terms_round", "lw_sumcheck_terms_round_device",
@@ -97,6 +100,11 @@ class StarkTransition(C.Structure):
     """lw_stark_transition_t"""
     _fields_ = [("period", C.c_uint64), ("offset", C.c_uint64), ("end_exemptions", C.c_uint64), ("exemptions_period", C.c_uint64),
                 ("periodic_exemptions_offset", C.c_uint64), ("coeff", C.c_uint64 * 4)]
+
+
+class StarkAirOp(C.Structure):
+    """lw_stark_air_op_t"""
+    _fields_ = [("op", C.c_uint8), ("src", C.c_uint8), ("index", C.c_uint16), ("row", C.c_uint32)]
 
 
 class Profile(C.Structure):
@@ -365,6 +373,11 @@ def lib():
     L.lw_stark_commit_composition_device.restype = i
     L.lw_stark_round2.argtypes = [i, vp, u32, u32, u32, vp, bp, u32, tp, u32, vp, u32, vp, C.POINTER(sz), vp, vp, vp]
     L.lw_stark_round2.restype = i
+    ap, u32p = C.POINTER(StarkAirOp), C.POINTER(u32)
+    L.lw_stark_transition_evaluations_device.argtypes = [i, ap, u32, vp, u32, vp, u32p, u32, u32, u32, u32, vp, C.c_uint64, vp]
+    L.lw_stark_transition_evaluations_device.restype = i
+    L.lw_stark_transition_evaluations.argtypes = [i, ap, u32, vp, u32, vp, u32p, u32, u32, u32, u32, vp]
+    L.lw_stark_transition_evaluations.restype = i
     L.lw_multilinear_evaluate.argtypes = [i, vp, u32, u32, vp, vp]
     L.lw_multilinear_evaluate.restype = i
     L.lw_multilinear_evaluate_device.argtypes = [i, vp, u32, u32, vp, vp, vp]

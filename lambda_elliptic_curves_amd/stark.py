@@ -275,3 +275,251 @@ def round2(field, columns, log2_trace, log2_blowup, coset_offset, boundary, tran
     if return_lde:
         out += (lde,)
     return out
+
+
+# ---- transition constraints from an AIR given as data (csrc/stark_air.hip): compute_transition as a straight-line program
+
+class Expr:
+    """A polynomial expression over frame cells and constants: cell() and const() are the leaves, + - * and unary - build
+    the tree.  Two uses of the same Python object are one sub-expression, computed once."""
+    __slots__ = ("kind", "a", "b")
+
+    def __init__(self, kind, a=None, b=None):
+        self.kind, self.a, self.b = kind, a, b
+
+    def _bin(self, kind, other):
+        return Expr(kind, self, other) if isinstance(other, Expr) else NotImplemented
+
+    def __add__(self, o):
+        return self._bin("add", o)
+
+    def __sub__(self, o):
+        return self._bin("sub", o)
+
+    def __mul__(self, o):
+        return self._bin("mul", o)
+
+    def __neg__(self):
+        return Expr("neg", self)
+
+    @property
+    def is_leaf(self):
+        return self.kind in ("cell", "const")
+
+
+def cell(col, row=0):
+    """column `col` of the frame at trace-row offset `row` (offset * STEP_SIZE + row in the step)"""
+    col, row = int(col), int(row)
+    if not (0 <= col < 1 << 16 and 0 <= row < 1 << 32):
+        from .errors import InputError
+        raise InputError(f"cell({col}, {row})")
+    return Expr("cell", col, row)
+
+
+def const(k):
+    """consts[k] of the call: a challenge or a literal of the AIR"""
+    k = int(k)
+    if not 0 <= k < L.AIR_MAX_CONSTS:
+        from .errors import InputError
+        raise InputError(f"const({k}): a program has at most {L.AIR_MAX_CONSTS} constants")
+    return Expr("const", k)
+
+
+AIR_OP_DTYPE = np.dtype([("op", "u1"), ("src", "u1"), ("index", "<u2"), ("row", "<u4")])   # lw_stark_air_op_t
+
+
+class AirProgram:
+    """ops: (n_ops,) AIR_OP_DTYPE; n_transitions constraints; n_tmps temporaries used; n_consts and n_cols: one more than
+    the highest constant and column the program reads; n_mul: its MUL count."""
+
+    def __init__(self, ops, n_transitions):
+        self.ops = np.ascontiguousarray(ops, dtype=AIR_OP_DTYPE).reshape(-1)
+        self.n_transitions = int(n_transitions)
+        op, src, idx = self.ops["op"], self.ops["src"], self.ops["index"].astype(np.int64)
+        reads = op <= L.AIR_MUL
+        top = lambda mask: int(idx[mask].max()) + 1 if mask.any() else 0
+        self.n_tmps = top(op == L.AIR_STORE)
+        self.n_consts = top(reads & (src == L.AIR_CONST))
+        self.n_cols = top(reads & (src == L.AIR_CELL))
+        self.n_mul = int((op == L.AIR_MUL).sum())
+
+    def __len__(self):
+        return self.ops.shape[0]
+
+
+def compile_transitions(exprs):
+    """[expr_0, expr_1, ...] -> AirProgram emitting T_c = expr_c.  A leaf operand is used directly; a compound right
+    operand is computed first and kept in a temporary while the left one is computed; a compound sub-expression used more
+    than once (the same object) is computed at its first use and kept in a temporary until its last.  More than
+    LW_STARK_AIR_MAX_TMPS temporaries alive at once, or more than LW_STARK_AIR_MAX_OPS ops: errors.InputError."""
+    from .errors import InputError
+    exprs = list(exprs)
+    uses, seen, stack = {}, set(), list(exprs)
+    for e in exprs:
+        if not isinstance(e, Expr):
+            raise InputError(f"not an expression: {e!r}")
+        uses[id(e)] = uses.get(id(e), 0) + 1
+    while stack:                                   # one visit per node, one count per edge
+        e = stack.pop()
+        if id(e) in seen or e.is_leaf:
+            continue
+        seen.add(id(e))
+        for ch in (e.a, e.b):
+            if isinstance(ch, Expr):
+                uses[id(ch)] = uses.get(id(ch), 0) + 1
+                stack.append(ch)
+    ops, free, kept = [], list(range(L.AIR_MAX_TMPS)), {}      # kept: id -> slot of a shared sub-expression already computed
+    OPC = {"add": L.AIR_ADD, "sub": L.AIR_SUB, "mul": L.AIR_MUL}
+
+    def emit(op, src=0, index=0, row=0):
+        if len(ops) >= L.AIR_MAX_OPS:
+            raise InputError(f"the program needs more than {L.AIR_MAX_OPS} ops")
+        ops.append((op, src, index, row))
+
+    def take():
+        if not free:
+            raise InputError(f"the expressions need more than {L.AIR_MAX_TMPS} temporaries at once")
+        return free.pop(0)
+
+    def give(slot):
+        free.append(slot)
+        free.sort()
+
+    def operand(e):
+        """(src, index, row) of an expression that needs no code: a leaf, or a shared one already in its temporary"""
+        if e.kind == "cell":
+            return (L.AIR_CELL, e.a, e.b)
+        if e.kind == "const":
+            return (L.AIR_CONST, e.a, 0)
+        if id(e) in kept:
+            return (L.AIR_TMP, kept[id(e)], 0)
+        return None
+
+    def used(e):
+        """one use of a kept sub-expression is over"""
+        if id(e) in kept:
+            uses[id(e)] -= 1
+            if uses[id(e)] == 0:
+                give(kept.pop(id(e)))
+
+    def gen(e):
+        """acc = e; whoever consumes acc calls used(e) afterwards"""
+        direct = operand(e)
+        if direct is not None:
+            emit(L.AIR_LOAD, *direct)
+            return
+        if e.kind == "neg":
+            gen(e.a)
+            emit(L.AIR_NEG)
+            used(e.a)
+        elif operand(e.b) is not None:
+            gen(e.a)
+            emit(OPC[e.kind], *operand(e.b))
+            used(e.a)
+            used(e.b)
+        else:
+            gen(e.b)
+            shared = id(e.b) in kept                # gen stored it in its own slot
+            slot = kept[id(e.b)] if shared else take()
+            if not shared:
+                emit(L.AIR_STORE, 0, slot)
+            gen(e.a)
+            emit(OPC[e.kind], L.AIR_TMP, slot, 0)
+            used(e.a)
+            if shared:
+                used(e.b)
+            else:
+                give(slot)
+        if uses.get(id(e), 0) > 1:                  # the first of several uses: keep it
+            kept[id(e)] = take()
+            emit(L.AIR_STORE, 0, kept[id(e)])
+
+    import sys
+    limit = sys.getrecursionlimit()
+    sys.setrecursionlimit(max(limit, 3 * L.AIR_MAX_OPS + 1000))
+    try:
+        for c, e in enumerate(exprs):
+            if c >= 1 << 16:
+                raise InputError("more than 65536 constraints")
+            gen(e)
+            emit(L.AIR_EMIT, 0, c)
+            used(e)
+    finally:
+        sys.setrecursionlimit(limit)
+    return AirProgram(np.array(ops, dtype=AIR_OP_DTYPE) if ops else np.zeros(0, AIR_OP_DTYPE), len(exprs))
+
+
+def _air_args(program, consts, col_log2_len, n_cols, n_lde):
+    """the program, the constants and the column lengths as the C calls take them (+ the objects that own the memory)"""
+    import ctypes as C
+    from .errors import LengthMismatch
+    ops = np.ascontiguousarray(program.ops, dtype=AIR_OP_DTYPE)
+    cs = np.ascontiguousarray(consts if consts is not None else np.zeros((0, 4), np.uint64), dtype=np.uint64).reshape(-1, 4)
+    if cs.shape[0] < program.n_consts:
+        raise LengthMismatch(f"{cs.shape[0]} constants for a program that reads constant {program.n_consts - 1}")
+    if n_cols < program.n_cols:
+        raise LengthMismatch(f"{n_cols} columns for a program that reads column {program.n_cols - 1}")
+    lens = None
+    if col_log2_len is not None:
+        lens = np.ascontiguousarray([int(x) for x in col_log2_len], dtype=np.uint32)
+        if lens.shape[0] != n_cols:
+            raise LengthMismatch(f"{lens.shape[0]} column lengths for {n_cols} columns")
+    col_elems = [n_lde if lens is None else 1 << int(x) for x in (lens if lens is not None else range(n_cols))]
+    return (ops, cs, lens, col_elems,
+            ops.ctypes.data_as(C.POINTER(L.StarkAirOp)) if ops.shape[0] else None, L.host_ptr(cs),
+            lens.ctypes.data_as(C.POINTER(C.c_uint32)) if lens is not None else None)
+
+
+def transition_evaluations_device(field, program, consts, t_columns, log2_trace, log2_blowup, col_log2_len=None, t_out=None, stream=None):
+    """The AIR's compute_transition at every LDE row (lw_stark_transition_evaluations_device): t_columns is a list of
+    resident columns, N = 2^(log2_trace + log2_blowup) elements each or 2^col_log2_len[c] for a short (periodic) one;
+    consts (n_consts, 4) host elements.  -> t_out (n_transitions, stride, 4) with row c = T_c in its first N elements, as
+    constraint_evaluations_device reads it with transition_stride_elems = stride.  A t_out of the caller's may have a
+    stride above N (the gap is not written); one too short for n_transitions rows of N: errors.LengthMismatch.
+    Enqueues on the stream and returns."""
+    import ctypes as C
+    import torch
+    from .errors import LengthMismatch, check
+    n_lde = 1 << (int(log2_trace) + int(log2_blowup))
+    ops, cs, lens, col_elems, p_ops, p_cs, p_lens = _air_args(program, consts, col_log2_len, len(t_columns), n_lde)
+    for c, (t, want) in enumerate(zip(t_columns, col_elems)):
+        if t.numel() < want * 4:
+            raise LengthMismatch(f"column {c}: {t.numel() // 4} elements, {want} needed")
+    T = program.n_transitions
+    if t_out is None:
+        dev = t_columns[0].device if len(t_columns) else "cuda"
+        t_out = torch.empty((max(T, 1), n_lde, 4), dtype=torch.int64, device=dev)
+    stride = int(t_out.shape[1]) if t_out.dim() == 3 else n_lde
+    if not t_out.is_contiguous() or (T and (stride < n_lde or t_out.numel() < ((T - 1) * stride + n_lde) * 4)):
+        raise LengthMismatch(f"t_out of shape {tuple(t_out.shape)} for {T} rows of {n_lde} elements")
+    ptrs = (C.c_void_p * max(1, len(t_columns)))(*[t.data_ptr() for t in t_columns])
+    check(L.lib().lw_stark_transition_evaluations_device(field.field, p_ops, ops.shape[0], p_cs, cs.shape[0], ptrs, p_lens, len(t_columns),
+                                                         int(log2_trace), int(log2_blowup), T, C.c_void_p(t_out.data_ptr()), stride,
+                                                         poly._stream(stream)))
+    return t_out
+
+
+def transition_evaluations(field, program, consts, columns, log2_trace, log2_blowup, col_log2_len=None):
+    """transition_evaluations_device on host arrays (lw_stark_transition_evaluations): columns is a list of (len, 4)
+    arrays (or one (n_cols, N, 4) array).  -> (n_transitions, N, 4) uint64"""
+    from .errors import LengthMismatch, check
+    n_lde = 1 << (int(log2_trace) + int(log2_blowup))
+    cols = [np.ascontiguousarray(c, dtype=np.uint64).reshape(-1, 4) for c in columns]
+    ops, cs, lens, col_elems, p_ops, p_cs, p_lens = _air_args(program, consts, col_log2_len, len(cols), n_lde)
+    for c, (a, want) in enumerate(zip(cols, col_elems)):
+        if a.shape[0] != want:
+            raise LengthMismatch(f"column {c}: {a.shape[0]} elements, {want} expected")
+    flat = np.concatenate(cols) if cols else np.zeros((0, 4), np.uint64)
+    out = np.zeros((program.n_transitions, n_lde, 4), np.uint64)
+    check(L.lib().lw_stark_transition_evaluations(field.field, p_ops, ops.shape[0], p_cs, cs.shape[0], L.host_ptr(flat), p_lens, len(cols),
+                                                  int(log2_trace), int(log2_blowup), program.n_transitions, L.host_ptr(out)))
+    return out
+
+
+def round2_program_device(field, t_columns, log2_trace, log2_blowup, coset_offset, boundary, transitions, program, consts, n_parts,
+                          col_log2_len=None, stream=None):
+    """round2_device with the transition evaluations computed on the device from the AIR's program: the T table never
+    leaves the device.  t_columns may end in short (periodic) columns, which no boundary constraint refers to.
+    -> what round2_device returns."""
+    t_tev = transition_evaluations_device(field, program, consts, t_columns, log2_trace, log2_blowup, col_log2_len=col_log2_len, stream=stream)
+    return round2_device(field, t_columns, log2_trace, log2_blowup, coset_offset, boundary, transitions, t_tev, n_parts, stream=stream)

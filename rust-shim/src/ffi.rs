@@ -424,6 +424,14 @@ extern "C" {
                            transitions: *const lw_stark_transition_t, n_transitions: u32, transition_evals: *const c_void,
                            n_parts: u32, out_parts_coeffs: *mut c_void, out_part_lens: *mut usize, out_root: *mut u8,
                            out_nodes_or_null: *mut u8, out_parts_lde_or_null: *mut c_void) -> c_int;
+    // ---- STARK transition constraints from an AIR given as data (the program and the constants on the host)
+    pub fn lw_stark_transition_evaluations_device(field: Field, ops: *const lw_stark_air_op_t, n_ops: u32, consts: *const c_void,
+                                                  n_consts: u32, d_columns: *const *const c_void, col_log2_len_or_null: *const u32,
+                                                  n_cols: u32, log2_trace: u32, log2_blowup: u32, n_transitions: u32,
+                                                  d_out: *mut c_void, out_stride_elems: u64, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_stark_transition_evaluations(field: Field, ops: *const lw_stark_air_op_t, n_ops: u32, consts: *const c_void,
+                                           n_consts: u32, columns: *const c_void, col_log2_len_or_null: *const u32, n_cols: u32,
+                                           log2_trace: u32, log2_blowup: u32, n_transitions: u32, out: *mut c_void) -> c_int;
 }
 
 /// lw_stark_boundary_t: one boundary constraint of lw_stark_constraint_evaluations_device
@@ -450,6 +458,35 @@ pub struct lw_stark_transition_t {
     pub periodic_exemptions_offset: u64,
     pub coeff: [u64; 4],
 }
+
+/// lw_stark_air_op_t: one instruction of an AIR transition program (lw_stark_transition_evaluations_device)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct lw_stark_air_op_t {
+    /// LW_STARK_AIR_LOAD .. LW_STARK_AIR_EMIT
+    pub op: u8,
+    /// LW_STARK_AIR_CELL / CONST / TMP, for LOAD, ADD, SUB and MUL
+    pub src: u8,
+    /// column, constant, temporary or constraint
+    pub index: u16,
+    /// trace-row offset of a CELL operand
+    pub row: u32,
+}
+/// lw_stark_air_opcode_t
+pub const LW_STARK_AIR_LOAD: u8 = 0;
+pub const LW_STARK_AIR_ADD: u8 = 1;
+pub const LW_STARK_AIR_SUB: u8 = 2;
+pub const LW_STARK_AIR_MUL: u8 = 3;
+pub const LW_STARK_AIR_NEG: u8 = 4;
+pub const LW_STARK_AIR_STORE: u8 = 5;
+pub const LW_STARK_AIR_EMIT: u8 = 6;
+/// lw_stark_air_src_t
+pub const LW_STARK_AIR_CELL: u8 = 0;
+pub const LW_STARK_AIR_CONST: u8 = 1;
+pub const LW_STARK_AIR_TMP: u8 = 2;
+pub const LW_STARK_AIR_MAX_OPS: u32 = 4096;
+pub const LW_STARK_AIR_MAX_TMPS: u32 = 8;
+pub const LW_STARK_AIR_MAX_CONSTS: u32 = 256;
 
 /// lw_poseidon_leaf_t: TreePoseidon (leaf = hash_single of one column)
 pub const LW_POSEIDON_LEAF_SINGLE: c_int = 0;
@@ -509,3 +546,4 @@ const _: () = assert!(core::mem::size_of::<lw_profile_t>() == 8 + 32 * 64);
 const _: () = assert!(core::mem::size_of::<lw_stark_tree_t>() == 56);
 const _: () = assert!(core::mem::size_of::<lw_stark_boundary_t>() == 80);
 const _: () = assert!(core::mem::size_of::<lw_stark_transition_t>() == 72);
+const _: () = assert!(core::mem::size_of::<lw_stark_air_op_t>() == 8);

@@ -546,6 +546,33 @@ pub fn stark_round2(field: Field, columns: &[[u64; 4]], log2_trace: u32, log2_bl
     Ok(out)
 }
 
+/// The AIR's `compute_transition` at every LDE row, from the AIR written as a program of `lw_stark_air_op_t` (include/lw_hip.h):
+/// `columns` holds the LDE columns back to back, `2^col_log2_len[c]` elements for column `c` (`None`: `N` each; a periodic
+/// column has `period * blowup`), `consts` the challenges and literals the program reads.  Returns `n_transitions x N`
+/// elements, row `c` = constraint `c`: the `transition_evals` of `stark_round2`.
+pub fn stark_transition_evaluations(field: Field, ops: &[ffi::lw_stark_air_op_t], consts: &[[u64; 4]], columns: &[[u64; 4]],
+                                    col_log2_len: Option<&[u32]>, n_cols: usize, log2_trace: u32, log2_blowup: u32,
+                                    n_transitions: usize) -> Result<Vec<[u64; 4]>, HipError> {
+    let n_lde = 1usize << (log2_trace + log2_blowup);
+    let want: usize = match col_log2_len {
+        Some(l) => {
+            assert_eq!(l.len(), n_cols, "col_log2_len: one entry per column");
+            l.iter().map(|&x| 1usize.checked_shl(x).unwrap_or(0)).sum()
+        }
+        None => n_cols * n_lde,
+    };
+    assert_eq!(columns.len(), want, "columns: the sum of the column lengths");
+    let mut out = vec![[0u64; 4]; n_transitions * n_lde];
+    // SAFETY: ops, consts and columns are valid for their lengths; `out` holds n_transitions x N elements.
+    let rc = unsafe {
+        ffi::lw_stark_transition_evaluations(field, ops.as_ptr(), ops.len() as u32, consts.as_ptr() as *const c_void, consts.len() as u32,
+                                             columns.as_ptr() as *const c_void, col_log2_len.map_or(core::ptr::null(), |l| l.as_ptr()),
+                                             n_cols as u32, log2_trace, log2_blowup, n_transitions as u32, out.as_mut_ptr() as *mut c_void)
+    };
+    check(rc)?;
+    Ok(out)
+}
+
 /// `grinding::generate_nonce` (provers/stark/src/grinding.rs:40-53) on the device: the smallest nonce in `[first, last]`
 /// whose hash has `grinding_factor` (1 ..= 63) leading zero bits, or `None`.
 pub fn stark_grinding_nonce(seed: &[u8; 32], grinding_factor: u8, first: u64, last: u64) -> Result<Option<u64>, HipError> {
