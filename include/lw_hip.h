@@ -271,7 +271,8 @@ int lw_polynomial_interpolate_fft(lw_field_t field, lw_layout_t layout, const vo
  * :232-234), rows are formed (columns2rows) and BatchedMerkleTree<BatchKeccak256Backend> is built
  * (crypto/src/merkle_tree/merkle.rs:31-56; field_element_vector.rs:41-58; utils.rs:44-72).  The permutation and the
  * transposition are folded into the leaf hash, nothing is copied.  nodes: (2*2^log2n - 1) x 32 bytes, root first,
- * leaves last — the reference's `nodes` vector.  n_cols = 1 is the FRI layer tree (Keccak256Backend). */
+ * leaves last — the reference's `nodes` vector.  n_cols = 1 is the FRI layer tree (Keccak256Backend).  col_stride_elems (both
+ * _device forms): elements between column starts, 0 = dense, at least 2^log2n otherwise. */
 int lw_stark_commit_columns(lw_field_t field, const void *columns, uint32_t n_cols, uint32_t log2n, int bit_reverse,
                             uint8_t *out_root /* 32 bytes */, uint8_t *out_nodes_or_null);
 int lw_stark_commit_columns_device(lw_field_t field, const void *d_columns, uint32_t n_cols, uint64_t col_stride_elems,

@@ -923,6 +923,10 @@ int lw_stark_commit_columns_layout_device(lw_field_t field, lw_layout_t layout, 
     int rc = commit_check(d_columns, d_nodes, n_cols, log2n);
     if (rc) return rc;
     if ((uint64_t)n_cols * eb >= (1ull << 31)) { set_error("%u columns per row", n_cols); return LW_ERR_BAD_ARG; }
+    if (col_stride_elems && col_stride_elems < (1ull << log2n)) {
+        set_error("column stride %llu below the column length", (unsigned long long)col_stride_elems);
+        return LW_ERR_BAD_ARG;
+    }
     Entry en(hip_stream);
     if (en.rc) return en.rc;
     if (col_stride_elems == 0) col_stride_elems = 1ull << log2n;

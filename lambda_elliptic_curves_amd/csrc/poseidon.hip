@@ -168,6 +168,10 @@ int lw_poseidon_commit_columns_device(const void *d_columns, uint32_t n_cols, ui
                                       int leaf_mode, void *d_nodes, uint8_t *out_root, void *hip_stream) {
     const int rc = commit_check(d_columns, d_nodes, n_cols, log2n, leaf_mode, true);
     if (rc) return rc;
+    if (col_stride_elems && col_stride_elems < (1ull << log2n)) {
+        set_error("column stride %llu below the column length", (unsigned long long)col_stride_elems);
+        return LW_ERR_BAD_ARG;
+    }
     return tree_commit_columns_device<PoseidonHash>(POSEIDON_NAMES, d_columns, n_cols, col_stride_elems, log2n, bit_reverse,
                                                     leaf_mode == LW_POSEIDON_LEAF_SINGLE, d_nodes, out_root, hip_stream);
 }

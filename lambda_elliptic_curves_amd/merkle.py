@@ -25,26 +25,28 @@ def commit_columns(field, columns, bit_reverse=True, return_nodes=False):
     return (root.tobytes(), nodes) if return_nodes else root.tobytes()
 
 
-def commit_columns_device(field, t_columns, n_cols, log2n, t_nodes, bit_reverse=True, stream=None):
-    """Device-resident: t_columns holds n_cols dense columns of 2^log2n elements, t_nodes (2*2^log2n - 1) * 32 bytes."""
+def commit_columns_device(field, t_columns, n_cols, log2n, t_nodes, bit_reverse=True, col_stride_elems=0, stream=None):
+    """Device-resident: t_columns holds n_cols columns of 2^log2n elements, col_stride_elems apart (0 = dense), t_nodes
+    (2*2^log2n - 1) * 32 bytes."""
     import torch
     if stream is None:
         stream = torch.cuda.current_stream().cuda_stream
     root = np.zeros(32, np.uint8)
-    check(L.lib().lw_stark_commit_columns_device(field.field, C.c_void_p(t_columns.data_ptr()), n_cols, 0, log2n,
+    check(L.lib().lw_stark_commit_columns_device(field.field, C.c_void_p(t_columns.data_ptr()), n_cols, int(col_stride_elems), log2n,
                                                  1 if bit_reverse else 0, C.c_void_p(t_nodes.data_ptr()),
                                                  root.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
     return root.tobytes()
 
 
-def commit_columns_layout_device(field, t_columns, n_cols, log2n, t_nodes, bit_reverse=True, stream=None):
+def commit_columns_layout_device(field, t_columns, n_cols, log2n, t_nodes, bit_reverse=True, col_stride_elems=0, stream=None):
     """commit_columns_device for any layout with an AsBytes in the reference (BabyBear u32 / u64-limb columns: the STARK LDE
     of BASELINE config 4)."""
     import torch
     if stream is None:
         stream = torch.cuda.current_stream().cuda_stream
     root = np.zeros(32, np.uint8)
-    check(L.lib().lw_stark_commit_columns_layout_device(field.field, field.layout, C.c_void_p(t_columns.data_ptr()), n_cols, 0, log2n,
+    check(L.lib().lw_stark_commit_columns_layout_device(field.field, field.layout, C.c_void_p(t_columns.data_ptr()), n_cols,
+                                                        int(col_stride_elems), log2n,
                                                         1 if bit_reverse else 0, C.c_void_p(t_nodes.data_ptr()),
                                                         root.ctypes.data_as(C.c_void_p), C.c_void_p(stream)))
     return root.tobytes()

@@ -99,9 +99,31 @@ def test_host_side_argument_checks_do_not_need_a_device():
         ("commit_columns_device row bytes", lambda: L.lw_stark_commit_columns_device(S, P, u32(1 << 26), sz(0), u32(0), i(0), P, N, N), _lib.ERR_BAD_ARG),
         ("commit_columns_layout_device ext4", lambda: L.lw_stark_commit_columns_layout_device(BB, EXT4, P, u32(1), sz(0), u32(2), i(0), P, N, N), _lib.ERR_BAD_ARG),
         ("commit_columns_layout_device null", lambda: L.lw_stark_commit_columns_layout_device(BB, R32, N, u32(1), sz(0), u32(2), i(0), P, N, N), _lib.ERR_BAD_ARG),
+        ("commit_columns_device column stride", lambda: L.lw_stark_commit_columns_device(S, P, u32(2), sz(3), u32(2), i(0), Q, N, N), _lib.ERR_BAD_ARG),
+        ("commit_columns_layout_device column stride", lambda: L.lw_stark_commit_columns_layout_device(BB, R32, P, u32(2), sz(3), u32(2), i(0), Q, N, N), _lib.ERR_BAD_ARG),
     ]
     got = {name: call() for name, call, _ in cases}
     assert got == {name: code for name, _, code in cases}
+
+
+def test_commit_wrappers_pass_the_column_stride_on():
+    """col_stride_elems of the two Keccak wrappers reaches the C entry: a stride below the column length comes back as that
+    entry's refusal, which is made before any device work (the pointers are host memory and are never followed)."""
+    from lambda_elliptic_curves_amd import errors, fft, merkle
+
+    class Buffer:
+        def __init__(self, nbytes):
+            self.a = np.zeros(nbytes, np.uint8)
+
+        def data_ptr(self):
+            return self.a.ctypes.data
+
+    cols, nodes = Buffer(2 * 4 * 32), Buffer(7 * 32)
+    for call, fld in ((merkle.commit_columns_device, fft.Stark252PrimeField), (merkle.commit_columns_device, fft.FrField),
+                      (merkle.commit_columns_layout_device, fft.Babybear31PrimeFieldU32), (merkle.commit_columns_layout_device, fft.Babybear31PrimeField)):
+        with pytest.raises(errors.HipError, match="column stride 3 below the column length"):
+            call(fld, cols, 2, 2, nodes, col_stride_elems=3, stream=0)
+    assert not cols.a.any() and not nodes.a.any()
 
 
 def test_product_never_touches_the_oracle():

@@ -40,13 +40,18 @@ def test_lde_then_commit_stays_on_device():
     assert root == O.merkle_commit_columns(exp_cols, True)[0].tobytes()
 
 
-@pytest.mark.parametrize("n_coeffs,domain", [(8, 16), (7, 8), (64, 256), (33, 64), (2, 2), (1024, 4096)])
-def test_fri_layer_matches_reference_composition(n_coeffs, domain):
+_FRI_SHAPES = [(8, 16), (7, 8), (64, 256), (33, 64), (2, 2), (1024, 4096)]
+
+
+# both 256-bit fields; the Stark252 cases keep the ids they had before Fr381 joined them
+@pytest.mark.parametrize("name,n_coeffs,domain", [("stark252", n, d) for n, d in _FRI_SHAPES] + [("fr381", n, d) for n, d in _FRI_SHAPES],
+                         ids=[f"{n}-{d}" for n, d in _FRI_SHAPES] + [f"fr381-{n}-{d}" for n, d in _FRI_SHAPES])
+def test_fri_layer_matches_reference_composition(name, n_coeffs, domain):
     # commit_phase loop body (provers/stark/src/fri/mod.rs:44-58) = 2*fold_polynomial + new_fri_layer (:115-141)
-    from lambda_elliptic_curves_amd import fft, merkle
-    from oracle import bigint_def as D
-    f, p = O.F_STARK252, D.P_STARK252
-    a = util.rand_elems("stark252", n_coeffs, 50 + n_coeffs)
+    from lambda_elliptic_curves_amd import merkle
+    fld, f = util.field_pairs()[name]
+    p = util.field_modulus(name)
+    a = util.rand_elems(name, n_coeffs, 50 + n_coeffs)
     a[-1, -1] |= np.uint64(1)
     zeta_c, off_c = 0x1234567890abcdef1234567, 9      # canonical challenge and (already squared) coset offset
     zeta, off = O.elems_to_mont(f, [zeta_c])[0], O.elems_to_mont(f, [off_c])[0]
@@ -58,7 +63,7 @@ def test_fri_layer_matches_reference_composition(n_coeffs, domain):
     exp_ev = O.bit_reverse_permute(f, O.evaluate_fft(f, exp_poly, 1, domain, off))
     leaves = exp_ev.reshape(domain // 2, 2, 4)            # chunks(2) of the permuted evaluation
     exp_nodes = O.merkle_commit_columns(np.ascontiguousarray(leaves.transpose(1, 0, 2)), bit_reverse=False)
-    poly, ev, root, nodes = merkle.fri_layer(fft.Stark252PrimeField, a, zeta, off, domain, return_nodes=True)
+    poly, ev, root, nodes = merkle.fri_layer(fld, a, zeta, off, domain, return_nodes=True)
     assert np.array_equal(poly, exp_poly)
     assert np.array_equal(ev, exp_ev)
     assert np.array_equal(nodes, exp_nodes) and root == exp_nodes[0].tobytes()

@@ -104,6 +104,8 @@ def test_argument_codes_need_no_device():
         ("commit_device single, 2 columns", lambda: L.lw_poseidon_commit_columns_device(P, u32(2), u64(0), u32(2), i(0), SINGLE, Q, N, N), BAD),
         ("commit bad leaf mode", lambda: L.lw_poseidon_commit_columns(P, u32(1), u32(2), i(0), i(2), Q, N), BAD),
         ("commit_device bad leaf mode", lambda: L.lw_poseidon_commit_columns_device(P, u32(1), u64(0), u32(2), i(0), i(-1), Q, N, N), BAD),
+        # columns that would overlap
+        ("commit_device column stride", lambda: L.lw_poseidon_commit_columns_device(P, u32(2), u64(3), u32(2), i(0), MANY, Q, N, N), BAD),
         # sizes past what can be addressed
         ("commit 2^32 leaves", lambda: L.lw_poseidon_commit_columns(P, u32(1), u32(32), i(0), MANY, Q, N), ALLOC),
         ("commit_device 2^32 leaves", lambda: L.lw_poseidon_commit_columns_device(P, u32(1), u64(0), u32(32), i(0), SINGLE, Q, N, N), ALLOC),
