@@ -1,11 +1,16 @@
-// The Merkle tree of an algebraic hash, written once for poseidon.hip and rpo.hip: three kernels, the schedule that
-// launches them, the argument helpers and the two commit_columns entry bodies.  A hash is a compile-time policy H, a
-// struct of constants and static __device__ __forceinline__ functions over byte addresses, so every kernel holds a
-// single inlined copy of H's permutation:
+// The Merkle tree of an algebraic hash and the host side of its entry points, written once for poseidon.hip, rpo.hip,
+// pedersen.hip and monolith.hip: three kernels, the schedule that launches them, the argument checks and the entry bodies
+// (flat batches and commit_columns).  A hash is a compile-time policy H, a struct of constants and static
+// __device__ __forceinline__ functions over byte addresses, so every kernel holds a single inlined copy of H's permutation:
 //   H::DIGEST_BYTES, H::ELEM_BYTES             a digest (a tree node), an input element
 //   H::parent(x, y, out)                       out = the parent of the digests at x and at y
 //   H::row(row, len, elem_stride, mode, out)   out = the digest of the `len` elements row[c * elem_stride], c = 0 .. len - 1;
 //                                              `mode` is H's own (Poseidon's leaf rule), wave-uniform like len
+//   H::ready(c)                                host: whatever parent and row read beyond their arguments (a table of the
+//                                              library, table_once below) is on the device; LW_OK at once if there is none.
+//                                              tree_pair_device and tree_rows_device call it before they launch, inside the
+//                                              call's one Entry, so a table and the kernels that read it share one hold of
+//                                              the lane and of SharedState::rw: no lw_hip_init can move the library between them
 #pragma once
 #include <string.h>
 #include <initializer_list>
@@ -65,14 +70,29 @@ static int launch_1d(Context &c, const char *name, void (*kernel)(P...), uint32_
 
 struct TreeNames { const char *rows, *pair, *top; };   // the profile lines of a hash's three kernels
 
+// A table of the library (a __device__ or __constant__ variable), filled from `host` before the first kernel that reads it
+// is enqueued.  `ready` lives with the shared state (one table per device, whichever lane asks first) and is cleared when
+// the device changes.
+template <class T> static int table_once(Context &c, bool &ready, const T &symbol, const void *host, size_t bytes) {
+    if (ready) return LW_OK;
+    ExclusiveScope excl(c);
+    if (ready) return LW_OK;
+    LW_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(symbol), host, bytes), LW_ERR_LAUNCH);
+    LW_HIP_CHECK(hipStreamSynchronize(nullptr), LW_ERR_LAUNCH);   // the lanes' streams do not wait for the null stream
+    ready = true;
+    return LW_OK;
+}
+
 template <class H>
 static int tree_pair_device(Context &c, const char *name, const void *d_x, const void *d_y, uint64_t stride, uint64_t n, void *d_out, hipStream_t s) {
-    return launch_1d(c, name, tree_pair_kernel<H>, blocks_for(n), s, d_x, d_y, stride, n, d_out);
+    const int rc = H::ready(c);
+    return rc ? rc : launch_1d(c, name, tree_pair_kernel<H>, blocks_for(n), s, d_x, d_y, stride, n, d_out);
 }
 template <class H>
 static int tree_rows_device(Context &c, const char *name, const void *d_base, uint64_t n, uint32_t len, uint64_t row_stride, uint64_t elem_stride,
                             int bitrev_bits, int mode, void *d_out, hipStream_t s) {
-    return launch_1d(c, name, tree_rows_kernel<H>, blocks_for(n), s, d_base, n, len, row_stride, elem_stride, bitrev_bits, mode, d_out);
+    const int rc = H::ready(c);
+    return rc ? rc : launch_1d(c, name, tree_rows_kernel<H>, blocks_for(n), s, d_base, n, len, row_stride, elem_stride, bitrev_bits, mode, d_out);
 }
 
 // d_nodes: (2 * 2^log2n - 1) digests, root first (crypto/src/merkle_tree/utils.rs:43-71: the level of 2^m nodes starts at
@@ -138,8 +158,82 @@ static int flat_check(uint64_t count, uint64_t limit, const char *noun, std::ini
     }
     return LW_OK;
 }
+// n_rows rows of row_len `unit`s ("elements", "words"), row_stride >= row_len apart; rows may be null when row_len = 0:
+// no row data is read
+static int rows_check(size_t n_rows, size_t row_len, size_t row_stride, uint64_t limit, const char *noun, const char *unit, const void *rows,
+                      const void *out, bool device) {
+    if (row_stride < row_len) { set_error("row stride %zu below the row length %zu", row_stride, row_len); return LW_ERR_BAD_ARG; }
+    if (row_len > ((size_t)1 << 31) || (row_stride && n_rows > (limit << 4) / row_stride)) {
+        set_error("%zu rows of %zu %s", n_rows, row_stride, unit);
+        return LW_ERR_ALLOC;
+    }
+    return row_len ? flat_check(n_rows, limit, noun, {rows, out}, device) : flat_check(n_rows, limit, noun, {out}, device);
+}
+// both commitment forms, after the hash's own lines; nodes_or_root: d_nodes (device form) or out_root (host form);
+// col_stride in elements, 0 = dense
+static int tree_commit_check(const void *columns, const void *nodes_or_root, uint32_t n_cols, uint64_t col_stride, uint32_t log2n,
+                             uint32_t max_log2n, bool device) {
+    if (!columns || !nodes_or_root || n_cols == 0) { set_error("null buffer or no columns"); return LW_ERR_BAD_ARG; }
+    if (device && (!aligned16(columns) || !aligned16(nodes_or_root))) { set_error("device buffers must be 16-byte aligned"); return LW_ERR_BAD_ARG; }
+    if (log2n > max_log2n) { set_error("2^%u leaves", log2n); return LW_ERR_ALLOC; }
+    if (col_stride && col_stride < (1ull << log2n)) {
+        set_error("column stride %llu below the column length", (unsigned long long)col_stride);
+        return LW_ERR_BAD_ARG;
+    }
+    return LW_OK;
+}
 
-// ---- the bodies of commit_columns, after the hash's own argument checks
+// ---- the body of a flat entry point, after its checks: `in` are the one or two inputs (pointer, bytes), `out` the output.
+// Device form: run(c, the caller's inputs, out, the caller's stream), enqueued only.  Host form, complete on return: the
+// inputs staged back to back in host_io_a on the lane's stream (an empty one is not copied), run, the output downloaded
+// from host_io_b, or with in_place from host_io_a, where run overwrote input 0.
+struct FlatIn { const void *p; size_t bytes; };
+template <class Run>
+static int flat_entry(void *hip_stream, bool device, std::initializer_list<FlatIn> in, void *out, size_t out_bytes, bool in_place, Run run) {
+    Entry en(hip_stream);
+    if (en.rc) return en.rc;
+    const void *d_in[2];
+    int k = 0;
+    if (device) {
+        for (const FlatIn &i : in) d_in[k++] = i.p;
+        return run(en.c, d_in, out, en.stream);
+    }
+    hipStream_t s = en.use_lane_stream();
+    if (!s) return en.rc;
+    Context &c = en.c;
+    size_t in_bytes = 0;
+    for (const FlatIn &i : in) in_bytes += i.bytes;
+    if (c.host_io_a.ensure(in_bytes ? in_bytes : 16) || (!in_place && c.host_io_b.ensure(out_bytes))) return LW_ERR_ALLOC;
+    char *at = (char *)c.host_io_a.p;
+    int rc = LW_OK;
+    for (const FlatIn &i : in) {
+        if (!rc && i.bytes) rc = upload(at, i.p, i.bytes, s);
+        d_in[k++] = at;
+        at += i.bytes;
+    }
+    void *d_out = in_place ? c.host_io_a.p : c.host_io_b.p;
+    if (!rc) rc = run(c, d_in, d_out, s);
+    return rc ? rc : download(out, d_out, out_bytes, s);
+}
+// the two flat hashes of H as entry bodies: out[i] = parent(x[i], y[i]); out[i] = H::row of row i, the rows row_stride
+// apart (the host form's are dense: row_stride = row_len)
+template <class H>
+static int tree_pair_entry(const char *name, const void *x, const void *y, size_t n, void *out, void *hip_stream, bool device) {
+    const size_t bytes = n * H::DIGEST_BYTES;
+    return flat_entry(hip_stream, device, {{x, bytes}, {y, bytes}}, out, bytes, false, [&](Context &c, const void *const *d_in, void *d_out, hipStream_t s) {
+        return tree_pair_device<H>(c, name, d_in[0], d_in[1], 1, n, d_out, s);
+    });
+}
+template <class H>
+static int tree_rows_entry(const char *name, const void *rows, size_t n_rows, size_t row_len, size_t row_stride, int mode, void *out,
+                           void *hip_stream, bool device) {
+    return flat_entry(hip_stream, device, {{rows, n_rows * row_len * H::ELEM_BYTES}}, out, n_rows * H::DIGEST_BYTES, false,
+                      [&](Context &c, const void *const *d_in, void *d_out, hipStream_t s) {
+                          return tree_rows_device<H>(c, name, d_in[0], n_rows, (uint32_t)row_len, row_stride, 1, -1, mode, d_out, s);
+                      });
+}
+
+// ---- the bodies of commit_columns, after the argument checks
 // device form: col_stride in elements, 0 = dense; the root goes to out_root (the stream is waited for) unless it is null
 template <class H>
 static int tree_commit_columns_device(const TreeNames &names, const void *d_columns, uint32_t n_cols, uint64_t col_stride, uint32_t log2n,

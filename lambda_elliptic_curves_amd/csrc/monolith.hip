@@ -106,17 +106,8 @@ static const MonolithTable &monolith_host_table() {   // every instance, generat
     });
     return table;
 }
-// MONOLITH_TABLE is filled before the first kernel that reads it is enqueued.  The flag lives with the shared state (one
-// table per device, whichever lane asks first) and is cleared when the device changes.
-static int ensure_monolith_table(Context &c) {
-    SharedState &sh = shared_state();
-    if (sh.monolith_table_ready) return LW_OK;
-    ExclusiveScope excl(c);
-    if (sh.monolith_table_ready) return LW_OK;
-    LW_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(MONOLITH_TABLE), &monolith_host_table(), sizeof(MonolithTable)), LW_ERR_LAUNCH);
-    LW_HIP_CHECK(hipStreamSynchronize(nullptr), LW_ERR_LAUNCH);   // the lanes' streams do not wait for the null stream
-    sh.monolith_table_ready = true;
-    return LW_OK;
+static int monolith_ready(Context &c) {   // before the first kernel that reads MONOLITH_TABLE is enqueued
+    return table_once(c, shared_state().monolith_table_ready, MONOLITH_TABLE, &monolith_host_table(), sizeof(MonolithTable));
 }
 
 // ---- kernels: one state per work-item; a state is W words, 16-byte aligned (W is a multiple of 4)
@@ -161,6 +152,7 @@ template <int W> __global__ __launch_bounds__(256) void monolith_layer_kernel(co
 // The policy of hash_tree.cuh over the width-16 permutation with R rounds: an element is a word, a digest 8 words.
 template <int R> struct MonolithHash {
     static constexpr uint64_t DIGEST_BYTES = 32, ELEM_BYTES = 4;
+    static int ready(Context &c) { return monolith_ready(c); }
     static __device__ __forceinline__ void permute(uint32_t (&s)[16]) { monolith_permute<16>(s, R, monolith_rc_of<16>(MONOLITH_TABLE, R), nullptr); }
     // compress: permute(left || right)[0..8]
     static __device__ __forceinline__ void parent(const char *x, const char *y, char *out) {
@@ -218,24 +210,11 @@ template <class F> static int monolith_with_width(uint32_t width, F f) {
 }
 
 static int monolith_permute_device(Context &c, uint32_t width, uint32_t rounds, const void *d_in, void *d_out, uint64_t n, hipStream_t s) {
-    const int rc = ensure_monolith_table(c);
+    const int rc = monolith_ready(c);
     if (rc) return rc;
     return monolith_with_width(width, [&](auto w) {
         return launch_1d(c, "monolith_permute_kernel", monolith_permute_kernel<decltype(w)::value>, blocks_for(n), s, d_in, d_out, n, rounds);
     });
-}
-static int monolith_rows_device(Context &c, uint32_t rounds, const void *d_rows, uint64_t n, size_t row_len, uint64_t row_stride, void *d_out,
-                                hipStream_t s) {
-    const int rc = ensure_monolith_table(c);
-    if (rc) return rc;
-    return monolith_with_rounds(rounds, [&](auto h) {
-        return tree_rows_device<decltype(h)>(c, MONOLITH_NAMES.rows, d_rows, n, (uint32_t)row_len, row_stride, 1, -1, 0, d_out, s);
-    });
-}
-static int monolith_pair_device(Context &c, uint32_t rounds, const void *d_x, const void *d_y, uint64_t n, void *d_out, hipStream_t s) {
-    const int rc = ensure_monolith_table(c);
-    if (rc) return rc;
-    return monolith_with_rounds(rounds, [&](auto h) { return tree_pair_device<decltype(h)>(c, MONOLITH_NAMES.pair, d_x, d_y, 1, n, d_out, s); });
 }
 
 // ---- argument checks: one per entry-point family, run before any device work
@@ -270,23 +249,49 @@ static int permute_entry(uint32_t width, uint32_t rounds, const void *states, si
     int rc = instance_check(width, rounds);
     if (!rc) rc = flat_check(n, MONOLITH_MAX_N, "Monolith", {states, out}, device);
     if (rc || n == 0) return rc;
-    Entry en(hip_stream);
-    if (en.rc) return en.rc;
-    if (device) return monolith_permute_device(en.c, width, rounds, states, out, n, en.stream);
-    hipStream_t s = en.use_lane_stream();
-    if (!s) return en.rc;
-    Context &c = en.c;
     const size_t bytes = n * width * 4;
-    if (c.host_io_a.ensure(bytes)) return LW_ERR_ALLOC;
-    int r = upload(c.host_io_a.p, states, bytes, s);
-    if (!r) r = monolith_permute_device(c, width, rounds, c.host_io_a.p, c.host_io_a.p, n, s);
-    return r ? r : download(out, c.host_io_a.p, bytes, s);
+    return flat_entry(hip_stream, device, {{states, bytes}}, out, bytes, true, [&](Context &c, const void *const *d_in, void *d_out, hipStream_t s) {
+        return monolith_permute_device(c, width, rounds, d_in[0], d_out, n, s);
+    });
 }
 int lw_monolith_permute(uint32_t width, uint32_t rounds, const uint32_t *states, size_t n, uint32_t *out) {
     return permute_entry(width, rounds, states, n, out, nullptr, false);
 }
 int lw_monolith_permute_device(uint32_t width, uint32_t rounds, const uint32_t *d_states, size_t n, uint32_t *d_out, void *hip_stream) {
     return permute_entry(width, rounds, d_states, n, d_out, hip_stream, true);
+}
+
+static int hash_entry(uint32_t rounds, const void *rows, size_t n_rows, size_t row_len, size_t row_stride, void *out, void *hip_stream,
+                      bool device) {
+    if (row_stride == 0) row_stride = row_len;
+    int rc = rounds_check(rounds);
+    if (!rc) rc = rows_check(n_rows, row_len, row_stride, MONOLITH_MAX_N, "Monolith", "words", rows, out, device);
+    if (rc || n_rows == 0) return rc;
+    return monolith_with_rounds(rounds, [&](auto h) {
+        return tree_rows_entry<decltype(h)>(MONOLITH_NAMES.rows, rows, n_rows, row_len, row_stride, 0, out, hip_stream, device);
+    });
+}
+int lw_monolith_hash(uint32_t rounds, const uint32_t *rows, size_t n_rows, size_t row_len, uint32_t *out) {
+    return hash_entry(rounds, rows, n_rows, row_len, 0, out, nullptr, false);
+}
+int lw_monolith_hash_device(uint32_t rounds, const uint32_t *d_rows, size_t n_rows, size_t row_len, size_t row_stride, uint32_t *d_out,
+                            void *hip_stream) {
+    return hash_entry(rounds, d_rows, n_rows, row_len, row_stride, d_out, hip_stream, true);
+}
+
+static int compress_entry(uint32_t rounds, const void *left, const void *right, size_t n, void *out, void *hip_stream, bool device) {
+    int rc = rounds_check(rounds);
+    if (!rc) rc = flat_check(n, MONOLITH_MAX_N, "Monolith", {left, right, out}, device);
+    if (rc || n == 0) return rc;
+    return monolith_with_rounds(rounds, [&](auto h) {
+        return tree_pair_entry<decltype(h)>(MONOLITH_NAMES.pair, left, right, n, out, hip_stream, device);
+    });
+}
+int lw_monolith_compress(uint32_t rounds, const uint32_t *left, const uint32_t *right, size_t n, uint32_t *out) {
+    return compress_entry(rounds, left, right, n, out, nullptr, false);
+}
+int lw_monolith_compress_device(uint32_t rounds, const uint32_t *d_left, const uint32_t *d_right, size_t n, uint32_t *d_out, void *hip_stream) {
+    return compress_entry(rounds, d_left, d_right, n, d_out, hip_stream, true);
 }
 
 int lw_monolith_layer_device(uint32_t width, uint32_t rounds, lw_monolith_layer_t layer, const uint32_t *d_states, size_t n, uint32_t *d_out,
@@ -301,7 +306,7 @@ int lw_monolith_layer_device(uint32_t width, uint32_t rounds, lw_monolith_layer_
     if (rc || n == 0) return rc;
     Entry en(hip_stream);
     if (en.rc) return en.rc;
-    rc = ensure_monolith_table(en.c);
+    rc = monolith_ready(en.c);
     if (rc) return rc;
     return monolith_with_width(width, [&](auto w) {
         return launch_1d(en.c, "monolith_layer_kernel", monolith_layer_kernel<decltype(w)::value>, blocks_for(n), en.stream, d_states, d_out,
@@ -309,85 +314,15 @@ int lw_monolith_layer_device(uint32_t width, uint32_t rounds, lw_monolith_layer_
     });
 }
 
-static int hash_entry(uint32_t rounds, const void *rows, size_t n_rows, size_t row_len, size_t row_stride, void *out, void *hip_stream,
-                      bool device) {
-    int rc = rounds_check(rounds);
-    if (rc) return rc;
-    if (row_stride == 0) row_stride = row_len;
-    if (row_stride < row_len) { set_error("row stride %zu below the row length %zu", row_stride, row_len); return LW_ERR_BAD_ARG; }
-    if (row_len > ((size_t)1 << 31) || (row_stride && n_rows > (MONOLITH_MAX_N << 4) / row_stride)) {
-        set_error("%zu rows of %zu words", n_rows, row_stride);
-        return LW_ERR_ALLOC;
-    }
-    rc = row_len ? flat_check(n_rows, MONOLITH_MAX_N, "Monolith", {rows, out}, device)
-                 : flat_check(n_rows, MONOLITH_MAX_N, "Monolith", {out}, device);   // no row data: rows is not read
-    if (rc || n_rows == 0) return rc;
-    Entry en(hip_stream);
-    if (en.rc) return en.rc;
-    if (device) return monolith_rows_device(en.c, rounds, rows, n_rows, row_len, row_stride, out, en.stream);
-    hipStream_t s = en.use_lane_stream();
-    if (!s) return en.rc;
-    Context &c = en.c;
-    const size_t in_bytes = n_rows * row_len * 4, out_bytes = n_rows * 32;
-    if (c.host_io_a.ensure(in_bytes ? in_bytes : 16) || c.host_io_b.ensure(out_bytes)) return LW_ERR_ALLOC;
-    int r = in_bytes ? upload(c.host_io_a.p, rows, in_bytes, s) : LW_OK;
-    if (!r) r = monolith_rows_device(c, rounds, c.host_io_a.p, n_rows, row_len, row_len, c.host_io_b.p, s);
-    return r ? r : download(out, c.host_io_b.p, out_bytes, s);
-}
-int lw_monolith_hash(uint32_t rounds, const uint32_t *rows, size_t n_rows, size_t row_len, uint32_t *out) {
-    return hash_entry(rounds, rows, n_rows, row_len, 0, out, nullptr, false);
-}
-int lw_monolith_hash_device(uint32_t rounds, const uint32_t *d_rows, size_t n_rows, size_t row_len, size_t row_stride, uint32_t *d_out,
-                            void *hip_stream) {
-    return hash_entry(rounds, d_rows, n_rows, row_len, row_stride, d_out, hip_stream, true);
-}
-
-static int compress_entry(uint32_t rounds, const void *left, const void *right, size_t n, void *out, void *hip_stream, bool device) {
-    int rc = rounds_check(rounds);
-    if (!rc) rc = flat_check(n, MONOLITH_MAX_N, "Monolith", {left, right, out}, device);
-    if (rc || n == 0) return rc;
-    Entry en(hip_stream);
-    if (en.rc) return en.rc;
-    if (device) return monolith_pair_device(en.c, rounds, left, right, n, out, en.stream);
-    hipStream_t s = en.use_lane_stream();
-    if (!s) return en.rc;
-    Context &c = en.c;
-    if (c.host_io_a.ensure(n * 64) || c.host_io_b.ensure(n * 32)) return LW_ERR_ALLOC;
-    char *dl = (char *)c.host_io_a.p, *dr = dl + n * 32;
-    int r = upload(dl, left, n * 32, s);
-    if (!r) r = upload(dr, right, n * 32, s);
-    if (!r) r = monolith_pair_device(c, rounds, dl, dr, n, c.host_io_b.p, s);
-    return r ? r : download(out, c.host_io_b.p, n * 32, s);
-}
-int lw_monolith_compress(uint32_t rounds, const uint32_t *left, const uint32_t *right, size_t n, uint32_t *out) {
-    return compress_entry(rounds, left, right, n, out, nullptr, false);
-}
-int lw_monolith_compress_device(uint32_t rounds, const uint32_t *d_left, const uint32_t *d_right, size_t n, uint32_t *d_out, void *hip_stream) {
-    return compress_entry(rounds, d_left, d_right, n, d_out, hip_stream, true);
-}
-
 // checks of both commitment forms; nodes_or_root: d_nodes (device form) or out_root (host form)
 static int commit_check(uint32_t rounds, const void *columns, const void *nodes_or_root, uint32_t n_cols, uint64_t col_stride, uint32_t log2n,
                         bool device) {
     const int rc = rounds_check(rounds);
-    if (rc) return rc;
-    if (!columns || !nodes_or_root || n_cols == 0) { set_error("null buffer or no columns"); return LW_ERR_BAD_ARG; }
-    if (device && (!aligned16(columns) || !aligned16(nodes_or_root))) { set_error("device buffers must be 16-byte aligned"); return LW_ERR_BAD_ARG; }
-    if (log2n > 30) { set_error("2^%u leaves", log2n); return LW_ERR_ALLOC; }
-    if (col_stride && col_stride < (1ull << log2n)) {
-        set_error("column stride %llu below the column length", (unsigned long long)col_stride);
-        return LW_ERR_BAD_ARG;
-    }
-    return LW_OK;
-}
-static int table_for_commit(void *hip_stream) {   // in a call of its own: the tree_commit_columns bodies take the lane themselves
-    Entry en(hip_stream);
-    return en.rc ? en.rc : ensure_monolith_table(en.c);
+    return rc ? rc : tree_commit_check(columns, nodes_or_root, n_cols, col_stride, log2n, 30, device);
 }
 int lw_monolith_commit_columns_device(uint32_t rounds, const uint32_t *d_columns, uint32_t n_cols, uint64_t col_stride, uint32_t log2n,
                                       int bit_reverse, uint32_t *d_nodes, uint32_t *out_root, void *hip_stream) {
-    int rc = commit_check(rounds, d_columns, d_nodes, n_cols, col_stride, log2n, true);
-    if (!rc) rc = table_for_commit(hip_stream);
+    const int rc = commit_check(rounds, d_columns, d_nodes, n_cols, col_stride, log2n, true);
     if (rc) return rc;
     return monolith_with_rounds(rounds, [&](auto h) {
         return tree_commit_columns_device<decltype(h)>(MONOLITH_NAMES, d_columns, n_cols, col_stride, log2n, bit_reverse, 0, d_nodes, out_root, hip_stream);
@@ -395,8 +330,7 @@ int lw_monolith_commit_columns_device(uint32_t rounds, const uint32_t *d_columns
 }
 int lw_monolith_commit_columns(uint32_t rounds, const uint32_t *columns, uint32_t n_cols, uint32_t log2n, int bit_reverse, uint32_t *out_root,
                                uint32_t *out_nodes_or_null) {
-    int rc = commit_check(rounds, columns, out_root, n_cols, 0, log2n, false);
-    if (!rc) rc = table_for_commit(nullptr);
+    const int rc = commit_check(rounds, columns, out_root, n_cols, 0, log2n, false);
     if (rc) return rc;
     return monolith_with_rounds(rounds, [&](auto h) {
         return tree_commit_columns_host<decltype(h)>(MONOLITH_NAMES, columns, n_cols, log2n, bit_reverse, 0, out_root, out_nodes_or_null);

@@ -12,8 +12,18 @@
 
 namespace lw {
 
+static const void *pedersen_host_table() {   // generated once per process
+    alignas(16) static char table[PEDERSEN_TABLE_BYTES];
+    static std::once_flag once;
+    std::call_once(once, [] { pedersen_fill_table(table); });
+    return table;
+}
+
 struct PedersenHash {   // the policy of hash_tree.cuh: an element and a digest are one Stark252 element
     static constexpr uint64_t DIGEST_BYTES = 32, ELEM_BYTES = 32;
+    static int ready(Context &c) {   // parent reads PEDERSEN_TABLE
+        return table_once(c, shared_state().pedersen_table_ready, PEDERSEN_TABLE, pedersen_host_table(), PEDERSEN_TABLE_BYTES);
+    }
     static __device__ __forceinline__ void parent(const char *x, const char *y, char *out) {
         fe_store<Stark252>(out, pedersen_hash(fe_load<Stark252>(x), fe_load<Stark252>(y), PEDERSEN_TABLE));
     }
@@ -43,31 +53,6 @@ __global__ __launch_bounds__(256) void pedersen_add_affine_kernel(const char *p,
     fe_store<Stark252>(out + i * 64 + 32, r.y);
 }
 
-// ---- the tables: generated once per process, uploaded once per device
-static const void *pedersen_host_table() {
-    alignas(16) static char table[PEDERSEN_TABLE_BYTES];
-    static std::once_flag once;
-    std::call_once(once, [] { pedersen_fill_table(table); });
-    return table;
-}
-// PEDERSEN_TABLE is filled before the first kernel that reads it is enqueued.  The flag lives with the shared state (one
-// table per device, whichever lane asks first) and is cleared when the device changes.
-static int ensure_pedersen_table(Context &c) {
-    SharedState &sh = shared_state();
-    if (sh.pedersen_table_ready) return LW_OK;
-    ExclusiveScope excl(c);
-    if (sh.pedersen_table_ready) return LW_OK;
-    LW_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(PEDERSEN_TABLE), pedersen_host_table(), PEDERSEN_TABLE_BYTES), LW_ERR_LAUNCH);
-    LW_HIP_CHECK(hipStreamSynchronize(nullptr), LW_ERR_LAUNCH);   // the lanes' streams do not wait for the null stream
-    sh.pedersen_table_ready = true;
-    return LW_OK;
-}
-
-static int pedersen_pair_device(Context &c, const void *d_x, const void *d_y, uint64_t n, void *d_out, hipStream_t s) {
-    const int rc = ensure_pedersen_table(c);
-    return rc ? rc : tree_pair_device<PedersenHash>(c, PEDERSEN_NAMES.pair, d_x, d_y, 1, n, d_out, s);
-}
-
 static constexpr uint64_t PEDERSEN_MAX_N = (uint64_t)1 << 36;   // the grid's block index stays below 2^31
 
 }  // namespace lw
@@ -85,18 +70,7 @@ int lw_pedersen_table(void *out) {
 static int hash_entry(const void *x, const void *y, size_t n, void *out, void *hip_stream, bool device) {
     const int rc = flat_check(n, PEDERSEN_MAX_N, "Pedersen", {x, y, out}, device);
     if (rc || n == 0) return rc;
-    Entry en(hip_stream);
-    if (en.rc) return en.rc;
-    if (device) return pedersen_pair_device(en.c, x, y, n, out, en.stream);
-    hipStream_t s = en.use_lane_stream();
-    if (!s) return en.rc;
-    Context &c = en.c;
-    if (c.host_io_a.ensure(n * 64) || c.host_io_b.ensure(n * 32)) return LW_ERR_ALLOC;
-    char *dx = (char *)c.host_io_a.p, *dy = dx + n * 32;
-    int r = upload(dx, x, n * 32, s);
-    if (!r) r = upload(dy, y, n * 32, s);
-    if (!r) r = pedersen_pair_device(c, dx, dy, n, c.host_io_b.p, s);
-    return r ? r : download(out, c.host_io_b.p, n * 32, s);
+    return tree_pair_entry<PedersenHash>(PEDERSEN_NAMES.pair, x, y, n, out, hip_stream, device);
 }
 int lw_pedersen_hash(const void *x, const void *y, size_t n, void *out) { return hash_entry(x, y, n, out, nullptr, false); }
 int lw_pedersen_hash_device(const void *d_x, const void *d_y, size_t n, void *d_out, void *hip_stream) {
@@ -115,31 +89,17 @@ int lw_pedersen_add_affine_device(const void *d_p, const void *d_z, const void *
 static int commit_check(const void *leaves, const void *nodes_or_root, uint32_t n_cols, uint32_t log2n, bool device) {
     if (!leaves || !nodes_or_root) { set_error("null buffer"); return LW_ERR_BAD_ARG; }
     if (n_cols != 1) { set_error("a Pedersen tree commits one column of leaf values, not %u", n_cols); return LW_ERR_BAD_ARG; }
-    if (device && (!aligned16(leaves) || !aligned16(nodes_or_root))) { set_error("device buffers must be 16-byte aligned"); return LW_ERR_BAD_ARG; }
-    if (log2n > 31) { set_error("2^%u leaves", log2n); return LW_ERR_ALLOC; }
-    return LW_OK;
+    return tree_commit_check(leaves, nodes_or_root, 1, 0, log2n, 31, device);
 }
 int lw_pedersen_commit_leaves_device(const void *d_leaves, uint32_t n_cols, uint32_t log2n, int bit_reverse, void *d_nodes, uint8_t *out_root,
                                      void *hip_stream) {
-    int rc = commit_check(d_leaves, d_nodes, n_cols, log2n, true);
+    const int rc = commit_check(d_leaves, d_nodes, n_cols, log2n, true);
     if (rc) return rc;
-    {
-        Entry en(hip_stream);   // the table first, in a call of its own: tree_commit_columns_device takes the lane itself
-        if (en.rc) return en.rc;
-        rc = ensure_pedersen_table(en.c);
-        if (rc) return rc;
-    }
     return tree_commit_columns_device<PedersenHash>(PEDERSEN_NAMES, d_leaves, 1, 0, log2n, bit_reverse, 0, d_nodes, out_root, hip_stream);
 }
 int lw_pedersen_commit_leaves(const void *leaves, uint32_t n_cols, uint32_t log2n, int bit_reverse, uint8_t *out_root, uint8_t *out_nodes_or_null) {
-    int rc = commit_check(leaves, out_root, n_cols, log2n, false);
+    const int rc = commit_check(leaves, out_root, n_cols, log2n, false);
     if (rc) return rc;
-    {
-        Entry en(nullptr);
-        if (en.rc) return en.rc;
-        rc = ensure_pedersen_table(en.c);
-        if (rc) return rc;
-    }
     return tree_commit_columns_host<PedersenHash>(PEDERSEN_NAMES, leaves, 1, log2n, bit_reverse, 0, out_root, out_nodes_or_null);
 }
 

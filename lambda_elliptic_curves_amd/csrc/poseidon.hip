@@ -32,6 +32,7 @@ __global__ __launch_bounds__(256) void poseidon_permute_kernel(const char *in, c
 
 struct PoseidonHash {   // the policy of hash_tree.cuh: an element and a digest are one Stark252 element
     static constexpr uint64_t DIGEST_BYTES = 32, ELEM_BYTES = 32;
+    static int ready(Context &) { return LW_OK; }   // the round keys come with the code object
     // word 0 of permute(x, y, 2) (mod.rs:59-64)
     static __device__ __forceinline__ void parent(const char *x, const char *y, char *out) {
         PFe s[3] = {fe_load<Stark252>(x), fe_load<Stark252>(y), poseidon_small(2)};
@@ -61,16 +62,6 @@ struct PoseidonHash {   // the policy of hash_tree.cuh: an element and a digest 
 };
 static constexpr TreeNames POSEIDON_NAMES = {"poseidon_sponge_kernel", "poseidon_pair_kernel", "poseidon_top_kernel"};
 
-static int poseidon_permute_device(Context &c, const void *d_in, void *d_out, uint64_t n, hipStream_t s) {
-    return launch_1d(c, "poseidon_permute_kernel", poseidon_permute_kernel, blocks_for(n), s, d_in, d_out, n);
-}
-static int poseidon_pair_device(Context &c, const void *d_x, const void *d_y, uint64_t n, void *d_out, hipStream_t s) {
-    return tree_pair_device<PoseidonHash>(c, POSEIDON_NAMES.pair, d_x, d_y, 1, n, d_out, s);
-}
-static int poseidon_rows_device(Context &c, const void *d_rows, uint64_t n, size_t row_len, bool single, void *d_out, hipStream_t s) {
-    return tree_rows_device<PoseidonHash>(c, POSEIDON_NAMES.rows, d_rows, n, (uint32_t)row_len, row_len, 1, -1, single, d_out, s);
-}
-
 // ---- argument checks: one per entry-point family, run before any device work
 static constexpr uint64_t POSEIDON_MAX_N = (uint64_t)1 << 36;   // the grid's block index stays below 2^31
 
@@ -83,16 +74,9 @@ extern "C" {
 static int permute_entry(const void *states, size_t n, void *out, void *hip_stream, bool device) {
     const int rc = flat_check(n, POSEIDON_MAX_N, "Poseidon", {states, out}, device);
     if (rc || n == 0) return rc;
-    Entry en(hip_stream);
-    if (en.rc) return en.rc;
-    if (device) return poseidon_permute_device(en.c, states, out, n, en.stream);
-    hipStream_t s = en.use_lane_stream();
-    if (!s) return en.rc;
-    Context &c = en.c;
-    if (c.host_io_a.ensure(n * 96)) return LW_ERR_ALLOC;
-    int r = upload(c.host_io_a.p, states, n * 96, s);
-    if (!r) r = poseidon_permute_device(c, c.host_io_a.p, c.host_io_a.p, n, s);
-    return r ? r : download(out, c.host_io_a.p, n * 96, s);
+    return flat_entry(hip_stream, device, {{states, n * 96}}, out, n * 96, true, [&](Context &c, const void *const *d_in, void *d_out, hipStream_t s) {
+        return launch_1d(c, "poseidon_permute_kernel", poseidon_permute_kernel, blocks_for(n), s, d_in[0], d_out, (uint64_t)n);
+    });
 }
 int lw_poseidon_permute(const void *states, size_t n, void *out) { return permute_entry(states, n, out, nullptr, false); }
 int lw_poseidon_permute_device(const void *d_states, size_t n, void *d_out, void *hip_stream) {
@@ -102,18 +86,7 @@ int lw_poseidon_permute_device(const void *d_states, size_t n, void *d_out, void
 static int hash_entry(const void *x, const void *y, size_t n, void *out, void *hip_stream, bool device) {
     const int rc = flat_check(n, POSEIDON_MAX_N, "Poseidon", {x, y, out}, device);
     if (rc || n == 0) return rc;
-    Entry en(hip_stream);
-    if (en.rc) return en.rc;
-    if (device) return poseidon_pair_device(en.c, x, y, n, out, en.stream);
-    hipStream_t s = en.use_lane_stream();
-    if (!s) return en.rc;
-    Context &c = en.c;
-    if (c.host_io_a.ensure(n * 64) || c.host_io_b.ensure(n * 32)) return LW_ERR_ALLOC;
-    char *dx = (char *)c.host_io_a.p, *dy = dx + n * 32;
-    int r = upload(dx, x, n * 32, s);
-    if (!r) r = upload(dy, y, n * 32, s);
-    if (!r) r = poseidon_pair_device(c, dx, dy, n, c.host_io_b.p, s);
-    return r ? r : download(out, c.host_io_b.p, n * 32, s);
+    return tree_pair_entry<PoseidonHash>(POSEIDON_NAMES.pair, x, y, n, out, hip_stream, device);
 }
 int lw_poseidon_hash(const void *x, const void *y, size_t n, void *out) { return hash_entry(x, y, n, out, nullptr, false); }
 int lw_poseidon_hash_device(const void *d_x, const void *d_y, size_t n, void *d_out, void *hip_stream) {
@@ -122,24 +95,9 @@ int lw_poseidon_hash_device(const void *d_x, const void *d_y, size_t n, void *d_
 
 // hash_single (single = true, row_len = 1) and hash_many
 static int rows_entry(const void *rows, size_t n_rows, size_t row_len, bool single, void *out, void *hip_stream, bool device) {
-    if (row_len > ((size_t)1 << 31) || (row_len && n_rows > (POSEIDON_MAX_N << 4) / row_len)) {
-        set_error("%zu rows of %zu elements", n_rows, row_len);
-        return LW_ERR_ALLOC;
-    }
-    int rc = row_len ? flat_check(n_rows, POSEIDON_MAX_N, "Poseidon", {rows, out}, device)
-                     : flat_check(n_rows, POSEIDON_MAX_N, "Poseidon", {out}, device);   // no row data: rows is not read
+    const int rc = rows_check(n_rows, row_len, row_len, POSEIDON_MAX_N, "Poseidon", "elements", rows, out, device);
     if (rc || n_rows == 0) return rc;
-    Entry en(hip_stream);
-    if (en.rc) return en.rc;
-    if (device) return poseidon_rows_device(en.c, rows, n_rows, row_len, single, out, en.stream);
-    hipStream_t s = en.use_lane_stream();
-    if (!s) return en.rc;
-    Context &c = en.c;
-    const size_t in_bytes = n_rows * row_len * 32;
-    if (c.host_io_a.ensure(in_bytes ? in_bytes : 32) || c.host_io_b.ensure(n_rows * 32)) return LW_ERR_ALLOC;
-    int r = in_bytes ? upload(c.host_io_a.p, rows, in_bytes, s) : LW_OK;
-    if (!r) r = poseidon_rows_device(c, c.host_io_a.p, n_rows, row_len, single, c.host_io_b.p, s);
-    return r ? r : download(out, c.host_io_b.p, n_rows * 32, s);
+    return tree_rows_entry<PoseidonHash>(POSEIDON_NAMES.rows, rows, n_rows, row_len, row_len, single, out, hip_stream, device);
 }
 int lw_poseidon_hash_single(const void *x, size_t n, void *out) { return rows_entry(x, n, 1, true, out, nullptr, false); }
 int lw_poseidon_hash_single_device(const void *d_x, size_t n, void *d_out, void *hip_stream) {
@@ -153,31 +111,25 @@ int lw_poseidon_hash_many_device(const void *d_rows, size_t n_rows, size_t row_l
 }
 
 // checks of both commitment forms; nodes_or_root: d_nodes (device form) or out_root (host form)
-static int commit_check(const void *columns, const void *nodes_or_root, uint32_t n_cols, uint32_t log2n, int leaf_mode, bool device) {
-    if (!columns || !nodes_or_root || n_cols == 0) { set_error("null buffer or no columns"); return LW_ERR_BAD_ARG; }
+static int commit_check(const void *columns, const void *nodes_or_root, uint32_t n_cols, uint64_t col_stride, uint32_t log2n, int leaf_mode,
+                        bool device) {
     if (leaf_mode != LW_POSEIDON_LEAF_SINGLE && leaf_mode != LW_POSEIDON_LEAF_MANY) { set_error("bad leaf mode %d", leaf_mode); return LW_ERR_BAD_ARG; }
-    if (leaf_mode == LW_POSEIDON_LEAF_SINGLE && n_cols != 1) {
+    if (leaf_mode == LW_POSEIDON_LEAF_SINGLE && n_cols > 1) {   // no columns at all: the refusal of tree_commit_check
         set_error("LW_POSEIDON_LEAF_SINGLE (TreePoseidon) commits one column, not %u", n_cols);
         return LW_ERR_BAD_ARG;
     }
-    if (device && (!aligned16(columns) || !aligned16(nodes_or_root))) { set_error("device buffers must be 16-byte aligned"); return LW_ERR_BAD_ARG; }
-    if (log2n > 31) { set_error("2^%u leaves", log2n); return LW_ERR_ALLOC; }
-    return LW_OK;
+    return tree_commit_check(columns, nodes_or_root, n_cols, col_stride, log2n, 31, device);
 }
 int lw_poseidon_commit_columns_device(const void *d_columns, uint32_t n_cols, uint64_t col_stride_elems, uint32_t log2n, int bit_reverse,
                                       int leaf_mode, void *d_nodes, uint8_t *out_root, void *hip_stream) {
-    const int rc = commit_check(d_columns, d_nodes, n_cols, log2n, leaf_mode, true);
+    const int rc = commit_check(d_columns, d_nodes, n_cols, col_stride_elems, log2n, leaf_mode, true);
     if (rc) return rc;
-    if (col_stride_elems && col_stride_elems < (1ull << log2n)) {
-        set_error("column stride %llu below the column length", (unsigned long long)col_stride_elems);
-        return LW_ERR_BAD_ARG;
-    }
     return tree_commit_columns_device<PoseidonHash>(POSEIDON_NAMES, d_columns, n_cols, col_stride_elems, log2n, bit_reverse,
                                                     leaf_mode == LW_POSEIDON_LEAF_SINGLE, d_nodes, out_root, hip_stream);
 }
 int lw_poseidon_commit_columns(const void *columns, uint32_t n_cols, uint32_t log2n, int bit_reverse, int leaf_mode, uint8_t *out_root,
                                uint8_t *out_nodes_or_null) {
-    const int rc = commit_check(columns, out_root, n_cols, log2n, leaf_mode, false);
+    const int rc = commit_check(columns, out_root, n_cols, 0, log2n, leaf_mode, false);
     if (rc) return rc;
     return tree_commit_columns_host<PoseidonHash>(POSEIDON_NAMES, columns, n_cols, log2n, bit_reverse, leaf_mode == LW_POSEIDON_LEAF_SINGLE,
                                                   out_root, out_nodes_or_null);

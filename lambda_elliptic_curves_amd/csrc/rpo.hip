@@ -29,6 +29,7 @@ template <int LV> struct RpoHash {   // the policy of hash_tree.cuh: an element 
     typedef RpoParams<LV> R;
     static constexpr int LEVEL = LV;
     static constexpr uint64_t DIGEST_BYTES = R::DIGEST * 8, ELEM_BYTES = 8;
+    static int ready(Context &) { return LW_OK; }   // the constants come with the code object
     // hash(left || right): 2 * DIGEST = RATE words, so one full block, word 0 of the state 0, one permutation at both
     // levels.  The digests are canonical (the kernels wrote them).
     static __device__ __forceinline__ void parent(const char *x, const char *y, char *out) {
@@ -69,19 +70,6 @@ static constexpr TreeNames RPO_NAMES = {"rpo_sponge_kernel", "rpo_pair_kernel", 
 
 // The run-time level becomes the template argument here and nowhere else: f(RpoHash<0>()) or f(RpoHash<1>()).
 template <class F> static int rpo_with_level(int level, F f) { return level == LW_RPO_128 ? f(RpoHash<0>()) : f(RpoHash<1>()); }
-static uint32_t rpo_width(int level) { return rpo_with_level(level, [](auto h) { return decltype(h)::R::M; }); }
-static uint32_t rpo_digest(int level) { return rpo_with_level(level, [](auto h) { return decltype(h)::R::DIGEST; }); }
-
-static int rpo_permute_device(Context &c, int level, const void *d_in, void *d_out, uint64_t n, hipStream_t s) {
-    return rpo_with_level(level, [&](auto h) {
-        return launch_1d(c, "rpo_permute_kernel", rpo_permute_kernel<decltype(h)::LEVEL>, blocks_for(n), s, d_in, d_out, n);
-    });
-}
-static int rpo_rows_device(Context &c, int level, const void *d_rows, uint64_t n, size_t row_len, uint64_t row_stride, void *d_out, hipStream_t s) {
-    return rpo_with_level(level, [&](auto h) {
-        return tree_rows_device<decltype(h)>(c, RPO_NAMES.rows, d_rows, n, (uint32_t)row_len, row_stride, 1, -1, 0, d_out, s);
-    });
-}
 
 // ---- argument checks: one per entry-point family, run before any device work
 static constexpr uint64_t RPO_MAX_N = (uint64_t)1 << 36;   // the grid's block index stays below 2^31
@@ -100,17 +88,12 @@ static int permute_entry(int level, const void *states, size_t n, void *out, voi
     int rc = level_check(level);
     if (!rc) rc = flat_check(n, RPO_MAX_N, "RPO", {states, out}, device);
     if (rc || n == 0) return rc;
-    Entry en(hip_stream);
-    if (en.rc) return en.rc;
-    if (device) return rpo_permute_device(en.c, level, states, out, n, en.stream);
-    hipStream_t s = en.use_lane_stream();
-    if (!s) return en.rc;
-    Context &c = en.c;
-    const size_t bytes = n * rpo_width(level) * 8;
-    if (c.host_io_a.ensure(bytes)) return LW_ERR_ALLOC;
-    int r = upload(c.host_io_a.p, states, bytes, s);
-    if (!r) r = rpo_permute_device(c, level, c.host_io_a.p, c.host_io_a.p, n, s);
-    return r ? r : download(out, c.host_io_a.p, bytes, s);
+    return rpo_with_level(level, [&](auto h) {
+        const size_t bytes = n * decltype(h)::R::M * 8;
+        return flat_entry(hip_stream, device, {{states, bytes}}, out, bytes, true, [&](Context &c, const void *const *d_in, void *d_out, hipStream_t s) {
+            return launch_1d(c, "rpo_permute_kernel", rpo_permute_kernel<decltype(h)::LEVEL>, blocks_for(n), s, d_in[0], d_out, (uint64_t)n);
+        });
+    });
 }
 int lw_rpo_permute(lw_rpo_level_t level, const uint64_t *states, size_t n, uint64_t *out) { return permute_entry(level, states, n, out, nullptr, false); }
 int lw_rpo_permute_device(lw_rpo_level_t level, const uint64_t *d_states, size_t n, uint64_t *d_out, void *hip_stream) {
@@ -119,28 +102,13 @@ int lw_rpo_permute_device(lw_rpo_level_t level, const uint64_t *d_states, size_t
 
 static int hash_entry(int level, const void *rows, size_t n_rows, size_t row_len, size_t row_stride, void *out, void *hip_stream,
                       bool device) {
-    int rc = level_check(level);
-    if (rc) return rc;
     if (row_stride == 0) row_stride = row_len;
-    if (row_stride < row_len) { set_error("row stride %zu below the row length %zu", row_stride, row_len); return LW_ERR_BAD_ARG; }
-    if (row_len > ((size_t)1 << 31) || (row_stride && n_rows > (RPO_MAX_N << 4) / row_stride)) {
-        set_error("%zu rows of %zu words", n_rows, row_stride);
-        return LW_ERR_ALLOC;
-    }
-    rc = row_len ? flat_check(n_rows, RPO_MAX_N, "RPO", {rows, out}, device)
-                 : flat_check(n_rows, RPO_MAX_N, "RPO", {out}, device);   // no row data: rows is not read
+    int rc = level_check(level);
+    if (!rc) rc = rows_check(n_rows, row_len, row_stride, RPO_MAX_N, "RPO", "words", rows, out, device);
     if (rc || n_rows == 0) return rc;
-    Entry en(hip_stream);
-    if (en.rc) return en.rc;
-    if (device) return rpo_rows_device(en.c, level, rows, n_rows, row_len, row_stride, out, en.stream);
-    hipStream_t s = en.use_lane_stream();
-    if (!s) return en.rc;
-    Context &c = en.c;
-    const size_t in_bytes = n_rows * row_len * 8, out_bytes = n_rows * rpo_digest(level) * 8;
-    if (c.host_io_a.ensure(in_bytes ? in_bytes : 16) || c.host_io_b.ensure(out_bytes)) return LW_ERR_ALLOC;
-    int r = in_bytes ? upload(c.host_io_a.p, rows, in_bytes, s) : LW_OK;
-    if (!r) r = rpo_rows_device(c, level, c.host_io_a.p, n_rows, row_len, row_len, c.host_io_b.p, s);
-    return r ? r : download(out, c.host_io_b.p, out_bytes, s);
+    return rpo_with_level(level, [&](auto h) {
+        return tree_rows_entry<decltype(h)>(RPO_NAMES.rows, rows, n_rows, row_len, row_stride, 0, out, hip_stream, device);
+    });
 }
 int lw_rpo_hash(lw_rpo_level_t level, const uint64_t *rows, size_t n_rows, size_t row_len, uint64_t *out) {
     return hash_entry(level, rows, n_rows, row_len, 0, out, nullptr, false);
@@ -154,15 +122,7 @@ int lw_rpo_hash_device(lw_rpo_level_t level, const uint64_t *d_rows, size_t n_ro
 static int commit_check(int level, const void *columns, const void *nodes_or_root, uint32_t n_cols, uint64_t col_stride, uint32_t log2n,
                         bool device) {
     const int rc = level_check(level);
-    if (rc) return rc;
-    if (!columns || !nodes_or_root || n_cols == 0) { set_error("null buffer or no columns"); return LW_ERR_BAD_ARG; }
-    if (device && (!aligned16(columns) || !aligned16(nodes_or_root))) { set_error("device buffers must be 16-byte aligned"); return LW_ERR_BAD_ARG; }
-    if (log2n > 30) { set_error("2^%u leaves", log2n); return LW_ERR_ALLOC; }
-    if (col_stride && col_stride < (1ull << log2n)) {
-        set_error("column stride %llu below the column length", (unsigned long long)col_stride);
-        return LW_ERR_BAD_ARG;
-    }
-    return LW_OK;
+    return rc ? rc : tree_commit_check(columns, nodes_or_root, n_cols, col_stride, log2n, 30, device);
 }
 int lw_rpo_commit_columns_device(lw_rpo_level_t level, const uint64_t *d_columns, uint32_t n_cols, uint64_t col_stride, uint32_t log2n,
                                  int bit_reverse, uint64_t *d_nodes, uint64_t *out_root, void *hip_stream) {

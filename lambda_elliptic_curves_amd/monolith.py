@@ -9,9 +9,9 @@ current stream.
 """
 import numpy as np
 
-from . import _lib as L
+from . import _lib as L, _tree
 from ._lib import device_ptr as _dp, host_ptr as _vp, stream_ptr as _stream
-from .errors import InputError, check
+from .errors import check
 
 P = (1 << 31) - 1
 WIDTHS = (8, 12, 16, 20, 24)
@@ -85,15 +85,8 @@ def commit_columns(rounds, columns, bit_reverse=True, return_nodes=False):
     cols = np.ascontiguousarray(columns, dtype=np.uint32)
     if cols.ndim != 2 or cols.shape[0] == 0:
         raise ValueError("commit_columns: columns is (n_cols, N) with at least one column")
-    n_cols, n = cols.shape
-    log2n = n.bit_length() - 1
-    if n == 0 or (1 << log2n) != n:
-        raise InputError(f"Input length is {n}, which is not a power of two")
-    root = np.zeros(DIGEST_LEN, np.uint32)
-    nodes = np.zeros((2 * n - 1, DIGEST_LEN), np.uint32) if return_nodes else None
-    check(L.lib().lw_monolith_commit_columns(rounds, _vp(cols), n_cols, log2n, 1 if bit_reverse else 0, _vp(root),
-                                             _vp(nodes) if return_nodes else None))
-    return (root, nodes) if return_nodes else root
+    return _tree.commit_host(cols, DIGEST_LEN, np.uint32, return_nodes, lambda log2n, root, nodes: L.lib().lw_monolith_commit_columns(
+        rounds, _vp(cols), cols.shape[0], log2n, 1 if bit_reverse else 0, root, nodes))
 
 
 # ---- device-resident forms: torch int32 tensors holding the same words, 16-byte aligned
@@ -128,7 +121,5 @@ def commit_columns_device(rounds, t_columns, n_cols, log2n, t_nodes, bit_reverse
     """t_columns: n_cols columns of 2^log2n words, col_stride words apart (0: dense), e.g. the output of circle.lde_device
     as it lies; t_nodes: (2 * 2^log2n - 1) x 8 int32, the tree (readable by merkle.open_trees_device as it is).  Returns
     the root (8,) uint32 after synchronising the stream, or None (nothing waited for) with return_root=False."""
-    root = np.zeros(DIGEST_LEN, np.uint32) if return_root else None
-    check(L.lib().lw_monolith_commit_columns_device(rounds, _dp(t_columns), n_cols, col_stride, log2n, 1 if bit_reverse else 0,
-                                                    _dp(t_nodes), _vp(root) if return_root else None, _stream(stream)))
-    return root
+    return _tree.commit_device(DIGEST_LEN, np.uint32, return_root, lambda root: L.lib().lw_monolith_commit_columns_device(
+        rounds, _dp(t_columns), n_cols, col_stride, log2n, 1 if bit_reverse else 0, _dp(t_nodes), root, _stream(stream)))

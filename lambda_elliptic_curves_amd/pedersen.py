@@ -4,9 +4,9 @@ identity leaves), batched on the device.  Elements are Stark252 FieldElements as
 significant limb first, Montgomery form, canonical.  Points are affine (x, y): (…, 2, 4)."""
 import numpy as np
 
-from . import _lib as L
+from . import _lib as L, _tree
 from ._lib import device_ptr as _dp, host_ptr as _vp, stream_ptr as _stream
-from .errors import InputError, check
+from .errors import check
 
 N_POINTS = 1890   # T1 || T2 || T3 || T4: 930 + 15 + 930 + 15
 
@@ -32,15 +32,8 @@ def commit_leaves(leaves, bit_reverse=True, return_nodes=False):
     cols = np.ascontiguousarray(leaves, dtype=np.uint64)
     if cols.ndim == 2:
         cols = cols.reshape(1, -1, 4)
-    n_cols, n = cols.shape[0], cols.shape[1]
-    log2n = n.bit_length() - 1
-    if n == 0 or (1 << log2n) != n:
-        raise InputError(f"Input length is {n}, which is not a power of two")
-    root = np.zeros(4, np.uint64)
-    nodes = np.zeros((2 * n - 1, 4), np.uint64) if return_nodes else None
-    check(L.lib().lw_pedersen_commit_leaves(_vp(cols), n_cols, log2n, 1 if bit_reverse else 0, _vp(root),
-                                            _vp(nodes) if return_nodes else None))
-    return (root, nodes) if return_nodes else root
+    return _tree.commit_host(cols, 4, np.uint64, return_nodes, lambda log2n, root, nodes: L.lib().lw_pedersen_commit_leaves(
+        _vp(cols), cols.shape[0], log2n, 1 if bit_reverse else 0, root, nodes))
 
 
 def table():
@@ -60,10 +53,8 @@ def commit_leaves_device(t_leaves, log2n, t_nodes, bit_reverse=True, return_root
     """t_leaves: 2^log2n leaf values; t_nodes: (2 * 2^log2n - 1) x 4 int64, the reference's `nodes` (readable by
     merkle.open_trees_device as it is).  Returns the root element (4,) uint64 after synchronising the stream, or None
     (nothing waited for) with return_root=False."""
-    root = np.zeros(4, np.uint64) if return_root else None
-    check(L.lib().lw_pedersen_commit_leaves_device(_dp(t_leaves), n_cols, log2n, 1 if bit_reverse else 0, _dp(t_nodes),
-                                                   _vp(root) if return_root else None, _stream(stream)))
-    return root
+    return _tree.commit_device(4, np.uint64, return_root, lambda root: L.lib().lw_pedersen_commit_leaves_device(
+        _dp(t_leaves), n_cols, log2n, 1 if bit_reverse else 0, _dp(t_nodes), root, _stream(stream)))
 
 
 def add_affine_device(t_p, t_z, t_q, n, t_out, stream=None):

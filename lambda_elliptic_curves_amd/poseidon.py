@@ -3,9 +3,9 @@ the Merkle trees built on it (TreePoseidon, BatchPoseidonTree), batched on the d
 FieldElements as everywhere else: (…, 4) uint64, most significant limb first, Montgomery form, canonical."""
 import numpy as np
 
-from . import _lib as L
+from . import _lib as L, _tree
 from ._lib import device_ptr as _dp, host_ptr as _vp, stream_ptr as _stream
-from .errors import InputError, check
+from .errors import check
 
 LEAF_SINGLE, LEAF_MANY = L.POSEIDON_LEAF_SINGLE, L.POSEIDON_LEAF_MANY
 
@@ -55,15 +55,8 @@ def commit_columns(columns, leaf_mode=LEAF_MANY, bit_reverse=True, return_nodes=
     hash_single); LEAF_MANY: BatchPoseidonTree (leaf = hash_many of the row).  Returns the root element (4,) uint64 (and
     the reference's `nodes`, (2N - 1, 4) root first, when return_nodes)."""
     cols = np.ascontiguousarray(columns, dtype=np.uint64)
-    n_cols, n = cols.shape[0], cols.shape[1]
-    log2n = n.bit_length() - 1
-    if n == 0 or (1 << log2n) != n:
-        raise InputError(f"Input length is {n}, which is not a power of two")
-    root = np.zeros(4, np.uint64)
-    nodes = np.zeros((2 * n - 1, 4), np.uint64) if return_nodes else None
-    check(L.lib().lw_poseidon_commit_columns(_vp(cols), n_cols, log2n, 1 if bit_reverse else 0, leaf_mode, _vp(root),
-                                             _vp(nodes) if return_nodes else None))
-    return (root, nodes) if return_nodes else root
+    return _tree.commit_host(cols, 4, np.uint64, return_nodes, lambda log2n, root, nodes: L.lib().lw_poseidon_commit_columns(
+        _vp(cols), cols.shape[0], log2n, 1 if bit_reverse else 0, leaf_mode, root, nodes))
 
 
 # ---- device-resident forms: torch int64 tensors holding the same (…, 4) limbs, 16-byte aligned
@@ -94,7 +87,5 @@ def commit_columns_device(t_columns, n_cols, log2n, t_nodes, leaf_mode=LEAF_MANY
     """t_columns: n_cols columns of 2^log2n elements, col_stride_elems apart (0: dense); t_nodes: (2 * 2^log2n - 1) x 4
     int64, the reference's `nodes` (readable by merkle.open_trees_device as it is).  Returns the root element (4,) uint64
     after synchronising the stream, or None (nothing waited for) with return_root=False."""
-    root = np.zeros(4, np.uint64) if return_root else None
-    check(L.lib().lw_poseidon_commit_columns_device(_dp(t_columns), n_cols, col_stride_elems, log2n, 1 if bit_reverse else 0,
-                                                    leaf_mode, _dp(t_nodes), _vp(root) if return_root else None, _stream(stream)))
-    return root
+    return _tree.commit_device(4, np.uint64, return_root, lambda root: L.lib().lw_poseidon_commit_columns_device(
+        _dp(t_columns), n_cols, col_stride_elems, log2n, 1 if bit_reverse else 0, leaf_mode, _dp(t_nodes), root, _stream(stream)))

@@ -8,6 +8,8 @@ kernel alone, 1 .. 9 add the top kernel, 10 adds one pair launch."""
 import ctypes as C
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -230,6 +232,27 @@ def test_tree_with_a_column_stride_and_the_host_form():
     leaves = [M.hash(ROUNDS, [int(cols[0, j])]) for j in (0, 2, 1, 3)]   # one tree tied to the integer form by hand
     l01, l23 = M.compress(ROUNDS, leaves[0], leaves[1]), M.compress(ROUNDS, leaves[2], leaves[3])
     assert exp.tolist() == [M.compress(ROUNDS, l01, l23), l01, l23] + leaves
+
+
+FIRST_CALL = """
+import sys, numpy as np, torch
+from lambda_elliptic_curves_amd import monolith
+cols = np.frombuffer(bytes.fromhex(sys.argv[1]), np.int32).reshape(2, 8)
+t_nodes = torch.zeros((15, 8), dtype=torch.int32, device="cuda")
+monolith.commit_columns_device(5, torch.from_numpy(cols.copy()).cuda(), 2, 3, t_nodes)
+print(t_nodes.cpu().numpy().tobytes().hex())
+"""
+
+
+def test_the_first_call_of_a_process_may_be_a_device_tree():
+    """The constants are uploaded inside the tree call (MonolithHash::ready), under the call's one hold of the lane: a
+    process whose first library call is commit_columns_device gets all 15 nodes right.  A tree built against a table that
+    is not there hashes against zeros."""
+    cols, exp = ref_tree(2, 3, True)
+    out = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", FIRST_CALL, cols.tobytes().hex()],
+                         cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert np.array_equal(np.frombuffer(bytes.fromhex(out.stdout.split()[-1]), np.uint32).reshape(15, 8), exp)
 
 
 # ---- 6. circle LDE -> commit on the resident output -> authentication paths read from the resident tree

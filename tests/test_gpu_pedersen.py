@@ -9,6 +9,8 @@ Launch boundaries of the tree (hash_tree.cuh tree_commit_device): a workgroup is
 everything from a level of 2^9 nodes down; every level above is one launch.  log2n = 9 and 10 straddle that boundary."""
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -185,6 +187,28 @@ def test_an_opening_folds_up_to_the_root():
             cur = R.hash(cur, sib) if i % 2 == 0 else R.hash(sib, cur)
             i >>= 1
         assert cur == root_int, pos
+
+
+FIRST_CALL = """
+import sys, numpy as np, torch
+from lambda_elliptic_curves_amd import pedersen
+leaves = np.frombuffer(bytes.fromhex(sys.argv[1]), np.int64).reshape(8, 4)
+t_nodes = torch.zeros((15, 4), dtype=torch.int64, device="cuda")
+pedersen.commit_leaves_device(torch.from_numpy(leaves.copy()).cuda(), 3, t_nodes)
+print(t_nodes.cpu().numpy().tobytes().hex())
+"""
+
+
+def test_the_first_call_of_a_process_may_be_a_device_tree():
+    """The lookup table is uploaded inside the tree call (PedersenHash::ready), under the call's one hold of the lane: a
+    process whose first library call is commit_leaves_device gets all 15 nodes right.  A tree built against a table that
+    is not there hashes against zeros."""
+    vals = rand_ints(8, 77)
+    out = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", FIRST_CALL, R.to_elems(vals).tobytes().hex()],
+                         cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    nodes = np.frombuffer(bytes.fromhex(out.stdout.split()[-1]), np.uint64).reshape(15, 4)
+    assert R.from_elems(nodes) == R.commit_leaves(vals, True)
 
 
 def test_two_columns_are_refused():

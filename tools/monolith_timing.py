@@ -6,7 +6,7 @@ sets and next to a copy of the same bytes.
              in permutations/s (width 24: 7 x 576 = 4032).  Bars, Bricks and the reductions are NOT in that count: their
              cost shows as distance from the ceiling.
   permute    monolith.permute_device at 2^20 and 2^24 states for (16, 5) and 2^20 for (24, 5), and a device-to-device
-             copy of the same bytes
+             copy of the same bytes; one state of (16, 5) through permute_device and through permute (the call itself)
   commit     monolith.commit_columns_device for 8 x 2^20 and 1 x 2^24 at R = 5, with the time of each of the three tree
              kernels (the shared schedule of hash_tree.cuh: one pair launch per wide level, the top kernel from 2^9 nodes)
 Every step is a process of its own under `timeout -k 10`, chained with &&: a step that fails or hangs ends the run.
@@ -24,7 +24,8 @@ sys.path.insert(0, ROOT)
 
 ROUNDS = 5
 MACS = {16: 7 * 256, 24: 7 * 576}   # width -> multiply-adds of the R + 2 = 7 Concrete layers
-STEPS = [("mac", 240), ("permute:16:20", 120), ("permute:16:24", 180), ("permute:24:20", 120), ("commit:8:20", 180), ("commit:1:24", 180)]
+# a trailing ":host" times the host form (staged, complete on return); at 2^0 a line is the cost of the call itself
+STEPS = [("mac", 240), ("permute:16:0", 120), ("permute:16:0:host", 120), ("permute:16:20", 120), ("permute:16:24", 180), ("permute:24:20", 120), ("commit:8:20", 180), ("commit:1:24", 180)]
 
 
 def timed(fn, reps=9):
@@ -54,12 +55,17 @@ def step(name):
     from lambda_elliptic_curves_amd import _lib, monolith
     rng = np.random.default_rng(47)
     dev = lambda a: torch.from_numpy(a.view(np.int32)).cuda()
-    kind, a, b = name.split(":")
+    kind, a, b, *host = name.split(":")
     if kind == "permute":
         width, n = int(a), 1 << int(b)
-        t = dev(rng.integers(0, 1 << 32, n * width, dtype=np.uint32))
+        t = rng.integers(0, 1 << 32, n * width, dtype=np.uint32)
+        if host:
+            med, lo, hi = timed(lambda: monolith.permute(width, ROUNDS, t), reps=201)
+            print(f"RESULT {width} Monolith-{width} R={ROUNDS} permute 2^{b}: {n} permutations, {med:9.3f} ms [{lo:9.3f} .. {hi:9.3f}] PERMS {n / med * 1e3:.6e}")
+            return 0
+        t = dev(t)
         t_out = torch.empty_like(t)
-        med, lo, hi = timed(lambda: monolith.permute_device(width, ROUNDS, t, n, t_out))
+        med, lo, hi = timed(lambda: monolith.permute_device(width, ROUNDS, t, n, t_out), reps=201 if n == 1 else 9)
         c_med, c_lo, c_hi = timed(lambda: t_out.copy_(t))
         print(f"RESULT {width} Monolith-{width} R={ROUNDS} permute_device 2^{b}: {n} permutations, {med:9.3f} ms [{lo:9.3f} .. {hi:9.3f}]; "
               f"copy of the same {4 * n * width} bytes {c_med:9.3f} ms [{c_lo:9.3f} .. {c_hi:9.3f}], ratio {med / c_med:.2f} PERMS {n / med * 1e3:.6e}")
@@ -91,7 +97,7 @@ def main():
     me = os.path.abspath(__file__)
     chain = " && ".join(f"timeout -k 10 {limit} {sys.executable} {me} --step {name}" for name, limit in STEPS)
     run = subprocess.run(chain, shell=True, capture_output=True, text=True, cwd=ROOT)
-    lines = ["# Monolith over Mersenne31: wall ms per call, median [min .. max] after a warm-up (9 calls; trees 5), stream synchronised"]
+    lines = ["# Monolith over Mersenne31: wall ms per call, median [min .. max] after a warm-up (9 calls; 201 at 2^0; trees 5), stream synchronised"]
     rate_mac = None
     for ln in run.stdout.splitlines():
         if ln.startswith("MAC"):

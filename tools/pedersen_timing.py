@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Starknet Pedersen hash on the device (csrc/pedersen.hip): hashes per second next to the ceiling the arithmetic sets.
   fe_mul     the Stark252 Montgomery product rate of tools/microbench (built by build()); rate / PRODUCTS is the ceiling
-  hash       pedersen.hash_device at 2^16 and 2^20 random pairs
+  hash       pedersen.hash_device at 2^16 and 2^20 random pairs; one pair through hash_device and through hash (the call itself)
   tree       pedersen.commit_leaves_device over 2^20 leaf values (2^20 - 1 hashes)
   resources  VGPRs, SGPRs, scratch and occupancy of every kernel of pedersen.hip, from the compiler's resource-usage
              remarks (a compile for gfx950, no device involved)
@@ -28,7 +28,8 @@ sys.path.insert(0, ROOT)
 # too high.
 ADDS, PER_ADD, REST = 118.0, 11, 8
 PRODUCTS = ADDS * PER_ADD + REST
-STEPS = [("fe_mul", 240), ("hash:16", 120), ("hash:20", 120), ("tree:20", 180), ("resources", 300)]
+# a trailing ":host" times the host form (staged, complete on return); at 2^0 a line is the cost of the call itself
+STEPS = [("fe_mul", 240), ("hash:0", 120), ("hash:0:host", 120), ("hash:16", 120), ("hash:20", 120), ("tree:20", 180), ("resources", 300)]
 
 
 def timed(fn, reps=9):
@@ -86,13 +87,14 @@ def step(name):
     from lambda_elliptic_curves_amd import pedersen
     from tools import inputs
     dev = lambda a: torch.from_numpy(a.view(np.int64)).cuda()
-    kind, log2n = name.split(":")
+    kind, log2n, *host = name.split(":")
     n = 1 << int(log2n)
     if kind == "hash":
-        t_x, t_y = dev(inputs.rand_elems("stark252", n, 41)), dev(inputs.rand_elems("stark252", n, 42))
+        x, y = inputs.rand_elems("stark252", n, 41), inputs.rand_elems("stark252", n, 42)
+        t_x, t_y = dev(x), dev(y)
         t_out = torch.empty((n, 4), dtype=torch.int64, device="cuda")
-        med, lo, hi = timed(lambda: pedersen.hash_device(t_x, t_y, n, t_out))
-        print(f"RESULT hash_device 2^{log2n}: {n} hashes, {med:9.3f} ms [{lo:9.3f} .. {hi:9.3f}] HASHES {n / med * 1e3:.6e}")
+        med, lo, hi = timed((lambda: pedersen.hash(x, y)) if host else (lambda: pedersen.hash_device(t_x, t_y, n, t_out)), reps=201 if n == 1 else 9)
+        print(f"RESULT hash{'' if host else '_device'} 2^{log2n}: {n} hashes, {med:9.3f} ms [{lo:9.3f} .. {hi:9.3f}] HASHES {n / med * 1e3:.6e}")
         return 0
     t_leaves = dev(inputs.rand_elems("stark252", n, 43))
     t_nodes = torch.empty((2 * n - 1, 4), dtype=torch.int64, device="cuda")
@@ -111,7 +113,7 @@ def main():
     me = os.path.abspath(__file__)
     chain = " && ".join(f"timeout -k 10 {limit} {sys.executable} {me} --step {name}" for name, limit in STEPS)
     run = subprocess.run(chain, shell=True, capture_output=True, text=True, cwd=ROOT)
-    lines = ["# Starknet Pedersen hash: wall ms per call, median [min .. max] after a warm-up (9 calls; the tree 5), stream synchronised",
+    lines = ["# Starknet Pedersen hash: wall ms per call, median [min .. max] after a warm-up (9 calls; 201 at 2^0; the tree 5), stream synchronised",
              f"# counted products per hash of uniform inputs: {ADDS:.1f} additions (2 x (62 x 15/16 + 7/8); 126 at most) x {PER_ADD} (8 M + 3 S, mixed Jacobian) "
              f"+ {REST} (Montgomery form in and out of the nibbles, the shift point, Z^-2 and X Z^-2, 2 inside fe_inv_fast) = {PRODUCTS:.0f};",
              "# the binary GCD of the one inversion per hash is VALU work outside the count, so the ceiling below is that much too high",

@@ -2,7 +2,7 @@
 """Starknet Poseidon on the device (csrc/poseidon.hip): permutations per second next to the ceiling the arithmetic sets.
   fe_mul     the Stark252 Montgomery product rate of tools/microbench (built by build()); one permutation is 214 products,
              so rate / 214 is the ceiling in permutations/s
-  permute    poseidon.permute_device at 2^20 and 2^24 states
+  permute    poseidon.permute_device at 2^20 and 2^24 states; one state through permute_device and through permute (the call itself)
   commit     poseidon.commit_columns_device for 1 x 2^20 and 1 x 2^24 (TreePoseidon) and 4 x 2^22 (BatchPoseidonTree)
 Every step is a process of its own under `timeout -k 10`, chained with &&: a step that fails or hangs ends the run.
 usage: poseidon_timing.py [--out FILE]        (poseidon_timing.py --step NAME runs one step)"""
@@ -21,7 +21,8 @@ PRODUCTS = 214   # 8 full rounds x 3 S-boxes x 2 + 83 partial rounds x 2
 # single-thread CPU figure, DERIVED: bench.py's cpu_baseline leg ran one Stark252 evaluate_fft of 2^24 elements at 2.04 M
 # elements/s (BENCH_r03.json), 12 products per element -> at most 41 ns per product -> 8.7 us per permutation
 CPU_NS_PER_PRODUCT = 1e9 / (2041730.9 * 12)
-STEPS = [("fe_mul", 240), ("permute:20", 120), ("permute:24", 180), ("commit:1:20:single", 120), ("commit:1:24:single", 240),
+# a trailing ":host" times the host form (staged, complete on return); at 2^0 a line is the cost of the call itself
+STEPS = [("fe_mul", 240), ("permute:0", 120), ("permute:0:host", 120), ("permute:20", 120), ("permute:24", 180), ("commit:1:20:single", 120), ("commit:1:24:single", 240),
          ("commit:4:22:many", 240)]
 
 
@@ -55,9 +56,10 @@ def step(name):
     kind, *rest = name.split(":")
     if kind == "permute":
         n = 1 << int(rest[0])
-        t = dev(inputs.rand_elems("stark252", 3 * n, 41))
-        med, lo, hi = timed(lambda: poseidon.permute_device(t, n))
-        print(f"RESULT permute_device 2^{rest[0]}: {n} permutations, {med:9.3f} ms [{lo:9.3f} .. {hi:9.3f}] PERMS {n / med * 1e3:.6e}")
+        host = rest[1:] == ["host"]
+        t = inputs.rand_elems("stark252", 3 * n, 41) if host else dev(inputs.rand_elems("stark252", 3 * n, 41))
+        med, lo, hi = timed((lambda: poseidon.permute(t)) if host else (lambda: poseidon.permute_device(t, n)), reps=201 if n == 1 else 9)
+        print(f"RESULT permute{'' if host else '_device'} 2^{rest[0]}: {n} permutations, {med:9.3f} ms [{lo:9.3f} .. {hi:9.3f}] PERMS {n / med * 1e3:.6e}")
         return 0
     n_cols, log2n, mode = int(rest[0]), int(rest[1]), rest[2]
     n = 1 << log2n
@@ -80,7 +82,7 @@ def main():
     me = os.path.abspath(__file__)
     chain = " && ".join(f"timeout -k 10 {limit} {sys.executable} {me} --step {name}" for name, limit in STEPS)
     run = subprocess.run(chain, shell=True, capture_output=True, text=True, cwd=ROOT)
-    lines = ["# Starknet Poseidon: wall ms per call, median [min .. max] after a warm-up (9 calls; trees 5), stream synchronised"]
+    lines = ["# Starknet Poseidon: wall ms per call, median [min .. max] after a warm-up (9 calls; 201 at 2^0; trees 5), stream synchronised"]
     ceiling = None
     for ln in run.stdout.splitlines():
         if ln.startswith("FE_MUL"):

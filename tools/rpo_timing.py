@@ -3,7 +3,7 @@
   gl_mul     the Goldilocks product rate of tools/microbench (built by build()); one permutation is 7 x m x 76 products,
              6384 at the 128-bit level and 8512 at the 160-bit level, so rate / 6384 (8512) is the ceiling in
              permutations/s.  The MDS layers are NOT in that count: their cost shows as distance from the ceiling.
-  permute    rpo.permute_device at 2^16 and 2^20 states, both levels
+  permute    rpo.permute_device at 2^16 and 2^20 states, both levels; one state through permute_device and through permute (the call itself)
   commit     rpo.commit_columns_device for 8 x 2^20 and 1 x 2^20, both levels
 Every step is a process of its own under `timeout -k 10`, chained with &&: a step that fails or hangs ends the run.
 usage: rpo_timing.py [--out FILE]        (rpo_timing.py --step NAME runs one step)"""
@@ -20,7 +20,8 @@ sys.path.insert(0, ROOT)
 
 PRODUCTS = {0: 7 * 12 * 76, 1: 7 * 16 * 76}   # level -> gl_mul per permutation: x^7 is 4 products, x^(1/7) 72
 NAMES = {0: "128", 1: "160"}
-STEPS = [("gl_mul", 240)]
+# a trailing ":host" times the host form (staged, complete on return); at 2^0 a line is the cost of the call itself
+STEPS = [("gl_mul", 240), ("permute:0:0", 120), ("permute:0:0:host", 120)]
 STEPS += [(f"permute:{lv}:{k}", 120) for lv in (0, 1) for k in (16, 20)]
 STEPS += [(f"commit:{lv}:{c}:20", 180) for lv in (0, 1) for c in (8, 1)]
 
@@ -56,9 +57,11 @@ def step(name):
     level = int(lv)
     if kind == "permute":
         n = 1 << int(rest[0])
-        t = dev(rng.integers(0, 1 << 64, n * rpo.state_width(level), dtype=np.uint64))
-        med, lo, hi = timed(lambda: rpo.permute_device(level, t, n))
-        print(f"RESULT {level} RPO-{NAMES[level]} permute_device 2^{rest[0]}: {n} permutations, {med:9.3f} ms [{lo:9.3f} .. {hi:9.3f}] PERMS {n / med * 1e3:.6e}")
+        host = rest[1:] == ["host"]
+        t = rng.integers(0, 1 << 64, n * rpo.state_width(level), dtype=np.uint64)
+        t = t if host else dev(t)
+        med, lo, hi = timed((lambda: rpo.permute(level, t)) if host else (lambda: rpo.permute_device(level, t, n)), reps=201 if n == 1 else 9)
+        print(f"RESULT {level} RPO-{NAMES[level]} permute{'' if host else '_device'} 2^{rest[0]}: {n} permutations, {med:9.3f} ms [{lo:9.3f} .. {hi:9.3f}] PERMS {n / med * 1e3:.6e}")
         return 0
     n_cols, log2n = int(rest[0]), int(rest[1])
     n = 1 << log2n
@@ -80,7 +83,7 @@ def main():
     me = os.path.abspath(__file__)
     chain = " && ".join(f"timeout -k 10 {limit} {sys.executable} {me} --step {name}" for name, limit in STEPS)
     run = subprocess.run(chain, shell=True, capture_output=True, text=True, cwd=ROOT)
-    lines = ["# Rescue Prime Optimized over Goldilocks: wall ms per call, median [min .. max] after a warm-up (9 calls; trees 5), stream synchronised"]
+    lines = ["# Rescue Prime Optimized over Goldilocks: wall ms per call, median [min .. max] after a warm-up (9 calls; 201 at 2^0; trees 5), stream synchronised"]
     rate_mul = None
     for ln in run.stdout.splitlines():
         if ln.startswith("GL_MUL"):
