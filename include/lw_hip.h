@@ -1031,6 +1031,78 @@ int lw_rpo_commit_columns(lw_rpo_level_t level, const uint64_t *columns, uint32_
 int lw_rpo_commit_columns_device(lw_rpo_level_t level, const uint64_t *d_columns, uint32_t n_cols, uint64_t col_stride,
                                  uint32_t log2n, int bit_reverse, uint64_t *d_nodes, uint64_t *out_root_or_null, void *hip_stream);
 
+/* ---- The quadratic extension of Goldilocks, Fp2 = F_p[t] / (t^2 - 7), and the prover steps that run in it ----
+ * Goldilocks64ExtensionField (math/src/field/fields/u64_goldilocks_field.rs:219-227 over extensions/quadratic.rs:79-118;
+ * also Plonky2's quadratic extension): what a STARK over Goldilocks needs after round 1 - out-of-domain evaluation, the
+ * DEEP composition and the FRI commit phase (fri::commit_phase<F, E>, provers/stark/src/fri/mod.rs:22-75, with F
+ * Goldilocks and E = Fp2).  Together with lw_goldilocks_lde_device and lw_rpo_commit_columns_device the Goldilocks path
+ * runs LDE -> RPO commit -> OOD -> DEEP -> FRI commit phase on data that stays in device memory.
+ *   word            as in the Goldilocks section: one u64, the residue itself; any u64 is accepted on input, every
+ *                   output word is canonical (< p)
+ *   Fp2 element     a = a0 + a1 t, t^2 = 7
+ *   host scalar     uint64_t[2] = {c0, c1}: the challenge, the points, the weights and the returned values
+ *   device vector   n elements are two PLANES of n words: plane c0, then plane c1 `stride` words later.  A stride of 0
+ *                   means n; a stride below n is LW_ERR_BAD_ARG.  This is the batch / batch_stride shape of
+ *                   lw_goldilocks_ntt_device and the n_cols / col_stride shape of lw_rpo_commit_columns_device: an Fp2
+ *                   vector goes through them with batch = 2 / n_cols = 2 as it is (the twiddles are in F, so an Fp2
+ *                   transform over a base-field domain is two base transforms).  There is no interleaved form.
+ * All entry points are _device forms under the stream and lane contract of the other *_device calls.  Device pointers
+ * must be 16-byte aligned (else LW_ERR_BAD_ARG).  Every argument check runs before any device work; n = 0 returns LW_OK
+ * without a device.  A call that hands a small result to the host (values, a root) waits for the stream; the others only
+ * enqueue.
+ *
+ * pointwise: out[i] = a[i] b[i] (LW_GL2_MUL), a[i]^2 (LW_GL2_SQR), a[i]^-1 (LW_GL2_INV), a[i] b[i] with b in F
+ * (LW_GL2_MUL_BASE: d_b is a single plane, b_stride is not read).  d_b is not read for SQR and INV and may be NULL.
+ * d_out == d_a or d_out == d_b (the whole vector, under the same stride) is allowed; any other overlap of d_out with an
+ * operand, like an unknown op, is LW_ERR_BAD_ARG.  The inverse of 0 is written as 0: the reference returns InvZeroError
+ * there, and 0 is the only element without an inverse (its norm a0^2 - 7 a1^2 vanishes only at 0, 7 being a non-residue).
+ *
+ * evaluate (STARK round 3): out_values[k m + j] = sum_i col_k[i] points[j]^i for n_cols base-field coefficient columns
+ * of n_coeffs words each, col_stride words apart, at m points of Fp2; out_values is host memory, n_cols m scalars.  A
+ * polynomial with Fp2 coefficients is its two planes passed as two columns, its value v0 + t v1.  No cap on n_cols or m.
+ * n_coeffs = 0 gives zeros.
+ *
+ * deep_quotients: the DEEP composition polynomial (compute_deep_composition_poly, provers/stark/src/prover.rs:643-714,
+ * over a weight matrix as lw_stark_deep_composition states it) in evaluation form.  For every row i of the LDE domain,
+ * x_i = h w^i in natural order, w the primitive 2^log2n-th root:
+ *     out[i] = sum_j ( sum_k weights[k][j] (col_k[i] - evals[k][j]) ) / (x_i - points[j])
+ * d_lde: n_cols base-field columns of 2^log2n words, col_stride apart.  points: m scalars; weights, evals: n_cols x m
+ * scalars, row k, column j (host).  A zero weight skips its pair.  A part with Fp2 values is its two planes as two columns,
+ * the weight of the c1 plane multiplied by t by the caller.  A point with c1 = 0 is LW_ERR_BAD_ARG: a base-field point can
+ * lie on the domain.  offset_or_null (h, NULL: 1; 0 mod p: LW_ERR_INV_ZERO), two_adic_root and the range of log2n as
+ * in lw_goldilocks_ntt_device.  d_out: an Fp2 vector of 2^log2n elements that overlaps no column.  n_cols = 0 or m = 0:
+ * LW_ERR_BAD_ARG.  lw_goldilocks_ntt_device (inverse, same offset, batch = 2) of the result gives the coefficients of
+ * the DEEP polynomial.
+ *
+ * fri_layer: the Fp2 counterpart of lw_stark_fri_layer_device (fri/mod.rs:44-58, 115-141).
+ *   fold        d_out_poly[i] = 2 (c[2i] + zeta c[2i+1]), the odd term absent past n_coeffs, as a zero-padded block of
+ *               max(2, next_pow2(ceil(n_coeffs / 2))) elements in two DENSE planes: the next layer's d_coeffs
+ *   fold only   d_nodes_or_null == NULL (the last step, whose coefficient 0 is the value sent); an evaluation or a root
+ *               asked for without nodes is LW_ERR_BAD_ARG
+ *   evaluation  d_out_evaluation receives evaluate_offset_fft(p', 1, Some(domain_size), offset) in natural order, two dense
+ *               planes of domain_size words.  offset_or_null is the layer's offset in F (already squared by the caller),
+ *               domain_size the layer's domain (already halved).  NULL with nodes: LW_ERR_BAD_ARG
+ *   tree        domain_size / 2 leaves; leaf j is the RPO hash (level as in lw_rpo_hash) of the four words (a.c0, a.c1,
+ *               b.c0, b.c1) of a = e[i], b = e[i + domain_size / 2], i = bitrev(j) over log2(domain_size) - 1 bits - the
+ *               reference's chunks of two of the bit-reversed vector; a node is the 2-to-1 hash of lw_rpo_commit_columns.
+ *               d_nodes: (domain_size - 1) digests, root first; lw_stark_open_trees_device reads an LW_RPO_128 tree as it
+ *               is.  out_root_or_null: one digest to host memory.
+ *   errors      domain_size not a power of two: LW_ERR_INPUT_NOT_POW2; below the block length, d_out_poly overlapping
+ *               d_coeffs (or any two buffers of the layer overlapping), an unknown level: LW_ERR_BAD_ARG */
+typedef enum { LW_GL2_MUL = 0, LW_GL2_SQR = 1, LW_GL2_INV = 2, LW_GL2_MUL_BASE = 3 } lw_gl2_op_t;
+int lw_goldilocks_ext2_pointwise_device(lw_gl2_op_t op, const uint64_t *d_a, size_t a_stride, const uint64_t *d_b, size_t b_stride,
+                                        uint64_t *d_out, size_t out_stride, size_t n, void *hip_stream);
+int lw_goldilocks_ext2_evaluate_device(const uint64_t *d_coeffs, uint32_t n_cols, size_t col_stride, size_t n_coeffs,
+                                       const uint64_t *points, uint32_t m, uint64_t *out_values, void *hip_stream);
+int lw_goldilocks_ext2_deep_quotients_device(const uint64_t *d_lde, uint32_t n_cols, size_t col_stride, uint32_t log2n,
+                                             const uint64_t *offset_or_null, uint64_t two_adic_root, const uint64_t *points,
+                                             uint32_t m, const uint64_t *weights, const uint64_t *evals, uint64_t *d_out,
+                                             size_t out_stride, void *hip_stream);
+int lw_goldilocks_ext2_fri_layer_device(const uint64_t *d_coeffs, size_t coeff_stride, size_t n_coeffs, const uint64_t *zeta,
+                                        const uint64_t *offset_or_null, size_t domain_size, uint64_t two_adic_root,
+                                        lw_rpo_level_t level, uint64_t *d_out_poly, uint64_t *d_out_evaluation_or_null,
+                                        uint64_t *d_nodes_or_null, uint64_t *out_root_or_null, void *hip_stream);
+
 /* ---- Monolith over Mersenne31 (crypto/src/hash/monolith/: MonolithMersenne31<WIDTH, NUM_FULL_ROUNDS>, from Plonky3) ----
  * The permutation, batched (one work-item per state), and for width 16 a hash, a 2-to-1 compression and a Merkle tree
  * built from it.  Words are Mersenne31 elements as in the circle FFT: one u32; every input word is read mod p = 2^31 - 1

@@ -98,7 +98,7 @@ __global__ void gl_mul_kernel(const uint64_t *a, const uint64_t *b, uint64_t *ou
 
 // ---------------------------------------------------------------- host
 // the primitive 2^order-th root g^(2^(32 - order)) (traits.rs:82-94) of the 2^32-th root g, or its inverse
-static uint64_t gl_host_root(uint64_t g, uint32_t order, bool inverse) {
+uint64_t gl_host_root(uint64_t g, uint32_t order, bool inverse) {
     for (uint32_t i = order; i < GL_TWO_ADICITY; i++) g = gl_mul(g, g);
     return inverse ? gl_inv(g) : g;
 }
@@ -179,8 +179,20 @@ static int gl_transform_device(Context &c, GlCall call, const uint64_t *d_in, ui
     return tile_transform_device<GoldilocksPolicy>(c, call, d_in, in_stride, in_log2, d_out, out_stride, L, batch, stream);
 }
 
-// ---- argument checks, before any device work
-static int gl_size_check(uint64_t log2n) {
+// the low-degree extension inside another call's Entry (the Fp2 FRI layer of goldilocks_ext.hip: batch = 2 planes); root and
+// offset are validated, offset = 1 is no coset
+int goldilocks_lde_locked(Context &c, const uint64_t *d_coeffs, uint32_t log2_coeffs, uint64_t in_stride, uint64_t *d_out, uint32_t log2n,
+                          uint64_t out_stride, uint32_t batch, uint64_t offset, uint64_t root, hipStream_t stream) {
+    GlCall call{};
+    call.inv = false;
+    call.root = root;
+    call.coset = offset != 1;
+    call.h = offset;
+    return gl_transform_device(c, call, d_coeffs, in_stride, log2_coeffs, d_out, out_stride, log2n, batch, stream);
+}
+
+// ---- argument checks, before any device work (the first two are goldilocks_ext.hip's too: internal.h)
+int gl_size_check(uint64_t log2n) {
     if (log2n > GL_TWO_ADICITY) {
         set_error("order %llu exceeds the field's two-adicity 32", (unsigned long long)log2n);
         return LW_ERR_ROOT_OF_UNITY;
@@ -191,7 +203,7 @@ static int gl_size_check(uint64_t log2n) {
     }
     return LW_OK;
 }
-static int gl_root_check(uint64_t &root) {
+int gl_root_check(uint64_t &root) {
     if (root == 0) { root = GL_TWO_ADIC_ROOT; return LW_OK; }
     uint64_t v = root;
     for (int i = 0; i < 31; i++) v = gl_mul(v, v);

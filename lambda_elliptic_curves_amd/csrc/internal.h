@@ -56,6 +56,19 @@ int fri_layer_device(Context &c, lw_field_t field, const void *d_coeffs, uint64_
                      uint32_t log2_domain, void *d_poly, uint32_t log2_block, void *d_eval, void *d_eval_br, void *d_nodes,
                      hipStream_t stream);
 
+// ---- goldilocks.hip
+int gl_size_check(uint64_t log2n);    // 2^log2n points: LW_ERR_ROOT_OF_UNITY above 32, LW_ERR_ORDER_TOO_LARGE above 30
+int gl_root_check(uint64_t &root);    // 0 becomes the reference's 2^32-th root; anything else must be a primitive one below p
+uint64_t gl_host_root(uint64_t g, uint32_t order, bool inverse);   // the primitive 2^order-th root of the 2^32-th root g, or its inverse
+int goldilocks_lde_locked(Context &c, const uint64_t *d_coeffs, uint32_t log2_coeffs, uint64_t in_stride, uint64_t *d_out, uint32_t log2n,
+                          uint64_t out_stride, uint32_t batch, uint64_t offset, uint64_t root, hipStream_t stream);
+
+// ---- rpo.hip
+int rpo_level_check(int level);   // LW_RPO_128 or LW_RPO_160, else LW_ERR_BAD_ARG
+// the tree of lw_rpo_commit_columns_device inside another call's Entry; group: RpoHash::row's element order (0: as it is)
+int rpo_commit_locked(Context &c, int level, const uint64_t *d_columns, uint32_t n_cols, uint64_t col_stride, uint32_t log2n, int bit_reverse,
+                      int group, uint64_t *d_nodes, hipStream_t stream);
+
 // ---- groth16.hip
 int groth16_h_device(Context &c, const void *d_l, const void *d_r, const void *d_o, uint32_t log2_gates, void *d_out, void *d_tmp,
                      hipStream_t stream);

@@ -47,18 +47,23 @@ template <int LV> struct RpoHash {   // the policy of hash_tree.cuh: an element 
     }
     // hash (rescue_prime_optimized.rs:205-230) of the `len` words row[c * elem_stride].  Word 0 of the state is 1 iff len is
     // no multiple of the rate; every block OVERWRITES the rate part; a partial last block is the words, a 1, zeros; len = 0
-    // runs no permutation and the digest is zeros.  len and the block count are wave-uniform.  No mode.
-    static __device__ __forceinline__ void row(const char *row, uint32_t len, uint64_t elem_stride, int, char *out) {
+    // runs no permutation and the digest is zeros.  len and the block count are wave-uniform.
+    // mode is a group size g (0: none): word c of the row is element (c mod g) (len / g) + c / g, so that `len / g` columns of
+    // each of g vectors hash element after element (the Fp2 FRI layer of goldilocks_ext.hip: g = 2 planes).  g divides len.
+    static __device__ __forceinline__ void row(const char *row, uint32_t len, uint64_t elem_stride, int mode, char *out) {
         uint64_t s[R::M];
 #pragma unroll
         for (int j = 0; j < R::M; j++) s[j] = 0;
         if (len % R::RATE) s[0] = 1;
         const uint32_t blocks = (len + R::RATE - 1) / R::RATE;
+        const uint32_t g = (uint32_t)mode, per = g ? len / g : 0;
         for (uint32_t b = 0; b < blocks; b++) {
 #pragma unroll
             for (int h = 0; h < R::RATE; h++) {
                 const uint32_t c = b * R::RATE + h;   // wave-uniform
-                s[R::CAP + h] = c < len ? gl_from_word(((const uint64_t *)row)[(uint64_t)c * elem_stride]) : (c == len ? 1 : 0);
+                uint32_t e = c;
+                if (g && c < len) e = (c % g) * per + c / g;
+                s[R::CAP + h] = c < len ? gl_from_word(((const uint64_t *)row)[(uint64_t)e * elem_stride]) : (c == len ? 1 : 0);
             }
             rpo_permute<LV>(s);
         }
@@ -73,9 +78,16 @@ template <class F> static int rpo_with_level(int level, F f) { return level == L
 
 // ---- argument checks: one per entry-point family, run before any device work
 static constexpr uint64_t RPO_MAX_N = (uint64_t)1 << 36;   // the grid's block index stays below 2^31
-static int level_check(int level) {
+int rpo_level_check(int level) {
     if (level != LW_RPO_128 && level != LW_RPO_160) { set_error("bad RPO level %d", level); return LW_ERR_BAD_ARG; }
     return LW_OK;
+}
+
+int rpo_commit_locked(Context &c, int level, const uint64_t *d_columns, uint32_t n_cols, uint64_t col_stride, uint32_t log2n, int bit_reverse,
+                      int group, uint64_t *d_nodes, hipStream_t stream) {
+    return rpo_with_level(level, [&](auto h) {
+        return tree_commit_device<decltype(h)>(c, RPO_NAMES, d_columns, n_cols, col_stride, log2n, bit_reverse, group, d_nodes, stream);
+    });
 }
 
 }  // namespace lw
@@ -85,7 +97,7 @@ using namespace lw;
 extern "C" {
 
 static int permute_entry(int level, const void *states, size_t n, void *out, void *hip_stream, bool device) {
-    int rc = level_check(level);
+    int rc = rpo_level_check(level);
     if (!rc) rc = flat_check(n, RPO_MAX_N, "RPO", {states, out}, device);
     if (rc || n == 0) return rc;
     return rpo_with_level(level, [&](auto h) {
@@ -103,7 +115,7 @@ int lw_rpo_permute_device(lw_rpo_level_t level, const uint64_t *d_states, size_t
 static int hash_entry(int level, const void *rows, size_t n_rows, size_t row_len, size_t row_stride, void *out, void *hip_stream,
                       bool device) {
     if (row_stride == 0) row_stride = row_len;
-    int rc = level_check(level);
+    int rc = rpo_level_check(level);
     if (!rc) rc = rows_check(n_rows, row_len, row_stride, RPO_MAX_N, "RPO", "words", rows, out, device);
     if (rc || n_rows == 0) return rc;
     return rpo_with_level(level, [&](auto h) {
@@ -121,7 +133,7 @@ int lw_rpo_hash_device(lw_rpo_level_t level, const uint64_t *d_rows, size_t n_ro
 // checks of both commitment forms; nodes_or_root: d_nodes (device form) or out_root (host form)
 static int commit_check(int level, const void *columns, const void *nodes_or_root, uint32_t n_cols, uint64_t col_stride, uint32_t log2n,
                         bool device) {
-    const int rc = level_check(level);
+    const int rc = rpo_level_check(level);
     return rc ? rc : tree_commit_check(columns, nodes_or_root, n_cols, col_stride, log2n, 30, device);
 }
 int lw_rpo_commit_columns_device(lw_rpo_level_t level, const uint64_t *d_columns, uint32_t n_cols, uint64_t col_stride, uint32_t log2n,

@@ -1,0 +1,136 @@
+"""The quadratic extension of Goldilocks, Fp2 = F_p[t] / (t^2 - 7) (Goldilocks64ExtensionField of the reference, Plonky2's
+quadratic extension), and the prover steps that run in it on device-resident data: out-of-domain evaluation, the DEEP
+composition in evaluation form and the FRI commit phase (fri::commit_phase<F, E> with F Goldilocks, E = Fp2).
+
+A host-side Fp2 scalar is a pair (c0, c1) of integers, a = c0 + c1 t.  A vector of n elements on the device is a torch
+int64 tensor of two PLANES of n words, c0 then c1 `stride` words later (0: dense): the same bytes lw_goldilocks_ntt_device
+takes as batch = 2 and lw_rpo_commit_columns_device as n_cols = 2, so goldilocks.ntt_device / lde_device transform an Fp2
+vector as it is.  Everything runs on torch's current stream unless `stream` is given.
+"""
+import numpy as np
+
+from . import _lib as L
+from .errors import check
+from .goldilocks import P, _offset_arg
+
+NON_RESIDUE = 7
+MUL, SQR, INV, MUL_BASE = L.GL2_MUL, L.GL2_SQR, L.GL2_INV, L.GL2_MUL_BASE
+RPO_128, RPO_160 = L.RPO_128, L.RPO_160
+_M64 = (1 << 64) - 1
+
+
+def _scalars(values, count):
+    """`count` Fp2 scalars [(c0, c1), ...] (or one pair when count is 1) -> a (count, 2) uint64 array"""
+    a = np.array([[int(c) & _M64 for c in v] for v in values], np.uint64).reshape(-1, 2) if count else np.zeros((0, 2), np.uint64)
+    if a.shape[0] != count:
+        raise ValueError(f"{a.shape[0]} Fp2 scalars where {count} are expected")
+    return a
+
+
+# ---- host-side helpers
+def times_t(a):
+    """(c0, c1) -> t (c0, c1) = (7 c1, c0): the weight of the c1 plane of an Fp2 column"""
+    return (NON_RESIDUE * int(a[1]) % P, int(a[0]) % P)
+
+
+def combine_planes(v0, v1):
+    """The value v0 + t v1 of a polynomial with Fp2 coefficients from the values of its two planes."""
+    t1 = times_t(v1)
+    return ((int(v0[0]) + t1[0]) % P, (int(v0[1]) + t1[1]) % P)
+
+
+def plane_weights(w):
+    """The two weight rows of an Fp2 column passed as its two planes: [w, t w] for each weight of the row."""
+    return [tuple(int(c) % P for c in x) for x in w], [times_t(x) for x in w]
+
+
+# ---- the calls
+def pointwise_device(op, t_a, t_b, t_out, n, a_stride=0, b_stride=0, out_stride=0, stream=None):
+    """t_out[i] = t_a[i] t_b[i] (MUL), t_a[i]^2 (SQR), t_a[i]^-1 (INV; the inverse of 0 is 0) or t_a[i] t_b[i] with t_b a
+    single plane of base-field words (MUL_BASE), for n elements.  t_b may be None for SQR and INV; t_out may be t_a or t_b."""
+    check(L.lib().lw_goldilocks_ext2_pointwise_device(op, L.device_ptr(t_a), a_stride, L.device_ptr(t_b) if t_b is not None else None, b_stride,
+                                                     L.device_ptr(t_out), out_stride, n, L.stream_ptr(stream)))
+    return t_out
+
+
+def evaluate_device(t_coeffs, n_cols, n_coeffs, points, col_stride=0, stream=None):
+    """Out-of-domain evaluation: n_cols base-field coefficient columns of n_coeffs words (col_stride apart) at the Fp2
+    `points` [(c0, c1), ...] -> an (n_cols, m, 2) uint64 array.  Waits for the stream."""
+    pts = _scalars(points, len(points))
+    out = np.zeros((n_cols, len(points), 2), np.uint64)
+    check(L.lib().lw_goldilocks_ext2_evaluate_device(L.device_ptr(t_coeffs), n_cols, col_stride, n_coeffs, L.host_ptr(pts), len(points),
+                                                    L.host_ptr(out), L.stream_ptr(stream)))
+    return out
+
+
+def evaluate_ext_device(t_coeffs, n_coeffs, points, plane_stride=0, stream=None):
+    """A polynomial with Fp2 coefficients (two planes) at the Fp2 points -> [(c0, c1), ...]."""
+    v = evaluate_device(t_coeffs, 2, n_coeffs, points, plane_stride, stream)
+    return [combine_planes(v[0, j], v[1, j]) for j in range(len(points))]
+
+
+def deep_quotients_device(t_lde, n_cols, log2n, points, weights, evals, t_out, col_stride=0, out_stride=0, offset=None, root=0, stream=None):
+    """t_out[i] = sum_j (sum_k weights[k][j] (col_k[i] - evals[k][j])) / (x_i - points[j]) over the 2^log2n rows of the LDE
+    domain x_i = offset w^i.  weights, evals: n_cols rows of m Fp2 scalars; t_out: an Fp2 vector of 2^log2n elements.  An Fp2
+    column is its two planes as two columns with the weight rows of plane_weights()."""
+    m = len(points)
+    pts, w, e = _scalars(points, m), _scalars([x for row in weights for x in row], n_cols * m), _scalars([x for row in evals for x in row], n_cols * m)
+    check(L.lib().lw_goldilocks_ext2_deep_quotients_device(L.device_ptr(t_lde), n_cols, col_stride, log2n, L.host_ptr(_offset_arg(offset)), root,
+                                                          L.host_ptr(pts), m, L.host_ptr(w), L.host_ptr(e), L.device_ptr(t_out), out_stride,
+                                                          L.stream_ptr(stream)))
+    return t_out
+
+
+def folded_block(n_coeffs):
+    """The length of the zero-padded block a fold of n_coeffs coefficients writes."""
+    return max(2, 1 << max((n_coeffs + 1) // 2 - 1, 0).bit_length())
+
+
+def digest_words(level):
+    return 4 if level == RPO_128 else 5
+
+
+def fri_layer_device(t_coeffs, n_coeffs, zeta, coset_offset, domain_size, level=RPO_128, coeff_stride=0, root=0, fold_only=False, stream=None):
+    """One layer of the FRI commit phase over Fp2: fold t_coeffs (an Fp2 vector of n_coeffs elements) with the challenge
+    zeta = (c0, c1), evaluate the result on the coset of `domain_size` points (already halved) with offset `coset_offset`
+    (already squared) and commit pairs of evaluations in an RPO tree.
+    -> (t_poly, t_evaluation, t_nodes, root): the folded block (two dense planes of folded_block(n_coeffs) words), the
+    evaluation (two dense planes of domain_size words), the (domain_size - 1) digests and the root as a uint64 array;
+    with fold_only the last three are None."""
+    import torch
+    z = _scalars([zeta], 1)
+    t_poly = torch.empty(2 * folded_block(n_coeffs), dtype=torch.int64, device=t_coeffs.device)
+    if fold_only:
+        check(L.lib().lw_goldilocks_ext2_fri_layer_device(L.device_ptr(t_coeffs), coeff_stride, n_coeffs, L.host_ptr(z), None, 0, root, level,
+                                                         L.device_ptr(t_poly), None, None, None, L.stream_ptr(stream)))
+        return t_poly, None, None, None
+    d = digest_words(level)
+    t_eval = torch.empty(2 * domain_size, dtype=torch.int64, device=t_coeffs.device)
+    t_nodes = torch.empty(max(domain_size - 1, 1) * d, dtype=torch.int64, device=t_coeffs.device)
+    out_root = np.zeros(d, np.uint64)
+    check(L.lib().lw_goldilocks_ext2_fri_layer_device(L.device_ptr(t_coeffs), coeff_stride, n_coeffs, L.host_ptr(z), L.host_ptr(_offset_arg(coset_offset)),
+                                                     domain_size, root, level, L.device_ptr(t_poly), L.device_ptr(t_eval), L.device_ptr(t_nodes),
+                                                     L.host_ptr(out_root), L.stream_ptr(stream)))
+    return t_poly, t_eval, t_nodes, out_root
+
+
+def fri_commit_phase_device(t_coeffs, n_coeffs, number_layers, coset_offset, domain_size, challenge, level=RPO_128, root=0, stream=None):
+    """fri::commit_phase (provers/stark/src/fri/mod.rs:22-75) over Fp2 on a device-resident polynomial: t_coeffs is an Fp2
+    vector of n_coeffs coefficients in dense planes, domain_size and coset_offset those of the LDE domain.
+    challenge(prev_root_or_None) -> (c0, c1) is the caller's transcript: called once per fold with the root of the layer
+    committed just before (None for the first), it absorbs that root and samples the next zeta.  number_layers - 1 layers
+    are committed, then one more fold gives the constant.
+    -> (last_value (c0, c1), [(t_evaluation, t_nodes, root), ...]), the layers left on the device."""
+    layers, prev = [], None
+    t_poly, n, h = t_coeffs, n_coeffs, int(coset_offset) % P
+    for _ in range(1, number_layers):
+        domain_size //= 2
+        h = h * h % P
+        t_poly, t_eval, t_nodes, layer_root = fri_layer_device(t_poly, n, challenge(prev), h, domain_size, level, root=root, stream=stream)
+        n = folded_block(n)   # the dense block, zero padding included, is the next layer's polynomial
+        layers.append((t_eval, t_nodes, layer_root))
+        prev = layer_root
+    t_last, _, _, _ = fri_layer_device(t_poly, n, challenge(prev), None, 0, level, root=root, fold_only=True, stream=stream)
+    block = t_last.numel() // 2
+    last = t_last.cpu().numpy().view(np.uint64)
+    return (int(last[0]), int(last[block])), layers

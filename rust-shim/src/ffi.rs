@@ -386,6 +386,21 @@ extern "C" {
     pub fn lw_rpo_commit_columns_device(level: c_int, d_columns: *const u64, n_cols: u32, col_stride: u64, log2n: u32,
                                         bit_reverse: c_int, d_nodes: *mut u64, out_root_or_null: *mut u64,
                                         hip_stream: *mut c_void) -> c_int;
+    // ---- Goldilocks quadratic extension F_p[t] / (t^2 - 7): an Fp2 vector is two planes of words, a host scalar is [c0, c1];
+    // op is LW_GL2_MUL / LW_GL2_SQR / LW_GL2_INV / LW_GL2_MUL_BASE
+    pub fn lw_goldilocks_ext2_pointwise_device(op: c_int, d_a: *const u64, a_stride: usize, d_b: *const u64, b_stride: usize,
+                                               d_out: *mut u64, out_stride: usize, n: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_goldilocks_ext2_evaluate_device(d_coeffs: *const u64, n_cols: u32, col_stride: usize, n_coeffs: usize,
+                                              points: *const u64, m: u32, out_values: *mut u64, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_goldilocks_ext2_deep_quotients_device(d_lde: *const u64, n_cols: u32, col_stride: usize, log2n: u32,
+                                                    offset_or_null: *const u64, two_adic_root: u64, points: *const u64, m: u32,
+                                                    weights: *const u64, evals: *const u64, d_out: *mut u64, out_stride: usize,
+                                                    hip_stream: *mut c_void) -> c_int;
+    pub fn lw_goldilocks_ext2_fri_layer_device(d_coeffs: *const u64, coeff_stride: usize, n_coeffs: usize, zeta: *const u64,
+                                               offset_or_null: *const u64, domain_size: usize, two_adic_root: u64, level: c_int,
+                                               d_out_poly: *mut u64, d_out_evaluation_or_null: *mut u64,
+                                               d_nodes_or_null: *mut u64, out_root_or_null: *mut u64,
+                                               hip_stream: *mut c_void) -> c_int;
     // ---- Monolith over Mersenne31: batched permutations (width 8 .. 24, rounds 1 .. 15); hash, compression and Merkle tree over width 16
     pub fn lw_monolith_permute(width: u32, rounds: u32, states: *const u32, n: usize, out: *mut u32) -> c_int;
     pub fn lw_monolith_permute_device(width: u32, rounds: u32, d_states: *const u32, n: usize, d_out: *mut u32,
@@ -533,6 +548,12 @@ pub const LW_FIELD_OP_TO_R64: c_int = 21;
 pub const LW_RPO_128: c_int = 0;
 /// lw_rpo_level_t: state 16, capacity 6, rate 10, digest 5 words
 pub const LW_RPO_160: c_int = 1;
+
+/// lw_gl2_op_t: the operation of lw_goldilocks_ext2_pointwise_device
+pub const LW_GL2_MUL: c_int = 0;
+pub const LW_GL2_SQR: c_int = 1;
+pub const LW_GL2_INV: c_int = 2;
+pub const LW_GL2_MUL_BASE: c_int = 3;
 
 /// lw_monolith_layer_t: the layer lw_monolith_layer_device applies
 pub const LW_MONOLITH_CONCRETE: c_int = 0;

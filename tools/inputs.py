@@ -5,6 +5,7 @@ import numpy as np
 P_BABYBEAR = 2013265921
 P_STARK252 = 0x800000000000011000000000000000000000000000000000000000000000001
 P_FR381 = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
+P_GOLDILOCKS = (1 << 64) - (1 << 32) + 1
 
 
 def field_pairs():
@@ -34,6 +35,8 @@ def rand_elems(name, n, seed):
         return rng.integers(0, P_BABYBEAR, size=n, dtype=np.uint64)
     if name == "babybear_ext4":
         return rng.integers(0, P_BABYBEAR, size=(n, 4), dtype=np.uint64)
+    if name == "goldilocks":
+        return rng.integers(0, P_GOLDILOCKS, size=n, dtype=np.uint64)
     raise KeyError(name)
 
 
