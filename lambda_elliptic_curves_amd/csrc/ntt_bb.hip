@@ -15,10 +15,8 @@
 
 namespace lw {
 
-constexpr int BB_TILE_LOG = 13;            // 8192 u32 = 32 KiB of LDS
-constexpr int BB_TILE = 1 << BB_TILE_LOG;
+constexpr int BB_TILE = 1 << BB_TILE_LOG;  // BB_TILE_LOG, BB_KMAX: ntt_plan.h
 constexpr int BB_THREADS = 256;
-constexpr int BB_KMAX = 4;                 // radix-16 register steps
 
 struct BbPassParams {
     const void *in;
@@ -423,8 +421,7 @@ static int bb_run(Context &c, lw_dir_t dir, uint32_t lgV, const void *d_in, void
         // (a 4-columns-per-lane variant of this kernel measured no faster — the pass is bound by butterfly issue and
         // LDS exchange, not by the width of its memory instructions)
         // full-size tiles (every pass of a transform of 2^18 words and more) take the kernels with the tile shape compiled in
-        const bool full = p.r >= 6 && p.r <= 8 && p.logC == BB_TILE_LOG - p.r && p.nsteps == 2 && p.k[0] == (p.r >= 7 ? 4u : 3u) &&
-                          p.k[1] == p.r - p.k[0] && (lgV == 0 || lgV == 2);
+        const uint32_t rx = bb_tile_rx(st, lgV);   // ntt_plan.h
 #define LW_BB_LAUNCH_R(LASTV, INV, OUTV, R)                                                                                          \
     do {                                                                                                                            \
         if (lgV == 0) hipLaunchKernelGGL((bb_pass_kernel<LASTV, INV, OUTV, R, 0>), grid, dim3(BB_THREADS), 0, stream, p);            \
@@ -432,9 +429,9 @@ static int bb_run(Context &c, lw_dir_t dir, uint32_t lgV, const void *d_in, void
     } while (0)
 #define LW_BB_LAUNCH(LASTV, INV, OUTV)                                                                                              \
     do {                                                                                                                            \
-        if (full && p.r == 8) LW_BB_LAUNCH_R(LASTV, INV, OUTV, 8);                                                                  \
-        else if (full && p.r == 7) LW_BB_LAUNCH_R(LASTV, INV, OUTV, 7);                                                             \
-        else if (full) LW_BB_LAUNCH_R(LASTV, INV, OUTV, 6);                                                                         \
+        if (rx == 8) LW_BB_LAUNCH_R(LASTV, INV, OUTV, 8);                                                                           \
+        else if (rx == 7) LW_BB_LAUNCH_R(LASTV, INV, OUTV, 7);                                                                      \
+        else if (rx == 6) LW_BB_LAUNCH_R(LASTV, INV, OUTV, 6);                                                                      \
         else hipLaunchKernelGGL((bb_pass_kernel<LASTV, INV, OUTV, 0, 0>), grid, dim3(BB_THREADS), 0, stream, p);                    \
     } while (0)
         if (last) {

@@ -119,6 +119,20 @@ inline PassSchedule schedule_passes(const NttPlan &pl, bool backward, bool alias
     return sc;
 }
 
+// BabyBear (ntt_bb.hip): the tile of a pass and the stages of a register step
+constexpr int BB_TILE_LOG = 13;   // 8192 u32 = 32 KiB of LDS
+constexpr int BB_KMAX = 4;        // radix-16 register steps
+
+// Which bb_pass_kernel a pass of a BabyBear transform takes: 8, 7 or 6 = the kernel with a full-size tile of that many
+// stages compiled in (2^(13 - r) columns x components, two register steps of 4+4, 4+3 or 3+3 stages, lgV = 0 or 2), 0 = the
+// kernel that takes its tile shape from the parameters.  Here, not in ntt_bb.hip, so that
+// tests/test_ntt_bb_shapes_cpu.py can tell without a device which sizes reach which instantiation.
+inline uint32_t bb_tile_rx(const PassStep &st, uint32_t lgV) {
+    const bool full = st.r >= 6 && st.r <= 8 && st.logC == BB_TILE_LOG - st.r && st.nsteps == 2 && st.k[0] == (st.r >= 7 ? 4u : 3u) &&
+                      st.k[1] == st.r - st.k[0] && (lgV == 0 || lgV == 2);
+    return full ? st.r : 0u;
+}
+
 // f(b0, nb) over a batch in chunks of at most MAX_BATCH columns, until one returns an error
 template <class F> inline int split_batch(uint32_t batch, F f) {
     for (uint32_t b0 = 0; b0 < batch; b0 += MAX_BATCH) {

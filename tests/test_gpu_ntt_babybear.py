@@ -151,6 +151,6 @@ def test_lde_batch_split_above_32768_blocks(name):
 
 
 @pytest.mark.parametrize("name", BB)
-@pytest.mark.parametrize("log_n", [1, 5, 8, 9])
+@pytest.mark.parametrize("log_n", [1, 5, 8, 9, 13, 16])
 def test_strided_columns_with_canaries_distinct_and_in_place(name, log_n):
     util.check_ntt_strided(name, log_n)

@@ -249,8 +249,9 @@ def check_ntt_lde_split(name):
 
 
 def check_ntt_strided(name, log2n):
-    """3 columns, n + 8 elements apart, canaries between them and behind the last: forward, inverse and coset forward,
-    into a second buffer and in place.  One pass up to 2^8 (in place: the staging copy), two at 2^9."""
+    """3 columns, n + 8 elements apart, canaries between them and behind the last: forward, inverse, coset forward and
+    coset inverse, into a second buffer and in place.  One pass up to 2^8 (in place: the staging copy), two from 2^9 on
+    (BabyBear at 2^13 and 2^16: the kernels with the tile shape compiled in)."""
     n, batch = 1 << log2n, 3
     stride = n + 8
     cols = ntt_columns(name, batch, n, 1600 + log2n)
@@ -260,7 +261,7 @@ def check_ntt_strided(name, log2n):
     a[:, :n] = cols
     a = a.reshape(batch * stride, W)
     off = offset_elem(name, 3)
-    for inverse, offset in ((False, None), (True, None), (False, off)):
+    for inverse, offset in ((False, None), (True, None), (False, off), (True, off)):
         want = np.full((batch, stride, W), canary, dt)
         for b in range(batch):
             want[b, :n] = ntt_oracle(name, cols[b], inverse=inverse, offset=offset)
