@@ -1103,6 +1103,88 @@ int lw_goldilocks_ext2_fri_layer_device(const uint64_t *d_coeffs, size_t coeff_s
                                         lw_rpo_level_t level, uint64_t *d_out_poly, uint64_t *d_out_evaluation_or_null,
                                         uint64_t *d_nodes_or_null, uint64_t *out_root_or_null, void *hip_stream);
 
+/* ---- The quartic extension of BabyBear, Fp4 = F_p[x] / (x^4 + 11), and the prover steps that run in it ----
+ * Degree4BabyBearExtensionField (math/src/field/fields/fft_friendly/quartic_babybear.rs; RISC Zero's extension): what a
+ * STARK over BabyBear needs after round 1 - out-of-domain evaluation, the DEEP composition and the FRI commit phase
+ * (fri::commit_phase<F, E>, provers/stark/src/fri/mod.rs:22-75, with F BabyBear and E = Fp4).  Together with
+ * lw_hip_ntt_lde_device and lw_stark_commit_columns_layout_device the BabyBear path runs LDE -> Keccak commit -> OOD ->
+ * DEEP -> FRI commit phase on data that stays in device memory.
+ *   word            one uint32_t, the stored Montgomery value with R = 2^32, canonical (< p = 2013265921): exactly
+ *                   LW_LAYOUT_BABYBEAR_U32_R32.  Inputs must be canonical; every output word is canonical.
+ *   Fp4 element     a = a0 + a1 x + a2 x^2 + a3 x^3, x^4 = -11
+ *   host scalar     uint32_t[4] = {c0, c1, c2, c3}, stored words: the challenge, the points, the weights and the returned
+ *                   values.  A host scalar word >= p is LW_ERR_BAD_ARG.
+ *   device vector   n elements are four PLANES of n words: c0, then c1 `stride` words later, and so on.  A stride of 0
+ *                   means n; a stride below n is LW_ERR_BAD_ARG.  This is the batch shape of lw_hip_ntt_device /
+ *                   lw_hip_ntt_lde_device and the n_cols / col_stride shape of lw_stark_commit_columns_layout_device: an
+ *                   Fp4 vector goes through them with batch = 4 / n_cols = 4 as it is (the twiddles are in F, so an Fp4
+ *                   transform over a base-field domain is four base transforms).  LW_LAYOUT_EXT4_INTERLEAVED stays the
+ *                   NTT-only layout it is; convert (below) is the bridge to it.
+ * All entry points are _device forms under the stream and lane contract of the other *_device calls.  Device pointers
+ * must be 16-byte aligned (else LW_ERR_BAD_ARG).  Every argument check runs before any device work; n = 0 returns LW_OK
+ * without a device.  A call that hands a small result to the host (values, a root) waits for the stream; the others only
+ * enqueue.
+ *
+ * pointwise: out[i] = a[i] b[i] (LW_BB4_MUL), a[i]^2 (LW_BB4_SQR), a[i]^-1 (LW_BB4_INV), a[i] b[i] with b in F
+ * (LW_BB4_MUL_BASE: d_b is a single plane, b_stride is not read).  d_b is not read for SQR and INV and may be NULL.
+ * d_out == d_a or d_out == d_b (the whole vector, under the same stride) is allowed; any other overlap of d_out with an
+ * operand, like an unknown op, is LW_ERR_BAD_ARG.  The inverse of 0 is written as 0: the reference returns an error
+ * there, and 0 is the only element without an inverse (x^4 + 11 is irreducible).
+ *
+ * convert: LW_BB4_TO_PLANES reads n elements of LW_LAYOUT_EXT4_INTERLEAVED from d_interleaved (four u64 words per
+ * element, each a 2^64 mod p, below p) and writes four planes of stored u32 words to d_planes, plane_stride apart;
+ * LW_BB4_TO_INTERLEAVED is the way back.  The two buffers must not overlap; an unknown direction is LW_ERR_BAD_ARG.
+ *
+ * evaluate (STARK round 3): out_values[k m + j] = sum_i col_k[i] points[j]^i for n_cols base-field coefficient columns
+ * of n_coeffs words each, col_stride words apart, at m points of Fp4; out_values is host memory, n_cols m scalars.  A
+ * polynomial with Fp4 coefficients is its four planes passed as four columns, its value sum_e x^e v_e.  No cap on n_cols
+ * or m.  n_coeffs = 0 gives zeros.
+ *
+ * deep_quotients: the DEEP composition polynomial (compute_deep_composition_poly, provers/stark/src/prover.rs:643-714,
+ * over a weight matrix as lw_stark_deep_composition states it) in evaluation form.  For every row i of the LDE domain,
+ * x_i = h w^i in natural order, w the library's primitive 2^log2n-th root of BabyBear (log2n > 24: LW_ERR_ROOT_OF_UNITY):
+ *     out[i] = sum_j ( sum_k weights[k][j] (col_k[i] - evals[k][j]) ) / (x_i - points[j])
+ * d_lde: n_cols base-field columns of 2^log2n words, col_stride apart.  points: m scalars; weights, evals: n_cols x m
+ * scalars, row k, column j (host).  A zero weight skips its pair.  A part with Fp4 values is its four planes as four
+ * columns, the weight of plane e multiplied by x^e by the caller.  A point whose c1, c2 and c3 are all zero is
+ * LW_ERR_BAD_ARG: a base-field point can lie on the domain.  offset_or_null: h as one stored word (NULL: 1; 0:
+ * LW_ERR_INV_ZERO).  d_out: an Fp4 vector of 2^log2n elements that overlaps no column.  n_cols = 0 or m = 0:
+ * LW_ERR_BAD_ARG.  lw_hip_ntt_device (inverse, same offset, batch = 4) of the result gives the coefficients of the DEEP
+ * polynomial.
+ *
+ * fri_layer: the Fp4 counterpart of lw_stark_fri_layer_device (fri/mod.rs:44-58, 115-141).
+ *   fold        d_out_poly[i] = 2 (c[2i] + zeta c[2i+1]), the odd term absent past n_coeffs, as a zero-padded block of
+ *               max(2, next_pow2(ceil(n_coeffs / 2))) elements in four DENSE planes: the next layer's d_coeffs
+ *   fold only   d_nodes_or_null == NULL (the last step, whose coefficient 0 is the value sent); an evaluation or a root
+ *               asked for without nodes is LW_ERR_BAD_ARG
+ *   evaluation  d_out_evaluation receives evaluate_offset_fft(p', 1, Some(domain_size), offset) in natural order, four
+ *               dense planes of domain_size words.  offset_or_null is the layer's offset in F (already squared by the
+ *               caller), domain_size the layer's domain (already halved).  NULL with nodes: LW_ERR_BAD_ARG
+ *   tree        Keccak-256, domain_size / 2 leaves; leaf j hashes the 32 bytes a.c0 a.c1 a.c2 a.c3 b.c0 b.c1 b.c2 b.c3, every
+ *               word big-endian (U32MontgomeryBackendPrimeField::as_bytes), of a = e[i], b = e[i + domain_size / 2],
+ *               i = bitrev(j) over log2(domain_size) - 1 bits - the reference's chunks of two of the bit-reversed vector
+ *               in a BatchedMerkleTree; a node is the 2-to-1 hash of lw_stark_commit_columns.  d_nodes:
+ *               (domain_size - 1) x 32 bytes, root first; lw_stark_open_trees_device reads the tree as it is.
+ *               out_root_or_null: 32 bytes to host memory.
+ *   errors      domain_size not a power of two: LW_ERR_INPUT_NOT_POW2; above 2^24: LW_ERR_ROOT_OF_UNITY; below the block
+ *               length, d_out_poly overlapping d_coeffs (or any two buffers of the layer overlapping): LW_ERR_BAD_ARG */
+typedef enum { LW_BB4_MUL = 0, LW_BB4_SQR = 1, LW_BB4_INV = 2, LW_BB4_MUL_BASE = 3 } lw_bb4_op_t;
+typedef enum { LW_BB4_TO_PLANES = 0, LW_BB4_TO_INTERLEAVED = 1 } lw_bb4_convert_t;
+int lw_babybear_ext4_pointwise_device(lw_bb4_op_t op, const uint32_t *d_a, size_t a_stride, const uint32_t *d_b, size_t b_stride,
+                                      uint32_t *d_out, size_t out_stride, size_t n, void *hip_stream);
+int lw_babybear_ext4_convert_device(lw_bb4_convert_t dir, uint64_t *d_interleaved, uint32_t *d_planes, size_t plane_stride, size_t n,
+                                    void *hip_stream);
+int lw_babybear_ext4_evaluate_device(const uint32_t *d_coeffs, uint32_t n_cols, size_t col_stride, size_t n_coeffs,
+                                     const uint32_t *points, uint32_t m, uint32_t *out_values, void *hip_stream);
+int lw_babybear_ext4_deep_quotients_device(const uint32_t *d_lde, uint32_t n_cols, size_t col_stride, uint32_t log2n,
+                                           const uint32_t *offset_or_null, const uint32_t *points, uint32_t m,
+                                           const uint32_t *weights, const uint32_t *evals, uint32_t *d_out, size_t out_stride,
+                                           void *hip_stream);
+int lw_babybear_ext4_fri_layer_device(const uint32_t *d_coeffs, size_t coeff_stride, size_t n_coeffs, const uint32_t *zeta,
+                                      const uint32_t *offset_or_null, size_t domain_size, uint32_t *d_out_poly,
+                                      uint32_t *d_out_evaluation_or_null, uint8_t *d_nodes_or_null, uint8_t *out_root_or_null,
+                                      void *hip_stream);
+
 /* ---- Monolith over Mersenne31 (crypto/src/hash/monolith/: MonolithMersenne31<WIDTH, NUM_FULL_ROUNDS>, from Plonky3) ----
  * The permutation, batched (one work-item per state), and for width 16 a hash, a 2-to-1 compression and a Merkle tree
  * built from it.  Words are Mersenne31 elements as in the circle FFT: one u32; every input word is read mod p = 2^31 - 1

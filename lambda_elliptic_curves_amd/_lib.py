@@ -23,6 +23,8 @@ PW_FIELD_STARK252, PW_FIELD_FR381, PW_FIELD_FR254, PW_FIELD_FP381, PW_FIELD_FP25
 POSEIDON_LEAF_SINGLE, POSEIDON_LEAF_MANY = 0, 1   # lw_poseidon_leaf_t
 RPO_128, RPO_160 = 0, 1   # lw_rpo_level_t
 GL2_MUL, GL2_SQR, GL2_INV, GL2_MUL_BASE = 0, 1, 2, 3   # lw_gl2_op_t
+BB4_MUL, BB4_SQR, BB4_INV, BB4_MUL_BASE = 0, 1, 2, 3   # lw_bb4_op_t
+BB4_TO_PLANES, BB4_TO_INTERLEAVED = 0, 1   # lw_bb4_convert_t
 MONOLITH_CONCRETE, MONOLITH_BARS, MONOLITH_BRICKS = 0, 1, 2   # lw_monolith_layer_t
 AIR_LOAD, AIR_ADD, AIR_SUB, AIR_MUL, AIR_NEG, AIR_STORE, AIR_EMIT = range(7)   # lw_stark_air_opcode_t
 AIR_CELL, AIR_CONST, AIR_TMP = 0, 1, 2   # lw_stark_air_src_t
@@ -61,6 +63,8 @@ EXPORTS = [
     "lw_goldilocks_mul_device",
     "lw_goldilocks_ext2_pointwise_device", "lw_goldilocks_ext2_evaluate_device", "lw_goldilocks_ext2_deep_quotients_device",
     "lw_goldilocks_ext2_fri_layer_device",
+    "lw_babybear_ext4_pointwise_device", "lw_babybear_ext4_convert_device", "lw_babybear_ext4_evaluate_device",
+    "lw_babybear_ext4_deep_quotients_device", "lw_babybear_ext4_fri_layer_device",
     "lw_rpo_permute", "lw_rpo_permute_device", "lw_rpo_hash", "lw_rpo_hash_device",
     "lw_rpo_commit_columns", "lw_rpo_commit_columns_device",
     "lw_monolith_permute", "lw_monolith_permute_device", "lw_monolith_hash", "lw_monolith_hash_device",
@@ -337,6 +341,16 @@ def lib():
     L.lw_goldilocks_ext2_deep_quotients_device.restype = i
     L.lw_goldilocks_ext2_fri_layer_device.argtypes = [vp, sz, sz, vp, vp, sz, C.c_uint64, i, vp, vp, vp, vp, vp]
     L.lw_goldilocks_ext2_fri_layer_device.restype = i
+    L.lw_babybear_ext4_pointwise_device.argtypes = [i, vp, sz, vp, sz, vp, sz, sz, vp]
+    L.lw_babybear_ext4_pointwise_device.restype = i
+    L.lw_babybear_ext4_convert_device.argtypes = [i, vp, vp, sz, sz, vp]
+    L.lw_babybear_ext4_convert_device.restype = i
+    L.lw_babybear_ext4_evaluate_device.argtypes = [vp, u32, sz, sz, vp, u32, vp, vp]
+    L.lw_babybear_ext4_evaluate_device.restype = i
+    L.lw_babybear_ext4_deep_quotients_device.argtypes = [vp, u32, sz, u32, vp, vp, u32, vp, vp, vp, sz, vp]
+    L.lw_babybear_ext4_deep_quotients_device.restype = i
+    L.lw_babybear_ext4_fri_layer_device.argtypes = [vp, sz, sz, vp, vp, sz, vp, vp, vp, vp, vp]
+    L.lw_babybear_ext4_fri_layer_device.restype = i
     L.lw_rpo_permute.argtypes = [i, vp, sz, vp]
     L.lw_rpo_permute.restype = i
     L.lw_rpo_permute_device.argtypes = [i, vp, sz, vp, vp]

@@ -1,0 +1,170 @@
+"""The quartic extension of BabyBear, Fp4 = F_p[x] / (x^4 + 11) (Degree4BabyBearExtensionField of the reference, RISC Zero's
+extension), and the prover steps that run in it on device-resident data: out-of-domain evaluation, the DEEP composition in
+evaluation form and the FRI commit phase (fri::commit_phase<F, E> with F BabyBear, E = Fp4).
+
+A word is a STORED BabyBear element: the Montgomery value a 2^32 mod p in a u32, below p (fft.Babybear31PrimeFieldU32's
+layout); to_mont / from_mont go between integers and words.  A host-side Fp4 scalar is a tuple (c0, c1, c2, c3) of words,
+a = c0 + c1 x + c2 x^2 + c3 x^3.  A vector of n elements on the device is a torch int32 tensor of four PLANES of n words,
+c0, then c1 `stride` words later, and so on (0: dense): the same bytes fft.ntt_device / fft.lde_device take as batch = 4
+and merkle.commit_columns_layout_device as n_cols = 4 under Babybear31PrimeFieldU32, so they transform and commit an Fp4
+vector as it is.  Everything runs on torch's current stream unless `stream` is given.
+"""
+import numpy as np
+
+from . import _lib as L
+from .errors import check
+
+P = 2013265921
+BETA = 11   # x^4 = -BETA
+MUL, SQR, INV, MUL_BASE = L.BB4_MUL, L.BB4_SQR, L.BB4_INV, L.BB4_MUL_BASE
+_R = 1 << 32
+_R_INV = pow(_R, -1, P)
+
+
+def to_mont(v):
+    """an integer -> its stored word v 2^32 mod p"""
+    return int(v) % P * _R % P
+
+
+def from_mont(w):
+    """a stored word -> the integer it stands for"""
+    return int(w) * _R_INV % P
+
+
+def _scalars(values, count):
+    """`count` Fp4 scalars [(c0, c1, c2, c3), ...] -> a (count, 4) uint32 array"""
+    a = np.array([[int(c) for c in v] for v in values], np.uint32).reshape(-1, 4) if count else np.zeros((0, 4), np.uint32)
+    if a.shape[0] != count:
+        raise ValueError(f"{a.shape[0]} Fp4 scalars where {count} are expected")
+    return a
+
+
+def _offset_arg(offset):
+    """a coset offset as one stored word, or None"""
+    return None if offset is None else np.array([int(offset)], np.uint32)
+
+
+# ---- host-side helpers (stored words in, stored words out: both maps are linear over F)
+def times_x(a):
+    """(c0, c1, c2, c3) -> x (c0, c1, c2, c3) = (-11 c3, c0, c1, c2)"""
+    return (-BETA * int(a[3]) % P, int(a[0]), int(a[1]), int(a[2]))
+
+
+def combine_planes(v):
+    """The value sum_e x^e v[e] of a polynomial with Fp4 coefficients from the values v[0 .. 3] of its four planes."""
+    total, shifted = [0, 0, 0, 0], [tuple(int(c) for c in e) for e in v]
+    for e in range(4):
+        w = shifted[e]
+        for _ in range(e):
+            w = times_x(w)
+        total = [(t + c) % P for t, c in zip(total, w)]
+    return tuple(total)
+
+
+def plane_weights(w):
+    """The four weight rows of an Fp4 column passed as its four planes: [w, x w, x^2 w, x^3 w] for each weight of the row."""
+    rows = [[tuple(int(c) for c in e) for e in w]]
+    for _ in range(3):
+        rows.append([times_x(e) for e in rows[-1]])
+    return rows
+
+
+# ---- the calls
+def pointwise_device(op, t_a, t_b, t_out, n, a_stride=0, b_stride=0, out_stride=0, stream=None):
+    """t_out[i] = t_a[i] t_b[i] (MUL), t_a[i]^2 (SQR), t_a[i]^-1 (INV; the inverse of 0 is 0) or t_a[i] t_b[i] with t_b a
+    single plane of base-field words (MUL_BASE), for n elements.  t_b may be None for SQR and INV; t_out may be t_a or t_b."""
+    check(L.lib().lw_babybear_ext4_pointwise_device(op, L.device_ptr(t_a), a_stride, L.device_ptr(t_b) if t_b is not None else None, b_stride,
+                                                   L.device_ptr(t_out), out_stride, n, L.stream_ptr(stream)))
+    return t_out
+
+
+def to_planes_device(t_interleaved, t_planes, n, plane_stride=0, stream=None):
+    """n elements of fft.Degree4BabyBearExtensionField's layout (4 x u64 per element, R = 2^64) -> four planes of stored words"""
+    check(L.lib().lw_babybear_ext4_convert_device(L.BB4_TO_PLANES, L.device_ptr(t_interleaved), L.device_ptr(t_planes), plane_stride, n,
+                                                 L.stream_ptr(stream)))
+    return t_planes
+
+
+def to_interleaved_device(t_planes, t_interleaved, n, plane_stride=0, stream=None):
+    """four planes of stored words -> n elements of fft.Degree4BabyBearExtensionField's layout"""
+    check(L.lib().lw_babybear_ext4_convert_device(L.BB4_TO_INTERLEAVED, L.device_ptr(t_interleaved), L.device_ptr(t_planes), plane_stride, n,
+                                                 L.stream_ptr(stream)))
+    return t_interleaved
+
+
+def evaluate_device(t_coeffs, n_cols, n_coeffs, points, col_stride=0, stream=None):
+    """Out-of-domain evaluation: n_cols base-field coefficient columns of n_coeffs words (col_stride apart) at the Fp4
+    `points` [(c0, c1, c2, c3), ...] -> an (n_cols, m, 4) uint32 array.  Waits for the stream."""
+    pts = _scalars(points, len(points))
+    out = np.zeros((n_cols, len(points), 4), np.uint32)
+    check(L.lib().lw_babybear_ext4_evaluate_device(L.device_ptr(t_coeffs), n_cols, col_stride, n_coeffs, L.host_ptr(pts), len(points),
+                                                  L.host_ptr(out), L.stream_ptr(stream)))
+    return out
+
+
+def evaluate_ext_device(t_coeffs, n_coeffs, points, plane_stride=0, stream=None):
+    """A polynomial with Fp4 coefficients (four planes) at the Fp4 points -> [(c0, c1, c2, c3), ...]."""
+    v = evaluate_device(t_coeffs, 4, n_coeffs, points, plane_stride, stream)
+    return [combine_planes(v[:, j]) for j in range(len(points))]
+
+
+def deep_quotients_device(t_lde, n_cols, log2n, points, weights, evals, t_out, col_stride=0, out_stride=0, offset=None, stream=None):
+    """t_out[i] = sum_j (sum_k weights[k][j] (col_k[i] - evals[k][j])) / (x_i - points[j]) over the 2^log2n rows of the LDE
+    domain x_i = offset w^i.  weights, evals: n_cols rows of m Fp4 scalars; t_out: an Fp4 vector of 2^log2n elements.  An Fp4
+    column is its four planes as four columns with the weight rows of plane_weights()."""
+    m = len(points)
+    pts, w, e = _scalars(points, m), _scalars([x for row in weights for x in row], n_cols * m), _scalars([x for row in evals for x in row], n_cols * m)
+    check(L.lib().lw_babybear_ext4_deep_quotients_device(L.device_ptr(t_lde), n_cols, col_stride, log2n, L.host_ptr(_offset_arg(offset)),
+                                                        L.host_ptr(pts), m, L.host_ptr(w), L.host_ptr(e), L.device_ptr(t_out), out_stride,
+                                                        L.stream_ptr(stream)))
+    return t_out
+
+
+def folded_block(n_coeffs):
+    """The length of the zero-padded block a fold of n_coeffs coefficients writes."""
+    return max(2, 1 << max((n_coeffs + 1) // 2 - 1, 0).bit_length())
+
+
+def fri_layer_device(t_coeffs, n_coeffs, zeta, coset_offset, domain_size, coeff_stride=0, fold_only=False, stream=None):
+    """One layer of the FRI commit phase over Fp4: fold t_coeffs (an Fp4 vector of n_coeffs elements) with the challenge
+    zeta = (c0, c1, c2, c3), evaluate the result on the coset of `domain_size` points (already halved) with offset
+    `coset_offset` (a stored word, already squared) and commit pairs of evaluations in a Keccak-256 tree.
+    -> (t_poly, t_evaluation, t_nodes, root): the folded block (four dense planes of folded_block(n_coeffs) words), the
+    evaluation (four dense planes of domain_size words), the (domain_size - 1) x 32 bytes of nodes and the root as 32 bytes;
+    with fold_only the last three are None."""
+    import torch
+    z = _scalars([zeta], 1)
+    t_poly = torch.empty(4 * folded_block(n_coeffs), dtype=torch.int32, device=t_coeffs.device)
+    if fold_only:
+        check(L.lib().lw_babybear_ext4_fri_layer_device(L.device_ptr(t_coeffs), coeff_stride, n_coeffs, L.host_ptr(z), None, 0, L.device_ptr(t_poly),
+                                                       None, None, None, L.stream_ptr(stream)))
+        return t_poly, None, None, None
+    t_eval = torch.empty(4 * domain_size, dtype=torch.int32, device=t_coeffs.device)
+    t_nodes = torch.empty((max(domain_size - 1, 1), 32), dtype=torch.uint8, device=t_coeffs.device)
+    out_root = np.zeros(32, np.uint8)
+    check(L.lib().lw_babybear_ext4_fri_layer_device(L.device_ptr(t_coeffs), coeff_stride, n_coeffs, L.host_ptr(z), L.host_ptr(_offset_arg(coset_offset)),
+                                                   domain_size, L.device_ptr(t_poly), L.device_ptr(t_eval), L.device_ptr(t_nodes),
+                                                   L.host_ptr(out_root), L.stream_ptr(stream)))
+    return t_poly, t_eval, t_nodes, out_root
+
+
+def fri_commit_phase_device(t_coeffs, n_coeffs, number_layers, coset_offset, domain_size, challenge, stream=None):
+    """fri::commit_phase (provers/stark/src/fri/mod.rs:22-75) over Fp4 on a device-resident polynomial: t_coeffs is an Fp4
+    vector of n_coeffs coefficients in dense planes, domain_size and coset_offset (a stored word) those of the LDE domain.
+    challenge(prev_root_or_None) -> (c0, c1, c2, c3) is the caller's transcript: called once per fold with the root of the
+    layer committed just before (None for the first), it absorbs that root and samples the next zeta.  number_layers - 1
+    layers are committed, then one more fold gives the constant.
+    -> (last_value (c0, c1, c2, c3), [(t_evaluation, t_nodes, root), ...]), the layers left on the device."""
+    layers, prev = [], None
+    t_poly, n, h = t_coeffs, n_coeffs, int(coset_offset)
+    for _ in range(1, number_layers):
+        domain_size //= 2
+        h = h * h % P * _R_INV % P   # the stored word of the squared offset
+        t_poly, t_eval, t_nodes, layer_root = fri_layer_device(t_poly, n, challenge(prev), h, domain_size, stream=stream)
+        n = folded_block(n)   # the dense block, zero padding included, is the next layer's polynomial
+        layers.append((t_eval, t_nodes, layer_root))
+        prev = layer_root
+    t_last, _, _, _ = fri_layer_device(t_poly, n, challenge(prev), None, 0, fold_only=True, stream=stream)
+    block = t_last.numel() // 4
+    last = t_last.cpu().numpy().view(np.uint32)
+    return tuple(int(last[e * block]) for e in range(4)), layers

@@ -54,9 +54,11 @@ __device__ __forceinline__ void merkle_subtree(uint64_t *nodes, uint64_t level_b
 //   32: MontgomeryBackendPrimeField<_, 4>, four u64 limbs most significant first (montgomery_backed_prime_fields.rs:367-373)
 //    8: MontgomeryBackendPrimeField<_, 1> (BabyBear on a u64 limb), the limb big-endian (same impl)
 //    4: U32MontgomeryBackendPrimeField (BabyBear u32), value().to_be_bytes() (u32_montgomery_backend_prime_field.rs:258-262)
-// RPL = 2 (EB = 32 only): the composition tree of commit_composition_polynomial (provers/stark/src/prover.rs:398-425), whose
+// RPL = 2 (EB = 32 or 4): the composition tree of commit_composition_polynomial (provers/stark/src/prover.rs:398-425), whose
 // leaf i hashes two committed rows, 2 i and 2 i + 1, i.e. natural rows rho = bitrev_log2n(i) and rho + n of the n_cols / 2
-// parts: element c of the leaf's stream is part c mod P of row rho + (c / P) n.  log2n counts the leaves.
+// parts: element c of the leaf's stream is part c mod P of row rho + (c / P) n.  log2n counts the leaves.  With EB = 4 and
+// four parts it is the leaf of a FRI layer over the quartic extension of BabyBear (babybear_ext.hip): the four planes of
+// e[rho], then those of e[rho + n].
 template <int EB, int RPL = 1>
 __global__ __launch_bounds__(256) void merkle_leaves_kernel(const void *cols_v, uint32_t n_cols, uint64_t col_stride, uint32_t log2n,
                                                             int bit_reverse, uint64_t *nodes, uint32_t fused_levels) {
@@ -92,8 +94,16 @@ __global__ __launch_bounds__(256) void merkle_leaves_kernel(const void *cols_v, 
             return __builtin_bswap64(cols[(uint64_t)s * col_stride + src]);
         } else {
             const uint32_t *cols = (const uint32_t *)cols_v;
-            const uint32_t e0 = cols[(uint64_t)(2 * s) * col_stride + src];
-            const uint32_t e1 = 2 * s + 1 < n_cols ? cols[(uint64_t)(2 * s + 1) * col_stride + src] : 0u;
+            auto elem = [&](uint32_t c) -> uint32_t {
+                if constexpr (RPL == 2) {
+                    const uint32_t parts = n_cols / 2, half = c / parts;
+                    return cols[(uint64_t)(c - half * parts) * col_stride + src + (half ? n : 0)];
+                } else {
+                    return cols[(uint64_t)c * col_stride + src];
+                }
+            };
+            const uint32_t e0 = elem(2 * s);
+            const uint32_t e1 = 2 * s + 1 < n_cols ? elem(2 * s + 1) : 0u;
             return (uint64_t)__builtin_bswap32(e0) | ((uint64_t)__builtin_bswap32(e1) << 32);
         }
     };
@@ -143,8 +153,8 @@ __global__ __launch_bounds__(256) void merkle_top_kernel(uint64_t *nodes, uint64
     }
 }
 
-// d_nodes: (2 * 2^log2n - 1) * 32 bytes, root first.  rows_per_leaf = 2 (32-byte elements): 2^log2n leaves over 2^(log2n + 1)
-// rows of n_cols / 2 columns (merkle_leaves_kernel, RPL = 2)
+// d_nodes: (2 * 2^log2n - 1) * 32 bytes, root first.  rows_per_leaf = 2 (32- or 4-byte elements): 2^log2n leaves over
+// 2^(log2n + 1) rows of n_cols / 2 columns (merkle_leaves_kernel, RPL = 2)
 int merkle_commit_device(Context &c, const void *d_cols, uint32_t n_cols, uint64_t col_stride, uint32_t log2n, int bit_reverse,
                          void *d_nodes, hipStream_t stream, uint32_t elem_bytes, uint32_t rows_per_leaf) {
     const uint64_t n = 1ull << log2n;
@@ -160,7 +170,9 @@ int merkle_commit_device(Context &c, const void *d_cols, uint32_t n_cols, uint64
     if (bit_reverse) bit_reverse = (leaf_fused == 0 && log2n >= 12) ? 2 : 1;
     hipEvent_t pe = c.prof_begin(stream);
     const dim3 grid((uint32_t)((n + 255) / 256));
-    if (rows_per_leaf == 2)
+    if (rows_per_leaf == 2 && elem_bytes == 4)
+        hipLaunchKernelGGL((merkle_leaves_kernel<4, 2>), grid, dim3(256), 0, stream, d_cols, n_cols, col_stride, log2n, bit_reverse, (uint64_t *)d_nodes, leaf_fused);
+    else if (rows_per_leaf == 2)
         hipLaunchKernelGGL((merkle_leaves_kernel<32, 2>), grid, dim3(256), 0, stream, d_cols, n_cols, col_stride, log2n, bit_reverse, (uint64_t *)d_nodes, leaf_fused);
     else if (elem_bytes == 4)
         hipLaunchKernelGGL((merkle_leaves_kernel<4>), grid, dim3(256), 0, stream, d_cols, n_cols, col_stride, log2n, bit_reverse, (uint64_t *)d_nodes, leaf_fused);

@@ -401,6 +401,22 @@ extern "C" {
                                                d_out_poly: *mut u64, d_out_evaluation_or_null: *mut u64,
                                                d_nodes_or_null: *mut u64, out_root_or_null: *mut u64,
                                                hip_stream: *mut c_void) -> c_int;
+    // ---- BabyBear quartic extension F_p[x] / (x^4 + 11): an Fp4 vector is four planes of stored u32 words (R = 2^32), a host
+    // scalar is [c0, c1, c2, c3]; op is LW_BB4_MUL / LW_BB4_SQR / LW_BB4_INV / LW_BB4_MUL_BASE, dir LW_BB4_TO_PLANES / LW_BB4_TO_INTERLEAVED
+    pub fn lw_babybear_ext4_pointwise_device(op: c_int, d_a: *const u32, a_stride: usize, d_b: *const u32, b_stride: usize,
+                                             d_out: *mut u32, out_stride: usize, n: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_babybear_ext4_convert_device(dir: c_int, d_interleaved: *mut u64, d_planes: *mut u32, plane_stride: usize, n: usize,
+                                           hip_stream: *mut c_void) -> c_int;
+    pub fn lw_babybear_ext4_evaluate_device(d_coeffs: *const u32, n_cols: u32, col_stride: usize, n_coeffs: usize,
+                                            points: *const u32, m: u32, out_values: *mut u32, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_babybear_ext4_deep_quotients_device(d_lde: *const u32, n_cols: u32, col_stride: usize, log2n: u32,
+                                                  offset_or_null: *const u32, points: *const u32, m: u32, weights: *const u32,
+                                                  evals: *const u32, d_out: *mut u32, out_stride: usize,
+                                                  hip_stream: *mut c_void) -> c_int;
+    pub fn lw_babybear_ext4_fri_layer_device(d_coeffs: *const u32, coeff_stride: usize, n_coeffs: usize, zeta: *const u32,
+                                             offset_or_null: *const u32, domain_size: usize, d_out_poly: *mut u32,
+                                             d_out_evaluation_or_null: *mut u32, d_nodes_or_null: *mut u8,
+                                             out_root_or_null: *mut u8, hip_stream: *mut c_void) -> c_int;
     // ---- Monolith over Mersenne31: batched permutations (width 8 .. 24, rounds 1 .. 15); hash, compression and Merkle tree over width 16
     pub fn lw_monolith_permute(width: u32, rounds: u32, states: *const u32, n: usize, out: *mut u32) -> c_int;
     pub fn lw_monolith_permute_device(width: u32, rounds: u32, d_states: *const u32, n: usize, d_out: *mut u32,
@@ -554,6 +570,15 @@ pub const LW_GL2_MUL: c_int = 0;
 pub const LW_GL2_SQR: c_int = 1;
 pub const LW_GL2_INV: c_int = 2;
 pub const LW_GL2_MUL_BASE: c_int = 3;
+
+/// lw_bb4_op_t: the operation of lw_babybear_ext4_pointwise_device
+pub const LW_BB4_MUL: c_int = 0;
+pub const LW_BB4_SQR: c_int = 1;
+pub const LW_BB4_INV: c_int = 2;
+pub const LW_BB4_MUL_BASE: c_int = 3;
+/// lw_bb4_convert_t: the direction of lw_babybear_ext4_convert_device
+pub const LW_BB4_TO_PLANES: c_int = 0;
+pub const LW_BB4_TO_INTERLEAVED: c_int = 1;
 
 /// lw_monolith_layer_t: the layer lw_monolith_layer_device applies
 pub const LW_MONOLITH_CONCRETE: c_int = 0;
