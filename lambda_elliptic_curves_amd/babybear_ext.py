@@ -12,6 +12,7 @@ vector as it is.  Everything runs on torch's current stream unless `stream` is g
 import numpy as np
 
 from . import _lib as L
+from ._ext_common import commit_phase, folded_block, scalars  # noqa: F401  (folded_block is part of this module's surface)
 from .errors import check
 
 P = 2013265921
@@ -33,10 +34,7 @@ def from_mont(w):
 
 def _scalars(values, count):
     """`count` Fp4 scalars [(c0, c1, c2, c3), ...] -> a (count, 4) uint32 array"""
-    a = np.array([[int(c) for c in v] for v in values], np.uint32).reshape(-1, 4) if count else np.zeros((0, 4), np.uint32)
-    if a.shape[0] != count:
-        raise ValueError(f"{a.shape[0]} Fp4 scalars where {count} are expected")
-    return a
+    return scalars(values, count, 4, np.uint32)
 
 
 def _offset_arg(offset):
@@ -120,11 +118,6 @@ def deep_quotients_device(t_lde, n_cols, log2n, points, weights, evals, t_out, c
     return t_out
 
 
-def folded_block(n_coeffs):
-    """The length of the zero-padded block a fold of n_coeffs coefficients writes."""
-    return max(2, 1 << max((n_coeffs + 1) // 2 - 1, 0).bit_length())
-
-
 def fri_layer_device(t_coeffs, n_coeffs, zeta, coset_offset, domain_size, coeff_stride=0, fold_only=False, stream=None):
     """One layer of the FRI commit phase over Fp4: fold t_coeffs (an Fp4 vector of n_coeffs elements) with the challenge
     zeta = (c0, c1, c2, c3), evaluate the result on the coset of `domain_size` points (already halved) with offset
@@ -155,16 +148,10 @@ def fri_commit_phase_device(t_coeffs, n_coeffs, number_layers, coset_offset, dom
     layer committed just before (None for the first), it absorbs that root and samples the next zeta.  number_layers - 1
     layers are committed, then one more fold gives the constant.
     -> (last_value (c0, c1, c2, c3), [(t_evaluation, t_nodes, root), ...]), the layers left on the device."""
-    layers, prev = [], None
-    t_poly, n, h = t_coeffs, n_coeffs, int(coset_offset)
-    for _ in range(1, number_layers):
-        domain_size //= 2
-        h = h * h % P * _R_INV % P   # the stored word of the squared offset
-        t_poly, t_eval, t_nodes, layer_root = fri_layer_device(t_poly, n, challenge(prev), h, domain_size, stream=stream)
-        n = folded_block(n)   # the dense block, zero padding included, is the next layer's polynomial
-        layers.append((t_eval, t_nodes, layer_root))
-        prev = layer_root
-    t_last, _, _, _ = fri_layer_device(t_poly, n, challenge(prev), None, 0, fold_only=True, stream=stream)
-    block = t_last.numel() // 4
-    last = t_last.cpu().numpy().view(np.uint32)
-    return tuple(int(last[e * block]) for e in range(4)), layers
+    def layer(t_poly, n, zeta, h, domain, fold_only):
+        return fri_layer_device(t_poly, n, zeta, h, domain, fold_only=fold_only, stream=stream)
+
+    def square(h):
+        return h * h % P * _R_INV % P   # the stored word of the squared offset
+
+    return commit_phase(layer, square, 4, t_coeffs, n_coeffs, number_layers, int(coset_offset), domain_size, challenge)

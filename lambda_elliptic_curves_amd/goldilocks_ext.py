@@ -10,6 +10,7 @@ vector as it is.  Everything runs on torch's current stream unless `stream` is g
 import numpy as np
 
 from . import _lib as L
+from ._ext_common import commit_phase, folded_block, scalars  # noqa: F401  (folded_block is part of this module's surface)
 from .errors import check
 from .goldilocks import P, _offset_arg
 
@@ -21,10 +22,7 @@ _M64 = (1 << 64) - 1
 
 def _scalars(values, count):
     """`count` Fp2 scalars [(c0, c1), ...] (or one pair when count is 1) -> a (count, 2) uint64 array"""
-    a = np.array([[int(c) & _M64 for c in v] for v in values], np.uint64).reshape(-1, 2) if count else np.zeros((0, 2), np.uint64)
-    if a.shape[0] != count:
-        raise ValueError(f"{a.shape[0]} Fp2 scalars where {count} are expected")
-    return a
+    return scalars(values, count, 2, np.uint64, _M64)
 
 
 # ---- host-side helpers
@@ -81,11 +79,6 @@ def deep_quotients_device(t_lde, n_cols, log2n, points, weights, evals, t_out, c
     return t_out
 
 
-def folded_block(n_coeffs):
-    """The length of the zero-padded block a fold of n_coeffs coefficients writes."""
-    return max(2, 1 << max((n_coeffs + 1) // 2 - 1, 0).bit_length())
-
-
 def digest_words(level):
     return 4 if level == RPO_128 else 5
 
@@ -121,16 +114,10 @@ def fri_commit_phase_device(t_coeffs, n_coeffs, number_layers, coset_offset, dom
     committed just before (None for the first), it absorbs that root and samples the next zeta.  number_layers - 1 layers
     are committed, then one more fold gives the constant.
     -> (last_value (c0, c1), [(t_evaluation, t_nodes, root), ...]), the layers left on the device."""
-    layers, prev = [], None
-    t_poly, n, h = t_coeffs, n_coeffs, int(coset_offset) % P
-    for _ in range(1, number_layers):
-        domain_size //= 2
-        h = h * h % P
-        t_poly, t_eval, t_nodes, layer_root = fri_layer_device(t_poly, n, challenge(prev), h, domain_size, level, root=root, stream=stream)
-        n = folded_block(n)   # the dense block, zero padding included, is the next layer's polynomial
-        layers.append((t_eval, t_nodes, layer_root))
-        prev = layer_root
-    t_last, _, _, _ = fri_layer_device(t_poly, n, challenge(prev), None, 0, level, root=root, fold_only=True, stream=stream)
-    block = t_last.numel() // 2
-    last = t_last.cpu().numpy().view(np.uint64)
-    return (int(last[0]), int(last[block])), layers
+    def layer(t_poly, n, zeta, h, domain, fold_only):
+        return fri_layer_device(t_poly, n, zeta, h, domain, level, root=root, fold_only=fold_only, stream=stream)
+
+    def square(h):
+        return h * h % P
+
+    return commit_phase(layer, square, 2, t_coeffs, n_coeffs, number_layers, int(coset_offset) % P, domain_size, challenge)

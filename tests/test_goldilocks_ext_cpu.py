@@ -150,6 +150,7 @@ def test_status_codes_need_no_device():
         ("pointwise overlap b", lambda: pw(MUL, A, 0, B, 0, at(1024 + 24), 0, 16), BAD),
         ("pointwise overlap base b", lambda: pw(MULB, A, 0, B, 0, at(1024 - 16 - 8), 0, 16), BAD),
         ("pointwise in place, other stride", lambda: pw(SQR, A, 16, N, 0, A, 64, 16), BAD),
+        ("pointwise out is a's other plane", lambda: pw(SQR, A, 16, N, 0, at(16), 16, 16), BAD),
         ("pointwise op 4", lambda: pw(4, A, 0, B, 0, O, 0, 16), BAD),
         ("pointwise op -1", lambda: pw(-1, A, 0, B, 0, O, 0, 16), BAD),
         ("pointwise n 0", lambda: pw(MUL, N, 0, N, 0, N, 0, 0), OK),

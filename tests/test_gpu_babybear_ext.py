@@ -216,6 +216,15 @@ def test_evaluate_two_tile_sums_per_work_item():
     assert E.evaluate_device(dev(X.np_store(res)), 1, 0, stored([z])).tolist() == [[[0, 0, 0, 0]]]   # n_coeffs = 0: zeros
 
 
+def test_evaluate_more_columns_than_the_grids_y_extent():
+    k = 65537   # two launches per kernel: columns 0 .. 65534, then 65535 and 65536
+    res = rand_res(2 * k, 57)
+    z = edge_point(3)
+    got = E.evaluate_device(dev(X.np_store(res)), k, 2, stored([z]), 2)
+    assert got.shape == (k, 1, 4)
+    assert [tuple(v) for v in got[:, 0].tolist()] == [X.store_elem(X.horner(c, z)) for c in res.reshape(k, 2).tolist()]
+
+
 # ---- DEEP quotients
 def deep_case(log2t, blowup, m, seed, h):
     T, log2n = 1 << log2t, log2t + blowup.bit_length() - 1

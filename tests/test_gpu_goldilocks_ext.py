@@ -175,6 +175,15 @@ def test_evaluate_two_tile_sums_per_work_item():
     assert tuple(got[0, 0].tolist()) == X.horner(words.tolist(), z)
 
 
+def test_evaluate_more_columns_than_the_grids_y_extent():
+    k = 65537   # two launches per kernel: columns 0 .. 65534, then 65535 and 65536
+    words = rand_words(2 * k, 58)
+    z = edge_point(3)
+    got = E.evaluate_device(dev(words), k, 2, [z], 2)
+    assert got.shape == (k, 1, 2)
+    assert [tuple(v) for v in got[:, 0].tolist()] == [X.horner(c, z) for c in words.reshape(k, 2).tolist()]
+
+
 # ---- DEEP quotients
 def deep_case(log2t, blowup, m, seed, h=7, root=G.OTHER_ROOT):
     T, log2n = 1 << log2t, log2t + blowup.bit_length() - 1
