@@ -1185,6 +1185,92 @@ int lw_babybear_ext4_fri_layer_device(const uint32_t *d_coeffs, size_t coeff_str
                                       uint32_t *d_out_evaluation_or_null, uint8_t *d_nodes_or_null, uint8_t *out_root_or_null,
                                       void *hip_stream);
 
+/* ---- STARK round 2 over Goldilocks with Fp2 and over BabyBear with Fp4: the composition polynomial ----
+ * round_2_compute_composition_polynomial (provers/stark/src/prover.rs:428-484) for a trace in a small field F whose random
+ * coefficients are in the extension E: ConstraintEvaluator::evaluate with the AIR's compute_transition given as a program,
+ * then interpolate_offset_fft, break_in_parts and the LDE of the parts.  Words, host scalars, planes and strides (0: dense),
+ * the 16-byte alignment of device pointers, offset_or_null and (Goldilocks only) two_adic_root are those of the two
+ * extension sections above.  Every argument check runs before any device work.  _device forms only.
+ *
+ * constraint_evaluations: ONE pass over the LDE columns, no row T_c is ever stored.  n = 2^log2_trace, N = n 2^log2_blowup,
+ * g and w the library's primitive n-th and N-th roots of F, h the offset, x_i = h w^i.  For every LDE row i in [0, N):
+ *     out[i] = sum_c coeff_c ( Z_c[i] T_c(i) )  +  sum_k coeff_k (col_k[i] - value_k) / (x_i - g^step_k)        (in E)
+ *   T_c(i)   what the program emits for constraint c at row i: ops, the accumulator machine with its 8 temporaries, the
+ *            CELL addressing col[(i + row 2^log2_blowup) mod len_col], the short (periodic) columns of
+ *            col_log2_len_or_null and the host check are exactly those of lw_stark_transition_evaluations_device.  Cells
+ *            and constants are words of F: Goldilocks words are any u64, canonicalised on load; BabyBear words and
+ *            constants must be below p (a constant that is not: LW_ERR_BAD_ARG; device words are the caller's promise).
+ *            Extension-valued (auxiliary) columns and extension-valued constants are out of scope.
+ *   Z_c[i]   the zerofier of lw_stark_constraint_evaluations_device, in F: cycle_c[i mod len_c] times the product of
+ *            (x_i - g^(n - k period)) over k = 1 .. end_exemptions, both cycle branches and the truncating divisions.
+ *            The cycle tables are built on the device.  Transitions whose five integers are all equal share one table and
+ *            one value per row; a call takes at most 8 distinct descriptors (more: LW_ERR_BAD_ARG).
+ *   coeff    one scalar of E per transition and per boundary constraint; value is one word of F.
+ *   d_columns  host array of n_cols device pointers; column c has N words (2^col_log2_len[c] for a short one; a boundary
+ *            constraint on a short column is LW_ERR_BAD_ARG).  d_out: an E vector of N elements, out_stride apart, that
+ *            overlaps no column; the words between two planes are not written.
+ * No denominator is zero unless h^N = 1 (a zero x^(n / period) - g^(...) or x - g^step forces x^n = 1), so nothing is
+ * looked for on the device: h^N = 1 with any constraint present, a NULL offset included, is LW_ERR_INV_ZERO from the
+ * host (a period that does not divide n is refused the same way where its truncated exponent allows a zero).  h = 0 mod p
+ * is LW_ERR_INV_ZERO as in the LDE calls.  The call only enqueues.  LW_ERR_BAD_ARG: period = 0, end_exemptions * period > n,
+ * col >= n_cols, a domain beyond the field's transform (2^30 for Goldilocks, 2^24 for BabyBear), a null or misaligned buffer,
+ * a malformed program (lw_hip_last_error names the op).  n_boundary = 0 or n_transitions = 0 is legal; both: zeros.
+ *
+ * composition_parts: the counterpart of lw_stark_composition_parts_device.  H = interpolate_offset_fft(d_evals, h) plane
+ * by plane; part j takes coefficients j, j + P, ... into a zero-padded block of L = next_power_of_two(ceil(N / P))
+ * elements; every part is evaluated at x_0 .. x_{N-1}.  Part j, plane e lies at plane index j D + e (D = 2 or 4) in both
+ * outputs: d_parts_coeffs is P D dense planes of L words, d_parts_lde_or_null P D dense planes of N words - the
+ * n_cols = P D shape of lw_rpo_commit_columns_device / lw_stark_commit_columns_layout_device, whose column commitment over
+ * these planes is the commitment of round 2, and the "part as D columns" shape of evaluate and deep_quotients.
+ * out_part_lens_or_null: per part the last index where any plane is not zero, plus one; asking for it synchronises.
+ * 1 <= n_parts <= N, else LW_ERR_BAD_ARG, like buffers that overlap.  d_evals is not modified. */
+typedef struct {
+    uint32_t col, reserved;
+    uint64_t step;
+    uint64_t value;
+    uint64_t coeff[2];
+} lw_gl2_boundary_t;
+typedef struct {
+    uint64_t period, offset, end_exemptions;
+    uint64_t exemptions_period; /* 0: none */
+    uint64_t periodic_exemptions_offset;
+    uint64_t coeff[2];
+} lw_gl2_transition_t;
+typedef struct {
+    uint32_t col, reserved;
+    uint64_t step;
+    uint32_t value;
+    uint32_t coeff[4];
+    uint32_t reserved2;
+} lw_bb4_boundary_t;
+typedef struct {
+    uint64_t period, offset, end_exemptions;
+    uint64_t exemptions_period; /* 0: none */
+    uint64_t periodic_exemptions_offset;
+    uint32_t coeff[4];
+} lw_bb4_transition_t;
+int lw_goldilocks_ext2_constraint_evaluations_device(const lw_stark_air_op_t *ops, uint32_t n_ops, const uint64_t *consts,
+                                                     uint32_t n_consts, const uint64_t *const *d_columns,
+                                                     const uint32_t *col_log2_len_or_null, uint32_t n_cols, uint32_t log2_trace,
+                                                     uint32_t log2_blowup, const uint64_t *offset_or_null, uint64_t two_adic_root,
+                                                     const lw_gl2_boundary_t *boundary, uint32_t n_boundary,
+                                                     const lw_gl2_transition_t *transitions, uint32_t n_transitions,
+                                                     uint64_t *d_out, size_t out_stride, void *hip_stream);
+int lw_goldilocks_ext2_composition_parts_device(const uint64_t *d_evals, size_t evals_stride, uint32_t log2_lde,
+                                                const uint64_t *offset_or_null, uint64_t two_adic_root, uint32_t n_parts,
+                                                uint64_t *d_parts_coeffs, uint64_t *d_parts_lde_or_null,
+                                                size_t *out_part_lens_or_null, void *hip_stream);
+int lw_babybear_ext4_constraint_evaluations_device(const lw_stark_air_op_t *ops, uint32_t n_ops, const uint32_t *consts,
+                                                   uint32_t n_consts, const uint32_t *const *d_columns,
+                                                   const uint32_t *col_log2_len_or_null, uint32_t n_cols, uint32_t log2_trace,
+                                                   uint32_t log2_blowup, const uint32_t *offset_or_null,
+                                                   const lw_bb4_boundary_t *boundary, uint32_t n_boundary,
+                                                   const lw_bb4_transition_t *transitions, uint32_t n_transitions,
+                                                   uint32_t *d_out, size_t out_stride, void *hip_stream);
+int lw_babybear_ext4_composition_parts_device(const uint32_t *d_evals, size_t evals_stride, uint32_t log2_lde,
+                                              const uint32_t *offset_or_null, uint32_t n_parts, uint32_t *d_parts_coeffs,
+                                              uint32_t *d_parts_lde_or_null, size_t *out_part_lens_or_null, void *hip_stream);
+
 /* ---- Monolith over Mersenne31 (crypto/src/hash/monolith/: MonolithMersenne31<WIDTH, NUM_FULL_ROUNDS>, from Plonky3) ----
  * The permutation, batched (one work-item per state), and for width 16 a hash, a 2-to-1 compression and a Merkle tree
  * built from it.  Words are Mersenne31 elements as in the circle FFT: one u32; every input word is read mod p = 2^31 - 1

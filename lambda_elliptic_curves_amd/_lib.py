@@ -65,6 +65,8 @@ EXPORTS = [
     "lw_goldilocks_ext2_fri_layer_device",
     "lw_babybear_ext4_pointwise_device", "lw_babybear_ext4_convert_device", "lw_babybear_ext4_evaluate_device",
     "lw_babybear_ext4_deep_quotients_device", "lw_babybear_ext4_fri_layer_device",
+    "lw_goldilocks_ext2_constraint_evaluations_device", "lw_goldilocks_ext2_composition_parts_device",
+    "lw_babybear_ext4_constraint_evaluations_device", "lw_babybear_ext4_composition_parts_device",
     "lw_rpo_permute", "lw_rpo_permute_device", "lw_rpo_hash", "lw_rpo_hash_device",
     "lw_rpo_commit_columns", "lw_rpo_commit_columns_device",
     "lw_monolith_permute", "lw_monolith_permute_device", "lw_monolith_hash", "lw_monolith_hash_device",
@@ -107,6 +109,29 @@ class StarkTransition(C.Structure):
     """lw_stark_transition_t"""
     _fields_ = [("period", C.c_uint64), ("offset", C.c_uint64), ("end_exemptions", C.c_uint64), ("exemptions_period", C.c_uint64),
                 ("periodic_exemptions_offset", C.c_uint64), ("coeff", C.c_uint64 * 4)]
+
+
+class Gl2Boundary(C.Structure):
+    """lw_gl2_boundary_t"""
+    _fields_ = [("col", C.c_uint32), ("reserved", C.c_uint32), ("step", C.c_uint64), ("value", C.c_uint64), ("coeff", C.c_uint64 * 2)]
+
+
+class Gl2Transition(C.Structure):
+    """lw_gl2_transition_t"""
+    _fields_ = [("period", C.c_uint64), ("offset", C.c_uint64), ("end_exemptions", C.c_uint64), ("exemptions_period", C.c_uint64),
+                ("periodic_exemptions_offset", C.c_uint64), ("coeff", C.c_uint64 * 2)]
+
+
+class Bb4Boundary(C.Structure):
+    """lw_bb4_boundary_t"""
+    _fields_ = [("col", C.c_uint32), ("reserved", C.c_uint32), ("step", C.c_uint64), ("value", C.c_uint32), ("coeff", C.c_uint32 * 4),
+                ("reserved2", C.c_uint32)]
+
+
+class Bb4Transition(C.Structure):
+    """lw_bb4_transition_t"""
+    _fields_ = [("period", C.c_uint64), ("offset", C.c_uint64), ("end_exemptions", C.c_uint64), ("exemptions_period", C.c_uint64),
+                ("periodic_exemptions_offset", C.c_uint64), ("coeff", C.c_uint32 * 4)]
 
 
 class StarkAirOp(C.Structure):
@@ -351,6 +376,17 @@ def lib():
     L.lw_babybear_ext4_deep_quotients_device.restype = i
     L.lw_babybear_ext4_fri_layer_device.argtypes = [vp, sz, sz, vp, vp, sz, vp, vp, vp, vp, vp]
     L.lw_babybear_ext4_fri_layer_device.restype = i
+    aop, u32q, szp = C.POINTER(StarkAirOp), C.POINTER(u32), C.POINTER(sz)
+    L.lw_goldilocks_ext2_constraint_evaluations_device.argtypes = [aop, u32, vp, u32, vp, u32q, u32, u32, u32, vp, C.c_uint64, C.POINTER(Gl2Boundary), u32,
+                                                                   C.POINTER(Gl2Transition), u32, vp, sz, vp]
+    L.lw_goldilocks_ext2_constraint_evaluations_device.restype = i
+    L.lw_goldilocks_ext2_composition_parts_device.argtypes = [vp, sz, u32, vp, C.c_uint64, u32, vp, vp, szp, vp]
+    L.lw_goldilocks_ext2_composition_parts_device.restype = i
+    L.lw_babybear_ext4_constraint_evaluations_device.argtypes = [aop, u32, vp, u32, vp, u32q, u32, u32, u32, vp, C.POINTER(Bb4Boundary), u32,
+                                                                 C.POINTER(Bb4Transition), u32, vp, sz, vp]
+    L.lw_babybear_ext4_constraint_evaluations_device.restype = i
+    L.lw_babybear_ext4_composition_parts_device.argtypes = [vp, sz, u32, vp, u32, vp, vp, szp, vp]
+    L.lw_babybear_ext4_composition_parts_device.restype = i
     L.lw_rpo_permute.argtypes = [i, vp, sz, vp]
     L.lw_rpo_permute.restype = i
     L.lw_rpo_permute_device.argtypes = [i, vp, sz, vp, vp]

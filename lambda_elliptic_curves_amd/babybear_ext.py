@@ -12,7 +12,8 @@ vector as it is.  Everything runs on torch's current stream unless `stream` is g
 import numpy as np
 
 from . import _lib as L
-from ._ext_common import commit_phase, folded_block, scalars  # noqa: F401  (folded_block is part of this module's surface)
+from . import _ext_common as X
+from ._ext_common import commit_phase, folded_block, part_block_len, scalars  # noqa: F401  (folded_block, part_block_len: this module's surface)
 from .errors import check
 
 P = 2013265921
@@ -155,3 +156,42 @@ def fri_commit_phase_device(t_coeffs, n_coeffs, number_layers, coset_offset, dom
         return h * h % P * _R_INV % P   # the stored word of the squared offset
 
     return commit_phase(layer, square, 4, t_coeffs, n_coeffs, number_layers, int(coset_offset), domain_size, challenge)
+
+
+# ---- round 2: the composition polynomial
+_R2 = X.Round2Spec(4, np.uint32, "int32", _scalars, _offset_arg, L.Bb4Boundary, L.Bb4Transition, "lw_babybear_ext4_constraint_evaluations_device",
+                   "lw_babybear_ext4_composition_parts_device", False)
+
+
+def constraint_evaluations_device(program, consts, t_columns, log2_trace, log2_blowup, boundary, transitions, t_out=None, out_stride=0, offset=None,
+                                  col_log2_len=None, stream=None):
+    """The evaluations of the composition polynomial on the LDE coset in one pass over the columns, no T_c rows stored:
+    t_out[i] = sum_c coeff_c Z_c[i] T_c(i) + sum_k coeff_k (col_k[i] - value_k) / (x_i - g^step_k), an Fp4 vector of
+    N = 2^(log2_trace + log2_blowup) elements.  program: stark.compile_transitions(...) with base-field constants `consts`
+    (stored words); t_columns: a list of resident columns of N stored words (2^col_log2_len[c] for a short one); boundary:
+    [(col, step, value, (c0, c1, c2, c3))]; transitions: [dict(period, offset, end_exemptions, exemptions_period,
+    periodic_exemptions_offset, coeff=(c0, c1, c2, c3))]; offset: a stored word.  Enqueues and returns t_out."""
+    return X.constraint_evaluations(_R2, program, consts, t_columns, log2_trace, log2_blowup, boundary, transitions, t_out, out_stride, offset, 0,
+                                    col_log2_len, stream)
+
+
+def composition_parts_device(t_evals, log2_lde, n_parts, evals_stride=0, offset=None, lde=True, lens=True, stream=None):
+    """interpolate_offset_fft of the four planes, break_in_parts and the LDE of every part.
+    -> (t_parts_coeffs: 4 P dense planes of part_block_len(log2_lde, P) words, part j plane e at plane 4 j + e; part_lens
+    (None with lens=False: nothing is waited for); t_parts_lde: 4 P dense planes of N words, or None)."""
+    return X.composition_parts(_R2, t_evals, log2_lde, n_parts, evals_stride, offset, 0, lde, lens, stream)
+
+
+def round2_device(program, consts, t_columns, log2_trace, log2_blowup, boundary, transitions, n_parts, offset=None, col_log2_len=None, stream=None):
+    """Round 2 on resident LDE columns: the constraint evaluations, the parts and the Keccak column commitment over the 4 P
+    planes of the parts' LDE (merkle.commit_columns_layout_device, bit-reversed rows).
+    -> (t_parts_coeffs, part_lens, t_parts_lde, t_nodes, root)"""
+    import torch
+    from . import fft, merkle
+    log2_lde = int(log2_trace) + int(log2_blowup)
+    t_ev = constraint_evaluations_device(program, consts, t_columns, log2_trace, log2_blowup, boundary, transitions, offset=offset,
+                                         col_log2_len=col_log2_len, stream=stream)
+    t_coeffs, lens, t_lde = composition_parts_device(t_ev, log2_lde, n_parts, offset=offset, stream=stream)
+    t_nodes = torch.empty((2 * (1 << log2_lde) - 1) * 32, dtype=torch.uint8, device=t_ev.device)
+    commit_root = merkle.commit_columns_layout_device(fft.Babybear31PrimeFieldU32, t_lde, 4 * int(n_parts), log2_lde, t_nodes, stream=stream)
+    return t_coeffs, lens, t_lde, t_nodes, commit_root

@@ -17,6 +17,7 @@
 // norm is never zero: x_i - z_j has a non-zero c1, c2 or c3 (checked).
 #include "babybear_ext.cuh"
 #include "ext_steps.cuh"
+#include "ext_round2.cuh"
 
 namespace lw {
 
@@ -28,6 +29,8 @@ struct Bb4Ext {
     static constexpr ExtNames NAMES{"bb4_pointwise_kernel", "bb4_eval_tile_kernel", "bb4_eval_fold_kernel", "bb4_deep_kernel", "bb4_fri_fold_kernel"};
     static constexpr word F_ONE = BabyBear::ONE;
     EXT_HD word fcanon(word x) { return x; }
+    EXT_HD word fadd(word a, word b) { return bb_add(a, b); }
+    EXT_HD word fsub(word a, word b) { return bb_sub(a, b); }
     EXT_HD word fmul(word a, word b) { return bb_mul(a, b); }
     EXT_HD word fpow(word a, uint64_t e) { return bb_pow(a, e); }
     EXT_HD word finv(word a) { return bb_inv(a); }
@@ -76,6 +79,7 @@ struct Bb4Ext {
         return bb4_mul(num, bb4_inv_with(d, b0, b2, ninv));
     }
     // as a loop, acc[][] indexed by a loop counter lives in scratch (272 bytes per lane at M = 4)
+    static constexpr int R2_ROWS_FEW = EXT_ROWS;   // boundary rows per work-item with one or two steps (ext_round2.cuh): E::finv is short and eight 4-byte words per lane load badly: four rows throughout
     static constexpr bool DEEP_BACK_BY_RECURSION = true;
 
     // host: every word of a scalar below p; the domain's root is the field's own
@@ -195,6 +199,38 @@ int lw_babybear_ext4_fri_layer_device(const uint32_t *d_coeffs, size_t coeff_str
                                                                       d_out_evaluation_or_null, lgd, 4, 0, offset_or_null, s, lgb);
                                      return rc ? rc : merkle_commit_device(c, d_out_evaluation_or_null, 8, domain_size, lgd - 1, 1, d_nodes_or_null, s, 4, 2);
                                  });
+}
+
+static constexpr ExtR2Names BB4_R2_NAMES{"bb4_r2_xtable_kernel", "bb4_r2_cycle_kernel", "bb4_r2_transition_kernel", "bb4_r2_boundary_kernel", "bb4_r2_split_kernel", "bb4_r2_lengths_kernel"};
+
+int lw_babybear_ext4_constraint_evaluations_device(const lw_stark_air_op_t *ops, uint32_t n_ops, const uint32_t *consts, uint32_t n_consts,
+                                                   const uint32_t *const *d_columns, const uint32_t *col_log2_len_or_null, uint32_t n_cols,
+                                                   uint32_t log2_trace, uint32_t log2_blowup, const uint32_t *offset_or_null,
+                                                   const lw_bb4_boundary_t *boundary, uint32_t n_boundary, const lw_bb4_transition_t *transitions,
+                                                   uint32_t n_transitions, uint32_t *d_out, size_t out_stride, void *hip_stream) {
+    return ext_r2_constraint_evaluations<Bb4Ext>(BB4_R2_NAMES, ops, n_ops, consts, n_consts, d_columns, col_log2_len_or_null, n_cols, log2_trace, log2_blowup,
+                                                 offset_or_null, 0, boundary, n_boundary, transitions, n_transitions, d_out, out_stride, hip_stream);
+}
+
+int lw_babybear_ext4_composition_parts_device(const uint32_t *d_evals, size_t evals_stride, uint32_t log2_lde, const uint32_t *offset_or_null,
+                                              uint32_t n_parts, uint32_t *d_parts_coeffs, uint32_t *d_parts_lde_or_null, size_t *out_part_lens_or_null,
+                                              void *hip_stream) {
+    // the four planes through the existing inverse transform (which keeps one stride for both sides: H takes the
+    // evaluations' stride), every plane of every part through the existing LDE
+    return ext_r2_composition_parts<Bb4Ext>(
+        BB4_R2_NAMES, d_evals, evals_stride, log2_lde, offset_or_null, 0, n_parts, d_parts_coeffs, d_parts_lde_or_null, out_part_lens_or_null, hip_stream,
+        [&](Context &c, const uint32_t *d_in, uint64_t in_stride, uint32_t *d_H, uint64_t h_stride, uint32_t lg, uint32_t, uint64_t, hipStream_t s) {
+            if (in_stride == h_stride)
+                return ntt_device_locked(c, LW_FIELD_BABYBEAR, LW_LAYOUT_BABYBEAR_U32_R32, LW_DIR_INVERSE, d_in, d_H, lg, 4, in_stride, offset_or_null, s);
+            int rc = LW_OK;
+            for (int e = 0; e < 4 && !rc; e++)
+                rc = ntt_device_locked(c, LW_FIELD_BABYBEAR, LW_LAYOUT_BABYBEAR_U32_R32, LW_DIR_INVERSE, d_in + e * in_stride, d_H + e * h_stride, lg, 1, 0,
+                                       offset_or_null, s);
+            return rc;
+        },
+        [&](Context &c, const uint32_t *d_coeffs, uint32_t lgL, uint32_t *d_lde, uint32_t lg, uint32_t batch, uint32_t, uint64_t, hipStream_t s) {
+            return ntt_device_locked(c, LW_FIELD_BABYBEAR, LW_LAYOUT_BABYBEAR_U32_R32, LW_DIR_FORWARD, d_coeffs, d_lde, lg, batch, 0, offset_or_null, s, lgL);
+        });
 }
 
 }  // extern "C"

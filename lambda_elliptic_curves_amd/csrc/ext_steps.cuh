@@ -32,6 +32,7 @@
 //   E::norm(x, pt)                            the norm of x - z in F, x in F: never zero for z outside F
 //   E::quotient(num, x, pt, ninv)             num / (x - z) from ninv = 1 / norm
 //   E::DEEP_BACK_BY_RECURSION                 the form of the way back through Montgomery's trick
+//   E::fadd, E::fsub, E::R2_ROWS_FEW          round 2 (ext_round2.cuh): sum and difference in F, the boundary kernel's rows per work-item
 // and on the host:
 //   E::words_check(words, count, what)        host scalars: LW_ERR_BAD_ARG unless every word is one the kernels may take
 //   E::size_check(log2n), E::root_check(root), E::offset(offset_or_null, h), E::domain_root(root, log2n)

@@ -191,6 +191,18 @@ int goldilocks_lde_locked(Context &c, const uint64_t *d_coeffs, uint32_t log2_co
     return gl_transform_device(c, call, d_coeffs, in_stride, log2_coeffs, d_out, out_stride, log2n, batch, stream);
 }
 
+// a whole transform inside another call's Entry (the Fp2 composition parts of goldilocks_ext.hip: the inverse of two planes);
+// root and offset are validated, offset = 1 is no coset
+int goldilocks_ntt_locked(Context &c, bool inverse, const uint64_t *d_in, uint64_t in_stride, uint64_t *d_out, uint64_t out_stride, uint32_t log2n,
+                          uint32_t batch, uint64_t offset, uint64_t root, hipStream_t stream) {
+    GlCall call{};
+    call.inv = inverse;
+    call.root = root;
+    call.coset = offset != 1;
+    call.h = offset;
+    return gl_transform_device(c, call, d_in, in_stride, log2n, d_out, out_stride, log2n, batch, stream);
+}
+
 // ---- argument checks, before any device work (the first two are goldilocks_ext.hip's too: internal.h)
 int gl_size_check(uint64_t log2n) {
     if (log2n > GL_TWO_ADICITY) {

@@ -12,6 +12,7 @@
 // zero: z1 != 0 is checked and 7 is a non-residue.  The way back through Montgomery's trick is a loop over (row, point).
 #include "goldilocks_ext.cuh"
 #include "ext_steps.cuh"
+#include "ext_round2.cuh"
 
 namespace lw {
 
@@ -23,6 +24,8 @@ struct Gl2Ext {
     static constexpr ExtNames NAMES{"gl2_pointwise_kernel", "gl2_eval_tile_kernel", "gl2_eval_fold_kernel", "gl2_deep_kernel", "gl2_fri_fold_kernel"};
     static constexpr word F_ONE = 1;
     EXT_HD word fcanon(word x) { return gl_from_word(x); }
+    EXT_HD word fadd(word a, word b) { return gl_add(a, b); }
+    EXT_HD word fsub(word a, word b) { return gl_sub(a, b); }
     EXT_HD word fmul(word a, word b) { return gl_mul(a, b); }
     EXT_HD word fpow(word a, uint64_t e) { return gl_pow(a, e); }
     EXT_HD word finv(word a) { return gl_inv(a); }
@@ -56,6 +59,7 @@ struct Gl2Ext {
     }
     // 1 / (x - z) = conj / norm, (x - z) conj = norm
     EXT_HD elem quotient(elem num, word x, deep_point p, word ninv) { return gl2_mul_base(gl2_mul(num, Gl2{gl_sub(x, p.z.c0), p.z.c1}), ninv); }
+    static constexpr int R2_ROWS_FEW = 8;   // boundary rows per work-item with one or two steps (ext_round2.cuh): E::finv is 127 products: shared by eight rows where the registers allow
     static constexpr bool DEEP_BACK_BY_RECURSION = false;
 
     // host: any u64 is a scalar; the caller may choose the two-adic root
@@ -136,6 +140,31 @@ int lw_goldilocks_ext2_fri_layer_device(const uint64_t *d_coeffs, size_t coeff_s
                                      const int rc = goldilocks_lde_locked(c, d_out_poly, lgb, padded, d_out_evaluation_or_null, lgd, domain_size, 2, h, root, s);
                                      return rc ? rc : rpo_commit_locked(c, (int)level, d_out_evaluation_or_null, 4, domain_size / 2, lgd - 1, 1, 2, d_nodes_or_null, s);
                                  });
+}
+
+static constexpr ExtR2Names GL2_R2_NAMES{"gl2_r2_xtable_kernel", "gl2_r2_cycle_kernel", "gl2_r2_transition_kernel", "gl2_r2_boundary_kernel", "gl2_r2_split_kernel", "gl2_r2_lengths_kernel"};
+
+int lw_goldilocks_ext2_constraint_evaluations_device(const lw_stark_air_op_t *ops, uint32_t n_ops, const uint64_t *consts, uint32_t n_consts,
+                                                     const uint64_t *const *d_columns, const uint32_t *col_log2_len_or_null, uint32_t n_cols,
+                                                     uint32_t log2_trace, uint32_t log2_blowup, const uint64_t *offset_or_null, uint64_t two_adic_root,
+                                                     const lw_gl2_boundary_t *boundary, uint32_t n_boundary, const lw_gl2_transition_t *transitions,
+                                                     uint32_t n_transitions, uint64_t *d_out, size_t out_stride, void *hip_stream) {
+    return ext_r2_constraint_evaluations<Gl2Ext>(GL2_R2_NAMES, ops, n_ops, consts, n_consts, d_columns, col_log2_len_or_null, n_cols, log2_trace, log2_blowup,
+                                                 offset_or_null, two_adic_root, boundary, n_boundary, transitions, n_transitions, d_out, out_stride, hip_stream);
+}
+
+int lw_goldilocks_ext2_composition_parts_device(const uint64_t *d_evals, size_t evals_stride, uint32_t log2_lde, const uint64_t *offset_or_null,
+                                                uint64_t two_adic_root, uint32_t n_parts, uint64_t *d_parts_coeffs, uint64_t *d_parts_lde_or_null,
+                                                size_t *out_part_lens_or_null, void *hip_stream) {
+    // both planes through the existing inverse transform, every plane of every part through the existing LDE
+    return ext_r2_composition_parts<Gl2Ext>(
+        GL2_R2_NAMES, d_evals, evals_stride, log2_lde, offset_or_null, two_adic_root, n_parts, d_parts_coeffs, d_parts_lde_or_null, out_part_lens_or_null, hip_stream,
+        [](Context &c, const uint64_t *d_in, uint64_t in_stride, uint64_t *d_H, uint64_t h_stride, uint32_t lg, uint64_t h, uint64_t root, hipStream_t s) {
+            return goldilocks_ntt_locked(c, true, d_in, in_stride, d_H, h_stride, lg, 2, h, root, s);
+        },
+        [](Context &c, const uint64_t *d_coeffs, uint32_t lgL, uint64_t *d_lde, uint32_t lg, uint32_t batch, uint64_t h, uint64_t root, hipStream_t s) {
+            return goldilocks_lde_locked(c, d_coeffs, lgL, (uint64_t)1 << lgL, d_lde, lg, (uint64_t)1 << lg, batch, h, root, s);
+        });
 }
 
 }  // extern "C"

@@ -62,6 +62,8 @@ int gl_root_check(uint64_t &root);    // 0 becomes the reference's 2^32-th root;
 uint64_t gl_host_root(uint64_t g, uint32_t order, bool inverse);   // the primitive 2^order-th root of the 2^32-th root g, or its inverse
 int goldilocks_lde_locked(Context &c, const uint64_t *d_coeffs, uint32_t log2_coeffs, uint64_t in_stride, uint64_t *d_out, uint32_t log2n,
                           uint64_t out_stride, uint32_t batch, uint64_t offset, uint64_t root, hipStream_t stream);
+int goldilocks_ntt_locked(Context &c, bool inverse, const uint64_t *d_in, uint64_t in_stride, uint64_t *d_out, uint64_t out_stride, uint32_t log2n,
+                          uint32_t batch, uint64_t offset, uint64_t root, hipStream_t stream);
 
 // ---- rpo.hip
 int rpo_level_check(int level);   // LW_RPO_128 or LW_RPO_160, else LW_ERR_BAD_ARG

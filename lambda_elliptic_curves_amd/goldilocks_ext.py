@@ -10,7 +10,8 @@ vector as it is.  Everything runs on torch's current stream unless `stream` is g
 import numpy as np
 
 from . import _lib as L
-from ._ext_common import commit_phase, folded_block, scalars  # noqa: F401  (folded_block is part of this module's surface)
+from . import _ext_common as X
+from ._ext_common import commit_phase, folded_block, part_block_len, scalars  # noqa: F401  (folded_block, part_block_len: this module's surface)
 from .errors import check
 from .goldilocks import P, _offset_arg
 
@@ -121,3 +122,43 @@ def fri_commit_phase_device(t_coeffs, n_coeffs, number_layers, coset_offset, dom
         return h * h % P
 
     return commit_phase(layer, square, 2, t_coeffs, n_coeffs, number_layers, int(coset_offset) % P, domain_size, challenge)
+
+
+# ---- round 2: the composition polynomial
+_R2 = X.Round2Spec(2, np.uint64, "int64", _scalars, _offset_arg, L.Gl2Boundary, L.Gl2Transition, "lw_goldilocks_ext2_constraint_evaluations_device",
+                   "lw_goldilocks_ext2_composition_parts_device", True)
+
+
+def constraint_evaluations_device(program, consts, t_columns, log2_trace, log2_blowup, boundary, transitions, t_out=None, out_stride=0, offset=None,
+                                  root=0, col_log2_len=None, stream=None):
+    """The evaluations of the composition polynomial on the LDE coset in one pass over the columns, no T_c rows stored:
+    t_out[i] = sum_c coeff_c Z_c[i] T_c(i) + sum_k coeff_k (col_k[i] - value_k) / (x_i - g^step_k), an Fp2 vector of
+    N = 2^(log2_trace + log2_blowup) elements.  program: stark.compile_transitions(...) with base-field constants `consts`
+    (integers); t_columns: a list of resident columns of N words (2^col_log2_len[c] for a short one); boundary:
+    [(col, step, value, (c0, c1))]; transitions: [dict(period, offset, end_exemptions, exemptions_period,
+    periodic_exemptions_offset, coeff=(c0, c1))].  Enqueues and returns t_out."""
+    return X.constraint_evaluations(_R2, program, consts, t_columns, log2_trace, log2_blowup, boundary, transitions, t_out, out_stride, offset, root,
+                                    col_log2_len, stream)
+
+
+def composition_parts_device(t_evals, log2_lde, n_parts, evals_stride=0, offset=None, root=0, lde=True, lens=True, stream=None):
+    """interpolate_offset_fft of the two planes, break_in_parts and the LDE of every part.
+    -> (t_parts_coeffs: 2 P dense planes of part_block_len(log2_lde, P) words, part j plane e at plane 2 j + e; part_lens
+    (None with lens=False: nothing is waited for); t_parts_lde: 2 P dense planes of N words, or None)."""
+    return X.composition_parts(_R2, t_evals, log2_lde, n_parts, evals_stride, offset, root, lde, lens, stream)
+
+
+def round2_device(program, consts, t_columns, log2_trace, log2_blowup, boundary, transitions, n_parts, offset=None, root=0, col_log2_len=None,
+                  level=RPO_128, stream=None):
+    """Round 2 on resident LDE columns: the constraint evaluations, the parts and the RPO column commitment over the 2 P
+    planes of the parts' LDE (rpo.commit_columns_device, bit-reversed rows).
+    -> (t_parts_coeffs, part_lens, t_parts_lde, t_nodes, root)"""
+    import torch
+    from . import rpo
+    log2_lde = int(log2_trace) + int(log2_blowup)
+    t_ev = constraint_evaluations_device(program, consts, t_columns, log2_trace, log2_blowup, boundary, transitions, offset=offset, root=root,
+                                         col_log2_len=col_log2_len, stream=stream)
+    t_coeffs, lens, t_lde = composition_parts_device(t_ev, log2_lde, n_parts, offset=offset, root=root, stream=stream)
+    t_nodes = torch.empty((2 * (1 << log2_lde) - 1) * digest_words(level), dtype=torch.int64, device=t_ev.device)
+    commit_root = rpo.commit_columns_device(level, t_lde, 2 * int(n_parts), log2_lde, t_nodes, stream=stream)
+    return t_coeffs, lens, t_lde, t_nodes, commit_root

@@ -417,6 +417,29 @@ extern "C" {
                                              offset_or_null: *const u32, domain_size: usize, d_out_poly: *mut u32,
                                              d_out_evaluation_or_null: *mut u32, d_nodes_or_null: *mut u8,
                                              out_root_or_null: *mut u8, hip_stream: *mut c_void) -> c_int;
+    // ---- STARK round 2 over Goldilocks with Fp2 and BabyBear with Fp4: the constraint evaluations in one pass over the LDE
+    // columns (the AIR's program, the zerofiers, the random linear combination in the extension, the boundary quotients)
+    // and the parts of the composition polynomial, part j plane e at plane j D + e
+    pub fn lw_goldilocks_ext2_constraint_evaluations_device(ops: *const lw_stark_air_op_t, n_ops: u32, consts: *const u64, n_consts: u32,
+                                                            d_columns: *const *const u64, col_log2_len_or_null: *const u32, n_cols: u32,
+                                                            log2_trace: u32, log2_blowup: u32, offset_or_null: *const u64,
+                                                            two_adic_root: u64, boundary: *const lw_gl2_boundary_t, n_boundary: u32,
+                                                            transitions: *const lw_gl2_transition_t, n_transitions: u32,
+                                                            d_out: *mut u64, out_stride: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_goldilocks_ext2_composition_parts_device(d_evals: *const u64, evals_stride: usize, log2_lde: u32,
+                                                       offset_or_null: *const u64, two_adic_root: u64, n_parts: u32,
+                                                       d_parts_coeffs: *mut u64, d_parts_lde_or_null: *mut u64,
+                                                       out_part_lens_or_null: *mut usize, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_babybear_ext4_constraint_evaluations_device(ops: *const lw_stark_air_op_t, n_ops: u32, consts: *const u32, n_consts: u32,
+                                                          d_columns: *const *const u32, col_log2_len_or_null: *const u32, n_cols: u32,
+                                                          log2_trace: u32, log2_blowup: u32, offset_or_null: *const u32,
+                                                          boundary: *const lw_bb4_boundary_t, n_boundary: u32,
+                                                          transitions: *const lw_bb4_transition_t, n_transitions: u32,
+                                                          d_out: *mut u32, out_stride: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_babybear_ext4_composition_parts_device(d_evals: *const u32, evals_stride: usize, log2_lde: u32,
+                                                     offset_or_null: *const u32, n_parts: u32, d_parts_coeffs: *mut u32,
+                                                     d_parts_lde_or_null: *mut u32, out_part_lens_or_null: *mut usize,
+                                                     hip_stream: *mut c_void) -> c_int;
     // ---- Monolith over Mersenne31: batched permutations (width 8 .. 24, rounds 1 .. 15); hash, compression and Merkle tree over width 16
     pub fn lw_monolith_permute(width: u32, rounds: u32, states: *const u32, n: usize, out: *mut u32) -> c_int;
     pub fn lw_monolith_permute_device(width: u32, rounds: u32, d_states: *const u32, n: usize, d_out: *mut u32,
@@ -488,6 +511,55 @@ pub struct lw_stark_transition_t {
     pub exemptions_period: u64,
     pub periodic_exemptions_offset: u64,
     pub coeff: [u64; 4],
+}
+
+/// lw_gl2_boundary_t: one boundary constraint of lw_goldilocks_ext2_constraint_evaluations_device (value in F, coeff in Fp2)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct lw_gl2_boundary_t {
+    pub col: u32,
+    pub reserved: u32,
+    pub step: u64,
+    pub value: u64,
+    pub coeff: [u64; 2],
+}
+
+/// lw_gl2_transition_t: the zerofier parameters and the Fp2 coefficient of one transition constraint
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct lw_gl2_transition_t {
+    pub period: u64,
+    pub offset: u64,
+    pub end_exemptions: u64,
+    /// 0: none
+    pub exemptions_period: u64,
+    pub periodic_exemptions_offset: u64,
+    pub coeff: [u64; 2],
+}
+
+/// lw_bb4_boundary_t: one boundary constraint of lw_babybear_ext4_constraint_evaluations_device (stored words)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct lw_bb4_boundary_t {
+    pub col: u32,
+    pub reserved: u32,
+    pub step: u64,
+    pub value: u32,
+    pub coeff: [u32; 4],
+    pub reserved2: u32,
+}
+
+/// lw_bb4_transition_t: the zerofier parameters and the Fp4 coefficient of one transition constraint
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct lw_bb4_transition_t {
+    pub period: u64,
+    pub offset: u64,
+    pub end_exemptions: u64,
+    /// 0: none
+    pub exemptions_period: u64,
+    pub periodic_exemptions_offset: u64,
+    pub coeff: [u32; 4],
 }
 
 /// lw_stark_air_op_t: one instruction of an AIR transition program (lw_stark_transition_evaluations_device)
@@ -591,5 +663,7 @@ const _: () = assert!(core::mem::size_of::<lw_kernel_time_t>() == 64);
 const _: () = assert!(core::mem::size_of::<lw_profile_t>() == 8 + 32 * 64);
 const _: () = assert!(core::mem::size_of::<lw_stark_tree_t>() == 56);
 const _: () = assert!(core::mem::size_of::<lw_stark_boundary_t>() == 80);
+const _: () = assert!(core::mem::size_of::<lw_gl2_boundary_t>() == 40 && core::mem::size_of::<lw_gl2_transition_t>() == 56);
+const _: () = assert!(core::mem::size_of::<lw_bb4_boundary_t>() == 40 && core::mem::size_of::<lw_bb4_transition_t>() == 56);
 const _: () = assert!(core::mem::size_of::<lw_stark_transition_t>() == 72);
 const _: () = assert!(core::mem::size_of::<lw_stark_air_op_t>() == 8);
