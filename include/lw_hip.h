@@ -1314,6 +1314,62 @@ int lw_monolith_constants(uint32_t width, uint32_t rounds, uint32_t *out_round_c
 int lw_monolith_layer_device(uint32_t width, uint32_t rounds, lw_monolith_layer_t layer, const uint32_t *d_states, size_t n,
                              uint32_t *d_out, void *hip_stream);
 
+/* ---- The quartic extension of Mersenne31 and the circle-STARK prover steps that run in it ----
+ * CM31 = F_p[i] / (i^2 + 1) and QM31 = CM31[u] / (u^2 - (2 + i)), Degree2ExtensionField / Degree4ExtensionField of
+ * math/src/field/fields/mersenne31/extensions.rs (mul, square, inv as there), with out-of-domain evaluation, the DEEP
+ * quotients and the circle FRI fold with its layer commitment.  Together with lw_circle_lde_device and
+ * lw_monolith_commit_columns_device the Mersenne31 path runs LDE -> commit -> OOD -> DEEP -> FRI commit phase on data that
+ * stays in device memory.
+ *   word            one uint32_t as in the circle FFT: any word is accepted and read as (w & p) + (w >> 31), every word
+ *                   handed back is the canonical residue
+ *   QM31 element    (c0 + c1 i) + (c2 + c3 i) u, the order of to_subfield_vec.  sigma(c0, c1, c2, c3) = (c0, c1, -c2, -c3).
+ *   host scalar     uint32_t[4] = {c0, c1, c2, c3}; a point (X, Y) of QM31^2 is uint32_t[8], X first
+ *   device vector   n elements are four PLANES of n words, c0, then c1 `stride` words later, and so on (0: n; below n:
+ *                   LW_ERR_BAD_ARG): the batch = 4 shape of lw_circle_*_device and the n_cols = 4 shape of
+ *                   lw_monolith_commit_columns_device
+ *   domain          the standard coset of 2^log2n points in natural order, point i = g_{2N} + i g_N = (x_i, y_i); log2n 1 .. 30
+ *                   (0: LW_ERR_BAD_ARG, above: LW_ERR_ORDER_TOO_LARGE)
+ * All entry points are _device forms under the stream and lane contract of the other *_device calls.  Device pointers
+ * must be 16-byte aligned (else LW_ERR_BAD_ARG).  Every argument check runs before any device work.  A call that hands a
+ * small result to the host (values, a root) waits for the stream; the others only enqueue.
+ *
+ * pointwise: as lw_babybear_ext4_pointwise_device, over QM31: MUL, SQR, INV (0 -> 0), MUL_BASE (d_b a single plane).
+ *
+ * evaluate: out_values[k m + j] = sum_i col_k[i] B_i(X_j, Y_j) for n_cols columns of 2^log2n base-field coefficients in the
+ * basis of lw_circle_evaluate_cfft, B_i(x, y) = y^(bit 0 of i) prod_{t >= 1} pi^(t-1)(x)^(bit t of i), pi(x) = 2x^2 - 1, at m
+ * points (host, 8 words each, not required to lie on the circle); out_values: host, n_cols m scalars.  A polynomial with
+ * QM31 coefficients is its four planes as four columns, its value v0 + i v1 + u v2 + i u v3.  n_cols = 0 or m = 0: LW_OK.
+ *
+ * deep_quotients: for every row i of the domain
+ *     out[i] = sum_j ( sum_k weights[k][j] (c_j col_k[i] - a_kj y_i - b_kj) ) / D_j(x_i, y_i)
+ * with c_j = sigma Y_j - Y_j, a_kj = sigma v_kj - v_kj, b_kj = v_kj c_j - a_kj Y_j for v_kj = evals[k][j], and the line
+ * through P_j and sigma P_j, D_j(x, y) = (Y_j - sigma Y_j) x + (sigma X_j - X_j) y + (X_j sigma Y_j - Y_j sigma X_j).  On
+ * the circle D_j vanishes at P_j and sigma P_j only.  points: m points; weights, evals: n_cols x m scalars, row k, column
+ * j (host).  A point with sigma P_j = P_j (the u-parts of X_j and Y_j zero) is LW_ERR_BAD_ARG, as are n_cols = 0, m = 0
+ * and d_out overlapping a column.  A column of QM31 values is its four planes as four columns, the weight of plane e
+ * multiplied by 1, i, u, iu by the caller.
+ *
+ * fri_layer: one fold of the circle FRI commit phase in evaluation form.  d_evals: 2^log2m = M values in natural order.
+ *     d_out[i] = ( v[i] + v[M-1-i] + zeta (v[i] - v[M-1-i]) / t_i ) / 2,  i < M / 2
+ * first != 0: the fold from the circle to the line, t_i = y_i of the coset of size M; first == 0: t_i = x_i of the coset
+ * of size 2M (log2m <= 29).  In coefficients this is c'_m = c_2m + zeta c_2m+1.  d_out may not overlap d_evals.
+ *   fold only   d_nodes_or_null == NULL; pair rows or a root asked for without nodes: LW_ERR_BAD_ARG
+ *   tree        the M / 2 folded values (at least 4) committed as lw_monolith_commit_columns_device(rounds, d_pairs, 8, 0,
+ *               log2m - 2, bit_reverse = 0): leaf i hashes out[i].c0..c3, out[M/2-1-i].c0..c3.  d_pairs: 2 M words, written
+ *               by the fold (eight columns of M / 4 words); d_nodes: (M / 2 - 1) x 8 words, root first, readable by
+ *               lw_stark_open_trees_device as it is; out_root_or_null: 8 words to host memory.  rounds 1 .. 15. */
+typedef enum { LW_M31EXT4_MUL = 0, LW_M31EXT4_SQR = 1, LW_M31EXT4_INV = 2, LW_M31EXT4_MUL_BASE = 3 } lw_m31ext4_op_t;
+int lw_mersenne31_ext4_pointwise_device(lw_m31ext4_op_t op, const uint32_t *d_a, size_t a_stride, const uint32_t *d_b, size_t b_stride,
+                                        uint32_t *d_out, size_t out_stride, size_t n, void *hip_stream);
+int lw_mersenne31_ext4_evaluate_device(const uint32_t *d_coeffs, uint32_t n_cols, size_t col_stride, uint32_t log2n,
+                                       const uint32_t *points, uint32_t m, uint32_t *out_values, void *hip_stream);
+int lw_mersenne31_ext4_deep_quotients_device(const uint32_t *d_lde, uint32_t n_cols, size_t col_stride, uint32_t log2n,
+                                             const uint32_t *points, uint32_t m, const uint32_t *weights, const uint32_t *evals,
+                                             uint32_t *d_out, size_t out_stride, void *hip_stream);
+int lw_mersenne31_ext4_fri_layer_device(const uint32_t *d_evals, size_t in_stride, uint32_t log2m, const uint32_t *zeta, int first,
+                                        uint32_t *d_out, size_t out_stride, uint32_t rounds, uint32_t *d_pairs_or_null,
+                                        uint32_t *d_nodes_or_null, uint32_t *out_root_or_null, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@ GL2_MUL, GL2_SQR, GL2_INV, GL2_MUL_BASE = 0, 1, 2, 3   # lw_gl2_op_t
 BB4_MUL, BB4_SQR, BB4_INV, BB4_MUL_BASE = 0, 1, 2, 3   # lw_bb4_op_t
 BB4_TO_PLANES, BB4_TO_INTERLEAVED = 0, 1   # lw_bb4_convert_t
 MONOLITH_CONCRETE, MONOLITH_BARS, MONOLITH_BRICKS = 0, 1, 2   # lw_monolith_layer_t
+M31EXT4_MUL, M31EXT4_SQR, M31EXT4_INV, M31EXT4_MUL_BASE = 0, 1, 2, 3   # lw_m31ext4_op_t
 AIR_LOAD, AIR_ADD, AIR_SUB, AIR_MUL, AIR_NEG, AIR_STORE, AIR_EMIT = range(7)   # lw_stark_air_opcode_t
 AIR_CELL, AIR_CONST, AIR_TMP = 0, 1, 2   # lw_stark_air_src_t
 AIR_MAX_OPS, AIR_MAX_TMPS, AIR_MAX_CONSTS = 4096, 8, 256   # LW_STARK_AIR_MAX_*
@@ -72,6 +73,8 @@ EXPORTS = [
     "lw_monolith_permute", "lw_monolith_permute_device", "lw_monolith_hash", "lw_monolith_hash_device",
     "lw_monolith_compress", "lw_monolith_compress_device", "lw_monolith_commit_columns", "lw_monolith_commit_columns_device",
     "lw_monolith_constants", "lw_monolith_layer_device",
+    "lw_mersenne31_ext4_pointwise_device", "lw_mersenne31_ext4_evaluate_device", "lw_mersenne31_ext4_deep_quotients_device",
+    "lw_mersenne31_ext4_fri_layer_device",
     "lw_field_batch_inverse", "lw_field_batch_inverse_device", "lw_field_batch_inverse_block",
     "lw_stark_constraint_evaluations_device", "lw_stark_composition_parts_device", "lw_stark_commit_composition_device",
     "lw_stark_round2", "lw_stark_transition_evaluations_device", "lw_stark_transition_evaluations",
@@ -419,6 +422,14 @@ def lib():
     L.lw_monolith_constants.restype = i
     L.lw_monolith_layer_device.argtypes = [u32, u32, i, vp, sz, vp, vp]
     L.lw_monolith_layer_device.restype = i
+    L.lw_mersenne31_ext4_pointwise_device.argtypes = [i, vp, sz, vp, sz, vp, sz, sz, vp]
+    L.lw_mersenne31_ext4_pointwise_device.restype = i
+    L.lw_mersenne31_ext4_evaluate_device.argtypes = [vp, u32, sz, u32, vp, u32, vp, vp]
+    L.lw_mersenne31_ext4_evaluate_device.restype = i
+    L.lw_mersenne31_ext4_deep_quotients_device.argtypes = [vp, u32, sz, u32, vp, u32, vp, vp, vp, sz, vp]
+    L.lw_mersenne31_ext4_deep_quotients_device.restype = i
+    L.lw_mersenne31_ext4_fri_layer_device.argtypes = [vp, sz, u32, vp, i, vp, sz, u32, vp, vp, vp, vp]
+    L.lw_mersenne31_ext4_fri_layer_device.restype = i
     L.lw_field_batch_inverse.argtypes = [i, vp, sz, vp]
     L.lw_field_batch_inverse.restype = i
     L.lw_field_batch_inverse_device.argtypes = [i, vp, sz, vp, vp]

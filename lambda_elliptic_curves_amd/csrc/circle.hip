@@ -149,6 +149,19 @@ static int circle_ensure_twiddles(Context &c, uint32_t L, hipStream_t stream) {
     });
 }
 
+// The cached inverse tables of a transform of 2^L words, for mersenne31_ext.hip (internal.h): *ix the inverse x-layers
+// 0 .. L - 2 (layer i at word 2^i - 1; null for L = 1), *iy the 2^(L-1) inverses of the y-layer of that size, both in the
+// order of the transform: entry j belongs to the point (1 + 4j) g.
+int circle_inverse_twiddles(Context &c, uint32_t L, hipStream_t stream, const uint32_t **ix, const uint32_t **iy) {
+    const int rc = circle_ensure_twiddles(c, L, stream);
+    if (rc) return rc;
+    const SharedState &sh = shared_state();
+    const uint32_t *xt = (const uint32_t *)sh.circle_x.buf.p;
+    *ix = L >= 2 && xt ? xt + (1ull << (sh.circle_x.log_n - 1)) : nullptr;
+    *iy = (const uint32_t *)sh.circle_y[L].buf.p + (1ull << (L - 1));
+    return LW_OK;
+}
+
 // the host side of a transform's passes (tile_run); the tables must be there (circle_ensure_twiddles)
 struct CircleCall {
     bool inv;

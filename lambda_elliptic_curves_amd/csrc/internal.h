@@ -65,6 +65,11 @@ int goldilocks_lde_locked(Context &c, const uint64_t *d_coeffs, uint32_t log2_co
 int goldilocks_ntt_locked(Context &c, bool inverse, const uint64_t *d_in, uint64_t in_stride, uint64_t *d_out, uint64_t out_stride, uint32_t log2n,
                           uint32_t batch, uint64_t offset, uint64_t root, hipStream_t stream);
 
+// ---- circle.hip
+// the cached inverse twiddles of a transform of 2^L words (built on demand): the x-layers 0 .. L - 2, layer i at word
+// 2^i - 1 (null for L = 1), and the y-layer of that size
+int circle_inverse_twiddles(Context &c, uint32_t L, hipStream_t stream, const uint32_t **ix, const uint32_t **iy);
+
 // ---- rpo.hip
 int rpo_level_check(int level);   // LW_RPO_128 or LW_RPO_160, else LW_ERR_BAD_ARG
 // the tree of lw_rpo_commit_columns_device inside another call's Entry; group: RpoHash::row's element order (0: as it is)

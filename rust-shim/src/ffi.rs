@@ -458,6 +458,19 @@ extern "C" {
     pub fn lw_monolith_constants(width: u32, rounds: u32, out_round_constants: *mut u32, out_mds: *mut u32) -> c_int;
     pub fn lw_monolith_layer_device(width: u32, rounds: u32, layer: c_int, d_states: *const u32, n: usize, d_out: *mut u32,
                                     hip_stream: *mut c_void) -> c_int;
+    // ---- the quartic extension of Mersenne31 (QM31) and the circle-STARK steps in it: words as in the circle FFT, a host
+    // scalar is [c0, c1, c2, c3], a point [X, Y] is 8 words; op is LW_M31EXT4_MUL / SQR / INV / MUL_BASE
+    pub fn lw_mersenne31_ext4_pointwise_device(op: c_int, d_a: *const u32, a_stride: usize, d_b: *const u32, b_stride: usize,
+                                               d_out: *mut u32, out_stride: usize, n: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_mersenne31_ext4_evaluate_device(d_coeffs: *const u32, n_cols: u32, col_stride: usize, log2n: u32,
+                                              points: *const u32, m: u32, out_values: *mut u32, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_mersenne31_ext4_deep_quotients_device(d_lde: *const u32, n_cols: u32, col_stride: usize, log2n: u32,
+                                                    points: *const u32, m: u32, weights: *const u32, evals: *const u32,
+                                                    d_out: *mut u32, out_stride: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_mersenne31_ext4_fri_layer_device(d_evals: *const u32, in_stride: usize, log2m: u32, zeta: *const u32, first: c_int,
+                                               d_out: *mut u32, out_stride: usize, rounds: u32, d_pairs_or_null: *mut u32,
+                                               d_nodes_or_null: *mut u32, out_root_or_null: *mut u32,
+                                               hip_stream: *mut c_void) -> c_int;
     // ---- batch inversion and STARK round 2 (the coset offset, the constraint tables and every small result on the host)
     pub fn lw_field_batch_inverse(field: Field, input: *const c_void, n: usize, out: *mut c_void) -> c_int;
     pub fn lw_field_batch_inverse_device(field: Field, d_in: *const c_void, n: usize, d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
@@ -652,6 +665,11 @@ pub const LW_BB4_MUL_BASE: c_int = 3;
 pub const LW_BB4_TO_PLANES: c_int = 0;
 pub const LW_BB4_TO_INTERLEAVED: c_int = 1;
 
+/// lw_m31ext4_op_t: the operation of lw_mersenne31_ext4_pointwise_device
+pub const LW_M31EXT4_MUL: c_int = 0;
+pub const LW_M31EXT4_SQR: c_int = 1;
+pub const LW_M31EXT4_INV: c_int = 2;
+pub const LW_M31EXT4_MUL_BASE: c_int = 3;
 /// lw_monolith_layer_t: the layer lw_monolith_layer_device applies
 pub const LW_MONOLITH_CONCRETE: c_int = 0;
 pub const LW_MONOLITH_BARS: c_int = 1;
