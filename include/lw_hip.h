@@ -1370,6 +1370,72 @@ int lw_mersenne31_ext4_fri_layer_device(const uint32_t *d_evals, size_t in_strid
                                         uint32_t *d_out, size_t out_stride, uint32_t rounds, uint32_t *d_pairs_or_null,
                                         uint32_t *d_nodes_or_null, uint32_t *out_root_or_null, void *hip_stream);
 
+/* ---- Circle STARK round 2 over Mersenne31 with QM31: the composition polynomial on the LDE coset in one pass, its parts ----
+ * Words, planes, strides (0: dense), the 16-byte alignment of device pointers and host scalars {c0, c1, c2, c3} are those
+ * of the lw_mersenne31_ext4_* section above.  n = 2^log2_trace, B = 2^log2_blowup, N = n B.  Trace points p_j = g_{2n} + j g_n,
+ * LDE points q_i = g_{2N} + i g_N, both in natural order; q_i + g_n = q_(i + B mod N).  A - C for circle points is
+ * (Ax Cx + Ay Cy, Ay Cx - Ax Cy).  The reference has no circle STARK prover: these lines are the definition.
+ *
+ * constraint_evaluations: ONE pass over the LDE columns, no row of transition evaluations is ever stored.  For every LDE
+ * row i in [0, N), in QM31:
+ *     out[i] = sum_c coeff_c T_c(i) E_c(q_i) / Z_c(q_i)  +  sum_k coeff_k (col_k[i] - value_k) (1 + x'_k) / y'_k
+ *   T_c(i)   what the program emits for constraint c at row i: ops, the accumulator machine with its 8 temporaries, the
+ *            CELL addressing col[(i + row B) mod len_col], the short (periodic) columns of col_log2_len_or_null and the host
+ *            check are exactly those of lw_stark_transition_evaluations_device.  Cells and constants are any u32, read as
+ *            (w & p) + (w >> 31).  A periodic column of period m_c is a column of m_c B words.
+ *   transition {period, offset, end_exemptions, coeff}: the constraint holds at the trace rows j = offset mod period, except
+ *            the last end_exemptions of those rows.  With m = n / period = 2^mu and c = p_offset:
+ *            Z(Q) = the y-coordinate of 2^(mu-1) (Q - c), that is mu - 1 doublings: simple zeros exactly at the constrained
+ *                   rows; on the LDE coset of period 2 B period in i and never zero when B >= 2;
+ *            E(Q) = prod_{k = 1 .. end_exemptions} (1 - (P_k.x Q.x + P_k.y Q.y)), P_k = p_(offset + (m - k) period): the line
+ *                   with a double zero at P_k.  There is no exemptions_period.
+ *            Transitions whose three integers are equal share one table of 1 / Z and one value per row; a call takes at
+ *            most 8 distinct descriptors.
+ *   boundary {col, step, value, coeff}: (x'_k, y'_k) = q_i - p_step.  (t - v)(1 + x') / y' is a polynomial exactly when
+ *            t(p_step) = v; y' vanishes at p_step and its antipode only, both trace points.
+ *   d_columns  host array of n_cols device pointers; column c has N words (2^col_log2_len[c] for a short one).  d_out: four
+ *            planes of N words, out_stride apart, that overlap no column; the words between two planes are not written.
+ * Every check runs before any device work and the call only enqueues.  LW_ERR_BAD_ARG: log2_trace < 1 or log2_trace +
+ * log2_blowup > 30; a period that is 0, not a power of two or above n / 2; offset >= period; end_exemptions > n / period;
+ * col >= n_cols or step >= n; a boundary constraint on a short column; more than 8 distinct descriptors; a malformed program
+ * (lw_hip_last_error names the op); a null or misaligned buffer; an out that overlaps a column.  LW_ERR_INV_ZERO:
+ * log2_blowup = 0 with any constraint present.  n_boundary = 0 or n_transitions = 0 is legal; both: zeros.
+ *
+ * composition_parts: the four planes of d_evals are interpolated (lw_circle_interpolate_cfft_device, batch = 4).  In the
+ * basis of lw_circle_evaluate_cfft bit t of a coefficient's index contributes the factor pi^(t-1)(x), so with
+ * L = 2^log2_part and P = n_parts part j is the CONTIGUOUS block of coefficients [j L, (j + 1) L) and
+ *     H(z) = sum_j M_j(z.x) H_j(z),   M_j = prod_{t: bit t of j set} pi^(log2_part + t - 1)(z.x).
+ * Part j, plane e lies at plane index 4 j + e in both outputs: d_parts_coeffs is 4 P dense planes of L words,
+ * d_parts_lde_or_null 4 P dense planes of N words, each the part on the LDE coset (its zero-padded coefficients through
+ * the forward transform of lw_circle_lde_device, the padding never written) - the n_cols = 4 P shape of
+ * lw_monolith_commit_columns_device and the "column as four planes" shape of evaluate and deep_quotients.
+ * out_tail_nonzero_or_null receives the number of non-zero words at the coefficient indices >= P L over the four planes
+ * (0 when the degree fits); asking for it synchronises.  d_evals is not modified.  LW_ERR_BAD_ARG: n_parts that is 0 or not
+ * a power of two, log2_part < 1, P L > N, overlapping buffers, a null or misaligned buffer; log2_lde as in the section above.
+ * The degree to budget: a transition of degree d in the cells with e end exemptions gives a quotient of total degree at
+ * most d n / 2 + 2 e - m / 2, a boundary constraint one of at most n / 2; a polynomial of total degree D has no coefficient
+ * at or above the smallest power of two greater than 2 D.  P L must reach that power of two for the tail to be 0. */
+typedef struct {
+    uint32_t col, reserved;
+    uint64_t step;
+    uint32_t value;
+    uint32_t coeff[4];
+    uint32_t reserved2;
+} lw_m31q_boundary_t;
+typedef struct {
+    uint64_t period, offset, end_exemptions;
+    uint32_t coeff[4];
+} lw_m31q_transition_t;
+int lw_mersenne31_ext4_constraint_evaluations_device(const lw_stark_air_op_t *ops, uint32_t n_ops, const uint32_t *consts,
+                                                     uint32_t n_consts, const uint32_t *const *d_columns,
+                                                     const uint32_t *col_log2_len_or_null, uint32_t n_cols, uint32_t log2_trace,
+                                                     uint32_t log2_blowup, const lw_m31q_boundary_t *boundary, uint32_t n_boundary,
+                                                     const lw_m31q_transition_t *transitions, uint32_t n_transitions,
+                                                     uint32_t *d_out, size_t out_stride, void *hip_stream);
+int lw_mersenne31_ext4_composition_parts_device(const uint32_t *d_evals, size_t evals_stride, uint32_t log2_lde, uint32_t log2_part,
+                                                uint32_t n_parts, uint32_t *d_parts_coeffs, uint32_t *d_parts_lde_or_null,
+                                                uint64_t *out_tail_nonzero_or_null, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,8 +43,8 @@ def commit_phase(layer, square, width, t_coeffs, n_coeffs, number_layers, coset_
 # ---- round 2: the composition polynomial (lw_*_constraint_evaluations_device, lw_*_composition_parts_device)
 class Round2Spec:
     """What a module hands to the shared round-2 calls: the number of planes, the numpy and torch types of a word, its
-    scalars(values, count), offset_arg(offset), the ctypes entries of the two tables, the names of the two C calls and
-    whether they take a two_adic_root."""
+    scalars(values, count), offset_arg(offset) (None: the calls take no coset offset, the domain is fixed), the ctypes
+    entries of the two tables, the names of the two C calls and whether they take a two_adic_root."""
 
     def __init__(self, width, word, torch_word, scalars, offset_arg, boundary, transition, constraints, parts, rooted):
         self.width, self.word, self.torch_word, self.scalars, self.offset_arg = width, word, torch_word, scalars, offset_arg
@@ -71,11 +71,15 @@ def _transition_table(spec, transitions):
     """[dict(period, offset, end_exemptions, exemptions_period (None / 0: none), periodic_exemptions_offset, coeff)] -> the
     module's transition array; coeff a scalar of E"""
     tab = (spec.transition * max(1, len(transitions)))()
+    periodic = any(name == "exemptions_period" for name, _ in spec.transition._fields_)   # a circle zerofier has none
     for k, t in enumerate(transitions):
         tab[k].period, tab[k].offset = int(t.get("period", 1)), int(t.get("offset", 0))
         tab[k].end_exemptions = int(t.get("end_exemptions", 0))
-        tab[k].exemptions_period = int(t.get("exemptions_period") or 0)
-        tab[k].periodic_exemptions_offset = int(t.get("periodic_exemptions_offset") or 0)
+        if periodic:
+            tab[k].exemptions_period = int(t.get("exemptions_period") or 0)
+            tab[k].periodic_exemptions_offset = int(t.get("periodic_exemptions_offset") or 0)
+        elif t.get("exemptions_period"):
+            raise ValueError("this extension's zerofiers have no exemptions_period")
         tab[k].coeff[:] = [int(x) for x in spec.scalars([t["coeff"]], 1)[0]]
     return tab
 
@@ -102,8 +106,9 @@ def constraint_evaluations(spec, program, consts, t_columns, log2_trace, log2_bl
         t_out = torch.empty(spec.width * n_lde, dtype=getattr(torch, spec.torch_word), device=t_columns[0].device if len(t_columns) else "cuda")
     ptrs = (C.c_void_p * max(1, len(t_columns)))(*[t.data_ptr() for t in t_columns])
     args = [ops.ctypes.data_as(C.POINTER(L.StarkAirOp)) if ops.shape[0] else None, ops.shape[0], L.host_ptr(cs), cs.shape[0], ptrs,
-            lens.ctypes.data_as(C.POINTER(C.c_uint32)) if lens is not None else None, len(t_columns), int(log2_trace), int(log2_blowup),
-            L.host_ptr(spec.offset_arg(offset))]
+            lens.ctypes.data_as(C.POINTER(C.c_uint32)) if lens is not None else None, len(t_columns), int(log2_trace), int(log2_blowup)]
+    if spec.offset_arg is not None:
+        args.append(L.host_ptr(spec.offset_arg(offset)))
     if spec.rooted:
         args.append(int(root))
     args += [_boundary_table(spec, boundary), len(boundary), _transition_table(spec, transitions), len(transitions), L.device_ptr(t_out), int(out_stride),

@@ -75,6 +75,7 @@ EXPORTS = [
     "lw_monolith_constants", "lw_monolith_layer_device",
     "lw_mersenne31_ext4_pointwise_device", "lw_mersenne31_ext4_evaluate_device", "lw_mersenne31_ext4_deep_quotients_device",
     "lw_mersenne31_ext4_fri_layer_device",
+    "lw_mersenne31_ext4_constraint_evaluations_device", "lw_mersenne31_ext4_composition_parts_device",
     "lw_field_batch_inverse", "lw_field_batch_inverse_device", "lw_field_batch_inverse_block",
     "lw_stark_constraint_evaluations_device", "lw_stark_composition_parts_device", "lw_stark_commit_composition_device",
     "lw_stark_round2", "lw_stark_transition_evaluations_device", "lw_stark_transition_evaluations",
@@ -135,6 +136,17 @@ class Bb4Transition(C.Structure):
     """lw_bb4_transition_t"""
     _fields_ = [("period", C.c_uint64), ("offset", C.c_uint64), ("end_exemptions", C.c_uint64), ("exemptions_period", C.c_uint64),
                 ("periodic_exemptions_offset", C.c_uint64), ("coeff", C.c_uint32 * 4)]
+
+
+class M31qBoundary(C.Structure):
+    """lw_m31q_boundary_t"""
+    _fields_ = [("col", C.c_uint32), ("reserved", C.c_uint32), ("step", C.c_uint64), ("value", C.c_uint32), ("coeff", C.c_uint32 * 4),
+                ("reserved2", C.c_uint32)]
+
+
+class M31qTransition(C.Structure):
+    """lw_m31q_transition_t"""
+    _fields_ = [("period", C.c_uint64), ("offset", C.c_uint64), ("end_exemptions", C.c_uint64), ("coeff", C.c_uint32 * 4)]
 
 
 class StarkAirOp(C.Structure):
@@ -430,6 +442,11 @@ def lib():
     L.lw_mersenne31_ext4_deep_quotients_device.restype = i
     L.lw_mersenne31_ext4_fri_layer_device.argtypes = [vp, sz, u32, vp, i, vp, sz, u32, vp, vp, vp, vp]
     L.lw_mersenne31_ext4_fri_layer_device.restype = i
+    L.lw_mersenne31_ext4_constraint_evaluations_device.argtypes = [aop, u32, vp, u32, vp, u32q, u32, u32, u32, C.POINTER(M31qBoundary), u32,
+                                                                   C.POINTER(M31qTransition), u32, vp, sz, vp]
+    L.lw_mersenne31_ext4_constraint_evaluations_device.restype = i
+    L.lw_mersenne31_ext4_composition_parts_device.argtypes = [vp, sz, u32, u32, u32, vp, vp, C.POINTER(C.c_uint64), vp]
+    L.lw_mersenne31_ext4_composition_parts_device.restype = i
     L.lw_field_batch_inverse.argtypes = [i, vp, sz, vp]
     L.lw_field_batch_inverse.restype = i
     L.lw_field_batch_inverse_device.argtypes = [i, vp, sz, vp, vp]

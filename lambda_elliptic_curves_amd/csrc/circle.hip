@@ -211,6 +211,22 @@ static int circle_lde_device(Context &c, const uint32_t *d_evals, uint32_t Lin, 
     });
 }
 
+// The two halves of the LDE for mersenne31_ext.hip (internal.h), each side under a stride of its own: interpolate_cfft of
+// `batch` columns of 2^L words, and evaluate_cfft(zero_pad(coeffs, 2^Lout)) of blocks of 2^Lin coefficients, the padding
+// never written.  The arguments are the caller's to check.
+int circle_interpolate_locked(Context &c, const uint32_t *d_in, uint64_t in_stride, uint32_t *d_out, uint64_t out_stride, uint32_t L, uint32_t batch,
+                              hipStream_t stream) {
+    const int rc = circle_ensure_twiddles(c, L, stream);
+    if (rc) return rc;
+    return tile_transform_device<CirclePolicy>(c, CircleCall{true}, d_in, in_stride, L, d_out, out_stride, L, batch, stream);
+}
+int circle_extend_locked(Context &c, const uint32_t *d_coeffs, uint32_t Lin, uint64_t in_stride, uint32_t *d_out, uint32_t Lout, uint64_t out_stride,
+                         uint32_t batch, hipStream_t stream) {
+    const int rc = circle_ensure_twiddles(c, Lout, stream);
+    if (rc) return rc;
+    return tile_transform_device<CirclePolicy>(c, CircleCall{false}, d_coeffs, in_stride, Lin, d_out, out_stride, Lout, batch, stream);
+}
+
 // ---- argument checks, before any device work
 static int circle_size_check(uint32_t log2n) {
     if (log2n > CIRCLE_MAX_LOG) {

@@ -69,6 +69,12 @@ int goldilocks_ntt_locked(Context &c, bool inverse, const uint64_t *d_in, uint64
 // the cached inverse twiddles of a transform of 2^L words (built on demand): the x-layers 0 .. L - 2, layer i at word
 // 2^i - 1 (null for L = 1), and the y-layer of that size
 int circle_inverse_twiddles(Context &c, uint32_t L, hipStream_t stream, const uint32_t **ix, const uint32_t **iy);
+// interpolate_cfft of `batch` columns of 2^L words, and evaluate_cfft(zero_pad(coeffs, 2^Lout)) of blocks of 2^Lin
+// coefficients (the padding never written): the two halves of the LDE, each side under its own stride
+int circle_interpolate_locked(Context &c, const uint32_t *d_in, uint64_t in_stride, uint32_t *d_out, uint64_t out_stride, uint32_t L, uint32_t batch,
+                              hipStream_t stream);
+int circle_extend_locked(Context &c, const uint32_t *d_coeffs, uint32_t Lin, uint64_t in_stride, uint32_t *d_out, uint32_t Lout, uint64_t out_stride,
+                         uint32_t batch, hipStream_t stream);
 
 // ---- rpo.hip
 int rpo_level_check(int level);   // LW_RPO_128 or LW_RPO_160, else LW_ERR_BAD_ARG

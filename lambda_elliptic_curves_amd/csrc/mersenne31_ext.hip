@@ -5,6 +5,7 @@
 //   evaluate         columns of base-field coefficients in the basis of evaluate_cfft at points of QM31^2
 //   deep_quotients   the quotients by the lines through P_j and sigma P_j over the standard coset, in evaluation form
 //   fri_layer        one circle FRI fold in evaluation form and, optionally, the Monolith tree over the folded pairs
+//   round 2          the fused constraint pass and the parts of the composition polynomial (circle_round2.cuh)
 // A vector of n elements is four PLANES of n words, `stride` words apart: circle.hip's batch = 4, monolith.hip's n_cols = 4.
 // The univariate steps of ext_steps.cuh do not apply: the domain is the standard coset g_{2N} + i g_N, the basis is a
 // product over the bits of the index, the quotients are by lines and the fold reads the inverse twiddles of circle.hip.
@@ -338,6 +339,8 @@ static int m31q_size_check(uint32_t log2n) {
 
 }  // namespace lw
 
+#include "circle_round2.cuh"   // round 2: the fused constraint pass and the parts, on M31qExt and m31q_size_check above
+
 using namespace lw;
 
 extern "C" {
@@ -428,6 +431,22 @@ int lw_mersenne31_ext4_fri_layer_device(const uint32_t *d_evals, size_t in_strid
     }
     // the tree of the existing commitment over the eight pair columns, on the same stream behind the fold
     return lw_monolith_commit_columns_device(rounds, d_pairs_or_null, 8, 0, log2m - 2, 0, d_nodes_or_null, out_root_or_null, hip_stream);
+}
+
+int lw_mersenne31_ext4_constraint_evaluations_device(const lw_stark_air_op_t *ops, uint32_t n_ops, const uint32_t *consts, uint32_t n_consts,
+                                                     const uint32_t *const *d_columns, const uint32_t *col_log2_len_or_null, uint32_t n_cols,
+                                                     uint32_t log2_trace, uint32_t log2_blowup, const lw_m31q_boundary_t *boundary, uint32_t n_boundary,
+                                                     const lw_m31q_transition_t *transitions, uint32_t n_transitions, uint32_t *d_out, size_t out_stride,
+                                                     void *hip_stream) {
+    return m31q_r2_constraint_evaluations(ops, n_ops, consts, n_consts, d_columns, col_log2_len_or_null, n_cols, log2_trace, log2_blowup, boundary, n_boundary,
+                                          transitions, n_transitions, d_out, out_stride, hip_stream);
+}
+
+int lw_mersenne31_ext4_composition_parts_device(const uint32_t *d_evals, size_t evals_stride, uint32_t log2_lde, uint32_t log2_part, uint32_t n_parts,
+                                                uint32_t *d_parts_coeffs, uint32_t *d_parts_lde_or_null, uint64_t *out_tail_nonzero_or_null,
+                                                void *hip_stream) {
+    return m31q_r2_composition_parts(d_evals, evals_stride, log2_lde, log2_part, n_parts, d_parts_coeffs, d_parts_lde_or_null, out_tail_nonzero_or_null,
+                                     hip_stream);
 }
 
 }  // extern "C"

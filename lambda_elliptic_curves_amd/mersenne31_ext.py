@@ -13,6 +13,7 @@ stream unless `stream` is given.
 import numpy as np
 
 from . import _lib as L
+from . import _ext_common as X
 from ._ext_common import scalars
 from .errors import InputError, check
 
@@ -150,3 +151,79 @@ def fri_commit_phase_device(t_evals, log2n, number_layers, rounds, challenge, in
     count = 1 << (log2n - number_layers)
     last = t_cur.cpu().numpy().view(np.uint32).reshape(4, count)
     return [tuple(int(last[e, i]) for e in range(4)) for i in range(count)], layers
+
+
+# ---- round 2: the composition polynomial on the circle
+def _mul(a, b):
+    """the product of two scalars (canonical words)"""
+    a0, a1, a2, a3 = a
+    b0, b1, b2, b3 = b
+    t0, t1 = (a2 * b2 - a3 * b3) % P, (a2 * b3 + a3 * b2) % P          # A1 B1, then (2 + i) A1 B1
+    return ((a0 * b0 - a1 * b1 + 2 * t0 - t1) % P, (a0 * b1 + a1 * b0 + 2 * t1 + t0) % P,
+            (a0 * b2 - a1 * b3 + a2 * b0 - a3 * b1) % P, (a0 * b3 + a1 * b2 + a2 * b1 + a3 * b0) % P)
+
+
+def part_factors(point, log2_part, n_parts):
+    """The factors M_j(X) of H(z) = sum_j M_j(z.x) H_j(z) for the parts of composition_parts_device at the point z = (X, Y):
+    M_j = prod_{t: bit t of j set} pi^(log2_part + t - 1)(X), pi(x) = 2 x^2 - 1 -> n_parts scalars."""
+    log2_part, n_parts = int(log2_part), int(n_parts)
+    if log2_part < 1 or n_parts < 1 or n_parts & (n_parts - 1):
+        raise InputError(f"mersenne31_ext: {n_parts} parts of 2^{log2_part} coefficients")
+    f = tuple(_word(c) for c in point[0])
+    for _ in range(log2_part - 1):
+        s = _mul(f, f)
+        f = ((2 * s[0] - 1) % P, 2 * s[1] % P, 2 * s[2] % P, 2 * s[3] % P)
+    out = [(1, 0, 0, 0)]
+    while len(out) < n_parts:          # f = pi^(log2_part + t - 1)(X) doubles the list at bit t
+        out += [_mul(m, f) for m in out]
+        s = _mul(f, f)
+        f = ((2 * s[0] - 1) % P, 2 * s[1] % P, 2 * s[2] % P, 2 * s[3] % P)
+    return out
+
+
+_R2 = X.Round2Spec(4, np.uint32, "int32", _scalars, None, L.M31qBoundary, L.M31qTransition, "lw_mersenne31_ext4_constraint_evaluations_device",
+                   "lw_mersenne31_ext4_composition_parts_device", False)
+
+
+def constraint_evaluations_device(program, consts, t_columns, log2_trace, log2_blowup, boundary, transitions, t_out=None, out_stride=0, col_log2_len=None,
+                                  stream=None):
+    """The evaluations of the composition polynomial on the LDE coset q_i = g_2N + i g_N in one pass over the columns, no
+    row of transition evaluations stored: t_out[i] = sum_c coeff_c T_c(i) E_c(q_i) / Z_c(q_i) + sum_k coeff_k (col_k[i] -
+    value_k) (1 + x'_k) / y'_k with (x'_k, y'_k) = q_i - p_step_k, a vector of N = 2^(log2_trace + log2_blowup) elements (Z, E
+    as lw_hip.h states them).  program: stark.compile_transitions(...) with base-field constants `consts`; t_columns: a list
+    of resident columns of N words (2^col_log2_len[c] for a short one); boundary: [(col, step, value, (c0, c1, c2, c3))];
+    transitions: [dict(period, offset, end_exemptions, coeff=(c0, c1, c2, c3))].  Enqueues and returns t_out."""
+    return X.constraint_evaluations(_R2, program, consts, t_columns, log2_trace, log2_blowup, boundary, transitions, t_out, out_stride, None, 0,
+                                    col_log2_len, stream)
+
+
+def composition_parts_device(t_evals, log2_lde, log2_part, n_parts, evals_stride=0, lde=True, tail=False, stream=None):
+    """interpolate_cfft of the four planes and the parts of the result: part j is the block of coefficients
+    [j L, (j + 1) L), L = 2^log2_part, and H(z) = sum_j part_factors(z, log2_part, n_parts)[j] H_j(z).
+    -> (t_parts_coeffs: 4 P dense planes of L words, part j plane e at plane 4 j + e; t_parts_lde: 4 P dense planes of N words,
+    every part on the LDE coset, or None; the number of non-zero words at the coefficient indices from P L on, or None with
+    tail=False: nothing is waited for)."""
+    import ctypes as C
+    import torch
+    P_, n_lde = max(int(n_parts), 1), 1 << int(log2_lde)
+    t_coeffs = torch.empty(4 * P_ << max(int(log2_part), 0), dtype=t_evals.dtype, device=t_evals.device)
+    t_lde = torch.empty(4 * P_ * n_lde, dtype=t_evals.dtype, device=t_evals.device) if lde else None
+    count = C.c_uint64(0)
+    check(L.lib().lw_mersenne31_ext4_composition_parts_device(L.device_ptr(t_evals), int(evals_stride), int(log2_lde), int(log2_part), int(n_parts),
+                                                             L.device_ptr(t_coeffs), L.device_ptr(t_lde) if lde else None, C.byref(count) if tail else None,
+                                                             L.stream_ptr(stream)))
+    return t_coeffs, t_lde, (int(count.value) if tail else None)
+
+
+def round2_device(program, consts, t_columns, log2_trace, log2_blowup, boundary, transitions, log2_part, n_parts, rounds, col_log2_len=None, stream=None):
+    """Round 2 on resident LDE columns: the constraint evaluations, the parts and the Monolith column commitment over the 4 P
+    planes of the parts on the LDE coset (monolith.commit_columns_device, bit-reversed rows).
+    -> (t_parts_coeffs, t_parts_lde, t_nodes: (2 N - 1) x 8 int32, root: (8,) uint32).  Waits for the stream."""
+    import torch
+    from . import monolith
+    log2_lde = int(log2_trace) + int(log2_blowup)
+    t_ev = constraint_evaluations_device(program, consts, t_columns, log2_trace, log2_blowup, boundary, transitions, col_log2_len=col_log2_len, stream=stream)
+    t_coeffs, t_lde, _ = composition_parts_device(t_ev, log2_lde, log2_part, n_parts, stream=stream)
+    t_nodes = torch.empty((2 * (1 << log2_lde) - 1, 8), dtype=torch.int32, device=t_ev.device)
+    root = monolith.commit_columns_device(int(rounds), t_lde, 4 * int(n_parts), log2_lde, t_nodes, stream=stream)
+    return t_coeffs, t_lde, t_nodes, root

@@ -471,6 +471,16 @@ extern "C" {
                                                d_out: *mut u32, out_stride: usize, rounds: u32, d_pairs_or_null: *mut u32,
                                                d_nodes_or_null: *mut u32, out_root_or_null: *mut u32,
                                                hip_stream: *mut c_void) -> c_int;
+    // ---- circle STARK round 2 over QM31: the fused constraint pass on the LDE coset and the parts (index blocks) of its result
+    pub fn lw_mersenne31_ext4_constraint_evaluations_device(ops: *const lw_stark_air_op_t, n_ops: u32, consts: *const u32, n_consts: u32,
+                                                            d_columns: *const *const u32, col_log2_len_or_null: *const u32, n_cols: u32,
+                                                            log2_trace: u32, log2_blowup: u32,
+                                                            boundary: *const lw_m31q_boundary_t, n_boundary: u32,
+                                                            transitions: *const lw_m31q_transition_t, n_transitions: u32,
+                                                            d_out: *mut u32, out_stride: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_mersenne31_ext4_composition_parts_device(d_evals: *const u32, evals_stride: usize, log2_lde: u32, log2_part: u32,
+                                                       n_parts: u32, d_parts_coeffs: *mut u32, d_parts_lde_or_null: *mut u32,
+                                                       out_tail_nonzero_or_null: *mut u64, hip_stream: *mut c_void) -> c_int;
     // ---- batch inversion and STARK round 2 (the coset offset, the constraint tables and every small result on the host)
     pub fn lw_field_batch_inverse(field: Field, input: *const c_void, n: usize, out: *mut c_void) -> c_int;
     pub fn lw_field_batch_inverse_device(field: Field, d_in: *const c_void, n: usize, d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
@@ -572,6 +582,30 @@ pub struct lw_bb4_transition_t {
     /// 0: none
     pub exemptions_period: u64,
     pub periodic_exemptions_offset: u64,
+    pub coeff: [u32; 4],
+}
+
+/// lw_m31q_boundary_t: one boundary constraint of lw_mersenne31_ext4_constraint_evaluations_device (any u32 is a word)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct lw_m31q_boundary_t {
+    pub col: u32,
+    pub reserved: u32,
+    /// the trace row, below n
+    pub step: u64,
+    pub value: u32,
+    pub coeff: [u32; 4],
+    pub reserved2: u32,
+}
+
+/// lw_m31q_transition_t: the zerofier parameters and the QM31 coefficient of one transition constraint on the circle
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct lw_m31q_transition_t {
+    /// a power of two from 1 to n / 2
+    pub period: u64,
+    pub offset: u64,
+    pub end_exemptions: u64,
     pub coeff: [u32; 4],
 }
 
@@ -683,5 +717,6 @@ const _: () = assert!(core::mem::size_of::<lw_stark_tree_t>() == 56);
 const _: () = assert!(core::mem::size_of::<lw_stark_boundary_t>() == 80);
 const _: () = assert!(core::mem::size_of::<lw_gl2_boundary_t>() == 40 && core::mem::size_of::<lw_gl2_transition_t>() == 56);
 const _: () = assert!(core::mem::size_of::<lw_bb4_boundary_t>() == 40 && core::mem::size_of::<lw_bb4_transition_t>() == 56);
+const _: () = assert!(core::mem::size_of::<lw_m31q_boundary_t>() == 40 && core::mem::size_of::<lw_m31q_transition_t>() == 40);
 const _: () = assert!(core::mem::size_of::<lw_stark_transition_t>() == 72);
 const _: () = assert!(core::mem::size_of::<lw_stark_air_op_t>() == 8);
