@@ -671,7 +671,13 @@ typedef enum {
     LW_STARK_AIR_STORE = 5,
     LW_STARK_AIR_EMIT = 6
 } lw_stark_air_opcode_t;
-typedef enum { LW_STARK_AIR_CELL = 0, LW_STARK_AIR_CONST = 1, LW_STARK_AIR_TMP = 2 } lw_stark_air_src_t;
+typedef enum {
+    LW_STARK_AIR_CELL = 0,
+    LW_STARK_AIR_CONST = 1,
+    LW_STARK_AIR_TMP = 2,
+    LW_STARK_AIR_XCELL = 3, /* the _rap_ entry points of the extension sections only: auxiliary column `index`, an element of E */
+    LW_STARK_AIR_XCONST = 4 /* the same: xconsts[index], an element of E */
+} lw_stark_air_src_t;
 typedef struct {
     uint8_t op, src;
     uint16_t index;
@@ -1200,7 +1206,7 @@ int lw_babybear_ext4_fri_layer_device(const uint32_t *d_coeffs, size_t coeff_str
  *            col_log2_len_or_null and the host check are exactly those of lw_stark_transition_evaluations_device.  Cells
  *            and constants are words of F: Goldilocks words are any u64, canonicalised on load; BabyBear words and
  *            constants must be below p (a constant that is not: LW_ERR_BAD_ARG; device words are the caller's promise).
- *            Extension-valued (auxiliary) columns and extension-valued constants are out of scope.
+ *            Extension-valued (auxiliary) columns and constants: the _rap_ entry points below.
  *   Z_c[i]   the zerofier of lw_stark_constraint_evaluations_device, in F: cycle_c[i mod len_c] times the product of
  *            (x_i - g^(n - k period)) over k = 1 .. end_exemptions, both cycle branches and the truncating divisions.
  *            The cycle tables are built on the device.  Transitions whose five integers are all equal share one table and
@@ -1270,6 +1276,86 @@ int lw_babybear_ext4_constraint_evaluations_device(const lw_stark_air_op_t *ops,
 int lw_babybear_ext4_composition_parts_device(const uint32_t *d_evals, size_t evals_stride, uint32_t log2_lde,
                                               const uint32_t *offset_or_null, uint32_t n_parts, uint32_t *d_parts_coeffs,
                                               uint32_t *d_parts_lde_or_null, size_t *out_part_lens_or_null, void *hip_stream);
+
+/* ---- RAP over Fp2 and Fp4: the auxiliary column of round 1 and a round 2 that reads it ----
+ * The randomized AIR with preprocessing (AIR::build_rap_challenges, AIR::build_auxiliary_trace, BoundaryConstraint::new_aux,
+ * get_aux_evaluation_element) for a trace in F whose challenges are in E: the auxiliary column is in E, D planes of words
+ * like every E vector here, so the LDE (batch = D), the column commitment (n_cols = D), evaluate and deep_quotients take it
+ * as D base columns.  Words, host scalars (D words each), planes, strides and alignment as in the sections above.
+ *
+ * aux_fractions: one column from the n rows of base columns,
+ *     f_i = (num_const + sum_j num_coeffs[j] col_{num_cols[j]}[i]) / (den_const + sum_j den_coeffs[j] col_{den_cols[j]}[i])
+ *     LW_EXT_AUX_PRODUCT   out[i] = f_0 ... f_i      with LW_EXT_AUX_EXCLUSIVE  out[0] = 1, out[i] = f_0 ... f_{i-1}
+ *     LW_EXT_AUX_SUM       out[i] = f_0 + ... + f_i  with LW_EXT_AUX_EXCLUSIVE  out[0] = 0, out[i] = f_0 + ... + f_{i-1}
+ *   (the grand product of a permutation or memory argument, inclusive as in read_only_memory.rs or exclusive as in
+ *   fibonacci_rap.rs, and a LogUp running sum).  d_columns: host array of n_cols device pointers to n words each; n >= 1 is
+ *   any length.  A list has at most LW_EXT_AUX_MAX_TERMS terms and may be empty (its arrays may then be NULL); a numerator
+ *   with no terms and the constant 1 costs no product.  d_out: D planes of n words, out_stride apart (0: n), the words
+ *   between the planes are not written; it overlaps no column.  d_total_or_null: D consecutive words on the device, the
+ *   product or the sum over all n rows (the last inclusive value).  out_zero_denominators_or_null: the number of rows
+ *   whose denominator is zero; asking for it synchronises and a count that is not zero is LW_ERR_INV_ZERO.  With a zero
+ *   denominator the contents of d_out and d_total are unspecified, asked for or not.  Without the pointer the call only
+ *   enqueues.  Reduce-then-scan in three launches whatever n; no workgroup waits for another.
+ *   Before any device work: n = 0, an unknown mode, more than 16 terms, a NULL table, col >= n_cols, a BabyBear scalar
+ *   word not below p, a null or misaligned buffer, a stride below n, d_out overlapping a column: LW_ERR_BAD_ARG; n above
+ *   2^36: LW_ERR_ALLOC.
+ *
+ * rap_constraint_evaluations: lw_*_constraint_evaluations_device with the same definition of out[i], where T_c and col_k
+ * are in E where the program or the constraint says so.  The arguments of that call, and
+ *   xconsts, n_xconsts     host scalars of E (D words each), at most LW_STARK_AIR_MAX_CONSTS: the operand XCONST
+ *   d_aux_columns, n_aux   host array of device pointers, each to D planes of N words aux_stride apart (0: N): the operand
+ *                          XCELL (column `index` at row offset `row`, addressed like CELL) and the boundary constraints
+ *                          with is_aux set
+ *   boundary               value is a scalar of E (BoundaryConstraints<FieldExtension>); non-zero high coordinates on a
+ *                          main-column constraint are legal.  col indexes d_aux_columns where is_aux is not 0.
+ * The host types every value of the (straight-line) program as F or E: an op on F operands runs the base-field
+ * arithmetic of the call above, F with E is a product by a base word, E with E a product in E.  The typed interpreter's
+ * loop is longer per op: a program with no E value at all was measured at 1.10 (Fp2) and 1.19 (Fp4) times the call above,
+ * which remains the one to take for such a program.  A program without the two sources and
+ * boundary values in F give the output of the call above bit for bit.  Further LW_ERR_BAD_ARG: an auxiliary column or
+ * extension constant index out of range (lw_hip_last_error names the op or the constraint), a null or misaligned
+ * auxiliary buffer, aux_stride below N, d_out overlapping an auxiliary column. */
+#define LW_EXT_AUX_MAX_TERMS 16
+typedef enum { LW_EXT_AUX_PRODUCT = 0, LW_EXT_AUX_SUM = 1, LW_EXT_AUX_EXCLUSIVE = 2 /* or-ed onto either */ } lw_ext_aux_mode_t;
+typedef struct {
+    uint32_t col, is_aux;
+    uint64_t step;
+    uint64_t value[2];
+    uint64_t coeff[2];
+} lw_gl2_rap_boundary_t;
+typedef struct {
+    uint32_t col, is_aux;
+    uint64_t step;
+    uint32_t value[4];
+    uint32_t coeff[4];
+} lw_bb4_rap_boundary_t;
+int lw_goldilocks_ext2_aux_fractions_device(const uint64_t *const *d_columns, uint32_t n_cols, size_t n, const uint64_t *num_const,
+                                            const uint32_t *num_cols, const uint64_t *num_coeffs, uint32_t n_num,
+                                            const uint64_t *den_const, const uint32_t *den_cols, const uint64_t *den_coeffs,
+                                            uint32_t n_den, uint32_t mode, uint64_t *d_out, size_t out_stride,
+                                            uint64_t *d_total_or_null, uint64_t *out_zero_denominators_or_null, void *hip_stream);
+int lw_babybear_ext4_aux_fractions_device(const uint32_t *const *d_columns, uint32_t n_cols, size_t n, const uint32_t *num_const,
+                                          const uint32_t *num_cols, const uint32_t *num_coeffs, uint32_t n_num,
+                                          const uint32_t *den_const, const uint32_t *den_cols, const uint32_t *den_coeffs,
+                                          uint32_t n_den, uint32_t mode, uint32_t *d_out, size_t out_stride,
+                                          uint32_t *d_total_or_null, uint64_t *out_zero_denominators_or_null, void *hip_stream);
+int lw_goldilocks_ext2_rap_constraint_evaluations_device(const lw_stark_air_op_t *ops, uint32_t n_ops, const uint64_t *consts,
+                                                         uint32_t n_consts, const uint64_t *xconsts, uint32_t n_xconsts,
+                                                         const uint64_t *const *d_columns, const uint32_t *col_log2_len_or_null,
+                                                         uint32_t n_cols, const uint64_t *const *d_aux_columns, uint32_t n_aux,
+                                                         size_t aux_stride, uint32_t log2_trace, uint32_t log2_blowup,
+                                                         const uint64_t *offset_or_null, uint64_t two_adic_root,
+                                                         const lw_gl2_rap_boundary_t *boundary, uint32_t n_boundary,
+                                                         const lw_gl2_transition_t *transitions, uint32_t n_transitions,
+                                                         uint64_t *d_out, size_t out_stride, void *hip_stream);
+int lw_babybear_ext4_rap_constraint_evaluations_device(const lw_stark_air_op_t *ops, uint32_t n_ops, const uint32_t *consts,
+                                                       uint32_t n_consts, const uint32_t *xconsts, uint32_t n_xconsts,
+                                                       const uint32_t *const *d_columns, const uint32_t *col_log2_len_or_null,
+                                                       uint32_t n_cols, const uint32_t *const *d_aux_columns, uint32_t n_aux,
+                                                       size_t aux_stride, uint32_t log2_trace, uint32_t log2_blowup,
+                                                       const uint32_t *offset_or_null, const lw_bb4_rap_boundary_t *boundary,
+                                                       uint32_t n_boundary, const lw_bb4_transition_t *transitions,
+                                                       uint32_t n_transitions, uint32_t *d_out, size_t out_stride, void *hip_stream);
 
 /* ---- Monolith over Mersenne31 (crypto/src/hash/monolith/: MonolithMersenne31<WIDTH, NUM_FULL_ROUNDS>, from Plonky3) ----
  * The permutation, batched (one work-item per state), and for width 16 a hash, a 2-to-1 compression and a Merkle tree

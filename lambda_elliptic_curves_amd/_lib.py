@@ -29,6 +29,8 @@ MONOLITH_CONCRETE, MONOLITH_BARS, MONOLITH_BRICKS = 0, 1, 2   # lw_monolith_laye
 M31EXT4_MUL, M31EXT4_SQR, M31EXT4_INV, M31EXT4_MUL_BASE = 0, 1, 2, 3   # lw_m31ext4_op_t
 AIR_LOAD, AIR_ADD, AIR_SUB, AIR_MUL, AIR_NEG, AIR_STORE, AIR_EMIT = range(7)   # lw_stark_air_opcode_t
 AIR_CELL, AIR_CONST, AIR_TMP = 0, 1, 2   # lw_stark_air_src_t
+AIR_XCELL, AIR_XCONST = 3, 4             # the same, of the _rap_ entry points: an auxiliary column, a constant of E
+EXT_AUX_PRODUCT, EXT_AUX_SUM, EXT_AUX_EXCLUSIVE, EXT_AUX_MAX_TERMS = 0, 1, 2, 16   # lw_ext_aux_mode_t, LW_EXT_AUX_MAX_TERMS
 AIR_MAX_OPS, AIR_MAX_TMPS, AIR_MAX_CONSTS = 4096, 8, 256   # LW_STARK_AIR_MAX_*
 (OK, ERR_INPUT_NOT_POW2, ERR_ORDER_TOO_LARGE, ERR_ROOT_OF_UNITY, ERR_LENGTH_MISMATCH, ERR_NO_DEVICE, ERR_ALLOC,
  ERR_LAUNCH, ERR_COMM, ERR_BAD_ARG, ERR_INV_ZERO) = (0, -1, -2, -3, -4, -5, -6, -7, -8, -9, -10)
@@ -68,6 +70,8 @@ EXPORTS = [
     "lw_babybear_ext4_deep_quotients_device", "lw_babybear_ext4_fri_layer_device",
     "lw_goldilocks_ext2_constraint_evaluations_device", "lw_goldilocks_ext2_composition_parts_device",
     "lw_babybear_ext4_constraint_evaluations_device", "lw_babybear_ext4_composition_parts_device",
+    "lw_goldilocks_ext2_aux_fractions_device", "lw_babybear_ext4_aux_fractions_device",
+    "lw_goldilocks_ext2_rap_constraint_evaluations_device", "lw_babybear_ext4_rap_constraint_evaluations_device",
     "lw_rpo_permute", "lw_rpo_permute_device", "lw_rpo_hash", "lw_rpo_hash_device",
     "lw_rpo_commit_columns", "lw_rpo_commit_columns_device",
     "lw_monolith_permute", "lw_monolith_permute_device", "lw_monolith_hash", "lw_monolith_hash_device",
@@ -124,6 +128,16 @@ class Gl2Transition(C.Structure):
     """lw_gl2_transition_t"""
     _fields_ = [("period", C.c_uint64), ("offset", C.c_uint64), ("end_exemptions", C.c_uint64), ("exemptions_period", C.c_uint64),
                 ("periodic_exemptions_offset", C.c_uint64), ("coeff", C.c_uint64 * 2)]
+
+
+class Gl2RapBoundary(C.Structure):
+    """lw_gl2_rap_boundary_t"""
+    _fields_ = [("col", C.c_uint32), ("is_aux", C.c_uint32), ("step", C.c_uint64), ("value", C.c_uint64 * 2), ("coeff", C.c_uint64 * 2)]
+
+
+class Bb4RapBoundary(C.Structure):
+    """lw_bb4_rap_boundary_t"""
+    _fields_ = [("col", C.c_uint32), ("is_aux", C.c_uint32), ("step", C.c_uint64), ("value", C.c_uint32 * 4), ("coeff", C.c_uint32 * 4)]
 
 
 class Bb4Boundary(C.Structure):
@@ -402,6 +416,15 @@ def lib():
     L.lw_babybear_ext4_constraint_evaluations_device.restype = i
     L.lw_babybear_ext4_composition_parts_device.argtypes = [vp, sz, u32, vp, u32, vp, vp, szp, vp]
     L.lw_babybear_ext4_composition_parts_device.restype = i
+    for name in ("lw_goldilocks_ext2_aux_fractions_device", "lw_babybear_ext4_aux_fractions_device"):
+        getattr(L, name).argtypes = [vp, u32, sz, vp, u32q, vp, u32, vp, u32q, vp, u32, u32, vp, sz, vp, C.POINTER(C.c_uint64), vp]
+        getattr(L, name).restype = i
+    L.lw_goldilocks_ext2_rap_constraint_evaluations_device.argtypes = [aop, u32, vp, u32, vp, u32, vp, u32q, u32, vp, u32, sz, u32, u32, vp, C.c_uint64,
+                                                                       C.POINTER(Gl2RapBoundary), u32, C.POINTER(Gl2Transition), u32, vp, sz, vp]
+    L.lw_goldilocks_ext2_rap_constraint_evaluations_device.restype = i
+    L.lw_babybear_ext4_rap_constraint_evaluations_device.argtypes = [aop, u32, vp, u32, vp, u32, vp, u32q, u32, vp, u32, sz, u32, u32, vp,
+                                                                     C.POINTER(Bb4RapBoundary), u32, C.POINTER(Bb4Transition), u32, vp, sz, vp]
+    L.lw_babybear_ext4_rap_constraint_evaluations_device.restype = i
     L.lw_rpo_permute.argtypes = [i, vp, sz, vp]
     L.lw_rpo_permute.restype = i
     L.lw_rpo_permute_device.argtypes = [i, vp, sz, vp, vp]

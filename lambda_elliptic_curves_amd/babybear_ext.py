@@ -195,3 +195,68 @@ def round2_device(program, consts, t_columns, log2_trace, log2_blowup, boundary,
     t_nodes = torch.empty((2 * (1 << log2_lde) - 1) * 32, dtype=torch.uint8, device=t_ev.device)
     commit_root = merkle.commit_columns_layout_device(fft.Babybear31PrimeFieldU32, t_lde, 4 * int(n_parts), log2_lde, t_nodes, stream=stream)
     return t_coeffs, lens, t_lde, t_nodes, commit_root
+
+
+# ---- RAP: the auxiliary column of round 1 and the round 2 that reads it
+PRODUCT, SUM = L.EXT_AUX_PRODUCT, L.EXT_AUX_SUM
+
+
+def _rap_interpolate(t_in, t_out, log2n, batch, root, stream):
+    from . import fft
+    fft.ntt_device(fft.Babybear31PrimeFieldU32, t_in, t_out, log2n, inverse=True, batch=batch, stream=stream)
+
+
+def _rap_lde(t_coeffs, log2_coeffs, t_out, log2n, batch, offset, root, stream):
+    from . import fft
+    fft.lde_device(fft.Babybear31PrimeFieldU32, t_coeffs, log2_coeffs, t_out, log2n, batch=batch, offset=_offset_arg(offset), stream=stream)
+
+
+def _rap_commit(t_lde, n_cols, log2n, stream):
+    import torch
+    from . import fft, merkle
+    t_nodes = torch.empty((2 * (1 << log2n) - 1) * 32, dtype=torch.uint8, device=t_lde.device)
+    return t_nodes, merkle.commit_columns_layout_device(fft.Babybear31PrimeFieldU32, t_lde, n_cols, log2n, t_nodes, stream=stream)
+
+
+_RAP = X.RapSpec(_R2, L.Bb4RapBoundary, "lw_babybear_ext4_rap_constraint_evaluations_device", "lw_babybear_ext4_aux_fractions_device", _rap_interpolate,
+                 _rap_lde, _rap_commit)
+
+
+def aux_fractions_device(t_columns, n, num, den, mode=PRODUCT, exclusive=False, t_out=None, out_stride=0, total=False, count_zeros=False, stream=None):
+    """The auxiliary column of a randomized AIR: with f_i = (a_0 + sum_j a_j col_{s_j}[i]) / (b_0 + sum_j b_j col_{t_j}[i]) over
+    the n rows of the base columns t_columns, the running product (PRODUCT) or sum (SUM) of the f_i, inclusive (out[i] takes
+    f_i in) or exclusive (out[0] = 1 or 0).  num = (a_0, [(s_j, a_j), ...]) and den likewise, the scalars in Fp4 (stored
+    words), at most 16 terms each.  -> (t_out: four planes of n words out_stride apart, t_total: the product or sum over all
+    rows as four words on the device, or None).  With count_zeros the call waits and raises errors.FieldError (.zero_denominators: how many) if a denominator
+    is zero; without it the call only enqueues and the output of such rows is unspecified."""
+    return X.aux_fractions(_RAP, t_columns, n, num, den, mode, exclusive, t_out, out_stride, total, count_zeros, stream)
+
+
+def rap_constraint_evaluations_device(program, consts, xconsts, t_columns, t_aux_columns, log2_trace, log2_blowup, boundary, transitions, t_out=None,
+                                      out_stride=0, aux_stride=0, offset=None, col_log2_len=None, stream=None):
+    """constraint_evaluations_device for a randomized AIR: the program may read auxiliary columns (stark.xcell) and constants
+    of Fp4 (stark.xconst).  xconsts: [(c0, c1, c2, c3)]; t_aux_columns: a list of resident Fp4 columns, four planes of N
+    stored words aux_stride apart each; boundary: [(col, step, value, coeff)] or [(col, step, value, coeff, is_aux)] with
+    value a stored word or four.  Enqueues and returns t_out."""
+    return X.rap_constraint_evaluations(_RAP, program, consts, xconsts, t_columns, t_aux_columns, log2_trace, log2_blowup, boundary, transitions, t_out,
+                                        out_stride, aux_stride, offset, 0, col_log2_len, stream)
+
+
+def round1_aux_device(t_columns, log2_trace, log2_blowup, num, den, mode=PRODUCT, exclusive=False, offset=None, count_zeros=False, stream=None):
+    """The second half of round 1 on resident trace columns of 2^log2_trace stored words: the auxiliary column
+    (aux_fractions_device), the interpolation of its four planes, their LDE (fft.lde_device with batch = 4) and the Keccak
+    column commitment over them.  count_zeros: wait for the column and raise errors.FieldError (with .zero_denominators) if a denominator is zero.
+    -> (t_aux, t_total, t_polys, t_lde, t_nodes, root)"""
+    return X.round1_aux(_RAP, t_columns, log2_trace, log2_blowup, num, den, mode, exclusive, offset, 0, count_zeros, stream)
+
+
+def round2_rap_device(program, consts, xconsts, t_columns, t_aux_columns, log2_trace, log2_blowup, boundary, transitions, n_parts, offset=None,
+                      col_log2_len=None, stream=None):
+    """round2_device with rap_constraint_evaluations_device in the place of constraint_evaluations_device.
+    -> (t_parts_coeffs, part_lens, t_parts_lde, t_nodes, root)"""
+    log2_lde = int(log2_trace) + int(log2_blowup)
+    t_ev = rap_constraint_evaluations_device(program, consts, xconsts, t_columns, t_aux_columns, log2_trace, log2_blowup, boundary, transitions,
+                                             offset=offset, col_log2_len=col_log2_len, stream=stream)
+    t_coeffs, lens, t_lde = composition_parts_device(t_ev, log2_lde, n_parts, offset=offset, stream=stream)
+    t_nodes, commit_root = _rap_commit(t_lde, 4 * int(n_parts), log2_lde, stream)
+    return t_coeffs, lens, t_lde, t_nodes, commit_root

@@ -18,6 +18,7 @@
 #include "babybear_ext.cuh"
 #include "ext_steps.cuh"
 #include "ext_round2.cuh"
+#include "ext_aux.cuh"
 
 namespace lw {
 
@@ -201,7 +202,8 @@ int lw_babybear_ext4_fri_layer_device(const uint32_t *d_coeffs, size_t coeff_str
                                  });
 }
 
-static constexpr ExtR2Names BB4_R2_NAMES{"bb4_r2_xtable_kernel", "bb4_r2_cycle_kernel", "bb4_r2_transition_kernel", "bb4_r2_boundary_kernel", "bb4_r2_split_kernel", "bb4_r2_lengths_kernel"};
+static constexpr ExtR2Names BB4_R2_NAMES{"bb4_r2_xtable_kernel", "bb4_r2_cycle_kernel", "bb4_r2_transition_kernel", "bb4_r2_boundary_kernel", "bb4_r2_split_kernel", "bb4_r2_lengths_kernel", "bb4_r2_rap_transition_kernel"};
+static constexpr ExtAuxNames BB4_AUX_NAMES{"bb4_aux_reduce_kernel", "bb4_aux_carry_kernel", "bb4_aux_rescan_kernel"};
 
 int lw_babybear_ext4_constraint_evaluations_device(const lw_stark_air_op_t *ops, uint32_t n_ops, const uint32_t *consts, uint32_t n_consts,
                                                    const uint32_t *const *d_columns, const uint32_t *col_log2_len_or_null, uint32_t n_cols,
@@ -231,6 +233,24 @@ int lw_babybear_ext4_composition_parts_device(const uint32_t *d_evals, size_t ev
         [&](Context &c, const uint32_t *d_coeffs, uint32_t lgL, uint32_t *d_lde, uint32_t lg, uint32_t batch, uint32_t, uint64_t, hipStream_t s) {
             return ntt_device_locked(c, LW_FIELD_BABYBEAR, LW_LAYOUT_BABYBEAR_U32_R32, LW_DIR_FORWARD, d_coeffs, d_lde, lg, batch, 0, offset_or_null, s, lgL);
         });
+}
+
+int lw_babybear_ext4_aux_fractions_device(const uint32_t *const *d_columns, uint32_t n_cols, size_t n, const uint32_t *num_const, const uint32_t *num_cols,
+        const uint32_t *num_coeffs, uint32_t n_num, const uint32_t *den_const, const uint32_t *den_cols, const uint32_t *den_coeffs, uint32_t n_den,
+        uint32_t mode, uint32_t *d_out, size_t out_stride, uint32_t *d_total_or_null, uint64_t *out_zero_denominators_or_null, void *hip_stream) {
+    return ext_aux_fractions<Bb4Ext>(BB4_AUX_NAMES, d_columns, n_cols, n, ExtAuxList<Bb4Ext>{num_const, num_cols, num_coeffs, n_num},
+                                    ExtAuxList<Bb4Ext>{den_const, den_cols, den_coeffs, n_den}, mode, d_out, out_stride, d_total_or_null,
+                                    out_zero_denominators_or_null, hip_stream);
+}
+
+int lw_babybear_ext4_rap_constraint_evaluations_device(const lw_stark_air_op_t *ops, uint32_t n_ops, const uint32_t *consts, uint32_t n_consts, const uint32_t *xconsts,
+        uint32_t n_xconsts, const uint32_t *const *d_columns, const uint32_t *col_log2_len_or_null, uint32_t n_cols, const uint32_t *const *d_aux_columns,
+        uint32_t n_aux, size_t aux_stride, uint32_t log2_trace, uint32_t log2_blowup, const uint32_t *offset_or_null,
+        const lw_bb4_rap_boundary_t *boundary, uint32_t n_boundary, const lw_bb4_transition_t *transitions, uint32_t n_transitions, uint32_t *d_out, size_t out_stride,
+        void *hip_stream) {
+    ExtR2Rap<Bb4Ext> rap{d_aux_columns, n_aux, aux_stride, xconsts, n_xconsts, {}, 0};
+    return ext_r2_constraint_evaluations<Bb4Ext>(BB4_R2_NAMES, ops, n_ops, consts, n_consts, d_columns, col_log2_len_or_null, n_cols, log2_trace, log2_blowup,
+                                                offset_or_null, 0, boundary, n_boundary, transitions, n_transitions, d_out, out_stride, hip_stream, &rap);
 }
 
 }  // extern "C"

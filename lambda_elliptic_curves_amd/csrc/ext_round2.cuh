@@ -31,7 +31,16 @@
 // ext_r2_split_kernel      break_in_parts over words: part j, plane e at plane j D + e
 // ext_r2_lengths_kernel    the stripped length of every part
 //
-// Out of scope: extension-valued (auxiliary) columns and extension-valued constants.
+//
+// The randomized AIR (the _rap_ entry points): auxiliary columns and constants in E.  An auxiliary column is D planes of N
+// words; the program reads it with XCELL and a constant of E with XCONST, and a boundary constraint may sit on it.
+// air_program_check_rap types every value of the straight-line program as F or E and writes the types into the op words, so
+// ext_r2_rap_transition_kernel, the interpreter above with two accumulators (a word and an element), branches on them with a
+// scalar branch: an op on F operands is E::fadd / E::fsub / E::fmul as above, F with E is E::mul_base, E with E is E::mul,
+// and an emitted element folds as beta_c (Z acc) with one E::mul.  A temporary that ever holds an element takes D LDS slots
+// [slot][coordinate][lane], any other one: (F temporaries + D E temporaries + classes) words per lane, 48 KiB (Fp2) or 40 KiB
+// (Fp4) at most.  The boundary kernel takes a template flag: a constraint on an auxiliary column adds E::mul(gamma_k,
+// aux_k[i]) where one on a main column adds E::mul_base, and v_k in E only changes the host's constant c_s.
 #pragma once
 #include <algorithm>
 #include "air_program.h"
@@ -95,6 +104,16 @@ template <class E> struct ExtR2Step {
     uint32_t first, count;
     typename E::elem constant;   // sum_k gamma_k v_k over the step's constraints
 };
+// gamma_k v_k with v_k a word of F (the boundary entries of the plain entry points) or a scalar of E (the _rap_ ones)
+template <class E> static typename E::elem ext_r2_times_value(typename E::elem gamma, const typename E::word &v) { return E::mul_base(gamma, E::fcanon(v)); }
+template <class E> static typename E::elem ext_r2_times_value(typename E::elem gamma, const typename E::word (&v)[E::D]) {
+    return E::mul(gamma, ext_elem_of<E>(v, 0));
+}
+template <class E> static int ext_r2_value_check(const typename E::word &v) { return E::words_check(&v, 1, "boundary value"); }
+template <class E> static int ext_r2_value_check(const typename E::word (&v)[E::D]) { return E::words_check(v, E::D, "boundary value"); }
+// whether a boundary entry sits on an auxiliary column: only the _rap_ entries have the member
+template <class B> static auto ext_r2_is_aux(const B &b, int) -> decltype(b.is_aux != 0) { return b.is_aux != 0; }
+template <class B> static bool ext_r2_is_aux(const B &, long) { return false; }
 template <class E, class B>
 static void ext_r2_step_groups(const B *bnd, uint32_t n_bnd, uint64_t n, typename E::word g, std::vector<uint32_t> &order, std::vector<ExtR2Step<E>> &steps) {
     order.resize(n_bnd);
@@ -105,7 +124,7 @@ static void ext_r2_step_groups(const B *bnd, uint32_t n_bnd, uint64_t n, typenam
         const B &b = bnd[order[q]];
         if (q == 0 || b.step % n != bnd[order[q - 1]].step % n) steps.push_back(ExtR2Step<E>{E::fpow(g, b.step % n), q, 0, E::zero()});
         steps.back().count++;
-        steps.back().constant = E::add(steps.back().constant, E::mul_base(ext_elem_of<E>(b.coeff, 0), E::fcanon(b.value)));
+        steps.back().constant = E::add(steps.back().constant, ext_r2_times_value<E>(ext_elem_of<E>(b.coeff, 0), b.value));
     }
 }
 // an element as the two 64-bit words the kernels read it back from
@@ -246,7 +265,118 @@ template <class E> __global__ __launch_bounds__(EXT_THREADS) void ext_r2_transit
     E::store(a.out, i, sum);
 }
 
-// bnd: per constraint (in the order of the steps) the address of its column, 0, gamma_k (two words)
+// The same tables, and
+//   ops      the words of air_program_check_rap: AIR_TYPED_ACC_EXT and AIR_TYPED_SRC_EXT in the op byte, LDS slots as the
+//            indices of temporaries
+//   xcells   per auxiliary column: the address of its plane 0, the stride of its planes in words
+//   xconsts  per constant of E: two words
+template <class E> struct ExtR2RapArgs {
+    const uint64_t *ops, *cells, *consts, *trans, *classes, *roots, *xcells, *xconsts;
+    uint64_t N;
+    uint32_t n_ops, log2_blowup, n_classes, n_slots, any_roots;
+    ExtR2Domain<E> dom;
+    ExtPlanes<E> out;
+};
+
+// the D LDS slots of a temporary that holds an element, as planes: element threadIdx.x is the lane's
+template <class E> __device__ __forceinline__ ExtPlanes<E> ext_r2_lds_planes(typename E::word *lds, uint32_t slot) {
+    ExtPlanes<E> v;
+#pragma unroll
+    for (int e = 0; e < E::D; e++) v.p[e] = lds + (size_t)(slot + e) * EXT_THREADS;
+    return v;
+}
+
+template <class E> __global__ __launch_bounds__(EXT_THREADS) void ext_r2_rap_transition_kernel(const ExtR2RapArgs<E> a) {
+    using word = typename E::word;
+    using elem = typename E::elem;
+    word *lds = (word *)ext_r2_lds;
+    const uint64_t i = (uint64_t)blockIdx.x * EXT_THREADS + threadIdx.x;
+    if (i >= a.N) return;
+    const word x = a.any_roots ? ext_r2_x<E>(a.dom, i) : E::F_ONE;
+#pragma unroll 1
+    for (uint32_t k = 0; k < a.n_classes; k++) {
+        const word *cycle = (const word *)ext_uniform(a.classes, 4 * k);
+        const uint64_t len = ext_uniform(a.classes, 4 * k + 1), meta = ext_uniform(a.classes, 4 * k + 2), root0 = ext_uniform(a.classes, 4 * k + 3);
+        word z = cycle[(meta & 1) ? (i & (len - 1)) : i % len];
+        const uint32_t n_roots = (uint32_t)(meta >> 32);
+#pragma unroll 1
+        for (uint32_t r = 0; r < n_roots; r++) z = E::fmul(z, E::fsub(x, (word)ext_uniform(a.roots, root0 + r)));
+        lds[(a.n_slots + k) * EXT_THREADS + threadIdx.x] = z;
+    }
+    elem sum = E::zero(), ea = E::zero();   // ea: the accumulator while it holds an element, acc: while it holds a word
+    word acc = 0;
+#pragma unroll 1
+    for (uint32_t pc = 0; pc < a.n_ops; pc++) {
+        const uint64_t o = ext_uniform(a.ops, pc);
+        const uint32_t op = (uint32_t)o & 0xfu, src = (uint32_t)(o >> 8) & 0xffu, index = (uint32_t)(o >> 16) & 0xffffu, row = (uint32_t)(o >> 32);
+        const bool acc_ext = o & AIR_TYPED_ACC_EXT, src_ext = o & AIR_TYPED_SRC_EXT;   // the host's: uniform
+        if (op <= LW_STARK_AIR_MUL && !src_ext) {
+            word s;
+            if (src == LW_STARK_AIR_CELL) {
+                const word *col = (const word *)ext_uniform(a.cells, 2 * index);
+                const uint64_t mask = ext_uniform(a.cells, 2 * index + 1);
+                s = E::fcanon(col[(i + ((uint64_t)row << a.log2_blowup)) & mask]);
+            } else if (src == LW_STARK_AIR_CONST) {
+                s = (word)ext_uniform(a.consts, index);
+            } else {
+                s = lds[index * EXT_THREADS + threadIdx.x];
+            }
+            if (!acc_ext) {   // F with F: as ext_r2_transition_kernel
+                if (op == LW_STARK_AIR_LOAD) acc = s;
+                else if (op == LW_STARK_AIR_ADD) acc = E::fadd(acc, s);
+                else if (op == LW_STARK_AIR_SUB) acc = E::fsub(acc, s);
+                else acc = E::fmul(acc, s);
+            } else if (op == LW_STARK_AIR_ADD) {
+                ea.c0 = E::fadd(ea.c0, s);
+            } else if (op == LW_STARK_AIR_SUB) {
+                ea.c0 = E::fsub(ea.c0, s);
+            } else {
+                ea = E::mul_base(ea, s);
+            }
+        } else if (op <= LW_STARK_AIR_MUL) {
+            elem se;
+            if (src == LW_STARK_AIR_XCELL) {
+                const word *col = (const word *)ext_uniform(a.xcells, 2 * index);
+                se = E::canon(E::load(ext_planes<E>(col, ext_uniform(a.xcells, 2 * index + 1)), (i + ((uint64_t)row << a.log2_blowup)) & (a.N - 1)));
+            } else if (src == LW_STARK_AIR_XCONST) {
+                se = ext_uniform_elem<E>(a.xconsts, 2 * index);
+            } else {
+                se = E::load(ext_r2_lds_planes<E>(lds, index), threadIdx.x);
+            }
+            if (op == LW_STARK_AIR_LOAD) {
+                ea = se;
+            } else if (acc_ext) {
+                if (op == LW_STARK_AIR_ADD) ea = E::add(ea, se);
+                else if (op == LW_STARK_AIR_SUB) ea = E::sub(ea, se);
+                else ea = E::mul(ea, se);
+            } else if (op == LW_STARK_AIR_ADD) {   // F with E: the word is the element (acc, 0, ...)
+                ea = se;
+                ea.c0 = E::fadd(acc, se.c0);
+            } else if (op == LW_STARK_AIR_SUB) {
+                ea = E::sub(E::zero(), se);
+                ea.c0 = E::fadd(ea.c0, acc);
+            } else {
+                ea = E::mul_base(se, acc);
+            }
+        } else if (op == LW_STARK_AIR_NEG) {
+            if (acc_ext) ea = E::sub(E::zero(), ea);
+            else acc = E::fsub(0, acc);
+        } else if (op == LW_STARK_AIR_STORE) {
+            if (acc_ext) E::store(ext_r2_lds_planes<E>(lds, index), threadIdx.x, ea);
+            else lds[index * EXT_THREADS + threadIdx.x] = acc;
+        } else {   // EMIT
+            const uint32_t cls = (uint32_t)ext_uniform(a.trans, 4 * index + 2);
+            const word z = lds[(a.n_slots + cls) * EXT_THREADS + threadIdx.x];
+            const elem beta = ext_uniform_elem<E>(a.trans, 4 * index);
+            if (acc_ext) sum = E::add(sum, E::mul(beta, E::mul_base(ea, z)));
+            else sum = E::add(sum, E::mul_base(beta, E::fmul(z, acc)));
+        }
+    }
+    E::store(a.out, i, sum);
+}
+
+// bnd: per constraint (in the order of the steps) the address of its column, 0 (AUX: the stride of an auxiliary column's
+// planes in words, 0 on a main column), gamma_k (two words)
 template <class E> struct ExtR2BoundaryArgs {
     const uint64_t *bnd;
     uint64_t N;
@@ -263,7 +393,7 @@ template <class E> struct ExtR2BoundaryArgs {
 // fewer.  Eight rows with few steps took Fp2's launch from 0.148 to 0.107 ms at 2^22 rows (E::finv is 127 products there) and
 // Fp4's from 0.052 to 0.082 ms (31 squarings, and a lane's eight 4-byte words are a quarter of a line): the extension says.  The way forward forms the denominators alone; the numerators of a step are formed on the way back, when the step's
 // inverses are due, so that only the denominators and their running products stay live across the inversion.
-template <class E, int R, int S> __global__ __launch_bounds__(EXT_THREADS) void ext_r2_boundary_kernel(const ExtR2BoundaryArgs<E> a) {
+template <class E, int R, int S, bool AUX = false> __global__ __launch_bounds__(EXT_THREADS) void ext_r2_boundary_kernel(const ExtR2BoundaryArgs<E> a) {
     using word = typename E::word;
     using elem = typename E::elem;
     const uint64_t row0 = ((uint64_t)blockIdx.x * EXT_THREADS + threadIdx.x) * R;
@@ -295,9 +425,17 @@ template <class E, int R, int S> __global__ __launch_bounds__(EXT_THREADS) void 
         for (uint32_t k = a.first[s]; k < a.first[s] + a.count[s]; k++) {
             const word *col = (const word *)ext_uniform(a.bnd, 4 * k) + row0;
             const elem gamma = ext_uniform_elem<E>(a.bnd, 4 * k + 2);
+            const uint64_t aux_stride = AUX ? ext_uniform(a.bnd, 4 * k + 1) : 0;
+            if (AUX && aux_stride) {
+                const ExtPlanes<E> aux = ext_planes<E>(col, aux_stride);
 #pragma unroll
-            for (int r = 0; r < R; r++)
-                if (row0 + r < a.N) t[r] = E::add(t[r], E::mul_base(gamma, E::fcanon(col[r])));   // N < R: the rows past the domain
+                for (int r = 0; r < R; r++)
+                    if (row0 + r < a.N) t[r] = E::add(t[r], E::mul(gamma, E::canon(E::load(aux, r))));
+            } else {
+#pragma unroll
+                for (int r = 0; r < R; r++)
+                    if (row0 + r < a.N) t[r] = E::add(t[r], E::mul_base(gamma, E::fcanon(col[r])));   // N < R: the rows past the domain
+            }
         }
 #pragma unroll
         for (int r = R - 1; r >= 0; r--) {
@@ -335,7 +473,18 @@ __global__ __launch_bounds__(EXT_THREADS) void ext_r2_lengths_kernel(const typen
     if (any) atomicMax(lens + j, (unsigned long long)(m + 1));
 }
 
-struct ExtR2Names { const char *xtable, *cycle, *transition, *boundary, *split, *lengths; };
+struct ExtR2Names { const char *xtable, *cycle, *transition, *boundary, *split, *lengths, *rap_transition; };
+
+// what the _rap_ entry points add to a call: the auxiliary columns, the constants of E and the typed program
+template <class E> struct ExtR2Rap {
+    const typename E::word *const *aux;
+    uint32_t n_aux;
+    size_t aux_stride;
+    const typename E::word *xconsts;
+    uint32_t n_xconsts;
+    std::vector<uint64_t> typed;   // the op words of air_program_check_rap
+    uint32_t n_slots;
+};
 
 // ---------------------------------------------------------------- host: the constraint evaluations
 static size_t ext_r2_round256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -346,7 +495,8 @@ template <class E, class B, class T>
 static int ext_r2_constraints_locked(Context &c, const ExtR2Names &names, const lw_stark_air_op_t *ops, uint32_t n_ops, const typename E::word *consts,
                                      uint32_t n_consts, const typename E::word *const *cols, const uint32_t *col_log2_len, uint32_t n_cols,
                                      uint32_t log2_trace, uint32_t log2_blowup, typename E::word h, uint64_t root, const B *bnd, uint32_t n_bnd, const T *tr,
-                                     uint32_t n_tr, uint32_t n_tmps, typename E::word *d_out, uint64_t out_stride, hipStream_t s) {
+                                     uint32_t n_tr, uint32_t n_tmps, typename E::word *d_out, uint64_t out_stride, hipStream_t s,
+                                     const ExtR2Rap<E> *rap = nullptr) {
     using word = typename E::word;
     const uint32_t log2_lde = log2_trace + log2_blowup;
     const uint64_t n = 1ull << log2_trace, N = 1ull << log2_lde;
@@ -370,8 +520,9 @@ static int ext_r2_constraints_locked(Context &c, const ExtR2Names &names, const 
     // workspace: [ops | cells | consts | trans | classes | roots | bnd] uploaded at once, then the cycle tables
     const size_t b_ops = ext_r2_round256((size_t)n_ops * 8), b_cells = ext_r2_round256((size_t)n_cols * 16), b_consts = ext_r2_round256((size_t)n_consts * 8),
                  b_trans = ext_r2_round256((size_t)n_tr * 32), b_classes = ext_r2_round256(classes.size() * 32), b_roots = ext_r2_round256(roots.size() * 8),
-                 b_bnd = ext_r2_round256((size_t)n_bnd * 32);
-    const size_t tables = b_ops + b_cells + b_consts + b_trans + b_classes + b_roots + b_bnd;
+                 b_bnd = ext_r2_round256((size_t)n_bnd * 32), b_xcells = rap ? ext_r2_round256((size_t)rap->n_aux * 16) : 0,
+                 b_xconsts = rap ? ext_r2_round256((size_t)rap->n_xconsts * 16) : 0;
+    const size_t o_bnd = b_ops + b_cells + b_consts + b_trans + b_classes + b_roots, tables = o_bnd + b_bnd + b_xcells + b_xconsts;
     const uint32_t hbits = (log2_lde + 1) / 2;
     const uint64_t nlo = 1ull << hbits, nhi = 1ull << (log2_lde - hbits);
     const size_t b_cycle = ext_r2_round256((size_t)ca.total * sizeof(word));
@@ -380,12 +531,13 @@ static int ext_r2_constraints_locked(Context &c, const ExtR2Names &names, const 
     ca.table = (word *)(d_tab + tables);
     word *d_x = (word *)(d_tab + tables + b_cycle);
     const ExtR2Domain<E> dom{d_x, d_x + nlo, hbits};
+    bool any_aux = false;   // a boundary constraint on an auxiliary column: the boundary kernel's AUX form
     if (tables) {
         int rc = deep_pin(c, tables);   // the caller's arrays are free on return
         if (rc) return rc;
         char *hp = (char *)c.deep_pin;
         memset(hp, 0, tables);
-        if (n_ops) memcpy(hp, ops, (size_t)n_ops * 8);
+        if (n_ops) memcpy(hp, rap ? (const void *)rap->typed.data() : (const void *)ops, (size_t)n_ops * 8);
         uint64_t *t = (uint64_t *)(hp + b_ops);
         for (uint32_t k = 0; k < n_cols; k++) {
             t[2 * k] = (uint64_t)(uintptr_t)cols[k];
@@ -408,10 +560,23 @@ static int ext_r2_constraints_locked(Context &c, const ExtR2Names &names, const 
         }
         t = (uint64_t *)(hp + b_ops + b_cells + b_consts + b_trans + b_classes);
         for (size_t k = 0; k < roots.size(); k++) t[k] = roots[k];
-        t = (uint64_t *)(hp + b_ops + b_cells + b_consts + b_trans + b_classes + b_roots);
+        t = (uint64_t *)(hp + o_bnd);
         for (uint32_t q = 0; q < n_bnd; q++) {
-            t[4 * q] = (uint64_t)(uintptr_t)cols[bnd[order[q]].col];
-            ext_r2_pack<E>(ext_elem_of<E>(bnd[order[q]].coeff, 0), t + 4 * q + 2);
+            const B &b = bnd[order[q]];
+            const bool on_aux = ext_r2_is_aux(b, 0);
+            any_aux = any_aux || on_aux;
+            t[4 * q] = (uint64_t)(uintptr_t)(on_aux ? rap->aux[b.col] : cols[b.col]);
+            t[4 * q + 1] = on_aux ? rap->aux_stride : 0;
+            ext_r2_pack<E>(ext_elem_of<E>(b.coeff, 0), t + 4 * q + 2);
+        }
+        if (rap) {
+            t = (uint64_t *)(hp + o_bnd + b_bnd);
+            for (uint32_t k = 0; k < rap->n_aux; k++) {
+                t[2 * k] = (uint64_t)(uintptr_t)rap->aux[k];
+                t[2 * k + 1] = rap->aux_stride;
+            }
+            t = (uint64_t *)(hp + o_bnd + b_bnd + b_xcells);
+            for (uint32_t k = 0; k < rap->n_xconsts; k++) ext_r2_pack<E>(ext_elem_of<E>(rap->xconsts, k), t + 2 * k);
         }
         LW_HIP_CHECK(hipMemcpyAsync(d_tab, hp, tables, hipMemcpyHostToDevice, s), LW_ERR_LAUNCH);
         LW_HIP_CHECK(hipEventRecord(c.deep_pin_read, s), LW_ERR_LAUNCH);
@@ -427,33 +592,59 @@ static int ext_r2_constraints_locked(Context &c, const ExtR2Names &names, const 
         ca.w = w;
         rc = launch_1d(c, names.cycle, ext_r2_cycle_kernel<E>, blocks_for((ca.total + EXT_ROWS - 1) / EXT_ROWS), s, ca);
         if (rc) return rc;
-        ExtR2Args<E> a;
-        memset(&a, 0, sizeof(a));
-        a.ops = (const uint64_t *)d_tab;
-        a.cells = (const uint64_t *)(d_tab + b_ops);
-        a.consts = (const uint64_t *)(d_tab + b_ops + b_cells);
-        a.trans = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts);
-        a.classes = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts + b_trans);
-        a.roots = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts + b_trans + b_classes);
-        a.N = N;
-        a.n_ops = n_ops;
-        a.log2_blowup = log2_blowup;
-        a.n_classes = ca.n_classes;
-        a.n_tmps = n_tmps;
-        a.any_roots = !roots.empty();
-        a.dom = dom;
-        a.out = ext_planes<E>(d_out, out_stride);
-        const size_t lds = (size_t)(n_tmps + a.n_classes) * sizeof(word) * EXT_THREADS;   // 16 slots, 32 KiB, at most
-        hipEvent_t pe = c.prof_begin(s);
-        hipLaunchKernelGGL(ext_r2_transition_kernel<E>, dim3(blocks_for(N)), dim3(EXT_THREADS), lds, s, a);
-        c.prof_end(names.transition, pe, s);
-        LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
+        if (rap) {
+            ExtR2RapArgs<E> ra;
+            memset(&ra, 0, sizeof(ra));
+            ra.ops = (const uint64_t *)d_tab;
+            ra.cells = (const uint64_t *)(d_tab + b_ops);
+            ra.consts = (const uint64_t *)(d_tab + b_ops + b_cells);
+            ra.trans = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts);
+            ra.classes = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts + b_trans);
+            ra.roots = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts + b_trans + b_classes);
+            ra.xcells = (const uint64_t *)(d_tab + o_bnd + b_bnd);
+            ra.xconsts = (const uint64_t *)(d_tab + o_bnd + b_bnd + b_xcells);
+            ra.N = N;
+            ra.n_ops = n_ops;
+            ra.log2_blowup = log2_blowup;
+            ra.n_classes = ca.n_classes;
+            ra.n_slots = rap->n_slots;
+            ra.any_roots = !roots.empty();
+            ra.dom = dom;
+            ra.out = ext_planes<E>(d_out, out_stride);
+            const size_t lds = (size_t)(rap->n_slots + ra.n_classes) * sizeof(word) * EXT_THREADS;   // 8 D + 8 slots at most: 48 KiB (Fp2), 40 KiB (Fp4)
+            hipEvent_t pe = c.prof_begin(s);
+            hipLaunchKernelGGL(ext_r2_rap_transition_kernel<E>, dim3(blocks_for(N)), dim3(EXT_THREADS), lds, s, ra);
+            c.prof_end(names.rap_transition, pe, s);
+            LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
+        } else {
+            ExtR2Args<E> a;
+            memset(&a, 0, sizeof(a));
+            a.ops = (const uint64_t *)d_tab;
+            a.cells = (const uint64_t *)(d_tab + b_ops);
+            a.consts = (const uint64_t *)(d_tab + b_ops + b_cells);
+            a.trans = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts);
+            a.classes = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts + b_trans);
+            a.roots = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts + b_trans + b_classes);
+            a.N = N;
+            a.n_ops = n_ops;
+            a.log2_blowup = log2_blowup;
+            a.n_classes = ca.n_classes;
+            a.n_tmps = n_tmps;
+            a.any_roots = !roots.empty();
+            a.dom = dom;
+            a.out = ext_planes<E>(d_out, out_stride);
+            const size_t lds = (size_t)(n_tmps + a.n_classes) * sizeof(word) * EXT_THREADS;   // 16 slots, 32 KiB, at most
+            hipEvent_t pe = c.prof_begin(s);
+            hipLaunchKernelGGL(ext_r2_transition_kernel<E>, dim3(blocks_for(N)), dim3(EXT_THREADS), lds, s, a);
+            c.prof_end(names.transition, pe, s);
+            LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
+        }
     } else if (n_bnd == 0) {
         for (int e = 0; e < E::D; e++) LW_HIP_CHECK(hipMemsetAsync(d_out + e * out_stride, 0, N * sizeof(word), s), LW_ERR_LAUNCH);
     }
     ExtR2BoundaryArgs<E> b;
     memset(&b, 0, sizeof(b));
-    b.bnd = (const uint64_t *)(d_tab + tables - b_bnd);
+    b.bnd = (const uint64_t *)(d_tab + o_bnd);
     b.N = N;
     b.dom = dom;
     b.w = w;
@@ -471,6 +662,11 @@ static int ext_r2_constraints_locked(Context &c, const ExtR2Names &names, const 
                                                : S == 2 ? ext_r2_boundary_kernel<E, E::R2_ROWS_FEW, 2>
                                                : S == 3 ? ext_r2_boundary_kernel<E, EXT_ROWS, 3>
                                                         : ext_r2_boundary_kernel<E, EXT_ROWS, 4>;
+        if (any_aux)
+            kernel = S == 1   ? ext_r2_boundary_kernel<E, E::R2_ROWS_FEW, 1, true>
+                     : S == 2 ? ext_r2_boundary_kernel<E, E::R2_ROWS_FEW, 2, true>
+                     : S == 3 ? ext_r2_boundary_kernel<E, EXT_ROWS, 3, true>
+                              : ext_r2_boundary_kernel<E, EXT_ROWS, 4, true>;
         const uint64_t rows = S <= 2 ? E::R2_ROWS_FEW : EXT_ROWS;
         rc = launch_1d(c, names.boundary, kernel, blocks_for((N + rows - 1) / rows), s, b);
         if (rc) return rc;
@@ -478,35 +674,52 @@ static int ext_r2_constraints_locked(Context &c, const ExtR2Names &names, const 
     return LW_OK;
 }
 
-// The body of the entry point.  The order of the checks: the domain, null tables, the program, the words of the constants,
-// the boundary entries, the transition entries and their classes, the device buffers, the root and the offset, h^N = 1.
+// The body of the entry points.  The order of the checks: the domain, null tables, the program, the words of the constants
+// (then of the constants of E), the boundary entries, the transition entries and their classes, the device buffers (out, the
+// columns, then the auxiliary stride and columns), the root and the offset, h^N = 1.  rap: the _rap_ entry points' additions
+// (aux, n_aux, aux_stride, xconsts, n_xconsts; typed and n_slots are filled here), nullptr for the plain ones.
 template <class E, class B, class T>
 static int ext_r2_constraint_evaluations(const ExtR2Names &names, const lw_stark_air_op_t *ops, uint32_t n_ops, const typename E::word *consts, uint32_t n_consts,
                                          const typename E::word *const *d_columns, const uint32_t *col_log2_len_or_null, uint32_t n_cols, uint32_t log2_trace,
                                          uint32_t log2_blowup, const typename E::word *offset_or_null, uint64_t two_adic_root, const B *boundary,
                                          uint32_t n_boundary, const T *transitions, uint32_t n_transitions, typename E::word *d_out, size_t out_stride,
-                                         void *hip_stream) {
+                                         void *hip_stream, ExtR2Rap<E> *rap = nullptr) {
     typedef unsigned __int128 u128;
     const uint64_t lg = (uint64_t)log2_trace + log2_blowup;
     if (lg > 63 || E::size_check((uint32_t)lg)) { set_error("an LDE domain of 2^%llu points is beyond the transform", (unsigned long long)lg); return LW_ERR_BAD_ARG; }
     const uint64_t n = 1ull << log2_trace, N = 1ull << lg;
-    if ((n_consts && n_consts <= LW_STARK_AIR_MAX_CONSTS && !consts) || (n_boundary && !boundary) || (n_transitions && !transitions) || (n_cols && !d_columns)) {
+    if ((n_consts && n_consts <= LW_STARK_AIR_MAX_CONSTS && !consts) || (n_boundary && !boundary) || (n_transitions && !transitions) || (n_cols && !d_columns) ||
+        (rap && ((rap->n_xconsts && rap->n_xconsts <= LW_STARK_AIR_MAX_CONSTS && !rap->xconsts) || (rap->n_aux && !rap->aux)))) {
         set_error("null table");
         return LW_ERR_BAD_ARG;
     }
     AirProgramInfo info;
     char msg[192];
-    if (!air_program_check(ops, n_ops, n_consts, col_log2_len_or_null, n_cols, log2_trace, (uint32_t)lg, n_transitions, &info, msg, sizeof(msg))) {
+    bool well_formed;
+    if (rap) {
+        rap->typed.assign(n_ops <= LW_STARK_AIR_MAX_OPS && ops ? n_ops : 0, 0);
+        well_formed = air_program_check_rap(ops, n_ops, n_consts, rap->n_xconsts, col_log2_len_or_null, n_cols, rap->n_aux, E::D, log2_trace, (uint32_t)lg,
+                                            n_transitions, rap->typed.empty() ? nullptr : rap->typed.data(), &info, msg, sizeof(msg));
+        rap->n_slots = info.n_lds_slots;
+    } else {
+        well_formed = air_program_check(ops, n_ops, n_consts, col_log2_len_or_null, n_cols, log2_trace, (uint32_t)lg, n_transitions, &info, msg, sizeof(msg));
+    }
+    if (!well_formed) {
         set_error("AIR program: %s", msg);
         return LW_ERR_BAD_ARG;
     }
     int rc = E::words_check(consts, n_consts, "constants");
+    if (!rc && rap) rc = E::words_check(rap->xconsts, (size_t)rap->n_xconsts * E::D, "extension constants");
     if (rc) return rc;
     for (uint32_t k = 0; k < n_boundary; k++) {
         const B &b = boundary[k];
-        if (b.col >= n_cols) { set_error("boundary constraint %u: column %u of %u", k, b.col, n_cols); return LW_ERR_BAD_ARG; }
-        if (col_log2_len_or_null && col_log2_len_or_null[b.col] != lg) { set_error("boundary constraint %u: column %u is a short one", k, b.col); return LW_ERR_BAD_ARG; }
-        if ((rc = E::words_check(&b.value, 1, "boundary value")) || (rc = E::words_check(b.coeff, E::D, "boundary coefficient"))) return rc;
+        if (ext_r2_is_aux(b, 0)) {
+            if (b.col >= rap->n_aux) { set_error("boundary constraint %u: auxiliary column %u of %u", k, b.col, rap->n_aux); return LW_ERR_BAD_ARG; }
+        } else {
+            if (b.col >= n_cols) { set_error("boundary constraint %u: column %u of %u", k, b.col, n_cols); return LW_ERR_BAD_ARG; }
+            if (col_log2_len_or_null && col_log2_len_or_null[b.col] != lg) { set_error("boundary constraint %u: column %u is a short one", k, b.col); return LW_ERR_BAD_ARG; }
+        }
+        if ((rc = ext_r2_value_check<E>(b.value)) || (rc = E::words_check(b.coeff, E::D, "boundary coefficient"))) return rc;
     }
     for (uint32_t k = 0; k < n_transitions; k++) {
         const T &t = transitions[k];
@@ -531,6 +744,16 @@ static int ext_r2_constraint_evaluations(const ExtR2Names &names, const lw_stark
             return LW_ERR_BAD_ARG;
         }
     }
+    if (rap) {
+        if ((rc = ext_stride(rap->aux_stride, N, "auxiliary columns"))) return rc;
+        for (uint32_t k = 0; k < rap->n_aux; k++) {
+            if (!rap->aux[k] || !aligned16(rap->aux[k])) { set_error("auxiliary column %u: null or misaligned buffer", k); return LW_ERR_BAD_ARG; }
+            if (ext_overlap<E>(rap->aux[k], ext_span<E>(rap->aux_stride, N), d_out, ext_span<E>(out_stride, N))) {
+                set_error("out overlaps auxiliary column %u", k);
+                return LW_ERR_BAD_ARG;
+            }
+        }
+    }
     typename E::word h;
     rc = E::root_check(two_adic_root);
     if (!rc) rc = E::offset(offset_or_null, h);
@@ -551,7 +774,7 @@ static int ext_r2_constraint_evaluations(const ExtR2Names &names, const lw_stark
     Entry en(hip_stream);
     if (en.rc) return en.rc;
     return ext_r2_constraints_locked<E>(en.c, names, ops, n_ops, consts, n_consts, d_columns, col_log2_len_or_null, n_cols, log2_trace, log2_blowup, h, two_adic_root,
-                                        boundary, n_boundary, transitions, n_transitions, info.n_tmps, d_out, out_stride, en.stream);
+                                        boundary, n_boundary, transitions, n_transitions, info.n_tmps, d_out, out_stride, en.stream, rap);
 }
 
 // ---------------------------------------------------------------- host: the parts

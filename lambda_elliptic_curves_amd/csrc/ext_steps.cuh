@@ -60,7 +60,7 @@ enum { EXT_MUL = LW_GL2_MUL, EXT_SQR = LW_GL2_SQR, EXT_INV = LW_GL2_INV, EXT_MUL
 
 // a vector on its way into a kernel: one pointer per plane, formed on the host
 template <class E> struct ExtPlanes { typename E::word *p[E::D]; };
-template <class E> static ExtPlanes<E> ext_planes(const typename E::word *p, size_t stride) {
+template <class E> static __host__ __device__ ExtPlanes<E> ext_planes(const typename E::word *p, size_t stride) {
     ExtPlanes<E> v;
     for (int e = 0; e < E::D; e++) v.p[e] = const_cast<typename E::word *>(p) + e * stride;
     return v;

@@ -13,6 +13,7 @@
 #include "goldilocks_ext.cuh"
 #include "ext_steps.cuh"
 #include "ext_round2.cuh"
+#include "ext_aux.cuh"
 
 namespace lw {
 
@@ -142,7 +143,8 @@ int lw_goldilocks_ext2_fri_layer_device(const uint64_t *d_coeffs, size_t coeff_s
                                  });
 }
 
-static constexpr ExtR2Names GL2_R2_NAMES{"gl2_r2_xtable_kernel", "gl2_r2_cycle_kernel", "gl2_r2_transition_kernel", "gl2_r2_boundary_kernel", "gl2_r2_split_kernel", "gl2_r2_lengths_kernel"};
+static constexpr ExtR2Names GL2_R2_NAMES{"gl2_r2_xtable_kernel", "gl2_r2_cycle_kernel", "gl2_r2_transition_kernel", "gl2_r2_boundary_kernel", "gl2_r2_split_kernel", "gl2_r2_lengths_kernel", "gl2_r2_rap_transition_kernel"};
+static constexpr ExtAuxNames GL2_AUX_NAMES{"gl2_aux_reduce_kernel", "gl2_aux_carry_kernel", "gl2_aux_rescan_kernel"};
 
 int lw_goldilocks_ext2_constraint_evaluations_device(const lw_stark_air_op_t *ops, uint32_t n_ops, const uint64_t *consts, uint32_t n_consts,
                                                      const uint64_t *const *d_columns, const uint32_t *col_log2_len_or_null, uint32_t n_cols,
@@ -165,6 +167,24 @@ int lw_goldilocks_ext2_composition_parts_device(const uint64_t *d_evals, size_t 
         [](Context &c, const uint64_t *d_coeffs, uint32_t lgL, uint64_t *d_lde, uint32_t lg, uint32_t batch, uint64_t h, uint64_t root, hipStream_t s) {
             return goldilocks_lde_locked(c, d_coeffs, lgL, (uint64_t)1 << lgL, d_lde, lg, (uint64_t)1 << lg, batch, h, root, s);
         });
+}
+
+int lw_goldilocks_ext2_aux_fractions_device(const uint64_t *const *d_columns, uint32_t n_cols, size_t n, const uint64_t *num_const, const uint32_t *num_cols,
+        const uint64_t *num_coeffs, uint32_t n_num, const uint64_t *den_const, const uint32_t *den_cols, const uint64_t *den_coeffs, uint32_t n_den,
+        uint32_t mode, uint64_t *d_out, size_t out_stride, uint64_t *d_total_or_null, uint64_t *out_zero_denominators_or_null, void *hip_stream) {
+    return ext_aux_fractions<Gl2Ext>(GL2_AUX_NAMES, d_columns, n_cols, n, ExtAuxList<Gl2Ext>{num_const, num_cols, num_coeffs, n_num},
+                                    ExtAuxList<Gl2Ext>{den_const, den_cols, den_coeffs, n_den}, mode, d_out, out_stride, d_total_or_null,
+                                    out_zero_denominators_or_null, hip_stream);
+}
+
+int lw_goldilocks_ext2_rap_constraint_evaluations_device(const lw_stark_air_op_t *ops, uint32_t n_ops, const uint64_t *consts, uint32_t n_consts, const uint64_t *xconsts,
+        uint32_t n_xconsts, const uint64_t *const *d_columns, const uint32_t *col_log2_len_or_null, uint32_t n_cols, const uint64_t *const *d_aux_columns,
+        uint32_t n_aux, size_t aux_stride, uint32_t log2_trace, uint32_t log2_blowup, const uint64_t *offset_or_null, uint64_t two_adic_root,
+        const lw_gl2_rap_boundary_t *boundary, uint32_t n_boundary, const lw_gl2_transition_t *transitions, uint32_t n_transitions, uint64_t *d_out, size_t out_stride,
+        void *hip_stream) {
+    ExtR2Rap<Gl2Ext> rap{d_aux_columns, n_aux, aux_stride, xconsts, n_xconsts, {}, 0};
+    return ext_r2_constraint_evaluations<Gl2Ext>(GL2_R2_NAMES, ops, n_ops, consts, n_consts, d_columns, col_log2_len_or_null, n_cols, log2_trace, log2_blowup,
+                                                offset_or_null, two_adic_root, boundary, n_boundary, transitions, n_transitions, d_out, out_stride, hip_stream, &rap);
 }
 
 }  // extern "C"

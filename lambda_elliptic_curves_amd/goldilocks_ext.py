@@ -162,3 +162,72 @@ def round2_device(program, consts, t_columns, log2_trace, log2_blowup, boundary,
     t_nodes = torch.empty((2 * (1 << log2_lde) - 1) * digest_words(level), dtype=torch.int64, device=t_ev.device)
     commit_root = rpo.commit_columns_device(level, t_lde, 2 * int(n_parts), log2_lde, t_nodes, stream=stream)
     return t_coeffs, lens, t_lde, t_nodes, commit_root
+
+
+# ---- RAP: the auxiliary column of round 1 and the round 2 that reads it
+PRODUCT, SUM = L.EXT_AUX_PRODUCT, L.EXT_AUX_SUM
+
+
+def _rap_interpolate(t_in, t_out, log2n, batch, root, stream):
+    from . import goldilocks
+    goldilocks.ntt_device(t_in, t_out, log2n, inverse=True, batch=batch, root=root, stream=stream)
+
+
+def _rap_lde(t_coeffs, log2_coeffs, t_out, log2n, batch, offset, root, stream):
+    from . import goldilocks
+    goldilocks.lde_device(t_coeffs, log2_coeffs, t_out, log2n, batch=batch, offset=offset, root=root, stream=stream)
+
+
+def _rap_commit(level):
+    def commit(t_lde, n_cols, log2n, stream):
+        import torch
+        from . import rpo
+        t_nodes = torch.empty((2 * (1 << log2n) - 1) * digest_words(level), dtype=torch.int64, device=t_lde.device)
+        return t_nodes, rpo.commit_columns_device(level, t_lde, n_cols, log2n, t_nodes, stream=stream)
+    return commit
+
+
+def _rap(level=RPO_128):
+    return X.RapSpec(_R2, L.Gl2RapBoundary, "lw_goldilocks_ext2_rap_constraint_evaluations_device", "lw_goldilocks_ext2_aux_fractions_device",
+                     _rap_interpolate, _rap_lde, _rap_commit(level))
+
+
+def aux_fractions_device(t_columns, n, num, den, mode=PRODUCT, exclusive=False, t_out=None, out_stride=0, total=False, count_zeros=False, stream=None):
+    """The auxiliary column of a randomized AIR: with f_i = (a_0 + sum_j a_j col_{s_j}[i]) / (b_0 + sum_j b_j col_{t_j}[i]) over
+    the n rows of the base columns t_columns, the running product (PRODUCT) or sum (SUM) of the f_i, inclusive (out[i] takes
+    f_i in) or exclusive (out[0] = 1 or 0).  num = (a_0, [(s_j, a_j), ...]) and den likewise, the scalars in Fp2, at most 16
+    terms each.  -> (t_out: two planes of n words out_stride apart, t_total: the product or sum over all rows as two words on
+    the device, or None).  With count_zeros the call waits and raises errors.FieldError (.zero_denominators: how many) if a denominator is zero; without it
+    the call only enqueues and the output of such rows is unspecified."""
+    return X.aux_fractions(_rap(), t_columns, n, num, den, mode, exclusive, t_out, out_stride, total, count_zeros, stream)
+
+
+def rap_constraint_evaluations_device(program, consts, xconsts, t_columns, t_aux_columns, log2_trace, log2_blowup, boundary, transitions, t_out=None,
+                                      out_stride=0, aux_stride=0, offset=None, root=0, col_log2_len=None, stream=None):
+    """constraint_evaluations_device for a randomized AIR: the program may read auxiliary columns (stark.xcell) and constants
+    of Fp2 (stark.xconst).  xconsts: [(c0, c1)]; t_aux_columns: a list of resident Fp2 columns, two planes of N words
+    aux_stride apart each; boundary: [(col, step, value, (c0, c1))] or [(col, step, value, (c0, c1), is_aux)] with value a
+    word or a pair.  Enqueues and returns t_out."""
+    return X.rap_constraint_evaluations(_rap(), program, consts, xconsts, t_columns, t_aux_columns, log2_trace, log2_blowup, boundary, transitions, t_out,
+                                        out_stride, aux_stride, offset, root, col_log2_len, stream)
+
+
+def round1_aux_device(t_columns, log2_trace, log2_blowup, num, den, mode=PRODUCT, exclusive=False, offset=None, root=0, level=RPO_128, count_zeros=False,
+                      stream=None):
+    """The second half of round 1 on resident trace columns of 2^log2_trace words: the auxiliary column (aux_fractions_device),
+    the interpolation of its two planes, their LDE (goldilocks.lde_device with batch = 2) and the RPO column commitment over
+    them.  count_zeros: wait for the column and raise errors.FieldError (with .zero_denominators) if a denominator is zero.
+    -> (t_aux, t_total, t_polys, t_lde, t_nodes, root)"""
+    return X.round1_aux(_rap(level), t_columns, log2_trace, log2_blowup, num, den, mode, exclusive, offset, root, count_zeros, stream)
+
+
+def round2_rap_device(program, consts, xconsts, t_columns, t_aux_columns, log2_trace, log2_blowup, boundary, transitions, n_parts, offset=None, root=0,
+                      col_log2_len=None, level=RPO_128, stream=None):
+    """round2_device with rap_constraint_evaluations_device in the place of constraint_evaluations_device.
+    -> (t_parts_coeffs, part_lens, t_parts_lde, t_nodes, root)"""
+    log2_lde = int(log2_trace) + int(log2_blowup)
+    t_ev = rap_constraint_evaluations_device(program, consts, xconsts, t_columns, t_aux_columns, log2_trace, log2_blowup, boundary, transitions,
+                                             offset=offset, root=root, col_log2_len=col_log2_len, stream=stream)
+    t_coeffs, lens, t_lde = composition_parts_device(t_ev, log2_lde, n_parts, offset=offset, root=root, stream=stream)
+    t_nodes, commit_root = _rap_commit(level)(t_lde, 2 * int(n_parts), log2_lde, stream)
+    return t_coeffs, lens, t_lde, t_nodes, commit_root

@@ -304,7 +304,7 @@ class Expr:
 
     @property
     def is_leaf(self):
-        return self.kind in ("cell", "const")
+        return self.kind in ("cell", "const", "xcell", "xconst")
 
 
 def cell(col, row=0):
@@ -325,12 +325,32 @@ def const(k):
     return Expr("const", k)
 
 
+def xcell(col, row=0):
+    """auxiliary column `col` of the frame at trace-row offset `row`, an element of the extension: the _rap_ entry points of
+    goldilocks_ext and babybear_ext only"""
+    col, row = int(col), int(row)
+    if not (0 <= col < 1 << 16 and 0 <= row < 1 << 32):
+        from .errors import InputError
+        raise InputError(f"xcell({col}, {row})")
+    return Expr("xcell", col, row)
+
+
+def xconst(k):
+    """xconsts[k] of the call, an element of the extension: a challenge of a randomized AIR"""
+    k = int(k)
+    if not 0 <= k < L.AIR_MAX_CONSTS:
+        from .errors import InputError
+        raise InputError(f"xconst({k}): a program has at most {L.AIR_MAX_CONSTS} extension constants")
+    return Expr("xconst", k)
+
+
 AIR_OP_DTYPE = np.dtype([("op", "u1"), ("src", "u1"), ("index", "<u2"), ("row", "<u4")])   # lw_stark_air_op_t
 
 
 class AirProgram:
     """ops: (n_ops,) AIR_OP_DTYPE; n_transitions constraints; n_tmps temporaries used; n_consts and n_cols: one more than
-    the highest constant and column the program reads; n_mul: its MUL count."""
+    the highest constant and column the program reads, n_xconsts and n_xcols the same of the extension's constants and the
+    auxiliary columns; n_mul: its MUL count."""
 
     def __init__(self, ops, n_transitions):
         self.ops = np.ascontiguousarray(ops, dtype=AIR_OP_DTYPE).reshape(-1)
@@ -341,6 +361,8 @@ class AirProgram:
         self.n_tmps = top(op == L.AIR_STORE)
         self.n_consts = top(reads & (src == L.AIR_CONST))
         self.n_cols = top(reads & (src == L.AIR_CELL))
+        self.n_xconsts = top(reads & (src == L.AIR_XCONST))
+        self.n_xcols = top(reads & (src == L.AIR_XCELL))
         self.n_mul = int((op == L.AIR_MUL).sum())
 
     def __len__(self):
@@ -391,6 +413,10 @@ def compile_transitions(exprs):
             return (L.AIR_CELL, e.a, e.b)
         if e.kind == "const":
             return (L.AIR_CONST, e.a, 0)
+        if e.kind == "xcell":
+            return (L.AIR_XCELL, e.a, e.b)
+        if e.kind == "xconst":
+            return (L.AIR_XCONST, e.a, 0)
         if id(e) in kept:
             return (L.AIR_TMP, kept[id(e)], 0)
         return None

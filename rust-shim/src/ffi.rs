@@ -440,6 +440,33 @@ extern "C" {
                                                      offset_or_null: *const u32, n_parts: u32, d_parts_coeffs: *mut u32,
                                                      d_parts_lde_or_null: *mut u32, out_part_lens_or_null: *mut usize,
                                                      hip_stream: *mut c_void) -> c_int;
+    // ---- RAP over Fp2 and Fp4: the auxiliary column (running product or sum of fractions) and the round 2 that reads it
+    pub fn lw_goldilocks_ext2_aux_fractions_device(d_columns: *const *const u64, n_cols: u32, n: usize, num_const: *const u64,
+                                                   num_cols: *const u32, num_coeffs: *const u64, n_num: u32, den_const: *const u64,
+                                                   den_cols: *const u32, den_coeffs: *const u64, n_den: u32, mode: u32, d_out: *mut u64,
+                                                   out_stride: usize, d_total_or_null: *mut u64,
+                                                   out_zero_denominators_or_null: *mut u64, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_babybear_ext4_aux_fractions_device(d_columns: *const *const u32, n_cols: u32, n: usize, num_const: *const u32,
+                                                 num_cols: *const u32, num_coeffs: *const u32, n_num: u32, den_const: *const u32,
+                                                 den_cols: *const u32, den_coeffs: *const u32, n_den: u32, mode: u32, d_out: *mut u32,
+                                                 out_stride: usize, d_total_or_null: *mut u32,
+                                                 out_zero_denominators_or_null: *mut u64, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_goldilocks_ext2_rap_constraint_evaluations_device(ops: *const lw_stark_air_op_t, n_ops: u32, consts: *const u64, n_consts: u32,
+                                                                xconsts: *const u64, n_xconsts: u32, d_columns: *const *const u64,
+                                                                col_log2_len_or_null: *const u32, n_cols: u32,
+                                                                d_aux_columns: *const *const u64, n_aux: u32, aux_stride: usize,
+                                                                log2_trace: u32, log2_blowup: u32, offset_or_null: *const u64,
+                                                                two_adic_root: u64, boundary: *const lw_gl2_rap_boundary_t, n_boundary: u32,
+                                                                transitions: *const lw_gl2_transition_t, n_transitions: u32,
+                                                                d_out: *mut u64, out_stride: usize, hip_stream: *mut c_void) -> c_int;
+    pub fn lw_babybear_ext4_rap_constraint_evaluations_device(ops: *const lw_stark_air_op_t, n_ops: u32, consts: *const u32, n_consts: u32,
+                                                              xconsts: *const u32, n_xconsts: u32, d_columns: *const *const u32,
+                                                              col_log2_len_or_null: *const u32, n_cols: u32,
+                                                              d_aux_columns: *const *const u32, n_aux: u32, aux_stride: usize,
+                                                              log2_trace: u32, log2_blowup: u32, offset_or_null: *const u32,
+                                                              boundary: *const lw_bb4_rap_boundary_t, n_boundary: u32,
+                                                              transitions: *const lw_bb4_transition_t, n_transitions: u32,
+                                                              d_out: *mut u32, out_stride: usize, hip_stream: *mut c_void) -> c_int;
     // ---- Monolith over Mersenne31: batched permutations (width 8 .. 24, rounds 1 .. 15); hash, compression and Merkle tree over width 16
     pub fn lw_monolith_permute(width: u32, rounds: u32, states: *const u32, n: usize, out: *mut u32) -> c_int;
     pub fn lw_monolith_permute_device(width: u32, rounds: u32, d_states: *const u32, n: usize, d_out: *mut u32,
@@ -572,6 +599,30 @@ pub struct lw_bb4_boundary_t {
     pub reserved2: u32,
 }
 
+/// lw_gl2_rap_boundary_t: one boundary constraint of lw_goldilocks_ext2_rap_constraint_evaluations_device, its value in Fp2
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct lw_gl2_rap_boundary_t {
+    pub col: u32,
+    /// not 0: col indexes the auxiliary columns
+    pub is_aux: u32,
+    pub step: u64,
+    pub value: [u64; 2],
+    pub coeff: [u64; 2],
+}
+
+/// lw_bb4_rap_boundary_t: one boundary constraint of lw_babybear_ext4_rap_constraint_evaluations_device, its value in Fp4
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct lw_bb4_rap_boundary_t {
+    pub col: u32,
+    /// not 0: col indexes the auxiliary columns
+    pub is_aux: u32,
+    pub step: u64,
+    pub value: [u32; 4],
+    pub coeff: [u32; 4],
+}
+
 /// lw_bb4_transition_t: the zerofier parameters and the Fp4 coefficient of one transition constraint
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
@@ -634,6 +685,14 @@ pub const LW_STARK_AIR_EMIT: u8 = 6;
 pub const LW_STARK_AIR_CELL: u8 = 0;
 pub const LW_STARK_AIR_CONST: u8 = 1;
 pub const LW_STARK_AIR_TMP: u8 = 2;
+/// the _rap_ entry points only: an auxiliary column, a constant of the extension
+pub const LW_STARK_AIR_XCELL: u8 = 3;
+pub const LW_STARK_AIR_XCONST: u8 = 4;
+/// lw_ext_aux_mode_t
+pub const LW_EXT_AUX_PRODUCT: u32 = 0;
+pub const LW_EXT_AUX_SUM: u32 = 1;
+pub const LW_EXT_AUX_EXCLUSIVE: u32 = 2;
+pub const LW_EXT_AUX_MAX_TERMS: u32 = 16;
 pub const LW_STARK_AIR_MAX_OPS: u32 = 4096;
 pub const LW_STARK_AIR_MAX_TMPS: u32 = 8;
 pub const LW_STARK_AIR_MAX_CONSTS: u32 = 256;
@@ -717,6 +776,7 @@ const _: () = assert!(core::mem::size_of::<lw_stark_tree_t>() == 56);
 const _: () = assert!(core::mem::size_of::<lw_stark_boundary_t>() == 80);
 const _: () = assert!(core::mem::size_of::<lw_gl2_boundary_t>() == 40 && core::mem::size_of::<lw_gl2_transition_t>() == 56);
 const _: () = assert!(core::mem::size_of::<lw_bb4_boundary_t>() == 40 && core::mem::size_of::<lw_bb4_transition_t>() == 56);
+const _: () = assert!(core::mem::size_of::<lw_gl2_rap_boundary_t>() == 48 && core::mem::size_of::<lw_bb4_rap_boundary_t>() == 48);
 const _: () = assert!(core::mem::size_of::<lw_m31q_boundary_t>() == 40 && core::mem::size_of::<lw_m31q_transition_t>() == 40);
 const _: () = assert!(core::mem::size_of::<lw_stark_transition_t>() == 72);
 const _: () = assert!(core::mem::size_of::<lw_stark_air_op_t>() == 8);
