@@ -523,6 +523,8 @@ int lw_stark_deep_composition_device(lw_field_t field, const void *const *d_poly
  * The result is the SMALLEST valid nonce in [first, last], which is what the reference's build without `parallel` returns
  * for [0, u64::MAX) (its rayon build returns any valid nonce).  *out_found = 1 and *out_nonce set, or *out_found = 0 and
  * *out_nonce untouched when the range holds none.  seed32 and the outputs are host memory in both forms.
+ * 2^64 - 1 is never a candidate, as in the reference, whose loop is 0..u64::MAX: last = 2^64 - 1 is accepted and means
+ * 2^64 - 2, and the range [2^64 - 1, 2^64 - 1] holds none.
  * grinding_factor outside 1 .. 63 (the reference's 1 << (64 - g) is undefined there; 0 means "no grinding", which is the
  * caller's decision), a null pointer, first > last: LW_ERR_BAD_ARG, before any device work.
  * The range is searched in ascending windows of lw_stark_grinding_window(grinding_factor) candidates, one bounded kernel

@@ -72,6 +72,15 @@ static int grind_check(const uint8_t *seed32, uint32_t grinding_factor, uint64_t
 // [first, last] in ascending windows, one launch each; the first window with a hit holds the smallest valid nonce
 static int grind_locked(Context &c, const uint8_t *seed32, uint32_t grinding_factor, uint64_t first, uint64_t last, uint64_t *out_nonce,
                         int *out_found, hipStream_t s) {
+    // 2^64 - 1 is never a candidate: the reference iterates 0..u64::MAX (grinding.rs:45), and it is the value *best holds
+    // while nothing is found.  last = 2^64 - 1 means 2^64 - 2; [2^64 - 1, 2^64 - 1] is empty.
+    if (last == ~0ull) {
+        if (first == ~0ull) {
+            *out_found = 0;
+            return LW_OK;
+        }
+        last = ~0ull - 1;
+    }
     GrindArgs g;
     uint8_t inner[32];
     grind_inner_hash(seed32, grinding_factor, inner);

@@ -84,6 +84,8 @@ def grinding_window(grinding_factor):
 def grinding_nonce(seed, grinding_factor, first=0, last=2**64 - 1, stream=None):
     """grinding::generate_nonce (provers/stark/src/grinding.rs:40-53) on the device: the smallest nonce in [first, last] with
     u64_be(Keccak256(Keccak256(PREFIX || seed || grinding_factor) || nonce_be)[0..8]) < 2^(64 - grinding_factor), or None.
+    2^64 - 1 is never a candidate, as in the reference's 0..u64::MAX: last = 2^64 - 1 means 2^64 - 2, and the range
+    [2^64 - 1, 2^64 - 1] gives None.
     stream: a HIP stream handle (lw_stark_grinding_nonce_device); None: the library's own stream."""
     import ctypes as C
     from .errors import check

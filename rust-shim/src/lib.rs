@@ -574,7 +574,8 @@ pub fn stark_transition_evaluations(field: Field, ops: &[ffi::lw_stark_air_op_t]
 }
 
 /// `grinding::generate_nonce` (provers/stark/src/grinding.rs:40-53) on the device: the smallest nonce in `[first, last]`
-/// whose hash has `grinding_factor` (1 ..= 63) leading zero bits, or `None`.
+/// whose hash has `grinding_factor` (1 ..= 63) leading zero bits, or `None`.  `u64::MAX` is never a candidate, as in the
+/// reference's `0..u64::MAX`: `last = u64::MAX` means `u64::MAX - 1`.
 pub fn stark_grinding_nonce(seed: &[u8; 32], grinding_factor: u8, first: u64, last: u64) -> Result<Option<u64>, HipError> {
     let (mut nonce, mut found) = (0u64, 0 as c_int);
     // SAFETY: the seed is 32 bytes; both outputs are valid for one value.

@@ -29,6 +29,14 @@ def smallest_nonce(seed, grinding_factor, first=0, last=2**64 - 1):
     return None
 
 
+def pointwise_nonces():
+    """nonces that put a bit into every byte of bswap64(nonce), its low half included: every 2^k, every single byte 0xff,
+    the three around 2^32, two patterns and the largest candidate, 2^64 - 2"""
+    out = [1 << k for k in range(64)] + [0xff << (8 * j) for j in range(8)]
+    out += [2**32 - 1, 2**32, 2**32 + 1, 2**63, 0x0123456789abcdef, 0xaaaaaaaaaaaaaaaa, 2**64 - 2]
+    return sorted(set(out))
+
+
 def bitrev(j, bits):
     return int(format(j, "0%db" % bits)[::-1], 2) if bits else 0
 

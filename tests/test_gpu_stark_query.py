@@ -98,6 +98,82 @@ def test_reference_vectors_at_factor_30_and_33(grinding, g):
     assert got is not None and got <= vector and R.is_valid_nonce(seed, got, g)
 
 
+# ---- grinding at nonces of the full width: v = bswap64(nonce) has a low half that is not zero from 2^32 on
+
+def test_pointwise_validity_at_full_width_nonces(grinding):
+    """first == last == nonce makes the search the predicate: one launch of one candidate per (seed, factor, nonce)"""
+    from lambda_elliptic_curves_amd import stark
+    nonces = [int(x, 16) for x in grinding["pointwise"]["nonces"]]
+    assert nonces == R.pointwise_nonces()
+    n_calls, wrong = 0, []
+    for name, rows in grinding["pointwise"]["valid"].items():
+        seed = grinding["seeds"][name]
+        for g in (1, 2, 3, 4):
+            for nonce, bit in zip(nonces, rows[str(g)]):
+                got = stark.grinding_nonce(seed, g, first=nonce, last=nonce)
+                assert got in (None, nonce)
+                n_calls += 1
+                if (got == nonce) != (bit == "1"):
+                    wrong.append((name, g, hex(nonce)))
+    assert n_calls == 2 * 4 * 77
+    assert not wrong, (len(wrong), wrong[:8])
+
+
+def test_searches_above_two_to_the_32(grinding):
+    """factor 8 over [first, first + 5000] from 2^32, 2^40 + 12345, 2^63 and 2^64 - 2^20, the ranges that end at 2^64 - 2 at
+    factors 8 and 20 (a hit or None, as the restatement says), on the library's stream and on the caller's"""
+    import torch
+    from lambda_elliptic_curves_amd import stark
+    own = torch.cuda.current_stream().cuda_stream
+    seen = set()
+    for s in grinding["searches"]:
+        seed, g, first, last = grinding["seeds"][s["seed"]], s["grinding_factor"], int(s["first"], 16), int(s["last"], 16)
+        want = None if s["nonce"] is None else int(s["nonce"], 16)
+        assert stark.grinding_nonce(seed, g, first=first, last=last) == want, s
+        assert stark.grinding_nonce(seed, g, first=first, last=last, stream=own) == want, s
+        seen.add((g, want is None))
+    assert {(8, False), (20, True), (1, False)} <= seen
+
+
+def test_the_largest_u64_is_never_a_candidate(grinding):
+    """grinding.rs:45 iterates 0..u64::MAX: last = 2^64 - 1 means 2^64 - 2, and [2^64 - 1, 2^64 - 1] holds nothing, although
+    the restatement finds 2^64 - 1 valid for seed B at factor 1"""
+    import torch
+    from lambda_elliptic_curves_amd import stark
+    seed, top = grinding["seeds"]["B"], 2**64 - 1
+    assert R.is_valid_nonce(seed, top, 1) and R.is_valid_nonce(seed, top - 1, 1)
+    for stream in (None, torch.cuda.current_stream().cuda_stream):
+        assert stark.grinding_nonce(seed, 1, first=top, last=top, stream=stream) is None
+        assert stark.grinding_nonce(seed, 1, first=top - 1, stream=stream) == top - 1
+        assert stark.grinding_nonce(seed, 1, first=top - 1, last=top - 1, stream=stream) == top - 1
+    for s in grinding["searches"]:              # a range that ends at 2^64 - 1 is the range that ends at 2^64 - 2
+        if int(s["last"], 16) == top - 1 and s["grinding_factor"] == 8:
+            want = int(s["nonce"], 16)
+            assert stark.grinding_nonce(grinding["seeds"][s["seed"]], 8, first=int(s["first"], 16), last=top) == want
+            assert stark.grinding_nonce(grinding["seeds"][s["seed"]], 8, first=int(s["first"], 16)) == want
+
+
+def test_two_windows_that_end_at_the_top_of_the_range(grinding):
+    """factor 63 over [2^64 - 2^28 - 3, 2^64 - 1]: a full window of 2^28 candidates, then the rest up to 2^64 - 2, whose
+    start + window - 1 would wrap.  None: a candidate is valid with probability 2^-63.  The time limit is ten times what
+    the rate of a search at factor 20 predicts for 2^28 candidates, plus a second."""
+    from lambda_elliptic_curves_amd import stark
+    seed, w = grinding["seeds"]["A"], stark.grinding_window(63)
+    first = 2**64 - w - 3
+    assert w == 1 << 28 and first + w - 1 < 2**64 - 2 < first + 2 * w - 1
+    stark.grinding_nonce(grinding["seeds"]["B"], 20, last=SMALLEST_B_20 - 1)   # warm-up
+    t0 = time.perf_counter()
+    assert stark.grinding_nonce(grinding["seeds"]["B"], 20, last=SMALLEST_B_20 - 1) is None
+    rate = SMALLEST_B_20 / (time.perf_counter() - t0)
+    limit = 10.0 * (w + 2) / rate + 1.0
+    t0 = time.perf_counter()
+    got = stark.grinding_nonce(seed, 63, first=first, last=2**64 - 1)
+    elapsed = time.perf_counter() - t0
+    print(f"factor 63: {w + 2} candidates in {elapsed:.3f} s, limit {limit:.2f} s")
+    assert got is None
+    assert elapsed < limit
+
+
 # ---- openings
 
 def _positions(leaves):

@@ -39,6 +39,40 @@ def test_restatement_smallest_nonces_up_to_factor_12(grinding):
                 assert R.smallest_nonce(grinding["seeds"][name], int(g)) == nonce, (name, g)
 
 
+def test_restatement_reproduces_the_full_width_nonces(grinding):
+    """the pointwise validities and the searches above 2^32 that tests/test_gpu_stark_query.py asks of the device"""
+    nonces = [int(x, 16) for x in grinding["pointwise"]["nonces"]]
+    assert nonces == R.pointwise_nonces() and max(nonces) == 2**64 - 2
+    assert {1 << k for k in range(64)} | {0xff << (8 * j) for j in range(8)} | {2**32 - 1, 2**32, 2**32 + 1} <= set(nonces)
+    assert sum(1 for x in nonces if x >= 2**32) == 40       # bswap64 of these has a low half that is not zero
+    for name, rows in grinding["pointwise"]["valid"].items():
+        assert sorted(rows) == ["1", "2", "3", "4"]
+        for g, row in rows.items():
+            inner = R.inner_hash(grinding["seeds"][name], int(g))
+            assert row == "".join("01"[R.is_valid_nonce(grinding["seeds"][name], x, int(g), inner)] for x in nonces), (name, g)
+            assert "0" in row and "1" in row
+    assert len(grinding["searches"]) == 13
+    for s in grinding["searches"]:
+        first, last = int(s["first"], 16), int(s["last"], 16)
+        assert 2**32 <= first <= last <= 2**64 - 2
+        want = None if s["nonce"] is None else int(s["nonce"], 16)
+        assert R.smallest_nonce(grinding["seeds"][s["seed"]], s["grinding_factor"], first, last) == want, s
+    offsets = {(int(s["first"], 16), s["seed"]): int(s["nonce"], 16) - int(s["first"], 16) for s in grinding["searches"]
+               if s["grinding_factor"] == 8 and int(s["last"], 16) == int(s["first"], 16) + 5000}
+    assert offsets == {(2**32, "A"): 141, (2**32, "B"): 254, (2**40 + 12345, "A"): 417, (2**40 + 12345, "B"): 212,
+                       (2**63, "A"): 194, (2**63, "B"): 546, (2**64 - 2**20, "A"): 200, (2**64 - 2**20, "B"): 513}
+    # 2^64 - 1 would be valid for seed B at factor 1; the reference never tries it, and neither does the library
+    assert R.is_valid_nonce(grinding["seeds"]["B"], 2**64 - 1, 1) and R.is_valid_nonce(grinding["seeds"]["B"], 2**64 - 2, 1)
+
+
+def test_the_documents_say_that_the_largest_u64_is_no_candidate():
+    from lambda_elliptic_curves_amd import stark
+    header = " ".join(open(os.path.join(ROOT, "include", "lw_hip.h")).read().replace("*", " ").split())
+    assert "2^64 - 1 is never a candidate" in header and "means 2^64 - 2" in header
+    doc = " ".join(stark.grinding_nonce.__doc__.split())
+    assert "2^64 - 1 is never a candidate" in doc and "last = 2^64 - 1 means 2^64 - 2" in doc
+
+
 # proof.deep_poly_openings[0].main_trace_polys.evaluations of the same proof (provers/stark/src/prover.rs:1438-1453)
 STONE_CASE_1_EVALUATIONS = [0x4de0d56f9cf97dff326c26592fbd4ae9ee756080b12c51cfe4864e9b8734f43,
                             0x1bc1aadf39f2faee64d84cb25f7a95d3dceac1016258a39fc90c9d370e69e8e]
