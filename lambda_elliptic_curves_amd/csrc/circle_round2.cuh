@@ -18,10 +18,9 @@
 // m31q_r2_cycle_kernel      1 / Z of the distinct transition descriptors (M31Q_R2_CLASSES at most), back to back, 2 B period
 //                           entries each; M31Q_R2_CYCLE_ROWS entries of a work-item share one m31_inv
 // m31q_r2_transition_kernel one work-item per LDE row.  It first forms E(q_i) cycle[i & mask] of every class and keeps it in
-//                           LDS, then runs the program exactly as ext_r2_transition_kernel does - ops, cell table, constants,
-//                           coefficients, classes and exemption points from wave-uniform addresses through the scalar cache -
-//                           and at EMIT c folds beta_c (class value x acc) into its QM31 accumulator with m31q_mul_base.
-//                           Temporaries and class values live in dynamic LDS as [slot][lane] words.  No T_c is stored.
+//                           LDS, then runs the program with air_run (air_interp.cuh) over words of M31qExt and at EMIT c
+//                           folds beta_c (class value x acc) into its QM31 accumulator with m31q_mul_base.  Temporaries and
+//                           class values live in dynamic LDS as [slot][lane] words.  No T_c is stored.
 // m31q_r2_boundary_kernel   up to M31Q_R2_STEPS distinct steps per launch, R consecutive rows per work-item: the R x S
 //                           denominators y' share ONE m31_inv (Montgomery's trick), the numerators sum_k gamma_k col_k[i] - c_s
 //                           (c_s = sum_k gamma_k v_k is the host's) are formed on the way back and multiplied by
@@ -34,6 +33,7 @@
 #include <algorithm>
 #include <vector>
 #include "mersenne31_ext.cuh"
+#include "r2_tables.h"
 
 namespace lw {
 
@@ -56,22 +56,13 @@ static inline CirclePt circle_r2_gen(uint32_t k) {
 // trace point p_j = g_{2n} + j g_n = (2j + 1) g_{2n}, j < n = 2^log2_trace <= 2^30
 static inline CirclePt circle_r2_trace_point(uint32_t log2_trace, uint64_t j) { return circle_mul((uint32_t)(2 * j + 1), circle_r2_gen(log2_trace + 1)); }
 
-struct CircleR2Desc {   // a transition's zerofier
+struct CircleR2Desc {   // a transition's zerofier: the classes of r2_classes
     uint64_t period, offset, end_exemptions;
+    template <class T> static CircleR2Desc of(const T &t) { return CircleR2Desc{t.period, t.offset, t.end_exemptions}; }
     bool operator==(const CircleR2Desc &o) const { return period == o.period && offset == o.offset && end_exemptions == o.end_exemptions; }
 };
-// the distinct descriptors in the order of their first appearance; class_of[c] indexes them
-template <class T> static void circle_r2_classes(const T *tr, uint32_t n_tr, std::vector<uint32_t> &class_of, std::vector<CircleR2Desc> &classes) {
-    class_of.assign(n_tr, 0);
-    classes.clear();
-    for (uint32_t c = 0; c < n_tr; c++) {
-        const CircleR2Desc d{tr[c].period, tr[c].offset, tr[c].end_exemptions};
-        uint32_t k = 0;
-        while (k < classes.size() && !(classes[k] == d)) k++;
-        if (k == classes.size()) classes.push_back(d);
-        class_of[c] = k;
-    }
-}
+// the name under which tests/circle_round2_host_main.cpp calls r2_classes
+template <class T> static void circle_r2_classes(const T *tr, uint32_t n_tr, std::vector<uint32_t> &class_of, std::vector<CircleR2Desc> &classes) { r2_classes(tr, n_tr, class_of, classes); }
 // a class's cycle: cycle[e] = 1 / y(2^doublings (q_e - c)), e < len = 2 B period (a power of two, at most N)
 struct CircleR2Cycle {
     CirclePt c;
@@ -134,8 +125,7 @@ static inline CircleR2Table circle_r2_table(uint32_t log2_lde) {
 }  // namespace lw
 
 #ifndef LW_CIRCLE_R2_TABLES_ONLY
-#include "air_program.h"
-#include "ext_round2.cuh"   // ext_uniform, ext_r2_round256
+#include "ext_round2.cuh"   // air_interp.cuh, and the checks the entry bodies share
 
 namespace lw {
 
@@ -197,11 +187,7 @@ __global__ __launch_bounds__(M31Q_THREADS) void m31q_r2_cycle_kernel(const M31qR
     }
 }
 
-// tables of 64-bit words, every one at a wave-uniform index:
-//   ops      lw_stark_air_op_t as one word: op | src << 8 | index << 16 | row << 32
-//   cells    per column: its address, its length - 1 (a power of two)
-//   consts   per constant: the word, in [0, p]
-//   trans    per constraint: beta_c (two words), its class, 0
+// The sections of air_interp.cuh (a constant is a word in [0, p]), and
 //   classes  per class: the address of its cycle table, the table's length - 1, its number of exemption points, the first of them
 //   expts    per exemption point: x | y << 32
 struct M31qR2Args {
@@ -211,12 +197,6 @@ struct M31qR2Args {
     M31qR2Domain dom;
     M31qPlanes out;
 };
-__device__ __forceinline__ Qm31 m31q_uniform_elem(const uint64_t *p, size_t k) {
-    const uint64_t w[2] = {ext_uniform(p, k), ext_uniform(p, k + 1)};
-    Qm31 v;
-    __builtin_memcpy(&v, w, 16);
-    return v;
-}
 
 extern __shared__ uint32_t m31q_r2_lds[];   // [slot][lane] words: the program's temporaries, then the classes' values
 
@@ -227,51 +207,28 @@ __global__ __launch_bounds__(M31Q_THREADS) void m31q_r2_transition_kernel(const 
     const CirclePt q = a.any_expts ? m31q_r2_point(a.dom, i) : CirclePt{1u, 0u};
 #pragma unroll 1
     for (uint32_t k = 0; k < a.n_classes; k++) {
-        const uint32_t *cycle = (const uint32_t *)ext_uniform(a.classes, 4 * k);
-        const uint64_t mask = ext_uniform(a.classes, 4 * k + 1), n_ex = ext_uniform(a.classes, 4 * k + 2), ex0 = ext_uniform(a.classes, 4 * k + 3);
-        uint32_t z = cycle[i & mask];
+        const uint32_t *cycle = (const uint32_t *)air_uniform(a.classes, 4 * k);
+        const uint64_t mask = air_uniform(a.classes, 4 * k + 1), n_ex = air_uniform(a.classes, 4 * k + 2), ex0 = air_uniform(a.classes, 4 * k + 3);
+        uint32_t v = cycle[i & mask];
 #pragma unroll 1
         for (uint64_t r = 0; r < n_ex; r++) {
-            const uint64_t pt = ext_uniform(a.expts, ex0 + r);
-            z = m31_mul(z, m31_sub(1u, m31_add(m31_mul((uint32_t)pt, q.x), m31_mul((uint32_t)(pt >> 32), q.y))));
+            const uint64_t pt = air_uniform(a.expts, ex0 + r);
+            v = m31_mul(v, m31_sub(1u, m31_add(m31_mul((uint32_t)pt, q.x), m31_mul((uint32_t)(pt >> 32), q.y))));
         }
-        lds[(a.n_tmps + k) * M31Q_THREADS + threadIdx.x] = z;
+        lds[(a.n_tmps + k) * M31Q_THREADS + threadIdx.x] = v;
     }
     Qm31 sum = m31q_zero();
-    uint32_t acc = 0;
-#pragma unroll 1
-    for (uint32_t pc = 0; pc < a.n_ops; pc++) {
-        const uint64_t o = ext_uniform(a.ops, pc);
-        const uint32_t op = (uint32_t)o & 0xffu, src = (uint32_t)(o >> 8) & 0xffu, index = (uint32_t)(o >> 16) & 0xffffu, row = (uint32_t)(o >> 32);
-        if (op <= LW_STARK_AIR_MUL) {
-            uint32_t s;
-            if (src == LW_STARK_AIR_CELL) {
-                const uint32_t *col = (const uint32_t *)ext_uniform(a.cells, 2 * index);
-                const uint64_t mask = ext_uniform(a.cells, 2 * index + 1);
-                s = m31_from_word(col[(i + ((uint64_t)row << a.log2_blowup)) & mask]);
-            } else if (src == LW_STARK_AIR_CONST) {
-                s = (uint32_t)ext_uniform(a.consts, index);
-            } else {
-                s = lds[index * M31Q_THREADS + threadIdx.x];
-            }
-            if (op == LW_STARK_AIR_LOAD) acc = s;
-            else if (op == LW_STARK_AIR_ADD) acc = m31_add(acc, s);
-            else if (op == LW_STARK_AIR_SUB) acc = m31_sub(acc, s);
-            else acc = m31_mul(acc, s);
-        } else if (op == LW_STARK_AIR_NEG) {
-            acc = m31_neg(acc);
-        } else if (op == LW_STARK_AIR_STORE) {
-            lds[index * M31Q_THREADS + threadIdx.x] = acc;
-        } else {   // EMIT: no row T_c, the term goes onto the sum
-            const uint32_t cls = (uint32_t)ext_uniform(a.trans, 4 * index + 2);
-            const uint32_t zt = m31_mul(lds[(a.n_tmps + cls) * M31Q_THREADS + threadIdx.x], acc);
-            sum = m31q_add(sum, m31q_mul_base(m31q_uniform_elem(a.trans, 4 * index), zt));
-        }
-    }
+    const uint64_t *trans = a.trans;
+    const uint32_t n_tmps = a.n_tmps;
+    air_run<AirWord<M31qExt, M31Q_THREADS>>(a.ops, a.n_ops, a.cells, a.consts, lds, i, a.log2_blowup, [&sum, trans, lds, n_tmps](uint32_t c, uint32_t acc) {
+        // no row T_c, the term goes onto the sum
+        const uint32_t cls = (uint32_t)air_uniform(trans, 4 * c + 2);
+        sum = m31q_add(sum, m31q_mul_base(air_uniform_elem<Qm31>(trans, 4 * c), m31_mul(lds[(n_tmps + cls) * M31Q_THREADS + threadIdx.x], acc)));
+    });
     M31qExt::store(a.out, i, sum);
 }
 
-// bnd: per constraint (in the order of the steps) the address of its column, 0, gamma_k (two words)
+// bnd: the section of air_interp.cuh
 struct M31qR2BoundaryArgs {
     const uint64_t *bnd;
     uint64_t N;
@@ -314,8 +271,8 @@ template <int R, int S> __global__ __launch_bounds__(M31Q_THREADS) void m31q_r2_
         for (int r = 0; r < R; r++) t[r] = m31q_zero();
 #pragma unroll 1
         for (uint32_t k = a.first[s]; k < a.first[s] + a.count[s]; k++) {
-            const uint32_t *col = (const uint32_t *)ext_uniform(a.bnd, 4 * k) + row0;
-            const Qm31 gamma = m31q_uniform_elem(a.bnd, 4 * k + 2);
+            const uint32_t *col = (const uint32_t *)air_uniform(a.bnd, 4 * k) + row0;
+            const Qm31 gamma = air_uniform_elem<Qm31>(a.bnd, 4 * k + 2);
 #pragma unroll
             for (int r = 0; r < R; r++)
                 if (row0 + r < a.N) t[r] = m31q_add(t[r], m31q_mul_base(gamma, m31_from_word(col[r])));   // N < R: the rows past the domain
@@ -355,7 +312,7 @@ static int m31q_r2_constraints_locked(Context &c, const lw_stark_air_op_t *ops, 
     std::vector<uint32_t> class_of, order;
     std::vector<CircleR2Desc> classes;
     std::vector<CircleR2Step> steps;
-    circle_r2_classes(tr, n_tr, class_of, classes);
+    r2_classes(tr, n_tr, class_of, classes);
     circle_r2_step_groups(bnd, n_bnd, log2_trace, order, steps);
     M31qR2CycleArgs ca;
     memset(&ca, 0, sizeof(ca));
@@ -367,56 +324,34 @@ static int m31q_r2_constraints_locked(Context &c, const lw_stark_air_op_t *ops, 
         ex0.push_back(expts.size());
         circle_r2_exemption_points(classes[k], log2_trace, expts);
     }
-    // workspace: [ops | cells | consts | trans | classes | expts | bnd] uploaded at once, then the cycle tables and the point table
-    const size_t b_ops = ext_r2_round256((size_t)n_ops * 8), b_cells = ext_r2_round256((size_t)n_cols * 16), b_consts = ext_r2_round256((size_t)n_consts * 8),
-                 b_trans = ext_r2_round256((size_t)n_tr * 32), b_classes = ext_r2_round256(classes.size() * 32), b_expts = ext_r2_round256(expts.size() * 8),
-                 b_bnd = ext_r2_round256((size_t)n_bnd * 32);
-    const size_t tables = b_ops + b_cells + b_consts + b_trans + b_classes + b_expts + b_bnd;
+    // workspace: the tables uploaded at once, then the cycle tables and the point table
+    R2Arena t;
+    const size_t s_ops = t.add((size_t)n_ops * 8), s_cells = t.add((size_t)n_cols * 16), s_consts = t.add((size_t)n_consts * 8), s_trans = t.add((size_t)n_tr * 32),
+                 s_classes = t.add(classes.size() * 32), s_expts = t.add(expts.size() * 8), s_bnd = t.add((size_t)n_bnd * 32);
+    const size_t tables = t.total;
     const CircleR2Table pt = circle_r2_table(log2_lde);
-    const size_t b_cycle = ext_r2_round256((size_t)ca.total * sizeof(uint32_t));
-    if (c.poly_ws.ensure(tables + b_cycle + (size_t)(pt.nlo + pt.nhi) * sizeof(uint2) + 256)) return LW_ERR_ALLOC;
-    char *d_tab = (char *)c.poly_ws.p;
-    ca.table = (uint32_t *)(d_tab + tables);
-    uint2 *d_pts = (uint2 *)(d_tab + tables + b_cycle);
+    const size_t s_cycle = t.add((size_t)ca.total * sizeof(uint32_t)), s_pts = t.add((size_t)(pt.nlo + pt.nhi) * sizeof(uint2));
+    int rc = air_tables_stage(c, t, tables);
+    if (rc) return rc;
+    ca.table = (uint32_t *)(t.dev + s_cycle);
+    uint2 *d_pts = (uint2 *)(t.dev + s_pts);
     const M31qR2Domain dom{d_pts, d_pts + pt.nlo, pt.hbits};
     if (tables) {
-        int rc = deep_pin(c, tables);   // the caller's arrays are free on return
-        if (rc) return rc;
-        char *hp = (char *)c.deep_pin;
-        memset(hp, 0, tables);
-        if (n_ops) memcpy(hp, ops, (size_t)n_ops * 8);
-        uint64_t *t = (uint64_t *)(hp + b_ops);
-        for (uint32_t k = 0; k < n_cols; k++) {
-            t[2 * k] = (uint64_t)(uintptr_t)cols[k];
-            t[2 * k + 1] = (col_log2_len ? 1ull << col_log2_len[k] : N) - 1;
-        }
-        t = (uint64_t *)(hp + b_ops + b_cells);
-        for (uint32_t k = 0; k < n_consts; k++) t[k] = m31_from_word(consts[k]);
-        t = (uint64_t *)(hp + b_ops + b_cells + b_consts);
-        for (uint32_t k = 0; k < n_tr; k++) {
-            const Qm31 beta = m31q_from_words(tr[k].coeff);
-            memcpy(t + 4 * k, &beta, 16);
-            t[4 * k + 2] = class_of[k];
-        }
-        t = (uint64_t *)(hp + b_ops + b_cells + b_consts + b_trans);
+        r2_fill_ops(t.h(s_ops), ops, n_ops);
+        r2_fill_cells(t.h(s_cells), cols, col_log2_len, n_cols, N);
+        for (uint32_t k = 0; k < n_consts; k++) t.h(s_consts)[k] = m31_from_word(consts[k]);
+        for (uint32_t k = 0; k < n_tr; k++) r2_fill_trans(t.h(s_trans), k, m31q_from_words(tr[k].coeff), class_of[k]);
+        uint64_t *cl = t.h(s_classes);
         for (size_t k = 0; k < classes.size(); k++) {
-            t[4 * k] = (uint64_t)(uintptr_t)(ca.table + ca.cy[k].off);
-            t[4 * k + 1] = ca.cy[k].len - 1;
-            t[4 * k + 2] = classes[k].end_exemptions;
-            t[4 * k + 3] = ex0[k];
+            cl[4 * k] = (uint64_t)(uintptr_t)(ca.table + ca.cy[k].off);
+            cl[4 * k + 1] = ca.cy[k].len - 1;
+            cl[4 * k + 2] = classes[k].end_exemptions;
+            cl[4 * k + 3] = ex0[k];
         }
-        t = (uint64_t *)(hp + b_ops + b_cells + b_consts + b_trans + b_classes);
-        for (size_t k = 0; k < expts.size(); k++) t[k] = expts[k];
-        t = (uint64_t *)(hp + b_ops + b_cells + b_consts + b_trans + b_classes + b_expts);
-        for (uint32_t q = 0; q < n_bnd; q++) {
-            const Qm31 gamma = m31q_from_words(bnd[order[q]].coeff);
-            t[4 * q] = (uint64_t)(uintptr_t)cols[bnd[order[q]].col];
-            memcpy(t + 4 * q + 2, &gamma, 16);
-        }
-        LW_HIP_CHECK(hipMemcpyAsync(d_tab, hp, tables, hipMemcpyHostToDevice, s), LW_ERR_LAUNCH);
-        LW_HIP_CHECK(hipEventRecord(c.deep_pin_read, s), LW_ERR_LAUNCH);
+        for (size_t k = 0; k < expts.size(); k++) t.h(s_expts)[k] = expts[k];
+        for (uint32_t q = 0; q < n_bnd; q++) r2_fill_bnd(t.h(s_bnd), q, cols[bnd[order[q]].col], 0, m31q_from_words(bnd[order[q]].coeff));
+        if ((rc = air_tables_upload(c, t, tables, s))) return rc;
     }
-    int rc = LW_OK;
     if (n_bnd || !expts.empty()) {   // the boundary kernel's points, and the transition kernel's when a class has exemptions
         rc = launch_1d(c, "m31q_r2_table_kernel", m31q_r2_table_kernel, blocks_for(pt.nlo + pt.nhi), s, d_pts, d_pts + pt.nlo, pt.nlo, pt.nhi, pt.hbits, pt.g2N);
         if (rc) return rc;
@@ -429,12 +364,12 @@ static int m31q_r2_constraints_locked(Context &c, const lw_stark_air_op_t *ops, 
         if (rc) return rc;
         M31qR2Args a;
         memset(&a, 0, sizeof(a));
-        a.ops = (const uint64_t *)d_tab;
-        a.cells = (const uint64_t *)(d_tab + b_ops);
-        a.consts = (const uint64_t *)(d_tab + b_ops + b_cells);
-        a.trans = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts);
-        a.classes = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts + b_trans);
-        a.expts = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts + b_trans + b_classes);
+        a.ops = t.d(s_ops);
+        a.cells = t.d(s_cells);
+        a.consts = t.d(s_consts);
+        a.trans = t.d(s_trans);
+        a.classes = t.d(s_classes);
+        a.expts = t.d(s_expts);
         a.N = N;
         a.n_ops = n_ops;
         a.log2_blowup = log2_blowup;
@@ -453,19 +388,14 @@ static int m31q_r2_constraints_locked(Context &c, const lw_stark_air_op_t *ops, 
     }
     M31qR2BoundaryArgs b;
     memset(&b, 0, sizeof(b));
-    b.bnd = (const uint64_t *)(d_tab + tables - b_bnd);
+    b.bnd = t.d(s_bnd);
     b.N = N;
     b.dom = dom;
     b.gN = pt.gN;
     b.out = ext_planes<M31qExt>(d_out, out_stride);
     for (size_t s0 = 0; s0 < steps.size(); s0 += M31Q_R2_STEPS) {
         const size_t S = steps.size() - s0 < (size_t)M31Q_R2_STEPS ? steps.size() - s0 : (size_t)M31Q_R2_STEPS;
-        for (size_t j = 0; j < S; j++) {
-            b.point[j] = steps[s0 + j].point;
-            b.first[j] = steps[s0 + j].first;
-            b.count[j] = steps[s0 + j].count;
-            b.constant[j] = steps[s0 + j].constant;
-        }
+        r2_fill_steps(b, steps, s0, S);
         b.accumulate = n_tr > 0 || s0 > 0;
         void (*kernel)(M31qR2BoundaryArgs) = S == 1   ? m31q_r2_boundary_kernel<M31Q_R2_ROWS, 1>
                                              : S == 2 ? m31q_r2_boundary_kernel<M31Q_R2_ROWS, 2>
@@ -489,20 +419,16 @@ static int m31q_r2_constraint_evaluations(const lw_stark_air_op_t *ops, uint32_t
         return LW_ERR_BAD_ARG;
     }
     const uint64_t n = 1ull << log2_trace, N = 1ull << lg;
-    if ((n_consts && n_consts <= LW_STARK_AIR_MAX_CONSTS && !consts) || (n_boundary && !boundary) || (n_transitions && !transitions) || (n_cols && !d_columns)) {
+    if (r2_null_tables(consts, n_consts, boundary, n_boundary, transitions, n_transitions, d_columns, n_cols)) {
         set_error("null table");
         return LW_ERR_BAD_ARG;
     }
     AirProgramInfo info;
-    char msg[192];
-    if (!air_program_check(ops, n_ops, n_consts, col_log2_len_or_null, n_cols, log2_trace, (uint32_t)lg, n_transitions, &info, msg, sizeof(msg))) {
-        set_error("AIR program: %s", msg);
-        return LW_ERR_BAD_ARG;
-    }
+    int rc = air_program_checked(ops, n_ops, n_consts, col_log2_len_or_null, n_cols, log2_trace, (uint32_t)lg, n_transitions, &info);
+    if (rc) return rc;
     for (uint32_t k = 0; k < n_boundary; k++) {
         const lw_m31q_boundary_t &b = boundary[k];
-        if (b.col >= n_cols) { set_error("boundary constraint %u: column %u of %u", k, b.col, n_cols); return LW_ERR_BAD_ARG; }
-        if (col_log2_len_or_null && col_log2_len_or_null[b.col] != lg) { set_error("boundary constraint %u: column %u is a short one", k, b.col); return LW_ERR_BAD_ARG; }
+        if ((rc = r2_boundary_col_check(k, b.col, n_cols, col_log2_len_or_null, lg))) return rc;
         if (b.step >= n) { set_error("boundary constraint %u: step %llu of a trace of %llu rows", k, (unsigned long long)b.step, (unsigned long long)n); return LW_ERR_BAD_ARG; }
     }
     for (uint32_t k = 0; k < n_transitions; k++) {
@@ -519,18 +445,8 @@ static int m31q_r2_constraint_evaluations(const lw_stark_air_op_t *ops, uint32_t
     }
     std::vector<uint32_t> class_of;
     std::vector<CircleR2Desc> classes;
-    circle_r2_classes(transitions, n_transitions, class_of, classes);
-    if (classes.size() > (size_t)M31Q_R2_CLASSES) { set_error("%zu distinct transition zerofiers: a call takes at most %d", classes.size(), M31Q_R2_CLASSES); return LW_ERR_BAD_ARG; }
-    int rc = ext_device_ptrs({d_out});
-    if (!rc) rc = ext_stride(out_stride, N, "out");
-    if (rc) return rc;
-    for (uint32_t k = 0; k < n_cols; k++) {
-        if (!d_columns[k] || !aligned16(d_columns[k])) { set_error("column %u: null or misaligned buffer", k); return LW_ERR_BAD_ARG; }
-        if (ext_overlap<M31qExt>(d_columns[k], col_log2_len_or_null ? (size_t)1 << col_log2_len_or_null[k] : N, d_out, ext_span<M31qExt>(out_stride, N))) {
-            set_error("out overlaps column %u", k);
-            return LW_ERR_BAD_ARG;
-        }
-    }
+    r2_classes(transitions, n_transitions, class_of, classes);
+    if ((rc = r2_class_cap_check(classes.size(), M31Q_R2_CLASSES)) || (rc = r2_buffers_check<M31qExt>(d_out, out_stride, N, d_columns, col_log2_len_or_null, n_cols))) return rc;
     if (log2_blowup == 0 && (n_boundary || n_transitions)) {
         set_error("a blow-up of 1: the LDE coset is the trace domain, where the zerofiers vanish");
         return LW_ERR_INV_ZERO;
@@ -569,7 +485,7 @@ static int m31q_r2_composition_parts(const uint32_t *d_evals, size_t evals_strid
     if (en.rc) return en.rc;
     Context &c = en.c;
     hipStream_t s = en.stream;
-    const size_t b_H = ext_r2_round256((size_t)4 * N * sizeof(uint32_t));
+    const size_t b_H = r2_round256((size_t)4 * N * sizeof(uint32_t));
     if (c.pipe_tmp.ensure(b_H + 8)) return LW_ERR_ALLOC;
     uint32_t *d_H = (uint32_t *)c.pipe_tmp.p;
     unsigned long long *d_count = (unsigned long long *)((char *)c.pipe_tmp.p + b_H);

@@ -18,7 +18,7 @@
 // Product mode is PLONK's form: with N_i the prefix product of the numerators through row i, S_i the product of the
 // denominators after row i and T the inverse of all of them, f_0 .. f_i = N_i S_i T, so no row is inverted.  Sum mode needs
 // every 1 / den_i: the EXT_AUX_E rows of a work-item share one E::inv (Montgomery's trick in registers).  The two lists are
-// one uploaded table read at wave-uniform indices (ext_uniform).  Rows from n on count as the neutral fraction.
+// one uploaded table read at wave-uniform indices (air_uniform).  Rows from n on count as the neutral fraction.
 // The carry launch is one workgroup whatever n: a work-item walks ceil(tiles / EXT_AUX_TOP) tile values serially (twice in
 // product mode), so its time grows linearly with n - 16 tiles a work-item at 2^20 rows, a third of the product call there,
 // and about 2^20 at the 2^36 rows the entry allows.  A 256-wide carry workgroup, or a second level of reduce-then-scan over
@@ -61,16 +61,16 @@ __device__ __forceinline__ void ext_aux_rows(const ExtAuxArgs<E> &a, uint64_t ba
     }
 #pragma unroll 1
     for (uint32_t j = 0; j < a.n_num; j++) {
-        const word *col = (const word *)ext_uniform(a.terms, 4 * (size_t)j) + base;
-        const elem cf = ext_uniform_elem<E>(a.terms, 4 * (size_t)j + 2);
+        const word *col = (const word *)air_uniform(a.terms, 4 * (size_t)j) + base;
+        const elem cf = air_uniform_elem<elem>(a.terms, 4 * (size_t)j + 2);
 #pragma unroll
         for (int e = 0; e < EXT_AUX_E; e++)
             if (base + e < a.n) num[e] = E::add(num[e], E::mul_base(cf, E::fcanon(col[e])));
     }
 #pragma unroll 1
     for (uint32_t j = a.n_num; j < a.n_num + a.n_den; j++) {
-        const word *col = (const word *)ext_uniform(a.terms, 4 * (size_t)j) + base;
-        const elem cf = ext_uniform_elem<E>(a.terms, 4 * (size_t)j + 2);
+        const word *col = (const word *)air_uniform(a.terms, 4 * (size_t)j) + base;
+        const elem cf = air_uniform_elem<elem>(a.terms, 4 * (size_t)j + 2);
 #pragma unroll
         for (int e = 0; e < EXT_AUX_E; e++)
             if (base + e < a.n) den[e] = E::add(den[e], E::mul_base(cf, E::fcanon(col[e])));
@@ -293,7 +293,7 @@ template <class E> struct ExtAuxList {
     uint32_t n;
 };
 
-// the uploaded table of the two lists: per term the column's address, 0 and the coefficient as ext_uniform_elem reads it
+// the uploaded table of the two lists: per term the column's address, 0 and the coefficient as air_uniform_elem reads it
 template <class E>
 static void ext_aux_pack_terms(const typename E::word *const *cols, const ExtAuxList<E> &num, const ExtAuxList<E> &den, uint64_t *t) {
     uint32_t at = 0;
@@ -301,7 +301,7 @@ static void ext_aux_pack_terms(const typename E::word *const *cols, const ExtAux
         for (uint32_t j = 0; j < l->n; j++, at++) {
             t[4 * at] = (uint64_t)(uintptr_t)cols[l->cols[j]];
             t[4 * at + 1] = 0;
-            ext_r2_pack<E>(ext_elem_of<E>(l->coeffs, j), t + 4 * at + 2);
+            r2_pack(ext_elem_of<E>(l->coeffs, j), t + 4 * at + 2);
         }
 }
 
@@ -346,7 +346,7 @@ static int ext_aux_fractions(const ExtAuxNames &names, const typename E::word *c
     Context &c = en.c;
     hipStream_t s = en.stream;
     const uint64_t nt = (n + EXT_AUX_TILE - 1) / EXT_AUX_TILE;
-    const size_t b_terms = ext_r2_round256((size_t)2 * EXT_AUX_TERMS * 32), b_tiles = ext_r2_round256((size_t)nt * sizeof(elem));
+    const size_t b_terms = r2_round256((size_t)2 * EXT_AUX_TERMS * 32), b_tiles = r2_round256((size_t)nt * sizeof(elem));
     if (c.poly_ws.ensure(b_terms + 4 * b_tiles + 256)) return LW_ERR_ALLOC;
     char *ws = (char *)c.poly_ws.p;
     ExtAuxArgs<E> a;

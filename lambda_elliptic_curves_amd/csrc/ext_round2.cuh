@@ -15,11 +15,9 @@
 // ext_r2_cycle_kernel      the cycle tables of the distinct transition descriptors (EXT_R2_CLASSES at most), back to back:
 //                          numerator / denominator per entry, EXT_ROWS entries of a work-item share one E::finv
 // ext_r2_transition_kernel one work-item per LDE row.  It first forms the zerofier value of every class at its row (cycle
-//                          entry times the end-exemption roots) and keeps it in LDS, then runs the program exactly as
-//                          air_transition_kernel does - ops, column table, constants and coefficients from wave-uniform
-//                          addresses through the scalar cache, the dispatch a scalar branch - and at EMIT c folds
-//                          beta_c (Z_class(c) acc) into its E accumulator with E::mul_base.  Temporaries and class values live
-//                          in LDS as [slot][lane] words: a slot known only at run time is an address there, not scratch.
+//                          entry times the end-exemption roots) and keeps it in LDS, then runs the program with air_run
+//                          (air_interp.cuh) over words of F and at EMIT c folds beta_c (Z_class(c) acc) into its E
+//                          accumulator with E::mul_base.  Temporaries and class values live in LDS as [slot][lane] words.
 //                          Writes out.
 // ext_r2_boundary_kernel   up to EXT_R2_STEPS distinct steps per launch, EXT_ROWS consecutive rows per work-item
 //                          (E::R2_ROWS_FEW with one or two steps): the rows x steps denominators inverted with ONE E::finv
@@ -35,15 +33,15 @@
 // The randomized AIR (the _rap_ entry points): auxiliary columns and constants in E.  An auxiliary column is D planes of N
 // words; the program reads it with XCELL and a constant of E with XCONST, and a boundary constraint may sit on it.
 // air_program_check_rap types every value of the straight-line program as F or E and writes the types into the op words, so
-// ext_r2_rap_transition_kernel, the interpreter above with two accumulators (a word and an element), branches on them with a
-// scalar branch: an op on F operands is E::fadd / E::fsub / E::fmul as above, F with E is E::mul_base, E with E is E::mul,
+// ext_r2_rap_transition_kernel, an interpreter with two accumulators (a word and an element), branches on them with a
+// scalar branch: an op on F operands is air_interp.cuh's as above, F with E is E::mul_base, E with E is E::mul,
 // and an emitted element folds as beta_c (Z acc) with one E::mul.  A temporary that ever holds an element takes D LDS slots
 // [slot][coordinate][lane], any other one: (F temporaries + D E temporaries + classes) words per lane, 48 KiB (Fp2) or 40 KiB
 // (Fp4) at most.  The boundary kernel takes a template flag: a constraint on an auxiliary column adds E::mul(gamma_k,
 // aux_k[i]) where one on a main column adds E::mul_base, and v_k in E only changes the host's constant c_s.
 #pragma once
 #include <algorithm>
-#include "air_program.h"
+#include "air_interp.cuh"
 #include "ext_steps.cuh"
 
 namespace lw {
@@ -52,25 +50,17 @@ constexpr int EXT_R2_CLASSES = 8;   // distinct transition descriptors per call 
 constexpr int EXT_R2_STEPS = 4;     // distinct boundary steps per launch: EXT_ROWS x EXT_R2_STEPS denominators per inversion
 
 // ---------------------------------------------------------------- host tables: plain arithmetic, no Context
-struct ExtR2Desc {   // a transition's zerofier
+struct ExtR2Desc {   // a transition's zerofier: the classes of r2_classes
     uint64_t period, offset, end_exemptions, exemptions_period, periodic_exemptions_offset;
+    template <class T> static ExtR2Desc of(const T &t) { return ExtR2Desc{t.period, t.offset, t.end_exemptions, t.exemptions_period, t.periodic_exemptions_offset}; }
     bool operator==(const ExtR2Desc &o) const {
         return period == o.period && offset == o.offset && end_exemptions == o.end_exemptions && exemptions_period == o.exemptions_period &&
                periodic_exemptions_offset == o.periodic_exemptions_offset;
     }
 };
-// the distinct descriptors in the order of their first appearance; class_of[c] indexes them
-template <class T> static void ext_r2_classes(const T *tr, uint32_t n_tr, std::vector<uint32_t> &class_of, std::vector<ExtR2Desc> &classes) {
-    class_of.assign(n_tr, 0);
-    classes.clear();
-    for (uint32_t c = 0; c < n_tr; c++) {
-        const ExtR2Desc d{tr[c].period, tr[c].offset, tr[c].end_exemptions, tr[c].exemptions_period, tr[c].periodic_exemptions_offset};
-        uint32_t k = 0;
-        while (k < classes.size() && !(classes[k] == d)) k++;
-        if (k == classes.size()) classes.push_back(d);
-        class_of[c] = k;
-    }
-}
+// the names under which the stand-alone host programs of tests/ call r2_classes and r2_pack
+template <class T> static void ext_r2_classes(const T *tr, uint32_t n_tr, std::vector<uint32_t> &class_of, std::vector<ExtR2Desc> &classes) { r2_classes(tr, n_tr, class_of, classes); }
+template <class E> static void ext_r2_pack(typename E::elem v, uint64_t *dst) { r2_pack(v, dst); }
 // cycle[e] = ((h w^e)^ne - nc) / ((h w^e)^de - dc) for e < len (the numerator 1 without an exemptions period), then the
 // roots g^(n - k period), k = 1 .. end_exemptions (zerofier_evaluations_on_extended_domain with its truncating divisions)
 template <class E> struct ExtR2Cycle {
@@ -127,22 +117,8 @@ static void ext_r2_step_groups(const B *bnd, uint32_t n_bnd, uint64_t n, typenam
         steps.back().constant = E::add(steps.back().constant, ext_r2_times_value<E>(ext_elem_of<E>(b.coeff, 0), b.value));
     }
 }
-// an element as the two 64-bit words the kernels read it back from
-template <class E> static void ext_r2_pack(typename E::elem v, uint64_t *dst) {
-    static_assert(sizeof(typename E::elem) == 16, "an element is two 64-bit words of a table");
-    memcpy(dst, &v, 16);
-}
 
 // ---------------------------------------------------------------- kernels
-// word `k` of a table at a wave-uniform address that nothing writes while the kernel runs: through the scalar cache
-__device__ __forceinline__ uint64_t ext_uniform(const uint64_t *p, size_t k) { return ((const __attribute__((address_space(4))) uint64_t *)(uintptr_t)p)[k]; }
-template <class E> __device__ __forceinline__ typename E::elem ext_uniform_elem(const uint64_t *p, size_t k) {
-    const uint64_t w[2] = {ext_uniform(p, k), ext_uniform(p, k + 1)};
-    typename E::elem v;
-    __builtin_memcpy(&v, w, 16);
-    return v;
-}
-
 // x_i = lo[i & (2^hbits - 1)] hi[i >> hbits]
 template <class E> struct ExtR2Domain {
     const typename E::word *lo, *hi;
@@ -197,22 +173,41 @@ template <class E> __global__ __launch_bounds__(EXT_THREADS) void ext_r2_cycle_k
     }
 }
 
-// tables of 64-bit words, every one at a wave-uniform index:
-//   ops      lw_stark_air_op_t as one word: op | src << 8 | index << 16 | row << 32
-//   cells    per column: its address, its length - 1 (a power of two)
-//   consts   per constant: the word
-//   trans    per constraint: beta_c (two words), its class, 0
+// The sections of air_interp.cuh, and
 //   classes  per class: the address of its cycle table, the table's length, pow2 | n_roots << 32, its first root
 //   roots    per root: the word
+// and for the RAP kernel
+//   ops      the words of air_program_check_rap: AIR_TYPED_ACC_EXT and AIR_TYPED_SRC_EXT in the op byte, LDS slots as the
+//            indices of temporaries
+//   xcells   per auxiliary column: the address of its plane 0, the stride of its planes in words
+//   xconsts  per constant of E: two words
 template <class E> struct ExtR2Args {
-    const uint64_t *ops, *cells, *consts, *trans, *classes, *roots;
+    const uint64_t *ops, *cells, *consts, *trans, *classes, *roots, *xcells, *xconsts;   // the last two null in the plain kernel
     uint64_t N;
-    uint32_t n_ops, log2_blowup, n_classes, n_tmps, any_roots;
+    uint32_t n_ops, log2_blowup, n_classes, n_slots, any_roots;   // n_slots: LDS slots of the temporaries (the plain kernel's n_tmps)
     ExtR2Domain<E> dom;
     ExtPlanes<E> out;
 };
 
 extern __shared__ uint64_t ext_r2_lds[];   // [slot][lane] words: the program's temporaries, then the classes' values
+
+// the zerofier value of every class at row i, cycle entry times the end-exemption roots, into the LDS slots from `first` on
+template <class E>
+__device__ __forceinline__ void ext_r2_class_values(const uint64_t *classes, const uint64_t *roots, uint32_t n_classes, uint32_t any_roots, const ExtR2Domain<E> dom,
+                                                    typename E::word *lds, uint32_t first, uint64_t i) {
+    using word = typename E::word;
+    const word x = any_roots ? ext_r2_x<E>(dom, i) : E::F_ONE;
+#pragma unroll 1
+    for (uint32_t k = 0; k < n_classes; k++) {
+        const word *cycle = (const word *)air_uniform(classes, 4 * k);
+        const uint64_t len = air_uniform(classes, 4 * k + 1), meta = air_uniform(classes, 4 * k + 2), root0 = air_uniform(classes, 4 * k + 3);
+        word v = cycle[(meta & 1) ? (i & (len - 1)) : i % len];
+        const uint32_t n_roots = (uint32_t)(meta >> 32);
+#pragma unroll 1
+        for (uint32_t r = 0; r < n_roots; r++) v = E::fmul(v, E::fsub(x, (word)air_uniform(roots, root0 + r)));
+        lds[(first + k) * EXT_THREADS + threadIdx.x] = v;
+    }
+}
 
 template <class E> __global__ __launch_bounds__(EXT_THREADS) void ext_r2_transition_kernel(const ExtR2Args<E> a) {
     using word = typename E::word;
@@ -220,63 +215,17 @@ template <class E> __global__ __launch_bounds__(EXT_THREADS) void ext_r2_transit
     word *lds = (word *)ext_r2_lds;
     const uint64_t i = (uint64_t)blockIdx.x * EXT_THREADS + threadIdx.x;
     if (i >= a.N) return;
-    const word x = a.any_roots ? ext_r2_x<E>(a.dom, i) : E::F_ONE;
-#pragma unroll 1
-    for (uint32_t k = 0; k < a.n_classes; k++) {
-        const word *cycle = (const word *)ext_uniform(a.classes, 4 * k);
-        const uint64_t len = ext_uniform(a.classes, 4 * k + 1), meta = ext_uniform(a.classes, 4 * k + 2), root0 = ext_uniform(a.classes, 4 * k + 3);
-        word z = cycle[(meta & 1) ? (i & (len - 1)) : i % len];
-        const uint32_t n_roots = (uint32_t)(meta >> 32);
-#pragma unroll 1
-        for (uint32_t r = 0; r < n_roots; r++) z = E::fmul(z, E::fsub(x, (word)ext_uniform(a.roots, root0 + r)));
-        lds[(a.n_tmps + k) * EXT_THREADS + threadIdx.x] = z;
-    }
+    ext_r2_class_values<E>(a.classes, a.roots, a.n_classes, a.any_roots, a.dom, lds, a.n_slots, i);
     elem sum = E::zero();
-    word acc = 0;
-#pragma unroll 1
-    for (uint32_t pc = 0; pc < a.n_ops; pc++) {
-        const uint64_t o = ext_uniform(a.ops, pc);
-        const uint32_t op = (uint32_t)o & 0xffu, src = (uint32_t)(o >> 8) & 0xffu, index = (uint32_t)(o >> 16) & 0xffffu, row = (uint32_t)(o >> 32);
-        if (op <= LW_STARK_AIR_MUL) {
-            word s;
-            if (src == LW_STARK_AIR_CELL) {
-                const word *col = (const word *)ext_uniform(a.cells, 2 * index);
-                const uint64_t mask = ext_uniform(a.cells, 2 * index + 1);
-                s = E::fcanon(col[(i + ((uint64_t)row << a.log2_blowup)) & mask]);
-            } else if (src == LW_STARK_AIR_CONST) {
-                s = (word)ext_uniform(a.consts, index);
-            } else {
-                s = lds[index * EXT_THREADS + threadIdx.x];
-            }
-            if (op == LW_STARK_AIR_LOAD) acc = s;
-            else if (op == LW_STARK_AIR_ADD) acc = E::fadd(acc, s);
-            else if (op == LW_STARK_AIR_SUB) acc = E::fsub(acc, s);
-            else acc = E::fmul(acc, s);
-        } else if (op == LW_STARK_AIR_NEG) {
-            acc = E::fsub(0, acc);
-        } else if (op == LW_STARK_AIR_STORE) {
-            lds[index * EXT_THREADS + threadIdx.x] = acc;
-        } else {   // EMIT: no row T_c, the term goes onto the sum
-            const uint32_t cls = (uint32_t)ext_uniform(a.trans, 4 * index + 2);
-            const word zt = E::fmul(lds[(a.n_tmps + cls) * EXT_THREADS + threadIdx.x], acc);
-            sum = E::add(sum, E::mul_base(ext_uniform_elem<E>(a.trans, 4 * index), zt));
-        }
-    }
+    const uint64_t *trans = a.trans;
+    const uint32_t n_slots = a.n_slots;
+    air_run<AirWord<E, EXT_THREADS>>(a.ops, a.n_ops, a.cells, a.consts, lds, i, a.log2_blowup, [&sum, trans, lds, n_slots](uint32_t c, word acc) {
+        // no row T_c, the term goes onto the sum
+        const uint32_t cls = (uint32_t)air_uniform(trans, 4 * c + 2);
+        sum = E::add(sum, E::mul_base(air_uniform_elem<elem>(trans, 4 * c), E::fmul(lds[(n_slots + cls) * EXT_THREADS + threadIdx.x], acc)));
+    });
     E::store(a.out, i, sum);
 }
-
-// The same tables, and
-//   ops      the words of air_program_check_rap: AIR_TYPED_ACC_EXT and AIR_TYPED_SRC_EXT in the op byte, LDS slots as the
-//            indices of temporaries
-//   xcells   per auxiliary column: the address of its plane 0, the stride of its planes in words
-//   xconsts  per constant of E: two words
-template <class E> struct ExtR2RapArgs {
-    const uint64_t *ops, *cells, *consts, *trans, *classes, *roots, *xcells, *xconsts;
-    uint64_t N;
-    uint32_t n_ops, log2_blowup, n_classes, n_slots, any_roots;
-    ExtR2Domain<E> dom;
-    ExtPlanes<E> out;
-};
 
 // the D LDS slots of a temporary that holds an element, as planes: element threadIdx.x is the lane's
 template <class E> __device__ __forceinline__ ExtPlanes<E> ext_r2_lds_planes(typename E::word *lds, uint32_t slot) {
@@ -286,46 +235,25 @@ template <class E> __device__ __forceinline__ ExtPlanes<E> ext_r2_lds_planes(typ
     return v;
 }
 
-template <class E> __global__ __launch_bounds__(EXT_THREADS) void ext_r2_rap_transition_kernel(const ExtR2RapArgs<E> a) {
+template <class E> __global__ __launch_bounds__(EXT_THREADS) void ext_r2_rap_transition_kernel(const ExtR2Args<E> a) {
     using word = typename E::word;
     using elem = typename E::elem;
+    using W = AirWord<E, EXT_THREADS>;
     word *lds = (word *)ext_r2_lds;
     const uint64_t i = (uint64_t)blockIdx.x * EXT_THREADS + threadIdx.x;
     if (i >= a.N) return;
-    const word x = a.any_roots ? ext_r2_x<E>(a.dom, i) : E::F_ONE;
-#pragma unroll 1
-    for (uint32_t k = 0; k < a.n_classes; k++) {
-        const word *cycle = (const word *)ext_uniform(a.classes, 4 * k);
-        const uint64_t len = ext_uniform(a.classes, 4 * k + 1), meta = ext_uniform(a.classes, 4 * k + 2), root0 = ext_uniform(a.classes, 4 * k + 3);
-        word z = cycle[(meta & 1) ? (i & (len - 1)) : i % len];
-        const uint32_t n_roots = (uint32_t)(meta >> 32);
-#pragma unroll 1
-        for (uint32_t r = 0; r < n_roots; r++) z = E::fmul(z, E::fsub(x, (word)ext_uniform(a.roots, root0 + r)));
-        lds[(a.n_slots + k) * EXT_THREADS + threadIdx.x] = z;
-    }
+    ext_r2_class_values<E>(a.classes, a.roots, a.n_classes, a.any_roots, a.dom, lds, a.n_slots, i);
     elem sum = E::zero(), ea = E::zero();   // ea: the accumulator while it holds an element, acc: while it holds a word
     word acc = 0;
 #pragma unroll 1
     for (uint32_t pc = 0; pc < a.n_ops; pc++) {
-        const uint64_t o = ext_uniform(a.ops, pc);
-        const uint32_t op = (uint32_t)o & 0xfu, src = (uint32_t)(o >> 8) & 0xffu, index = (uint32_t)(o >> 16) & 0xffffu, row = (uint32_t)(o >> 32);
-        const bool acc_ext = o & AIR_TYPED_ACC_EXT, src_ext = o & AIR_TYPED_SRC_EXT;   // the host's: uniform
+        const AirOp o = air_decode(air_uniform(a.ops, pc));
+        const uint32_t op = o.op & 0xfu, index = o.index;
+        const bool acc_ext = o.word & AIR_TYPED_ACC_EXT, src_ext = o.word & AIR_TYPED_SRC_EXT;   // the host's: uniform
         if (op <= LW_STARK_AIR_MUL && !src_ext) {
-            word s;
-            if (src == LW_STARK_AIR_CELL) {
-                const word *col = (const word *)ext_uniform(a.cells, 2 * index);
-                const uint64_t mask = ext_uniform(a.cells, 2 * index + 1);
-                s = E::fcanon(col[(i + ((uint64_t)row << a.log2_blowup)) & mask]);
-            } else if (src == LW_STARK_AIR_CONST) {
-                s = (word)ext_uniform(a.consts, index);
-            } else {
-                s = lds[index * EXT_THREADS + threadIdx.x];
-            }
+            const word s = air_operand<W>(o, a.cells, a.consts, lds, i, a.log2_blowup);
             if (!acc_ext) {   // F with F: as ext_r2_transition_kernel
-                if (op == LW_STARK_AIR_LOAD) acc = s;
-                else if (op == LW_STARK_AIR_ADD) acc = E::fadd(acc, s);
-                else if (op == LW_STARK_AIR_SUB) acc = E::fsub(acc, s);
-                else acc = E::fmul(acc, s);
+                acc = air_apply<W>(op, acc, s);
             } else if (op == LW_STARK_AIR_ADD) {
                 ea.c0 = E::fadd(ea.c0, s);
             } else if (op == LW_STARK_AIR_SUB) {
@@ -335,11 +263,11 @@ template <class E> __global__ __launch_bounds__(EXT_THREADS) void ext_r2_rap_tra
             }
         } else if (op <= LW_STARK_AIR_MUL) {
             elem se;
-            if (src == LW_STARK_AIR_XCELL) {
-                const word *col = (const word *)ext_uniform(a.xcells, 2 * index);
-                se = E::canon(E::load(ext_planes<E>(col, ext_uniform(a.xcells, 2 * index + 1)), (i + ((uint64_t)row << a.log2_blowup)) & (a.N - 1)));
-            } else if (src == LW_STARK_AIR_XCONST) {
-                se = ext_uniform_elem<E>(a.xconsts, 2 * index);
+            if (o.src == LW_STARK_AIR_XCELL) {
+                const word *col = (const word *)air_uniform(a.xcells, 2 * index);
+                se = E::canon(E::load(ext_planes<E>(col, air_uniform(a.xcells, 2 * index + 1)), (i + ((uint64_t)o.row << a.log2_blowup)) & (a.N - 1)));
+            } else if (o.src == LW_STARK_AIR_XCONST) {
+                se = air_uniform_elem<elem>(a.xconsts, 2 * index);
             } else {
                 se = E::load(ext_r2_lds_planes<E>(lds, index), threadIdx.x);
             }
@@ -360,23 +288,22 @@ template <class E> __global__ __launch_bounds__(EXT_THREADS) void ext_r2_rap_tra
             }
         } else if (op == LW_STARK_AIR_NEG) {
             if (acc_ext) ea = E::sub(E::zero(), ea);
-            else acc = E::fsub(0, acc);
+            else acc = W::neg(acc);
         } else if (op == LW_STARK_AIR_STORE) {
             if (acc_ext) E::store(ext_r2_lds_planes<E>(lds, index), threadIdx.x, ea);
-            else lds[index * EXT_THREADS + threadIdx.x] = acc;
+            else W::put(lds, index, acc);
         } else {   // EMIT
-            const uint32_t cls = (uint32_t)ext_uniform(a.trans, 4 * index + 2);
-            const word z = lds[(a.n_slots + cls) * EXT_THREADS + threadIdx.x];
-            const elem beta = ext_uniform_elem<E>(a.trans, 4 * index);
-            if (acc_ext) sum = E::add(sum, E::mul(beta, E::mul_base(ea, z)));
-            else sum = E::add(sum, E::mul_base(beta, E::fmul(z, acc)));
+            const uint32_t cls = (uint32_t)air_uniform(a.trans, 4 * index + 2);
+            const word zc = lds[(a.n_slots + cls) * EXT_THREADS + threadIdx.x];
+            const elem beta = air_uniform_elem<elem>(a.trans, 4 * index);
+            if (acc_ext) sum = E::add(sum, E::mul(beta, E::mul_base(ea, zc)));
+            else sum = E::add(sum, E::mul_base(beta, E::fmul(zc, acc)));
         }
     }
     E::store(a.out, i, sum);
 }
 
-// bnd: per constraint (in the order of the steps) the address of its column, 0 (AUX: the stride of an auxiliary column's
-// planes in words, 0 on a main column), gamma_k (two words)
+// bnd: the section of air_interp.cuh
 template <class E> struct ExtR2BoundaryArgs {
     const uint64_t *bnd;
     uint64_t N;
@@ -423,9 +350,9 @@ template <class E, int R, int S, bool AUX = false> __global__ __launch_bounds__(
         for (int r = 0; r < R; r++) t[r] = E::zero();
 #pragma unroll 1
         for (uint32_t k = a.first[s]; k < a.first[s] + a.count[s]; k++) {
-            const word *col = (const word *)ext_uniform(a.bnd, 4 * k) + row0;
-            const elem gamma = ext_uniform_elem<E>(a.bnd, 4 * k + 2);
-            const uint64_t aux_stride = AUX ? ext_uniform(a.bnd, 4 * k + 1) : 0;
+            const word *col = (const word *)air_uniform(a.bnd, 4 * k) + row0;
+            const elem gamma = air_uniform_elem<elem>(a.bnd, 4 * k + 2);
+            const uint64_t aux_stride = AUX ? air_uniform(a.bnd, 4 * k + 1) : 0;
             if (AUX && aux_stride) {
                 const ExtPlanes<E> aux = ext_planes<E>(col, aux_stride);
 #pragma unroll
@@ -487,8 +414,6 @@ template <class E> struct ExtR2Rap {
 };
 
 // ---------------------------------------------------------------- host: the constraint evaluations
-static size_t ext_r2_round256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // B, T: the extension's boundary and transition entries (lw_gl2_boundary_t, lw_bb4_boundary_t, ...).  cols: n_cols device
 // pointers (host array).  Everything is checked; enqueue only.
 template <class E, class B, class T>
@@ -504,7 +429,7 @@ static int ext_r2_constraints_locked(Context &c, const ExtR2Names &names, const 
     std::vector<uint32_t> class_of, order;
     std::vector<ExtR2Desc> classes;
     std::vector<ExtR2Step<E>> steps;
-    ext_r2_classes(tr, n_tr, class_of, classes);
+    r2_classes(tr, n_tr, class_of, classes);
     ext_r2_step_groups<E>(bnd, n_bnd, n, g, order, steps);
     ExtR2CycleArgs<E> ca;
     memset(&ca, 0, sizeof(ca));
@@ -517,71 +442,50 @@ static int ext_r2_constraints_locked(Context &c, const ExtR2Names &names, const 
         root0.push_back(roots.size());
         ext_r2_roots<E>(classes[k], n, g, roots);
     }
-    // workspace: [ops | cells | consts | trans | classes | roots | bnd] uploaded at once, then the cycle tables
-    const size_t b_ops = ext_r2_round256((size_t)n_ops * 8), b_cells = ext_r2_round256((size_t)n_cols * 16), b_consts = ext_r2_round256((size_t)n_consts * 8),
-                 b_trans = ext_r2_round256((size_t)n_tr * 32), b_classes = ext_r2_round256(classes.size() * 32), b_roots = ext_r2_round256(roots.size() * 8),
-                 b_bnd = ext_r2_round256((size_t)n_bnd * 32), b_xcells = rap ? ext_r2_round256((size_t)rap->n_aux * 16) : 0,
-                 b_xconsts = rap ? ext_r2_round256((size_t)rap->n_xconsts * 16) : 0;
-    const size_t o_bnd = b_ops + b_cells + b_consts + b_trans + b_classes + b_roots, tables = o_bnd + b_bnd + b_xcells + b_xconsts;
+    // workspace: the tables uploaded at once, then the cycle tables and the table of the coset
+    R2Arena t;
+    const size_t s_ops = t.add((size_t)n_ops * 8), s_cells = t.add((size_t)n_cols * 16), s_consts = t.add((size_t)n_consts * 8), s_trans = t.add((size_t)n_tr * 32),
+                 s_classes = t.add(classes.size() * 32), s_roots = t.add(roots.size() * 8), s_bnd = t.add((size_t)n_bnd * 32),
+                 s_xcells = t.add(rap ? (size_t)rap->n_aux * 16 : 0), s_xconsts = t.add(rap ? (size_t)rap->n_xconsts * 16 : 0);
+    const size_t tables = t.total;
     const uint32_t hbits = (log2_lde + 1) / 2;
     const uint64_t nlo = 1ull << hbits, nhi = 1ull << (log2_lde - hbits);
-    const size_t b_cycle = ext_r2_round256((size_t)ca.total * sizeof(word));
-    if (c.poly_ws.ensure(tables + b_cycle + (size_t)(nlo + nhi) * sizeof(word) + 256)) return LW_ERR_ALLOC;
-    char *d_tab = (char *)c.poly_ws.p;
-    ca.table = (word *)(d_tab + tables);
-    word *d_x = (word *)(d_tab + tables + b_cycle);
+    const size_t s_cycle = t.add((size_t)ca.total * sizeof(word)), s_x = t.add((size_t)(nlo + nhi) * sizeof(word));
+    int rc = air_tables_stage(c, t, tables);
+    if (rc) return rc;
+    ca.table = (word *)(t.dev + s_cycle);
+    word *d_x = (word *)(t.dev + s_x);
     const ExtR2Domain<E> dom{d_x, d_x + nlo, hbits};
     bool any_aux = false;   // a boundary constraint on an auxiliary column: the boundary kernel's AUX form
     if (tables) {
-        int rc = deep_pin(c, tables);   // the caller's arrays are free on return
-        if (rc) return rc;
-        char *hp = (char *)c.deep_pin;
-        memset(hp, 0, tables);
-        if (n_ops) memcpy(hp, rap ? (const void *)rap->typed.data() : (const void *)ops, (size_t)n_ops * 8);
-        uint64_t *t = (uint64_t *)(hp + b_ops);
-        for (uint32_t k = 0; k < n_cols; k++) {
-            t[2 * k] = (uint64_t)(uintptr_t)cols[k];
-            t[2 * k + 1] = (col_log2_len ? 1ull << col_log2_len[k] : N) - 1;
-        }
-        t = (uint64_t *)(hp + b_ops + b_cells);
-        for (uint32_t k = 0; k < n_consts; k++) t[k] = E::fcanon(consts[k]);
-        t = (uint64_t *)(hp + b_ops + b_cells + b_consts);
-        for (uint32_t k = 0; k < n_tr; k++) {
-            ext_r2_pack<E>(ext_elem_of<E>(tr[k].coeff, 0), t + 4 * k);
-            t[4 * k + 2] = class_of[k];
-        }
-        t = (uint64_t *)(hp + b_ops + b_cells + b_consts + b_trans);
+        r2_fill_ops(t.h(s_ops), rap ? (const void *)rap->typed.data() : (const void *)ops, n_ops);
+        r2_fill_cells(t.h(s_cells), cols, col_log2_len, n_cols, N);
+        for (uint32_t k = 0; k < n_consts; k++) t.h(s_consts)[k] = E::fcanon(consts[k]);
+        for (uint32_t k = 0; k < n_tr; k++) r2_fill_trans(t.h(s_trans), k, ext_elem_of<E>(tr[k].coeff, 0), class_of[k]);
+        uint64_t *cl = t.h(s_classes);
         for (size_t k = 0; k < classes.size(); k++) {
             const uint64_t len = ca.cy[k].len;
-            t[4 * k] = (uint64_t)(uintptr_t)(ca.table + ca.cy[k].off);
-            t[4 * k + 1] = len;
-            t[4 * k + 2] = ((len & (len - 1)) == 0 ? 1u : 0u) | classes[k].end_exemptions << 32;
-            t[4 * k + 3] = root0[k];
+            cl[4 * k] = (uint64_t)(uintptr_t)(ca.table + ca.cy[k].off);
+            cl[4 * k + 1] = len;
+            cl[4 * k + 2] = ((len & (len - 1)) == 0 ? 1u : 0u) | classes[k].end_exemptions << 32;
+            cl[4 * k + 3] = root0[k];
         }
-        t = (uint64_t *)(hp + b_ops + b_cells + b_consts + b_trans + b_classes);
-        for (size_t k = 0; k < roots.size(); k++) t[k] = roots[k];
-        t = (uint64_t *)(hp + o_bnd);
+        for (size_t k = 0; k < roots.size(); k++) t.h(s_roots)[k] = roots[k];
         for (uint32_t q = 0; q < n_bnd; q++) {
             const B &b = bnd[order[q]];
             const bool on_aux = ext_r2_is_aux(b, 0);
             any_aux = any_aux || on_aux;
-            t[4 * q] = (uint64_t)(uintptr_t)(on_aux ? rap->aux[b.col] : cols[b.col]);
-            t[4 * q + 1] = on_aux ? rap->aux_stride : 0;
-            ext_r2_pack<E>(ext_elem_of<E>(b.coeff, 0), t + 4 * q + 2);
+            r2_fill_bnd(t.h(s_bnd), q, on_aux ? rap->aux[b.col] : cols[b.col], on_aux ? rap->aux_stride : 0, ext_elem_of<E>(b.coeff, 0));
         }
         if (rap) {
-            t = (uint64_t *)(hp + o_bnd + b_bnd);
             for (uint32_t k = 0; k < rap->n_aux; k++) {
-                t[2 * k] = (uint64_t)(uintptr_t)rap->aux[k];
-                t[2 * k + 1] = rap->aux_stride;
+                t.h(s_xcells)[2 * k] = (uint64_t)(uintptr_t)rap->aux[k];
+                t.h(s_xcells)[2 * k + 1] = rap->aux_stride;
             }
-            t = (uint64_t *)(hp + o_bnd + b_bnd + b_xcells);
-            for (uint32_t k = 0; k < rap->n_xconsts; k++) ext_r2_pack<E>(ext_elem_of<E>(rap->xconsts, k), t + 2 * k);
+            for (uint32_t k = 0; k < rap->n_xconsts; k++) r2_pack(ext_elem_of<E>(rap->xconsts, k), t.h(s_xconsts) + 2 * k);
         }
-        LW_HIP_CHECK(hipMemcpyAsync(d_tab, hp, tables, hipMemcpyHostToDevice, s), LW_ERR_LAUNCH);
-        LW_HIP_CHECK(hipEventRecord(c.deep_pin_read, s), LW_ERR_LAUNCH);
+        if ((rc = air_tables_upload(c, t, tables, s))) return rc;
     }
-    int rc = LW_OK;
     if (n_tr || n_bnd) {
         rc = launch_1d(c, names.xtable, ext_r2_xtable_kernel<E>, blocks_for(nlo + nhi), s, d_x, d_x + nlo, nlo, nhi, w, E::fpow(w, nlo), h);
         if (rc) return rc;
@@ -592,71 +496,46 @@ static int ext_r2_constraints_locked(Context &c, const ExtR2Names &names, const 
         ca.w = w;
         rc = launch_1d(c, names.cycle, ext_r2_cycle_kernel<E>, blocks_for((ca.total + EXT_ROWS - 1) / EXT_ROWS), s, ca);
         if (rc) return rc;
+        ExtR2Args<E> a;
+        memset(&a, 0, sizeof(a));
+        a.ops = t.d(s_ops);
+        a.cells = t.d(s_cells);
+        a.consts = t.d(s_consts);
+        a.trans = t.d(s_trans);
+        a.classes = t.d(s_classes);
+        a.roots = t.d(s_roots);
         if (rap) {
-            ExtR2RapArgs<E> ra;
-            memset(&ra, 0, sizeof(ra));
-            ra.ops = (const uint64_t *)d_tab;
-            ra.cells = (const uint64_t *)(d_tab + b_ops);
-            ra.consts = (const uint64_t *)(d_tab + b_ops + b_cells);
-            ra.trans = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts);
-            ra.classes = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts + b_trans);
-            ra.roots = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts + b_trans + b_classes);
-            ra.xcells = (const uint64_t *)(d_tab + o_bnd + b_bnd);
-            ra.xconsts = (const uint64_t *)(d_tab + o_bnd + b_bnd + b_xcells);
-            ra.N = N;
-            ra.n_ops = n_ops;
-            ra.log2_blowup = log2_blowup;
-            ra.n_classes = ca.n_classes;
-            ra.n_slots = rap->n_slots;
-            ra.any_roots = !roots.empty();
-            ra.dom = dom;
-            ra.out = ext_planes<E>(d_out, out_stride);
-            const size_t lds = (size_t)(rap->n_slots + ra.n_classes) * sizeof(word) * EXT_THREADS;   // 8 D + 8 slots at most: 48 KiB (Fp2), 40 KiB (Fp4)
-            hipEvent_t pe = c.prof_begin(s);
-            hipLaunchKernelGGL(ext_r2_rap_transition_kernel<E>, dim3(blocks_for(N)), dim3(EXT_THREADS), lds, s, ra);
-            c.prof_end(names.rap_transition, pe, s);
-            LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
-        } else {
-            ExtR2Args<E> a;
-            memset(&a, 0, sizeof(a));
-            a.ops = (const uint64_t *)d_tab;
-            a.cells = (const uint64_t *)(d_tab + b_ops);
-            a.consts = (const uint64_t *)(d_tab + b_ops + b_cells);
-            a.trans = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts);
-            a.classes = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts + b_trans);
-            a.roots = (const uint64_t *)(d_tab + b_ops + b_cells + b_consts + b_trans + b_classes);
-            a.N = N;
-            a.n_ops = n_ops;
-            a.log2_blowup = log2_blowup;
-            a.n_classes = ca.n_classes;
-            a.n_tmps = n_tmps;
-            a.any_roots = !roots.empty();
-            a.dom = dom;
-            a.out = ext_planes<E>(d_out, out_stride);
-            const size_t lds = (size_t)(n_tmps + a.n_classes) * sizeof(word) * EXT_THREADS;   // 16 slots, 32 KiB, at most
-            hipEvent_t pe = c.prof_begin(s);
-            hipLaunchKernelGGL(ext_r2_transition_kernel<E>, dim3(blocks_for(N)), dim3(EXT_THREADS), lds, s, a);
-            c.prof_end(names.transition, pe, s);
-            LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
+            a.xcells = t.d(s_xcells);
+            a.xconsts = t.d(s_xconsts);
         }
+        a.N = N;
+        a.n_ops = n_ops;
+        a.log2_blowup = log2_blowup;
+        a.n_classes = ca.n_classes;
+        a.n_slots = rap ? rap->n_slots : n_tmps;
+        a.any_roots = !roots.empty();
+        a.dom = dom;
+        a.out = ext_planes<E>(d_out, out_stride);
+        // plain: 16 slots, 32 KiB, at most; RAP: 8 D + 8 slots, 48 KiB (Fp2), 40 KiB (Fp4)
+        const size_t lds = (size_t)(a.n_slots + a.n_classes) * sizeof(word) * EXT_THREADS;
+        void (*kernel)(ExtR2Args<E>) = rap ? ext_r2_rap_transition_kernel<E> : ext_r2_transition_kernel<E>;
+        hipEvent_t pe = c.prof_begin(s);
+        hipLaunchKernelGGL(kernel, dim3(blocks_for(N)), dim3(EXT_THREADS), lds, s, a);
+        c.prof_end(rap ? names.rap_transition : names.transition, pe, s);
+        LW_HIP_CHECK(hipGetLastError(), LW_ERR_LAUNCH);
     } else if (n_bnd == 0) {
         for (int e = 0; e < E::D; e++) LW_HIP_CHECK(hipMemsetAsync(d_out + e * out_stride, 0, N * sizeof(word), s), LW_ERR_LAUNCH);
     }
     ExtR2BoundaryArgs<E> b;
     memset(&b, 0, sizeof(b));
-    b.bnd = (const uint64_t *)(d_tab + o_bnd);
+    b.bnd = t.d(s_bnd);
     b.N = N;
     b.dom = dom;
     b.w = w;
     b.out = ext_planes<E>(d_out, out_stride);
     for (size_t s0 = 0; s0 < steps.size(); s0 += EXT_R2_STEPS) {
         const size_t S = steps.size() - s0 < (size_t)EXT_R2_STEPS ? steps.size() - s0 : (size_t)EXT_R2_STEPS;
-        for (size_t j = 0; j < S; j++) {
-            b.point[j] = steps[s0 + j].point;
-            b.first[j] = steps[s0 + j].first;
-            b.count[j] = steps[s0 + j].count;
-            b.constant[j] = steps[s0 + j].constant;
-        }
+        r2_fill_steps(b, steps, s0, S);
         b.accumulate = n_tr > 0 || s0 > 0;
         void (*kernel)(ExtR2BoundaryArgs<E>) = S == 1   ? ext_r2_boundary_kernel<E, E::R2_ROWS_FEW, 1>
                                                : S == 2 ? ext_r2_boundary_kernel<E, E::R2_ROWS_FEW, 2>
@@ -670,6 +549,38 @@ static int ext_r2_constraints_locked(Context &c, const ExtR2Names &names, const 
         const uint64_t rows = S <= 2 ? E::R2_ROWS_FEW : EXT_ROWS;
         rc = launch_1d(c, names.boundary, kernel, blocks_for((N + rows - 1) / rows), s, b);
         if (rc) return rc;
+    }
+    return LW_OK;
+}
+
+// The checks that the bodies of the entry points here and in circle_round2.cuh share, texts included.
+static bool r2_null_tables(const void *consts, uint32_t n_consts, const void *boundary, uint32_t n_boundary, const void *transitions, uint32_t n_transitions,
+                           const void *d_columns, uint32_t n_cols) {
+    return (n_consts && n_consts <= LW_STARK_AIR_MAX_CONSTS && !consts) || (n_boundary && !boundary) || (n_transitions && !transitions) || (n_cols && !d_columns);
+}
+// boundary constraint k sits on main column col: in range and not a short column
+static int r2_boundary_col_check(uint32_t k, uint32_t col, uint32_t n_cols, const uint32_t *col_log2_len_or_null, uint64_t lg) {
+    if (col >= n_cols) { set_error("boundary constraint %u: column %u of %u", k, col, n_cols); return LW_ERR_BAD_ARG; }
+    if (col_log2_len_or_null && col_log2_len_or_null[col] != lg) { set_error("boundary constraint %u: column %u is a short one", k, col); return LW_ERR_BAD_ARG; }
+    return LW_OK;
+}
+static int r2_class_cap_check(size_t n_classes, int cap) {
+    if (n_classes > (size_t)cap) { set_error("%zu distinct transition zerofiers: a call takes at most %d", n_classes, cap); return LW_ERR_BAD_ARG; }
+    return LW_OK;
+}
+// out and its stride (0 becomes N), then every column: not null, aligned, not under out
+template <class E>
+static int r2_buffers_check(const typename E::word *d_out, size_t &out_stride, uint64_t N, const typename E::word *const *d_columns, const uint32_t *col_log2_len_or_null,
+                            uint32_t n_cols) {
+    int rc = ext_device_ptrs({d_out});
+    if (!rc) rc = ext_stride(out_stride, N, "out");
+    if (rc) return rc;
+    for (uint32_t k = 0; k < n_cols; k++) {
+        if (!d_columns[k] || !aligned16(d_columns[k])) { set_error("column %u: null or misaligned buffer", k); return LW_ERR_BAD_ARG; }
+        if (ext_overlap<E>(d_columns[k], col_log2_len_or_null ? (size_t)1 << col_log2_len_or_null[k] : N, d_out, ext_span<E>(out_stride, N))) {
+            set_error("out overlaps column %u", k);
+            return LW_ERR_BAD_ARG;
+        }
     }
     return LW_OK;
 }
@@ -688,36 +599,34 @@ static int ext_r2_constraint_evaluations(const ExtR2Names &names, const lw_stark
     const uint64_t lg = (uint64_t)log2_trace + log2_blowup;
     if (lg > 63 || E::size_check((uint32_t)lg)) { set_error("an LDE domain of 2^%llu points is beyond the transform", (unsigned long long)lg); return LW_ERR_BAD_ARG; }
     const uint64_t n = 1ull << log2_trace, N = 1ull << lg;
-    if ((n_consts && n_consts <= LW_STARK_AIR_MAX_CONSTS && !consts) || (n_boundary && !boundary) || (n_transitions && !transitions) || (n_cols && !d_columns) ||
+    if (r2_null_tables(consts, n_consts, boundary, n_boundary, transitions, n_transitions, d_columns, n_cols) ||
         (rap && ((rap->n_xconsts && rap->n_xconsts <= LW_STARK_AIR_MAX_CONSTS && !rap->xconsts) || (rap->n_aux && !rap->aux)))) {
         set_error("null table");
         return LW_ERR_BAD_ARG;
     }
     AirProgramInfo info;
-    char msg[192];
-    bool well_formed;
+    int rc;
     if (rap) {
+        char msg[192];
         rap->typed.assign(n_ops <= LW_STARK_AIR_MAX_OPS && ops ? n_ops : 0, 0);
-        well_formed = air_program_check_rap(ops, n_ops, n_consts, rap->n_xconsts, col_log2_len_or_null, n_cols, rap->n_aux, E::D, log2_trace, (uint32_t)lg,
-                                            n_transitions, rap->typed.empty() ? nullptr : rap->typed.data(), &info, msg, sizeof(msg));
+        if (!air_program_check_rap(ops, n_ops, n_consts, rap->n_xconsts, col_log2_len_or_null, n_cols, rap->n_aux, E::D, log2_trace, (uint32_t)lg, n_transitions,
+                                   rap->typed.empty() ? nullptr : rap->typed.data(), &info, msg, sizeof(msg))) {
+            set_error("AIR program: %s", msg);
+            return LW_ERR_BAD_ARG;
+        }
         rap->n_slots = info.n_lds_slots;
-    } else {
-        well_formed = air_program_check(ops, n_ops, n_consts, col_log2_len_or_null, n_cols, log2_trace, (uint32_t)lg, n_transitions, &info, msg, sizeof(msg));
+    } else if ((rc = air_program_checked(ops, n_ops, n_consts, col_log2_len_or_null, n_cols, log2_trace, (uint32_t)lg, n_transitions, &info))) {
+        return rc;
     }
-    if (!well_formed) {
-        set_error("AIR program: %s", msg);
-        return LW_ERR_BAD_ARG;
-    }
-    int rc = E::words_check(consts, n_consts, "constants");
+    rc = E::words_check(consts, n_consts, "constants");
     if (!rc && rap) rc = E::words_check(rap->xconsts, (size_t)rap->n_xconsts * E::D, "extension constants");
     if (rc) return rc;
     for (uint32_t k = 0; k < n_boundary; k++) {
         const B &b = boundary[k];
         if (ext_r2_is_aux(b, 0)) {
             if (b.col >= rap->n_aux) { set_error("boundary constraint %u: auxiliary column %u of %u", k, b.col, rap->n_aux); return LW_ERR_BAD_ARG; }
-        } else {
-            if (b.col >= n_cols) { set_error("boundary constraint %u: column %u of %u", k, b.col, n_cols); return LW_ERR_BAD_ARG; }
-            if (col_log2_len_or_null && col_log2_len_or_null[b.col] != lg) { set_error("boundary constraint %u: column %u is a short one", k, b.col); return LW_ERR_BAD_ARG; }
+        } else if ((rc = r2_boundary_col_check(k, b.col, n_cols, col_log2_len_or_null, lg))) {
+            return rc;
         }
         if ((rc = ext_r2_value_check<E>(b.value)) || (rc = E::words_check(b.coeff, E::D, "boundary coefficient"))) return rc;
     }
@@ -732,18 +641,8 @@ static int ext_r2_constraint_evaluations(const ExtR2Names &names, const lw_stark
     }
     std::vector<uint32_t> class_of;
     std::vector<ExtR2Desc> classes;
-    ext_r2_classes(transitions, n_transitions, class_of, classes);
-    if (classes.size() > (size_t)EXT_R2_CLASSES) { set_error("%zu distinct transition zerofiers: a call takes at most %d", classes.size(), EXT_R2_CLASSES); return LW_ERR_BAD_ARG; }
-    rc = ext_device_ptrs({d_out});
-    if (!rc) rc = ext_stride(out_stride, N, "out");
-    if (rc) return rc;
-    for (uint32_t k = 0; k < n_cols; k++) {
-        if (!d_columns[k] || !aligned16(d_columns[k])) { set_error("column %u: null or misaligned buffer", k); return LW_ERR_BAD_ARG; }
-        if (ext_overlap<E>(d_columns[k], col_log2_len_or_null ? (size_t)1 << col_log2_len_or_null[k] : N, d_out, ext_span<E>(out_stride, N))) {
-            set_error("out overlaps column %u", k);
-            return LW_ERR_BAD_ARG;
-        }
-    }
+    r2_classes(transitions, n_transitions, class_of, classes);
+    if ((rc = r2_class_cap_check(classes.size(), EXT_R2_CLASSES)) || (rc = r2_buffers_check<E>(d_out, out_stride, N, d_columns, col_log2_len_or_null, n_cols))) return rc;
     if (rap) {
         if ((rc = ext_stride(rap->aux_stride, N, "auxiliary columns"))) return rc;
         for (uint32_t k = 0; k < rap->n_aux; k++) {
@@ -815,7 +714,7 @@ static int ext_r2_composition_parts(const ExtR2Names &names, const typename E::w
     if (en.rc) return en.rc;
     Context &c = en.c;
     hipStream_t s = en.stream;
-    const size_t b_H = ext_r2_round256((size_t)E::D * N * sizeof(word));
+    const size_t b_H = r2_round256((size_t)E::D * N * sizeof(word));
     if (c.pipe_tmp.ensure(b_H + (size_t)n_parts * 8)) return LW_ERR_ALLOC;
     word *d_H = (word *)c.pipe_tmp.p;
     unsigned long long *d_lens = (unsigned long long *)((char *)c.pipe_tmp.p + b_H);

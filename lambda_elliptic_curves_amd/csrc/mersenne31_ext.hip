@@ -35,6 +35,9 @@ struct M31qExt {
     static constexpr const char *NAME = "QM31";
     static constexpr ExtNames NAMES{"m31q_pointwise_kernel", "m31q_eval_tile_kernel", "m31q_eval_fold_kernel", "m31q_deep_kernel", "m31q_fri_fold_kernel"};
     EXT_HD word fcanon(word x) { return m31_from_word(x); }
+    EXT_HD word fadd(word a, word b) { return m31_add(a, b); }   // fadd, fsub, fmul: the interpreter of circle_round2.cuh (AirWord)
+    EXT_HD word fsub(word a, word b) { return m31_sub(a, b); }
+    EXT_HD word fmul(word a, word b) { return m31_mul(a, b); }
     EXT_HD elem load(ExtPlanes<M31qExt> v, uint64_t i) { return Qm31{m31_from_word(v.p[0][i]), m31_from_word(v.p[1][i]), m31_from_word(v.p[2][i]), m31_from_word(v.p[3][i])}; }
     EXT_HD void store(ExtPlanes<M31qExt> v, uint64_t i, elem a) {
         v.p[0][i] = m31_canon(a.c0);

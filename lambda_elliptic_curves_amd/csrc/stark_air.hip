@@ -4,100 +4,77 @@
 // lw_stark_constraint_evaluations_device (stark_round2.hip) reads.  air_program.h checks the program on the host; the
 // kernel relies on every index being in range and checks nothing.
 //
-// air_transition_kernel   one work-item per LDE row.  The program counter, the op and its fields are the same for every
-//                         lane: the ops, the column table and the constants are read from wave-uniform addresses through
-//                         the scalar cache and the dispatch is a scalar branch, so no lane diverges.  acc and the operand
-//                         are the only field elements in registers.  The temporaries live in LDS as limb planes
-//                         [slot][limb][lane]: a slot index known only at run time would turn a register array into
-//                         scratch memory, while in LDS it is an address; a lane reads and writes its own words only,
-//                         so there is no barrier and consecutive lanes hit consecutive banks.  The launch asks for the
-//                         slots the program stores (AirProgramInfo::n_tmps), 4 KiB each for AIR_THREADS lanes:
+// air_transition_kernel   one work-item per LDE row runs the program with air_run (air_interp.cuh) over the value policy
+//                         AirFe<F> and stores the accumulator at EMIT c as element i of row T_c.  The temporaries live in LDS
+//                         as limb planes [slot][limb][lane], so that consecutive lanes hit consecutive banks.  The launch
+//                         asks for the slots the program stores (AirProgramInfo::n_tmps), 4 KiB each for AIR_THREADS lanes:
 //                         a program without temporaries uses no LDS, one with all eight 32 KiB.
 // Arithmetic is the canonical fe_add / fe_sub / fe_mul / fe_neg of field.cuh: every value held or stored is in [0, p).
 #include <string.h>
 #include <vector>
-#include "internal.h"
 #include "field.cuh"
-#include "air_program.h"
+#include "air_interp.cuh"
 
 namespace lw {
 
 constexpr int AIR_THREADS = 128;   // 8 slots x 8 limbs x 4 bytes x 128 lanes = 32 KiB of LDS at most
 
-struct alignas(16) AirCell {
-    const char *col;
-    uint64_t mask;                 // len_col - 1 (a power of two)
-};
 struct AirArgs {
-    const uint64_t *ops;           // lw_stark_air_op_t as one word: op | src << 8 | index << 16 | row << 32
-    const AirCell *cells;
-    const char *consts;
+    const uint64_t *ops, *cells, *consts;   // the sections of air_interp.cuh; a constant is 32 bytes as fe_load reads them
     char *out;
     uint64_t out_stride;           // elements between the rows of two constraints
     uint64_t N;
     uint32_t n_ops, log2_blowup;
 };
 
-// word `k` of the u64 array at a wave-uniform address of memory nothing writes while the kernel runs: through the scalar cache
-__device__ __forceinline__ uint64_t air_uniform(const void *p, size_t k) {
-    return ((const __attribute__((address_space(4))) uint64_t *)(uintptr_t)p)[k];
-}
-template <class F>
-__device__ __forceinline__ Fe<F> air_uniform_fe(const char *p) {
-    constexpr int N = F::N;
-    uint32_t m[N];
+// a 256-bit element of F in [0, p), limb planes [slot][limb][lane] in LDS
+template <class F> struct AirFe {
+    using value = Fe<F>;
+    using lds_word = uint32_t;
+    static __device__ __forceinline__ value zero() { return Fe<F>::zero(); }
+    static __device__ __forceinline__ value cell(uint64_t col, uint64_t pos) { return fe_load<F>((const char *)col + pos * 32); }
+    static __device__ __forceinline__ value constant(const uint64_t *consts, uint32_t index) {
+        constexpr int N = F::N;
+        uint32_t m[N];
 #pragma unroll
-    for (int j = 0; j < N / 2; j++) {
-        const uint64_t x = air_uniform(p, j);
-        m[2 * j] = (uint32_t)x;
-        m[2 * j + 1] = (uint32_t)(x >> 32);
+        for (int j = 0; j < N / 2; j++) {
+            const uint64_t x = air_uniform(consts, (size_t)index * (N / 2) + j);
+            m[2 * j] = (uint32_t)x;
+            m[2 * j + 1] = (uint32_t)(x >> 32);
+        }
+        value r;
+#pragma unroll
+        for (int k = 0; k < N; k++) r.v[k] = m[mem_index<F>(k)];
+        return r;
     }
-    Fe<F> r;
+    static __device__ __forceinline__ value tmp(const lds_word *lds, uint32_t slot) {
+        value s;
 #pragma unroll
-    for (int k = 0; k < N; k++) r.v[k] = m[mem_index<F>(k)];
-    return r;
-}
+        for (int k = 0; k < F::N; k++) s.v[k] = lds[(slot * F::N + k) * AIR_THREADS + threadIdx.x];
+        return s;
+    }
+    static __device__ __forceinline__ void put(lds_word *lds, uint32_t slot, const value &v) {
+#pragma unroll
+        for (int k = 0; k < F::N; k++) lds[(slot * F::N + k) * AIR_THREADS + threadIdx.x] = v.v[k];
+    }
+    static __device__ __forceinline__ value add(const value &a, const value &b) { return fe_add<F>(a, b); }
+    static __device__ __forceinline__ value sub(const value &a, const value &b) { return fe_sub<F>(a, b); }
+    static __device__ __forceinline__ value mul(const value &a, const value &b) { return fe_mul<F>(a, b); }
+    static __device__ __forceinline__ value neg(const value &a) { return fe_neg<F>(a); }
+};
 
 template <class F>
 __global__ __launch_bounds__(AIR_THREADS) void air_transition_kernel(const AirArgs a) {
-    extern __shared__ uint32_t air_tmp[];   // [slot][limb][lane]
-    constexpr int N = F::N;
+    extern __shared__ uint32_t air_tmp[];
     const uint64_t i = (uint64_t)blockIdx.x * AIR_THREADS + threadIdx.x;
     if (i >= a.N) return;
-    Fe<F> acc = Fe<F>::zero();
-#pragma unroll 1
-    for (uint32_t pc = 0; pc < a.n_ops; pc++) {
-        const uint64_t w = air_uniform(a.ops, pc);
-        const uint32_t op = (uint32_t)w & 0xffu, src = (uint32_t)(w >> 8) & 0xffu, index = (uint32_t)(w >> 16) & 0xffffu, row = (uint32_t)(w >> 32);
-        if (op <= LW_STARK_AIR_MUL) {
-            Fe<F> s;
-            if (src == LW_STARK_AIR_CELL) {
-                const char *col = (const char *)air_uniform(a.cells, 2 * index);
-                const uint64_t mask = air_uniform(a.cells, 2 * index + 1);
-                s = fe_load<F>(col + ((i + ((uint64_t)row << a.log2_blowup)) & mask) * 32);
-            } else if (src == LW_STARK_AIR_CONST) {
-                s = air_uniform_fe<F>(a.consts + (size_t)index * 32);
-            } else {
-#pragma unroll
-                for (int k = 0; k < N; k++) s.v[k] = air_tmp[(index * N + k) * AIR_THREADS + threadIdx.x];
-            }
-            if (op == LW_STARK_AIR_LOAD) acc = s;
-            else if (op == LW_STARK_AIR_ADD) acc = fe_add<F>(acc, s);
-            else if (op == LW_STARK_AIR_SUB) acc = fe_sub<F>(acc, s);
-            else acc = fe_mul<F>(acc, s);
-        } else if (op == LW_STARK_AIR_NEG) {
-            acc = fe_neg<F>(acc);
-        } else if (op == LW_STARK_AIR_STORE) {
-#pragma unroll
-            for (int k = 0; k < N; k++) air_tmp[(index * N + k) * AIR_THREADS + threadIdx.x] = acc.v[k];
-        } else {   // EMIT
-            fe_store<F>(a.out + ((uint64_t)index * a.out_stride + i) * 32, acc);
-        }
-    }
+    char *const out = a.out + i * 32;
+    const uint64_t row_bytes = a.out_stride * 32;
+    air_run<AirFe<F>>(a.ops, a.n_ops, a.cells, a.consts, air_tmp, i, a.log2_blowup,
+                      [=](uint32_t c, const Fe<F> &acc) { fe_store<F>(out + c * row_bytes, acc); });
 }
 
 // ---- host side ----
-static size_t air_round256(size_t b) { return (b + 255) & ~(size_t)255; }
 static bool air_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // The checks of both forms that need no device; *info out
@@ -111,12 +88,7 @@ static int air_check(lw_field_t field, const lw_stark_air_op_t *ops, uint32_t n_
     const uint64_t lg = (uint64_t)log2_trace + log2_blowup;
     if (lg > 34 || lg > field_two_adicity(field)) { set_error("an LDE domain of 2^%llu points is beyond the NTT", (unsigned long long)lg); return LW_ERR_BAD_ARG; }
     if (n_consts <= LW_STARK_AIR_MAX_CONSTS && n_consts && !consts) { set_error("null constants"); return LW_ERR_BAD_ARG; }
-    char msg[192];
-    if (!air_program_check(ops, n_ops, n_consts, col_log2_len, n_cols, log2_trace, (uint32_t)lg, n_transitions, info, msg, sizeof(msg))) {
-        set_error("AIR program: %s", msg);
-        return LW_ERR_BAD_ARG;
-    }
-    return LW_OK;
+    return air_program_checked(ops, n_ops, n_consts, col_log2_len, n_cols, log2_trace, (uint32_t)lg, n_transitions, info);
 }
 
 // cols: n_cols device pointers (host array).  Enqueue only.
@@ -126,27 +98,19 @@ static int air_locked(Context &c, const lw_stark_air_op_t *ops, uint32_t n_ops, 
                       uint32_t n_transitions, const AirProgramInfo &info, void *d_out, uint64_t out_stride, hipStream_t s) {
     if (n_ops == 0 || n_transitions == 0) return LW_OK;   // nothing is emitted
     const uint64_t N = 1ull << log2_lde;
-    const size_t b_ops = air_round256((size_t)n_ops * sizeof(lw_stark_air_op_t)), b_cells = air_round256((size_t)n_cols * sizeof(AirCell)),
-                 b_consts = air_round256((size_t)n_consts * 32), tables = b_ops + b_cells + b_consts;
-    if (c.poly_ws.ensure(tables)) return LW_ERR_ALLOC;
-    int rc = deep_pin(c, tables);   // one upload through the lane's pinned staging: the caller's arrays are free on return
+    R2Arena t;   // one upload through the lane's pinned staging
+    const size_t s_ops = t.add((size_t)n_ops * sizeof(lw_stark_air_op_t)), s_cells = t.add((size_t)n_cols * 16), s_consts = t.add((size_t)n_consts * 32);
+    int rc = air_tables_stage(c, t, t.total);
     if (rc) return rc;
-    char *hp = (char *)c.deep_pin, *d_tab = (char *)c.poly_ws.p;
-    memset(hp, 0, tables);
-    memcpy(hp, ops, (size_t)n_ops * sizeof(lw_stark_air_op_t));
-    AirCell *cells = (AirCell *)(hp + b_ops);
-    for (uint32_t k = 0; k < n_cols; k++) {
-        cells[k].col = (const char *)cols[k];
-        cells[k].mask = (col_log2_len ? 1ull << col_log2_len[k] : N) - 1;
-    }
-    if (n_consts) memcpy(hp + b_ops + b_cells, consts, (size_t)n_consts * 32);
-    LW_HIP_CHECK(hipMemcpyAsync(d_tab, hp, tables, hipMemcpyHostToDevice, s), LW_ERR_LAUNCH);
-    LW_HIP_CHECK(hipEventRecord(c.deep_pin_read, s), LW_ERR_LAUNCH);
+    r2_fill_ops(t.h(s_ops), ops, n_ops);
+    r2_fill_cells(t.h(s_cells), cols, col_log2_len, n_cols, N);
+    if (n_consts) memcpy(t.h(s_consts), consts, (size_t)n_consts * 32);
+    if ((rc = air_tables_upload(c, t, t.total, s))) return rc;
     AirArgs a;
     memset(&a, 0, sizeof(a));
-    a.ops = (const uint64_t *)d_tab;
-    a.cells = (const AirCell *)(d_tab + b_ops);
-    a.consts = d_tab + b_ops + b_cells;
+    a.ops = t.d(s_ops);
+    a.cells = t.d(s_cells);
+    a.consts = t.d(s_consts);
     a.out = (char *)d_out;
     a.out_stride = out_stride;
     a.N = N;
